@@ -174,6 +174,25 @@ def write_full_record(out, path):
     return written
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy (float64 stays float64, everything else float32), all of them or none; the
+    inputs of the timed steps are seeded, so two builds run with the same arguments can be compared file for file."""
+    host = {}
+    for name, t in arrays.items():
+        x = t.detach().cpu().numpy()
+        host[name] = np.ascontiguousarray(x, dtype=np.float64 if x.dtype == np.float64 else np.float32)
+    total = sum(x.nbytes for x in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError('--dump-outputs: %d bytes exceed the %d-byte budget' % (total, DUMP_MAX_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, x in host.items():
+        np.save(os.path.join(path, name + '.npy'), x)
+    return total
+
+
 def cpu_model():
     try:
         for line in open('/proc/cpuinfo'):
@@ -451,6 +470,9 @@ def main():
     ap.add_argument('--psnr-iters', type=int, default=PSNR_ITERS)
     ap.add_argument('--psnr-cpu-worker', nargs=2, metavar=('IN', 'OUT'), help=argparse.SUPPRESS)
     ap.add_argument('--full-out', default=os.path.join(ROOT, 'bench_full.json'), help='where the full record (all sibling blocks) goes')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='after the timed steps, write what the last one computed as DIR/<name>.npy: its '
+                                                          'loss pair and render outputs, the parameters, gradient and Adam moments it left, '
+                                                          'the leaf-error table (rank 0)')
     a = ap.parse_args()
     if a.psnr_cpu_worker:
         return psnr_cpu_worker(*a.psnr_cpu_worker)
@@ -711,7 +733,16 @@ def main():
     ops.set_math(MAIN_MODE)
     fastnerf.render.set_compact('0')
     tr, _, kte, _ = new_trainer()
-    dt, loss2, t_local = timed(lambda i: step(tr, i)[0], 0, a.warmup, a.steps)
+    last = {}
+
+    def headline_step(i):
+        last['loss2'], last['out'] = step(tr, i)
+        return last['loss2']
+    dt, loss2, t_local = timed(headline_step, 0, a.warmup, a.steps)
+    if a.dump_outputs and rank == 0:    # before the sustained leg steps this trainer on
+        dump_outputs(a.dump_outputs, dict(
+            {'loss2': last['loss2']}, **{k: last['out'][k] for k in last['out']}, params=tr.flat, grad=tr.grad, adam_m=tr.m, adam_v=tr.v,
+            leaf_table=table.view(torch.float32).view(n_img, max_leaves)))
     per_rank_ms = [1e3 * t_local / a.steps]
     allreduce_ms = None
     if world > 1:

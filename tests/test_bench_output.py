@@ -1,8 +1,11 @@
 """bench.py's output contract on the CPU (no GPU, no kernels): the headline line a harness parses from a TAIL WINDOW of the combined
-output must be short, complete and last; `--gpus N` without a launcher must re-execute under torch.distributed.run."""
+output must be short, complete and last; `--gpus N` without a launcher must re-execute under torch.distributed.run.  One GPU test runs
+the headline leg with --dump-outputs."""
 import json
 import os
 import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -127,3 +130,46 @@ def test_write_full_record(tmp_path):
     p = str(tmp_path / 'full.json')
     B.write_full_record(out, p)
     assert json.load(open(p))['other_configs']['configs[2]_quadtree']['workload'].startswith('x')
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path):
+    import numpy as np
+    import torch
+    d = str(tmp_path / 'dump')
+    total = B.dump_outputs(d, {'a': torch.arange(6, dtype=torch.int32).view(2, 3), 'b': torch.ones(4, dtype=torch.float64),
+                               'c': torch.full((5,), 0.5)})
+    got = {n: np.load(os.path.join(d, n + '.npy')) for n in ('a', 'b', 'c')}
+    assert sorted(os.listdir(d)) == ['a.npy', 'b.npy', 'c.npy'] and total == 6 * 4 + 4 * 8 + 5 * 4
+    assert got['a'].dtype == np.float32 and got['a'].shape == (2, 3) and got['a'][1, 2] == 5.0
+    assert got['b'].dtype == np.float64 and got['c'].dtype == np.float32 and np.all(got['c'] == 0.5)
+    over = str(tmp_path / 'over')
+    try:
+        B.dump_outputs(over, {'x': torch.zeros(B.DUMP_MAX_BYTES // 4 + 1)})
+    except RuntimeError as e:
+        assert 'budget' in str(e)
+    else:
+        raise AssertionError('an over-budget dump must fail')
+    assert not os.path.exists(over)          # all or nothing
+
+
+@pytest.mark.gpu
+def test_dump_outputs_of_the_timed_path(tmp_path):
+    """bench.py --dump-outputs on the headline leg: the last timed step's loss pair (the headline's final_loss), its render outputs,
+    the state the step left, the leaf table; float32, under 64 MB; --steps is the number of timed steps."""
+    import subprocess
+    import numpy as np
+    d = str(tmp_path / 'dump')
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--sustained-steps', '0', '--no-siblings',
+           '--psnr-iters', '0', '--no-cpu-baseline', '--full-out', str(tmp_path / 'full.json'), '--dump-outputs', d]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    j = json.loads(r.stdout.strip().splitlines()[-1])
+    assert j['steps'] == 2 and j['ms_per_step'] > 0
+    got = {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+    want = {'loss2', 'rgb_map', 'disp_map', 'acc_map', 'raw', 'rgb0', 'disp0', 'acc0', 'z_std', 'weights', 'z_vals', 'depth_map',
+            'z_samples', 'weights0', 'z0', 'params', 'grad', 'adam_m', 'adam_v', 'leaf_table'}
+    assert set(got) == want and all(x.dtype == np.float32 for x in got.values())
+    assert sum(x.nbytes for x in got.values()) <= 64 << 20
+    assert got['loss2'].tolist() == j['final_loss']
+    assert got['rgb_map'].shape == (B.N_RAYS, 3) and got['raw'].shape == (B.N_RAYS, B.S1, 4) and got['leaf_table'].shape == (100, 256)
+    assert all(np.isfinite(x).all() for x in got.values()) and got['leaf_table'].max() > 0 and np.abs(got['grad']).max() > 0

@@ -5,7 +5,6 @@ recorded from the reference) and the G9 adjust sequences."""
 import os
 import pickle
 import pickletools
-import subprocess
 import sys
 import types
 
@@ -82,22 +81,59 @@ def test_written_pickle_names_reference_classes(golden_dir, tmp_path):
     assert all(np.array_equal(back[i].leaf_array(), g[f'leaves_t{i}']) for i in range(2))
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference/nerf-ours'), reason='needs the reference checkout (build container)')
+def _unpickle_as_reference(path):
+    """What the reference's `pickle.load(f)` restores: instances of classes looked up in a module named `tree`, with their
+    __dict__ set from the file (its QuadTree / QuadTreeNode define no __setstate__).  Returned as plain nested data: class name,
+    then every attribute with its Python type, so that 16 and 16.0 differ."""
+    stub = types.ModuleType('tree')
+    stub.QuadTree = type('QuadTree', (), {'__module__': 'tree'})
+    stub.QuadTreeNode = type('QuadTreeNode', (), {'__module__': 'tree'})
+    prev = sys.modules.get('tree')
+    sys.modules['tree'] = stub
+    try:
+        with open(path, 'rb') as f:
+            obj = pickle.load(f)
+    finally:
+        if prev is None:
+            del sys.modules['tree']
+        else:
+            sys.modules['tree'] = prev
+
+    def state(o):
+        if isinstance(o, list):
+            return [state(x) for x in o]
+        if isinstance(o, (stub.QuadTree, stub.QuadTreeNode)):
+            return (type(o).__name__, {k: state(v) for k, v in vars(o).items()})
+        if isinstance(o, np.ndarray):
+            return ('ndarray', o.dtype.str, o.shape)
+        return (type(o).__name__, o)
+    return state(obj)
+
+
 def test_reference_loads_written_pickle(golden_dir, tmp_path):
+    """The file save_quadtrees writes restores, through the reference's reader, the same objects as the file the reference itself
+    wrote for the same two trees (G16: g16_treeDivide_ref.pkl): node for node the same coordinates with the same Python types and
+    the same children, the same QuadTree attributes.  The reference's get_children / area / __str__ read nothing else.  The one
+    attribute that differs by design is QuadTree.image: the reference pickles its input image, this package writes None."""
     g = np.load(os.path.join(golden_dir, 'g16_treepkl.npz'))
     p = str(tmp_path / 'treeDivide_0002.pkl')
     save_quadtrees([QuadTree.from_leaves(32, 24, g[f'leaves_t{i}'], float(g[f'minarea_t{i}'])) for i in range(2)], p)
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = ("import sys, pickle, numpy as np\n"
-            f"sys.path.insert(0, {os.path.join(root, 'oracle')!r}); from make_golden import install_stubs; install_stubs()\n"
-            "sys.path.insert(0, '/root/reference/nerf-ours'); import tree as T\n"
-            f"qt = pickle.load(open({p!r}, 'rb')); g = np.load({os.path.join(golden_dir, 'g16_treepkl.npz')!r})\n"
-            "assert type(qt[0]) is T.QuadTree\n"
-            "for i, t in enumerate(qt):\n"
-            "    a = np.array([[c.x0, c.y0, c.x1, c.y1] for c in T.get_children(t.root)])\n"
-            "    assert np.array_equal(a, g['leaves_t%d' % i]) and t.minArea == float(g['minarea_t%d' % i])\n"
-            "    assert t.root.children[0].area > 0 and str(t.root)\n")
-    subprocess.run([sys.executable, '-c', code], check=True)
+    ours = _unpickle_as_reference(p)
+    ref = _unpickle_as_reference(os.path.join(golden_dir, 'g16_treeDivide_ref.pkl'))
+    assert len(ours) == len(ref) == 2
+    for i, (t, r) in enumerate(zip(ours, ref)):
+        assert t[0] == r[0] == 'QuadTree' and sorted(t[1]) == sorted(r[1])
+        assert r[1]['image'][0] == 'ndarray' and t[1]['image'] == ('NoneType', None)
+        for k in r[1]:
+            if k != 'image':
+                assert t[1][k] == r[1][k], (i, k)
+        assert t[1]['minArea'] == ('float', float(g[f'minarea_t{i}']))
+
+        def leaves(node):
+            kids = node[1]['children']
+            return [node] if not kids else [x for c in kids for x in leaves(c)]
+        got = np.array([[n[1][c][1] for c in ('x0', 'y0', 'x1', 'y1')] for n in leaves(t[1]['root'])])
+        assert np.array_equal(got, g[f'leaves_t{i}'])
 
 
 def test_variance_gated_constructor(golden_dir):
