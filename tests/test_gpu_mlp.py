@@ -282,8 +282,9 @@ def test_mlp_edge_cases(fn, weights, math_mode):
 
 def test_large_batch_consistency(fn, weights):
     """Several tiles per persistent workgroup (the size class where a timing-dependent corruption of the training
-    forward once showed up): inference and training forwards agree bit for bit, run to run, and the two math
-    modes agree to fp32-rounding class; gradients are deterministic."""
+    forward once showed up): inference and training forwards agree bit for bit, run to run, and the math modes
+    agree with the fp32-MFMA mode to fp32-rounding class (bf16x6: same logit bound, gradients within the relative L2
+    bound of test_mlp_backward_ragged_point_counts); gradients are deterministic."""
     flat = flat_of(weights).cuda()
     gen = torch.Generator().manual_seed(123)
     n, S = 2048, 96                       # 196 608 points = 3072 tiles of 64
@@ -295,7 +296,7 @@ def test_large_batch_consistency(fn, weights):
     out = {}
     old = fn.ops.get_math()
     try:
-        for mode in ('fp32', 'bf16x3'):
+        for mode in ('fp32', 'bf16x3', 'bf16x6'):
             fn.ops.set_math(mode)
             pf, pb = fn.ops.mlp_pack(flat)
             act = torch.empty(fn.ops.act_floats(n * S)).cuda()
@@ -318,6 +319,11 @@ def test_large_batch_consistency(fn, weights):
     assert d < 2e-5, d
     ga, gb = out['fp32'][1], out['bf16x3'][1]
     assert (ga - gb).abs().max().item() < 2e-2 * ga.abs().max().item()   # ReLU-mask-flip floor, DESIGN section 4
+    d6 = (out['fp32'][0] - out['bf16x6'][0]).abs().max().item()
+    assert d6 < 2e-5, d6
+    g6 = out['bf16x6'][1]
+    rel = ((g6 - ga).double().norm() / ga.double().norm()).item()
+    assert rel < 2e-3, rel
 
 
 def test_training_forward_stress_at_bench_size(fn, weights, math_mode):
@@ -358,52 +364,48 @@ def test_training_forward_stress_at_bench_size(fn, weights, math_mode):
             assert np.abs(alpha - want).max() < 2e-5 * max(1.0, np.abs(want).max()), tile
 
 
-def test_tile_scheduler_back_to_back_and_streams(fn, weights):
+def test_tile_scheduler_back_to_back_and_streams(fn, weights, math_mode):
     """The persistent forward / dX kernels draw their tiles from a self-resetting ticket counter (one counter pair per
     launch from a pool): many launches of very different sizes, back to back and interleaved on two streams, must
-    reproduce the single-launch results bit for bit (a stale or shared counter would skip or repeat tiles)."""
-    old = fn.ops.get_math()
-    fn.ops.set_math('bf16x3')
-    try:
-        flat = flat_of(weights).cuda()
-        pf, pb = fn.ops.mlp_pack(flat)
-        gen = torch.Generator().manual_seed(5)
-        sizes = [(1, 1), (1, 63), (1, 64), (5, 13), (64, 64), (257, 192), (700, 100)]   # (rays, samples): 1 .. 70 000 points
-        cases = []
-        for n, S in sizes:
-            ro = torch.randn(n, 3, generator=gen) * 0.3
-            rd = torch.randn(n, 3, generator=gen)
-            rays = torch.from_numpy(O.make_ray_batch(ro, rd, 2.0, 6.0).numpy()).cuda()
-            z = torch.sort(torch.rand(n, S, generator=gen) * 4 + 2, -1).values.cuda()
-            cot = torch.randn(n, S, 4, generator=gen).cuda()
+    reproduce the single-launch results bit for bit (a stale or shared counter would skip or repeat tiles).  Every math
+    mode: bf16x3 runs csrc/mlp_bf16.hip's kernels, fp32 and bf16x6 the ticket-scheduled forward of csrc/mlp_fwd.hip."""
+    flat = flat_of(weights).cuda()
+    pf, pb = fn.ops.mlp_pack(flat)
+    gen = torch.Generator().manual_seed(5)
+    sizes = [(1, 1), (1, 63), (1, 64), (5, 13), (64, 64), (257, 192), (700, 100)]   # (rays, samples): 1 .. 70 000 points
+    cases = []
+    for n, S in sizes:
+        ro = torch.randn(n, 3, generator=gen) * 0.3
+        rd = torch.randn(n, 3, generator=gen)
+        rays = torch.from_numpy(O.make_ray_batch(ro, rd, 2.0, 6.0).numpy()).cuda()
+        z = torch.sort(torch.rand(n, S, generator=gen) * 4 + 2, -1).values.cuda()
+        cot = torch.randn(n, S, 4, generator=gen).cuda()
+        act = torch.empty(fn.ops.act_floats(n * S)).cuda()
+        raw = fn.ops.mlp_fwd(rays, z, flat, pf, act=act).clone()
+        dact = torch.empty(fn.ops.dact_floats(n * S)).cuda()
+        partial = torch.empty(fn.ops.mlp_bwd_partial_floats()).cuda()
+        grads = torch.zeros(fn.ops.NET_PARAMS).cuda()
+        fn.ops.mlp_bwd(cot, act, flat, pb, dact, partial, grads)
+        cases.append((rays, z, cot, raw, grads.clone()))
+    torch.cuda.synchronize()
+    order = torch.randint(0, len(cases), (120,), generator=gen).tolist()
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    results = []
+    for k, ci in enumerate(order):
+        rays, z, cot, raw_ref, g_ref = cases[ci]
+        with torch.cuda.stream(streams[k & 1]):
+            n, S = z.shape
             act = torch.empty(fn.ops.act_floats(n * S)).cuda()
-            raw = fn.ops.mlp_fwd(rays, z, flat, pf, act=act).clone()
+            raw = fn.ops.mlp_fwd(rays, z, flat, pf, act=act)
             dact = torch.empty(fn.ops.dact_floats(n * S)).cuda()
             partial = torch.empty(fn.ops.mlp_bwd_partial_floats()).cuda()
             grads = torch.zeros(fn.ops.NET_PARAMS).cuda()
             fn.ops.mlp_bwd(cot, act, flat, pb, dact, partial, grads)
-            cases.append((rays, z, cot, raw, grads.clone()))
-        torch.cuda.synchronize()
-        order = torch.randint(0, len(cases), (120,), generator=gen).tolist()
-        streams = [torch.cuda.Stream(), torch.cuda.Stream()]
-        results = []
-        for k, ci in enumerate(order):
-            rays, z, cot, raw_ref, g_ref = cases[ci]
-            with torch.cuda.stream(streams[k & 1]):
-                n, S = z.shape
-                act = torch.empty(fn.ops.act_floats(n * S)).cuda()
-                raw = fn.ops.mlp_fwd(rays, z, flat, pf, act=act)
-                dact = torch.empty(fn.ops.dact_floats(n * S)).cuda()
-                partial = torch.empty(fn.ops.mlp_bwd_partial_floats()).cuda()
-                grads = torch.zeros(fn.ops.NET_PARAMS).cuda()
-                fn.ops.mlp_bwd(cot, act, flat, pb, dact, partial, grads)
-                results.append((ci, raw, grads, act, dact, partial))
-        torch.cuda.synchronize()
-        for ci, raw, grads, *_ in results:
-            assert torch.equal(raw, cases[ci][3]), ci
-            assert torch.equal(grads, cases[ci][4]), ci
-    finally:
-        fn.ops.set_math(old)
+            results.append((ci, raw, grads, act, dact, partial))
+    torch.cuda.synchronize()
+    for ci, raw, grads, *_ in results:
+        assert torch.equal(raw, cases[ci][3]), (math_mode, ci)
+        assert torch.equal(grads, cases[ci][4]), (math_mode, ci)
 
 
 def test_bf16x6_decomposition_is_exact_and_products_have_fp32_width(fn, weights):
