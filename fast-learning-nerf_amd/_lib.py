@@ -53,6 +53,7 @@ SIGNATURES = {
     'fastnerf_mlp_bwd': (I, [L, I, P, P, P, P, P, P, P, P]),
     'fastnerf_raw2outputs_fwd': (I, [L, I, P, P, P, P, I, P, P, P, P, P, P]),
     'fastnerf_raw2outputs_bwd': (I, [L, I, P, P, P, P, I, P, P, P]),
+    'fastnerf_raw2outputs_bwd_full': (I, [L, I, P, P, P, P, I, P, P, P, P, P, P, P, P, P]),
     'fastnerf_sample_pdf_merge': (I, [L, I, I, P, P, I, P, U64, P, P, P, P]),
     'fastnerf_sample_pdf': (I, [L, I, I, P, P, I, P, U64, P, P]),
     'fastnerf_mse_leafmax': (I, [L, P, P, P, F, P, P, P, P, I, P, P]),

@@ -38,6 +38,19 @@ __device__ __forceinline__ float wave_scan_add(float v, int lane) {
   return v;
 }
 
+// three independent inclusive add-scans, interleaved so that their cross-lane latencies overlap
+__device__ __forceinline__ void wave_scan_add3(float& a, float& b, float& c, int lane) {
+#pragma unroll
+  for (int o = 1; o < WAVE; o <<= 1) {
+    const float ta = __shfl_up(a, o, WAVE), tb = __shfl_up(b, o, WAVE), tc = __shfl_up(c, o, WAVE);
+    if (lane >= o) {
+      a += ta;
+      b += tb;
+      c += tc;
+    }
+  }
+}
+
 __device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 struct SampleVals {
@@ -222,6 +235,138 @@ __global__ void __launch_bounds__(256) raw2outputs_bwd_kernel(int64_t n, int S, 
         out[j].y = g1 * w[j] * v[j].c[1] * (1.0f - v[j].c[1]);
         out[j].z = g2 * w[j] * v[j].c[2] * (1.0f - v[j].c[2]);
         out[j].w = dsig;
+        suffix += G[j] * w[j];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < MAXC; ++j)
+      if (j < cnt) *reinterpret_cast<float4*>(draw + (r * S + lane * C + j) * 4) = out[j];
+  }
+}
+
+// d(rgb, disp, acc, weights, depth)/d(raw) of the nerf-ours rule (render.py:149-192).  Same mapping and scans as
+// raw2outputs_bwd_kernel.  The upstream gradient of the weights is
+//   dL/dw_i = G_i + a + b z_i,   G_i = g_rgb.c_i - gbg + g_w[i],   a = g_acc',  b = g_depth'
+// with the disparity folded into the per-ray a / b: disp = 1 / max(1e-10, depth / acc), so on the unclamped branch
+//   d disp/d acc = disp / acc,  d disp/d depth = -disp^2 / acc;
+// on the clamp branch disp is constant (half the gradient on the exact tie, as torch.max splits it); where the forward wrote
+// NaN (acc == 0) a non-zero g_disp makes a and b NaN, as the reference's autograd does.  acc / depth are the forward's own
+// outputs, so the branch is decided on the values the forward used.
+//
+// G goes through the rgb-only kernel's suffix formula  dalpha_i = G_i T_i - sum_{j>i} G_j w_j / t_i.  For a + b z that
+// formula cancels (for a constant it is T_i - (T_i - T_end + ...) / t_i: noise of order eps * T_i around a value of order
+// T_end), so its closed form is used instead (t_j = 1 - alpha_j + eps, dz_j = z_j - z_{j-1}):
+//   d acc/d alpha_i   = (T_end       - eps sum_{j>i} T_j) / t_i
+//   d depth/d alpha_i = (z_last T_end - sum_{j>i} (dz_j + eps z_j) T_j) / t_i
+// one more suffix sum, of h_j = (a eps + b (dz_j + eps z_j)) T_j, and every term has one sign.
+// Each upstream pointer may be NULL (= zero).  With all four new ones NULL every instruction on the path of
+// raw2outputs_bwd_kernel runs in the same order: bit-identical draw.
+__global__ void __launch_bounds__(256) raw2outputs_bwd_full_kernel(
+    int64_t n, int S, const float* __restrict__ raw, const float* __restrict__ z, const float* __restrict__ rays,
+    const float* __restrict__ noise, int white, const float* __restrict__ acc_f, const float* __restrict__ depth_f,
+    const float* __restrict__ g_rgb, const float* __restrict__ g_disp, const float* __restrict__ g_acc,
+    const float* __restrict__ g_w, const float* __restrict__ g_depth, float* __restrict__ draw) {
+  const CompCfg cfg = nerf_cfg();
+  const int lane = threadIdx.x & 63;
+  const int C = (S + WAVE - 1) / WAVE;
+  const int64_t wave0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  const bool ray_terms = g_acc || g_depth || g_disp;
+  for (int64_t r = wave0; r < n; r += nwaves) {
+    const float* rr = rays + r * 11;
+    const float dnorm = sqrtf(fadd(fadd(fmul(rr[3], rr[3]), fmul(rr[4], rr[4])), fmul(rr[5], rr[5])));
+    const float g0 = g_rgb ? g_rgb[r * 3] : 0.0f, g1 = g_rgb ? g_rgb[r * 3 + 1] : 0.0f, g2 = g_rgb ? g_rgb[r * 3 + 2] : 0.0f;
+    const float gbg = white ? (g0 + g1 + g2) : 0.0f;
+    const float ga0 = g_acc ? g_acc[r] : 0.0f, gd0 = g_depth ? g_depth[r] : 0.0f;
+    float ga = ga0, gd = gd0;
+    float kd = 0.0f;   // != 0: the disparity's share of (a + b z_last), -kd * sum_j w_j (z_last - z_j), is needed
+    if (g_disp) {
+      const float gq = g_disp[r];
+      if (gq != 0.0f) {
+        const float a = acc_f[r], dep = depth_f[r], q = dep / a;
+        if (q != q) {
+          ga = q; gd = q;  // NaN
+        } else if (q >= 1e-10f) {
+          const float disp = 1.0f / q;
+          const float gqe = q == 1e-10f ? 0.5f * gq : gq;
+          const float k = gqe * disp / a;
+          ga += k;
+          gd -= k * disp;
+          kd = gqe / dep / dep;
+        }
+      }
+    }
+    const float zlast = ray_terms ? z[r * S + S - 1] : 0.0f;
+    SampleVals v[MAXC];
+    int cnt;
+    eval_chunk<true>(S, C, lane, raw + r * S * 4, z + r * S, noise ? noise + r * S : nullptr, dnorm, v, cnt, cfg, 0.f);
+    float prod = 1.0f;
+#pragma unroll
+    for (int j = 0; j < MAXC; ++j)
+      if (j < cnt) prod *= v[j].t;
+    const float incl = wave_scan_mul(prod, lane);
+    float T0 = __shfl_up(incl, 1, WAVE);
+    if (lane == 0) T0 = 1.0f;
+    // z of the sample before this lane's chunk (for dz of its first sample; lane 0's is never summed)
+    float zprev = 0.0f;
+#pragma unroll
+    for (int j = 0; j < MAXC; ++j)
+      if (j < cnt) zprev = v[j].z;
+    zprev = __shfl_up(zprev, 1, WAVE);
+    float w[MAXC], G[MAXC], Tj[MAXC], h[MAXC];
+    float gw_chunk = 0.f, h_chunk = 0.f, dlast = 0.f;
+    float T = T0;
+#pragma unroll
+    for (int j = 0; j < MAXC; ++j) {
+      if (j < cnt) {
+        Tj[j] = T;
+        w[j] = v[j].alpha * T;
+        G[j] = g0 * v[j].c[0] + g1 * v[j].c[1] + g2 * v[j].c[2] - gbg;
+        if (g_w) G[j] = G[j] + g_w[r * S + lane * C + j];
+        gw_chunk += G[j] * w[j];
+        if (ray_terms) {
+          const float dz = v[j].z - zprev;
+          h[j] = (ga * cfg.eps + gd * (dz + cfg.eps * v[j].z)) * T;
+          h_chunk += h[j];
+          zprev = v[j].z;
+          dlast += w[j] * (zlast - v[j].z);
+        }
+        T *= v[j].t;
+      }
+    }
+    float incl_gw = gw_chunk, incl_h = h_chunk, incl_d = dlast;
+    if (ray_terms)
+      wave_scan_add3(incl_gw, incl_h, incl_d, lane);
+    else
+      incl_gw = wave_scan_add(gw_chunk, lane);
+    const float total = __shfl(incl_gw, WAVE - 1, WAVE);
+    float suffix = total - incl_gw;
+    float suffix_h = 0.f, end_term = 0.f;
+    if (ray_terms) {
+      suffix_h = __shfl(incl_h, WAVE - 1, WAVE) - incl_h;
+      // (a + b z_last) T_end.  Its disparity part k (1 - disp z_last) cancels when the last sample holds the depth; written
+      // as -(g_disp / depth^2) (acc z_last - depth) with acc z_last - depth = sum_j w_j (z_last - z_j) >= 0, it does not
+      float coef = ga + gd * zlast;
+      if (kd != 0.0f) coef = (ga0 + gd0 * zlast) - kd * __shfl(incl_d, WAVE - 1, WAVE);
+      end_term = coef * __shfl(incl, WAVE - 1, WAVE);
+    }
+    float4 out[MAXC];
+#pragma unroll
+    for (int j = MAXC - 1; j >= 0; --j) {
+      if (j < cnt) {
+        // (+ 0.0f: the rgb-only kernel adds its zero bg_lambda term here; kept so that -0 sums round the same way)
+        float dalpha;
+        if (ray_terms) {
+          dalpha = G[j] * Tj[j] - (suffix - (end_term - suffix_h)) / v[j].t;   // one division for both suffix terms
+          suffix_h += h[j];
+        } else {
+          dalpha = G[j] * Tj[j] - (suffix + 0.0f) / v[j].t;
+        }
+        const float dact = dalpha * v[j].dist * (1.0f - v[j].alpha);
+        out[j].x = g0 * w[j] * v[j].c[0] * (1.0f - v[j].c[0]);
+        out[j].y = g1 * w[j] * v[j].c[1] * (1.0f - v[j].c[1]);
+        out[j].z = g2 * w[j] * v[j].c[2] * (1.0f - v[j].c[2]);
+        out[j].w = (v[j].sig > 0.0f) ? dact : 0.0f;
         suffix += G[j] * w[j];
       }
     }
@@ -422,6 +567,19 @@ extern "C" int fastnerf_raw2outputs_bwd(int64_t n, int S, const float* raw, cons
   hipLaunchKernelGGL(raw2outputs_bwd_kernel, dim3(grid_waves(n)), dim3(256), 0, fn::S(stream), n, S, raw, z, rays11,
                      noise, white_bkgd, g_rgb, draw, CompCfg{0, 1e-10f, 0, 1, 0}, (const float*)nullptr,
                      (const float*)nullptr);
+  FN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fastnerf_raw2outputs_bwd_full(int64_t n, int S, const float* raw, const float* z, const float* rays11,
+                                             const float* noise, int white_bkgd, const float* acc, const float* depth,
+                                             const float* g_rgb, const float* g_disp, const float* g_acc, const float* g_w,
+                                             const float* g_depth, float* draw, fn_stream_t stream) {
+  FN_CHECK_ARG(n >= 0 && S >= 1 && S <= WAVE * MAXC, "n>=0, 1<=S<=512");
+  FN_CHECK_ARG(n == 0 || (raw && z && rays11 && draw && (!g_disp || (acc && depth))), "null pointer");
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(raw2outputs_bwd_full_kernel, dim3(grid_waves(n)), dim3(256), 0, fn::S(stream), n, S, raw, z, rays11,
+                     noise, white_bkgd, acc, depth, g_rgb, g_disp, g_acc, g_w, g_depth, draw);
   FN_LAUNCH_CHECK();
   return 0;
 }

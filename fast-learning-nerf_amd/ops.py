@@ -423,6 +423,23 @@ def raw2outputs_bwd(raw, z, rays11, g_rgb, noise=None, white_bkgd=False, draw=No
     return draw
 
 
+def raw2outputs_bwd_full(raw, z, rays11, acc, depth, g_rgb=None, g_disp=None, g_acc=None, g_w=None, g_depth=None, noise=None,
+                         white_bkgd=False, draw=None):
+    """d(rgb, disp, acc, weights, depth)/d(raw) [n,S,4] (render.py:149-192).  acc / depth: the forward's outputs; every upstream
+    gradient may be None (= zero).  With only g_rgb, bit-identical to raw2outputs_bwd."""
+    require_gpu(raw, z, rays11, acc, depth, g_rgb, g_disp, g_acc, g_w, g_depth, noise)
+    n, S = z.shape
+    if draw is None:
+        draw = torch.empty(n, S, 4, device=z.device, dtype=torch.float32)
+    g = [None if t is None else _f32(t) for t in (g_rgb, g_disp, g_acc, g_w, g_depth)]
+    for t, shp in zip(g, ((n, 3), (n,), (n,), (n, S), (n,))):
+        assert t is None or tuple(t.shape) == shp, (tuple(t.shape), shp)
+    check(lib().fastnerf_raw2outputs_bwd_full(n, S, ptr(raw), ptr(z), ptr(rays11), ptr(noise), int(bool(white_bkgd)),
+                                              ptr(None if acc is None else _f32(acc)), ptr(None if depth is None else _f32(depth)),
+                                              *[ptr(t) for t in g], ptr(draw), stream()), 'fastnerf_raw2outputs_bwd_full')
+    return draw
+
+
 def sample_pdf_merge(z, weights, Ni, det=False, u=None, seed=0, want_samples=True):
     require_gpu(z, weights, u)
     n, S = z.shape

@@ -7,7 +7,9 @@ raw2outputs (:149-192), render_path (:94-146).  `render_rays` runs the fused dev
 
 and, when autograd is recording, registers ONE autograd node whose backward runs
 raw2outputs_bwd + mlp_bwd for both nets and hands the flat gradients to the NeRF parameters,
-so the reference's `loss.backward(); optimizer.step()` loop works unchanged.
+so the reference's `loss.backward(); optimizer.step()` loop works unchanged.  Networks that are not fastnerf
+NeRF modules take the closure route instead (`_render_rays_closure`): the caller's `network_query_fn` runs in torch
+between the same HIP sampling and compositing kernels, differentiable through torch.ops.fastnerf.raw2outputs_full.
 """
 import os
 
@@ -286,32 +288,91 @@ class _RenderRaysFn(torch.autograd.Function):
 
 
 def raw2outputs(raw, z_vals, rays_d, raw_noise_std=0, white_bkgd=False, pytest=False):
-    """render.py:149-192 -> (rgb_map, disp_map, acc_map, weights, depth_map).  Forward only."""
+    """render.py:149-192 -> (rgb_map, disp_map, acc_map, weights, depth_map).  When `raw` requires grad, all five outputs are
+    differentiable w.r.t. `raw` (torch.ops.fastnerf.raw2outputs_full, the reference's autograd formula); `z_vals` and `rays_d`
+    are not differentiated (no caller in the reference needs it) and raise when they ask to be."""
     n, S = z_vals.shape
     rays11 = torch.zeros(n, 11, device=z_vals.device, dtype=torch.float32)
-    rays11[:, 3:6] = rays_d
+    rays11[:, 3:6] = rays_d.detach()
     noise = None
     if raw_noise_std > 0.:
         noise = torch.randn(n, S, device=z_vals.device) * raw_noise_std
         if pytest:
             noise = _pytest_rand((n, S), z_vals.device) * raw_noise_std
+    if torch.is_grad_enabled() and raw.requires_grad:
+        if z_vals.requires_grad or rays_d.requires_grad:
+            raise NotImplementedError('raw2outputs differentiates w.r.t. raw only: z_vals / rays_d must not require grad')
+        return torch.ops.fastnerf.raw2outputs_full(raw.float().contiguous(), z_vals.contiguous().float(), rays11, noise, white_bkgd)
     return ops.raw2outputs_fwd(raw.contiguous().float(), z_vals.contiguous().float(), rays11, noise, white_bkgd)
+
+
+def _unwrap(net):
+    return getattr(net, 'module', net) if net is not None else None
+
+
+def _composite(raw, z, rays11, noise, white_bkgd):
+    """Compositing of the closure route: the network's first four channels (a closure may return more, e.g. output_ch = 5),
+    differentiable w.r.t. raw through every output when autograd records."""
+    raw4 = raw[..., :4].float().contiguous()
+    if torch.is_grad_enabled() and raw4.requires_grad:
+        return torch.ops.fastnerf.raw2outputs_full(raw4, z, rays11, noise, white_bkgd)
+    return ops.raw2outputs_fwd(raw4, z, rays11, noise, white_bkgd)
+
+
+def _render_rays_closure(ray_batch, rays11, network_fn, network_fine, network_query_fn, N_samples, N_importance, retraw, lindisp,
+                         perturb, white_bkgd, t_rand, u, noise0, noise1):
+    """render.py:195-305 for any torch network: sampling, inverse-CDF + merge and compositing run on the HIP kernels, the
+    network runs as `network_query_fn(pts, viewdirs, net)` in torch, and autograd reaches its parameters through
+    raw2outputs_full.  Random draws follow the fused route (same injected tensors, same host-RNG seed draws)."""
+    if network_query_fn is None:
+        raise TypeError('render_rays with a network that is not a fastnerf NeRF needs network_query_fn(pts, viewdirs, net)')
+    viewdirs = ray_batch[:, -3:] if ray_batch.shape[-1] > 8 else None      # render.py:218
+    seed0 = _next_seed() if (perturb and t_rand is None) else 0
+    z = ops.sample_coarse(rays11, N_samples, lindisp=lindisp, perturb=bool(perturb), t_rand=t_rand, seed=seed0)
+    rays_o, rays_d = rays11[:, 0:3], rays11[:, 3:6]
+    pts = rays_o[..., None, :] + rays_d[..., None, :] * z[..., :, None]      # render.py:268
+    raw = network_query_fn(pts, viewdirs, network_fn)
+    rgb, disp, acc, weights, _ = _composite(raw, z, rays11, noise0, white_bkgd)
+    ret = {}
+    if N_importance > 0:
+        ret['rgb0'], ret['disp0'], ret['acc0'] = rgb, disp, acc
+        seed1 = _next_seed() if (perturb and u is None) else 0
+        # sample_pdf(mid(z), weights[1:-1]) on the detached weights (render.py:279-283) + sort(cat)
+        z1, _, z_std = ops.sample_pdf_merge(z, weights.detach().contiguous(), N_importance, det=(perturb == 0.), u=u, seed=seed1,
+                                            want_samples=False)
+        pts = rays_o[..., None, :] + rays_d[..., None, :] * z1[..., :, None]
+        raw = network_query_fn(pts, viewdirs, network_fine if network_fine is not None else network_fn)
+        rgb, disp, acc, _, _ = _composite(raw, z1, rays11, noise1, white_bkgd)
+        ret['z_std'] = z_std
+    out = {'rgb_map': rgb, 'disp_map': disp, 'acc_map': acc}
+    if retraw:
+        out['raw'] = raw
+    out.update(ret)
+    return out
 
 
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
                 N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False):
-    """render.py:195-305.  `network_query_fn` is accepted for signature compatibility; positional
-    encoding + MLP run fused inside the HIP kernels, so `network_fn`/`network_fine` must be
-    fastnerf NeRF modules (anything else raises -- there is no fallback path)."""
-    net_c = getattr(network_fn, 'module', network_fn)
-    net_f = getattr(network_fine, 'module', network_fine) if network_fine is not None else None
-    if not isinstance(net_c, NeRF) or (net_f is not None and not isinstance(net_f, NeRF)):
-        raise TypeError('render_rays needs fastnerf NeRF modules (the HIP path has no generic fallback)')
+    """render.py:195-305.  Two routes, chosen by the networks (after `.module` unwrapping):
+
+    * fastnerf NeRF modules (8 x 256): positional encoding + MLP run fused inside the HIP kernels; `network_query_fn` is
+      accepted for signature compatibility and never called.
+    * any other torch network (`network_fine` too, when given): `network_query_fn(pts, viewdirs, net)` is called on the
+      points of both passes, as the reference does; sampling and compositing still run on the HIP kernels, and every map is
+      differentiable w.r.t. the network's parameters.
+
+    A NeRF paired with another kind of network raises TypeError (the fused route would not train the other one)."""
+    net_c = _unwrap(network_fn)
+    net_f = _unwrap(network_fine)
+    fused = isinstance(net_c, NeRF)
+    if (net_f is not None and isinstance(net_f, NeRF) != fused):
+        raise TypeError('render_rays needs either fastnerf NeRF modules for both networks (fused HIP route) or torch networks '
+                        'for both, called through network_query_fn (closure route); got a NeRF paired with another network')
     if ray_batch.shape[-1] not in (8, 11):
         raise ValueError('ray batches are [N,8] (o, d, near, far) or [N,11] (+ view directions), render.py:216-219')
-    if ray_batch.shape[-1] == 11 and not net_c.use_viewdirs:
+    if fused and ray_batch.shape[-1] == 11 and not net_c.use_viewdirs:
         raise ValueError('a ray batch with view directions needs networks built with use_viewdirs=True')
-    if ray_batch.shape[-1] == 8 and net_c.use_viewdirs:
+    if fused and ray_batch.shape[-1] == 8 and net_c.use_viewdirs:
         raise ValueError('networks built with use_viewdirs=True need ray batches with view directions [N,11]')
     ops.require_gpu(ray_batch)
     rays11 = ray_batch.contiguous().float()
@@ -330,6 +391,9 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             noise1 = _pytest_rand((n, N_samples + N_importance), dev) * raw_noise_std
         else:      # one Philox launch for both passes (the injected-tensor path above stays for pytest=True)
             noise0, noise1 = ops.sigma_noise(n, N_samples, N_samples + N_importance if N_importance > 0 else 0, raw_noise_std, _next_seed(), dev)
+    if not fused:
+        return _render_rays_closure(ray_batch, rays11, network_fn, network_fine, network_query_fn, N_samples, N_importance, retraw,
+                                    lindisp, perturb, white_bkgd, t_rand, u, noise0, noise1)
     cfg = dict(rays11=rays11, net_c=net_c, net_f=net_f, N_samples=N_samples, N_importance=N_importance,
                lindisp=lindisp, perturb=perturb, white_bkgd=white_bkgd, t_rand=t_rand, u=u, noise0=noise0,
                noise1=noise1,

@@ -35,10 +35,23 @@ def batchify(fn, chunk):
 
 def run_network(inputs, viewdirs, fn, embed_fn=None, embeddirs_fn=None, netchunk=1024 * 64):
     """run_nerf.py:50-64: PE + MLP on explicit points [N,S,3] with per-ray viewdirs [N,3].
-    Runs the fused HIP forward by expressing every point as a ray with o=pt, d=0."""
+    A fastnerf NeRF runs the fused HIP forward (forward only) by expressing every point as a ray with o=pt, d=0.  Any other
+    torch network runs as the reference does: flatten, `embed_fn` (get_embedder's HIP positional encoding), expanded and
+    embedded viewdirs when given, `batchify(fn, netchunk)`, reshape -- differentiable w.r.t. the network's parameters."""
     net = getattr(fn, 'module', fn)
     if not isinstance(net, NeRF):
-        raise TypeError('run_network needs a fastnerf NeRF module')
+        if embed_fn is None:
+            raise TypeError('run_network with a network that is not a fastnerf NeRF needs embed_fn (run_nerf.py:50-64)')
+        inputs_flat = torch.reshape(inputs, [-1, inputs.shape[-1]])
+        embedded = embed_fn(inputs_flat)
+        if viewdirs is not None:
+            if embeddirs_fn is None:
+                raise TypeError('run_network: viewdirs given without embeddirs_fn')
+            input_dirs = viewdirs[:, None].expand(inputs.shape)
+            input_dirs_flat = torch.reshape(input_dirs, [-1, input_dirs.shape[-1]])
+            embedded = torch.cat([embedded, embeddirs_fn(input_dirs_flat)], -1)
+        outputs_flat = batchify(fn, netchunk)(embedded)
+        return torch.reshape(outputs_flat, list(inputs.shape[:-1]) + [outputs_flat.shape[-1]])
     ops.require_gpu(inputs, viewdirs)
     if (viewdirs is not None) != net.use_viewdirs:
         raise ValueError('viewdirs must be given exactly when the network was built with use_viewdirs=True')

@@ -14,6 +14,8 @@ in this package.
     torch.ops.fastnerf.mlp_fwd(rays11, z, params, packed_fwd)                  -> raw                model.py:38-63 (+ PE)
     torch.ops.fastnerf.raw2outputs(raw, z, rays11, noise, white_bkgd)          -> (rgb, disp, acc, weights, depth)   render.py:149-192
                                                                                   differentiable w.r.t. raw through rgb
+    torch.ops.fastnerf.raw2outputs_full(raw, z, rays11, noise, white_bkgd)     -> (rgb, disp, acc, weights, depth)   render.py:149-192
+                                                                                  differentiable w.r.t. raw through all five
     torch.ops.fastnerf.sample_pdf_merge(z, weights, Ni, det, u, seed)          -> (z_all, z_samples, z_std)          run_nerf_helpers.py:112-155 + render.py:283
     torch.ops.fastnerf.mse_leafmax(rgb, rgb0, target, grad_scale, leaf_tag, max_leaves, table) -> (loss2, g_rgb, g_rgb0)   (table mutated)
     torch.ops.fastnerf.adam_step(params, grads, m, v, lr, step, beta1, beta2, eps)             -> ()  (params, m, v mutated)
@@ -123,6 +125,51 @@ def _r2o_backward(ctx, g_rgb, g_disp, g_acc, g_w, g_depth):
 raw2outputs.register_autograd(_r2o_backward, setup_context=_r2o_setup)
 
 
+@_lib_def('fastnerf::raw2outputs_full', mutates_args=())
+def raw2outputs_full(raw: Tensor, z: Tensor, rays11: Tensor, noise: Optional[Tensor], white_bkgd: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    return ops.raw2outputs_fwd(raw.contiguous(), z.contiguous(), rays11, noise, white_bkgd)
+
+
+@raw2outputs_full.register_fake
+def _(raw, z, rays11, noise, white_bkgd):
+    n, S = z.shape
+    return z.new_empty((n, 3)), z.new_empty((n,)), z.new_empty((n,)), z.new_empty((n, S)), z.new_empty((n,))
+
+
+@_lib_def('fastnerf::raw2outputs_bwd_full', mutates_args=())
+def raw2outputs_bwd_full(raw: Tensor, z: Tensor, rays11: Tensor, acc: Tensor, depth: Tensor, g_rgb: Optional[Tensor],
+                         g_disp: Optional[Tensor], g_acc: Optional[Tensor], g_w: Optional[Tensor], g_depth: Optional[Tensor],
+                         noise: Optional[Tensor], white_bkgd: bool) -> Tensor:
+    return ops.raw2outputs_bwd_full(raw.contiguous(), z.contiguous(), rays11, acc, depth, g_rgb, g_disp, g_acc, g_w, g_depth,
+                                    noise, white_bkgd)
+
+
+@raw2outputs_bwd_full.register_fake
+def _(raw, z, rays11, acc, depth, g_rgb, g_disp, g_acc, g_w, g_depth, noise, white_bkgd):
+    return raw.new_empty(raw.shape)
+
+
+def _r2o_full_setup(ctx, inputs, output):
+    raw, z, rays11, noise, white_bkgd = inputs
+    _, _, acc, _, depth = output
+    ctx.save_for_backward(raw, z, rays11, noise if noise is not None else raw.new_empty(0), acc, depth)
+    ctx.has_noise, ctx.white = noise is not None, white_bkgd
+    ctx.set_materialize_grads(False)      # an output nobody differentiates arrives as None: the kernel skips its read
+
+
+def _r2o_full_backward(ctx, g_rgb, g_disp, g_acc, g_w, g_depth):
+    # every output of render.py:149-192 reaches raw, as in the reference's autograd (z and rays_d are not differentiated)
+    raw, z, rays11, noise, acc, depth = ctx.saved_tensors
+    if all(g is None for g in (g_rgb, g_disp, g_acc, g_w, g_depth)):
+        return None, None, None, None, None
+    draw = torch.ops.fastnerf.raw2outputs_bwd_full(raw, z, rays11, acc, depth, g_rgb, g_disp, g_acc, g_w, g_depth,
+                                                   noise if ctx.has_noise else None, ctx.white)
+    return draw, None, None, None, None
+
+
+raw2outputs_full.register_autograd(_r2o_full_backward, setup_context=_r2o_full_setup)
+
+
 @_lib_def('fastnerf::sample_pdf_merge', mutates_args=())
 def sample_pdf_merge(z: Tensor, weights: Tensor, Ni: int, det: bool, u: Optional[Tensor], seed: int) -> Tuple[Tensor, Tensor, Tensor]:
     return ops.sample_pdf_merge(z, weights, Ni, det=det, u=u, seed=seed)
@@ -160,5 +207,5 @@ def _(draw):
     return draw.new_empty((draw.numel() // 4,), dtype=torch.int32), draw.new_empty((2,), dtype=torch.int32)
 
 
-OPS = ['gen_rays_pixels', 'pack_rays', 'sample_coarse', 'posenc', 'mlp_fwd', 'raw2outputs', 'raw2outputs_bwd', 'sample_pdf_merge',
-       'mse_leafmax', 'adam_step', 'compact_live']
+OPS = ['gen_rays_pixels', 'pack_rays', 'sample_coarse', 'posenc', 'mlp_fwd', 'raw2outputs', 'raw2outputs_bwd', 'raw2outputs_full',
+       'raw2outputs_bwd_full', 'sample_pdf_merge', 'mse_leafmax', 'adam_step', 'compact_live']

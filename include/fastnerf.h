@@ -93,6 +93,14 @@ int fastnerf_raw2outputs_fwd(int64_t n, int S, const float* raw, const float* z,
 int fastnerf_raw2outputs_bwd(int64_t n, int S, const float* raw, const float* z, const float* rays11,
                              const float* noise, int white_bkgd, const float* g_rgb, float* draw,
                              fn_stream_t stream);
+/* d(rgb_map, disp, acc, weights, depth)/d(raw) (render.py:149-192, every output differentiable as in the
+ * reference's autograd): upstream g_rgb [n,3], g_disp [n], g_acc [n], g_w [n,S], g_depth [n], each NULL = zero.
+ * acc / depth: the forward's outputs (needed when g_disp != NULL: they decide the disparity clamp and its NaN
+ * branch).  -> draw [n,S,4].  With only g_rgb given, bit-identical to fastnerf_raw2outputs_bwd. */
+int fastnerf_raw2outputs_bwd_full(int64_t n, int S, const float* raw, const float* z, const float* rays11,
+                                  const float* noise, int white_bkgd, const float* acc, const float* depth,
+                                  const float* g_rgb, const float* g_disp, const float* g_acc, const float* g_w,
+                                  const float* g_depth, float* draw, fn_stream_t stream);
 /* sample_pdf (run_nerf_helpers.py:112-155) on bins = mid(z), weights[1:-1],
  * followed by sort(cat[z, z_samples]) (render.py:279-283).  u: [n,Ni] injected
  * uniforms or NULL; det!=0 -> linspace(0,1,Ni); else Philox(seed).
