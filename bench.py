@@ -15,7 +15,10 @@ with fp32 accumulation on v_mfma_f32_16x16x32_bf16 -- the dropped terms are <= 2
 against fp64 its logits / head-layer gradients are as close as the fp32-MFMA kernels' (tests/test_gpu_mlp.py::
 test_bf16x6_decomposition_is_exact_and_products_have_fp32_width, profiles/r03_precision_vs_fp64.md).
 
-Everything else rides in the same JSON line as named sibling blocks and never feeds `value`:
+A plain run does only what `value` needs: set-up, W warm-up and K timed steps, --dump-outputs if given, the headline line.  Everything
+else runs with --full only, rides in the same JSON line as named sibling blocks and never feeds `value`: the sustained leg, the roofline
+of the dominant launch, the stand-alone all-reduce timings (N>1), the strong-scaling leg that --scaling auto adds on several GPUs, and
+on one GPU:
   fp32_mfma_mode     the same protocol on v_mfma_f32_32x32x2_f32 (an fp32 FMA chain bit for bit; 157 TFLOP/s ceiling);
   split_bf16_mode    the same protocol in the split-bf16 mode (3 bf16 MFMA products per fp32 product, 16-bit operands: faster and
                      NARROWER than fp32, hence not the headline), plus that mode on a trained sparse scene with the exact
@@ -28,13 +31,13 @@ Everything else rides in the same JSON line as named sibling blocks and never fe
                      short CPU-oracle baseline at the same shape;
   inference          render()-style rays/s;   cpu_baseline   the CPU oracle timed on this box's host cores.
 
-  python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+  python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--full]
   N>1: either under the launcher (python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...) or BARE
   (python bench.py --gpus N ...): without WORLD_SIZE in the environment the script re-executes itself under that launcher.
 
 OUTPUT CONTRACT.  Rank 0 prints exactly ONE line on stdout, LAST: the headline record (headline_record(): <= 4 KB -- metric, value, unit,
-n_gpus, steps, warmup, ms_per_step, dtype, config, roofline, cpu_baseline, psnr, a few scalars of the siblings).  The full record with
-every sibling block is written to bench_full.json (--full-out; also copied under gpurun_out/ when that directory exists) BEFORE that
+n_gpus, steps, warmup, ms_per_step, dtype, config, roofline, cpu_baseline, psnr, a few scalars of the siblings; the blocks of --full are
+null in a plain run).  With --full the full record with every sibling block is written to bench_full.json (--full-out) BEFORE that
 line, never to stdout / stderr (a harness that keeps only a tail window of the combined output must still find the headline).
 The GPU legs import nothing from oracle/; only the CPU legs (cpu_baseline, psnr_vs_cpu.cpu) do.
 """
@@ -461,7 +464,10 @@ def main():
     ap.add_argument('--scaling', choices=['weak', 'strong', 'both', 'auto'], default='auto',
                     help='weak: 4096 rays per GPU per step (`value`); strong: 4096 rays per step split over the GPUs (`value`); both: `value` '
                          'is the weak number and the line also carries scaling_weak / scaling_strong blocks (one invocation, both curves); '
-                         'auto (default): weak on one GPU, both on several')
+                         'auto (default): weak, except both on several GPUs with --full')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, run every other leg as well: sustained steps, roofline, all-reduce timings (N>1), the sibling '
+                         'legs, PSNR vs the CPU oracle, CPU baselines; writes the full record to --full-out.  The options below shape these legs')
     ap.add_argument('--sustained-steps', type=int, default=150)
     ap.add_argument('--scene-steps', type=int, default=600, help='untimed optimisation steps of the sparse-scene sibling leg')
     ap.add_argument('--no-cpu-baseline', action='store_true', help='skip both CPU legs (cpu_baseline, psnr_vs_cpu.cpu)')
@@ -469,7 +475,7 @@ def main():
     ap.add_argument('--cpu-protocol', choices=['full', 'short'], default='full')
     ap.add_argument('--psnr-iters', type=int, default=PSNR_ITERS)
     ap.add_argument('--psnr-cpu-worker', nargs=2, metavar=('IN', 'OUT'), help=argparse.SUPPRESS)
-    ap.add_argument('--full-out', default=os.path.join(ROOT, 'bench_full.json'), help='where the full record (all sibling blocks) goes')
+    ap.add_argument('--full-out', default=os.path.join(ROOT, 'bench_full.json'), help='where --full writes the full record (all sibling blocks)')
     ap.add_argument('--dump-outputs', metavar='DIR', help='after the timed steps, write what the last one computed as DIR/<name>.npy: its '
                                                           'loss pair and render outputs, the parameters, gradient and Adam moments it left, '
                                                           'the leaf-error table (rank 0)')
@@ -489,14 +495,14 @@ def main():
     torch.cuda.set_device(local)
     dev = torch.device('cuda', local)
     if a.scaling == 'auto':
-        a.scaling = 'both' if world > 1 else 'weak'
+        a.scaling = 'both' if world > 1 and a.full else 'weak'
     both = a.scaling == 'both'
     # weak is the contract's default and the reference's own practice: nerf++-ours/ddp_train_nerf.py:201-202 quotes its rates at a FIXED
     # batch per GPU (1920 rays on 2 GPUs, 2880 on 3)
     n_local = N_RAYS // world if a.scaling == 'strong' else N_RAYS      # rays per rank per step (of the leg that is `value`)
     n_step = n_local * world                                          # rays per step, whole job
-    siblings = rank == 0 and world == 1 and not a.no_siblings
-    psnr_leg = rank == 0 and world == 1 and a.psnr_iters > 0
+    siblings = a.full and rank == 0 and world == 1 and not a.no_siblings
+    psnr_leg = a.full and rank == 0 and world == 1 and a.psnr_iters > 0
 
     args = fastnerf.run_nerf.make_args(N_importance=N_IMPORTANCE, N_samples=N_SAMPLES, perturb=1.0, white_bkgd=True,
                                        no_reload=True, lrate=5e-4, lrate_decay=500, N_rand=n_local)
@@ -750,6 +756,7 @@ def main():
         gathered = [torch.zeros_like(tl) for _ in range(world)]
         torch.distributed.all_gather(gathered, tl)
         per_rank_ms = [float(g[0]) for g in gathered]
+    if world > 1 and a.full:
         # the step's data-path collectives, timed alone: all-reduce(SUM) of each net's half of the flat gradient (2.38 MB each;
         # in the step the fine net's runs beside the coarse pass's backward)
         Nn = ops.NET_PARAMS
@@ -758,7 +765,7 @@ def main():
                         'whole_buffer': time_launch(lambda: parallel.all_reduce_sum(tr.grad), 20),
                         'overlapped_with_coarse_backward': bool(tr.overlap_allreduce)}
     sustained = None
-    if a.sustained_steps > 0:   # power-managed clocks settle within seconds: the same stream of steps for a few seconds more
+    if a.full and a.sustained_steps > 0:   # power-managed clocks settle within seconds: the same stream of steps for a few seconds more
         ts, _, _ = timed(lambda i: step(tr, i)[0], a.warmup + a.steps, 0, a.sustained_steps)
         sustained = leg(ts, a.sustained_steps, wall_seconds=ts)
     # ---- --scaling both: the OTHER curve in the same invocation (every rank takes part: the steps hold collectives) ------------------
@@ -782,7 +789,7 @@ def main():
         strong_blk = scaling_leg(max(1, N_RAYS // world))
         strong_blk['note'] = '4096 rays per step split over the ranks (BASELINE configs[1] as ONE job): value / (the N=1 value) is the strong-scaling factor'
         scaling_blocks = {'weak': weak_blk, 'strong': strong_blk}
-    roof = mlp_roofline(tr, MAIN_MODE) if rank == 0 else None
+    roof = mlp_roofline(tr, MAIN_MODE) if a.full and rank == 0 else None
     step_tflops = n_step * a.steps / dt * TRAIN_FLOP_PER_RAY / 1e12 / world
 
     # =====================================================================================================================
@@ -1029,7 +1036,7 @@ def main():
                 if isinstance(ls_, dict) and 'delta_db' in ls_:
                     psnr_head.update(lockstep_delta_db=ls_['delta_db'], lockstep_max_rel_loss_diff=ls_.get('max_rel_loss_diff'))
             psnr_head['paired_ensemble'] = PAIRED_PSNR_NOTE
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             cpu = guarded('cpu_baseline', lambda: cpu_baseline(a.cpu_protocol))
             if cpu is not None and cfg_blocks:
                 def cfg_cpu():
@@ -1104,7 +1111,7 @@ def main():
             'siblings_summary': summary,
             'errors': errors,
         }
-        out['full_record'] = write_full_record(out, a.full_out)
+        out['full_record'] = write_full_record(out, a.full_out) if a.full else None
         sys.stderr.flush()
         print(json.dumps(headline_record(out)), flush=True)      # the ONE stdout line, last
     if world > 1:

@@ -1,6 +1,6 @@
 """bench.py's output contract on the CPU (no GPU, no kernels): the headline line a harness parses from a TAIL WINDOW of the combined
-output must be short, complete and last; `--gpus N` without a launcher must re-execute under torch.distributed.run.  One GPU test runs
-the headline leg with --dump-outputs."""
+output must be short, complete and last; `--gpus N` without a launcher must re-execute under torch.distributed.run.  Two GPU tests run
+the headline leg: a plain run (nothing of --full in it), and one with --dump-outputs."""
 import json
 import os
 import sys
@@ -173,3 +173,28 @@ def test_dump_outputs_of_the_timed_path(tmp_path):
     assert got['loss2'].tolist() == j['final_loss']
     assert got['rgb_map'].shape == (B.N_RAYS, 3) and got['raw'].shape == (B.N_RAYS, B.S1, 4) and got['leaf_table'].shape == (100, 256)
     assert all(np.isfinite(x).all() for x in got.values()) and got['leaf_table'].max() > 0 and np.abs(got['grad']).max() > 0
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_alone(tmp_path):
+    """bench.py without --full: set-up, warm-up, the timed steps and the headline line.  None of the legs of --full leaves a trace in
+    the line, no full record is written, and the run spends well under a minute outside its steps (the CPU legs of --full alone take
+    minutes)."""
+    import subprocess
+    import time
+    full_out = tmp_path / 'full.json'
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '4', '--warmup', '2', '--full-out', str(full_out)]
+    t0 = time.perf_counter()
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert lines[-1].startswith('{"metric"') and sum(l.startswith('{') for l in lines) == 1
+    j = json.loads(lines[-1])
+    assert j['n_gpus'] == 1 and j['steps'] == 4 and j['warmup'] == 2 and j['scaling'] == 'weak' and j['dtype'] == 'f32'
+    assert abs(j['value'] - B.N_RAYS * 4 / (j['ms_per_step'] * 4e-3)) < 1e-6 * j['value']
+    for k in ('roofline', 'cpu_baseline', 'psnr', 'siblings', 'allreduce_ms', 'full_record', 'errors'):
+        assert j[k] is None, k
+    assert 'sustained_ms_per_step' not in j and 'scaling_weak' not in j and 'scaling_strong' not in j
+    assert not full_out.exists()
+    assert wall - 6 * j['ms_per_step'] * 1e-3 < 60.0, wall

@@ -20,7 +20,7 @@ def _run(backend, port, scaling, full_out, launcher=True):
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
     if backend:
         env['FASTNERF_DIST_BACKEND'] = backend
-    args = ['--gpus', '2', '--steps', '3', '--warmup', '1', '--sustained-steps', '5', '--scaling', scaling, '--full-out', full_out]
+    args = ['--gpus', '2', '--steps', '3', '--warmup', '1', '--full', '--sustained-steps', '5', '--scaling', scaling, '--full-out', full_out]
     if launcher:
         cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
                '--master-port', str(port), os.path.join(ROOT, 'bench.py')] + args
@@ -83,8 +83,9 @@ def test_bench_eight_ranks_on_what_the_box_has(scaling, tmp_path):
         env['FASTNERF_DIST_BACKEND'] = 'gloo'
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
         env.pop(k, None)
-    # 'both' is what the bare driver command gets (--scaling auto -> both on several GPUs): `value` is the weak leg, both curves' points ride along
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--steps', '2', '--warmup', '1', '--sustained-steps', '0',
+    # 'both' is what the bare driver command gets with --full (--scaling auto -> both on several GPUs): `value` is the weak leg, both curves'
+    # points ride along
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--steps', '2', '--warmup', '1', '--full', '--sustained-steps', '0',
            '--full-out', os.path.join(str(tmp_path), 'full.json')] + (['--scaling', scaling] if scaling != 'both' else [])
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]

@@ -11,7 +11,7 @@ R=${1:-r06}
 O=gpurun_out/prof_$R
 rm -rf $O; mkdir -p $O
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench -o bench -- \
-  python bench.py --steps 20 --warmup 5 --no-cpu-baseline --psnr-iters 0 < /dev/null > $O/bench.log 2>&1
+  python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --psnr-iters 0 < /dev/null > $O/bench.log 2>&1
 for mode in ${MODES:-bf16x6 fp32 bf16x3}; do
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/steps_$mode -o steps -- \
     python tools/prof_r03.py steps $mode 6 < /dev/null > $O/steps_$mode.log 2>&1

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Turns the rocprofv3 outputs of tools/collect_profiles.sh <round> (gpurun_out/prof_<round>) into the committed summaries of that round (python tools/summarize_prof.py r06):
 
-  profiles/<round>_bench_kernel_stats.csv              rocprofv3 --kernel-trace --stats of `python bench.py --steps 20 --warmup 5 --no-cpu-baseline --psnr-iters 0`
+  profiles/<round>_bench_kernel_stats.csv              rocprofv3 --kernel-trace --stats of `python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --psnr-iters 0`
   profiles/<round>_steps_<mode>_kernel_stats.csv       ... of 3 + 6 optimisation steps of the headline protocol in math mode <mode> (tools/prof_r03.py)
   profiles/<round>_pmc_traffic.json                    HBM bytes per launch of the MLP kernels and per optimisation step, per math mode, from the
                                                    PMC passes (FETCH_SIZE and WRITE_SIZE in separate runs, kernel-trace only; counters are in KB;
@@ -110,7 +110,7 @@ def main():
     md = ['# Round %s rocprofv3 summary (MI355X, 1 GPU)' % RND[1:].lstrip('0'), '',
           'Collected by `tools/collect_profiles.sh %s` (through gpurun), summarised by `tools/summarize_prof.py %s`.' % (RND, RND), '',
           '## bench.py under the profiler', '',
-          '`rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --psnr-iters 0`', '',
+          '`rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --psnr-iters 0`', '',
           'bench line of that run (`profiles/%s_bench_line_under_rocprof.json`)' % RND + ': **%.0f rays/s, %.2f ms/step** '
           'in the headline mode (%s); sibling legs of the same process, ms per step: %s; bf16x6 on the trained sparse scene, compacted backward: %s.' % (
               j['value'], j['ms_per_step'], j['config']['math_mode'], json.dumps((j.get('siblings') or {}).get('ms_per_step')),
