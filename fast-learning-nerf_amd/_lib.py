@@ -121,6 +121,12 @@ SIGNATURES = {
     'fastnerf_allreduce_leaf_sumcount': (I, [P, P, P, L, P]),
     'fastnerf_leaf_table_reset': (I, [P, L, P]),
     'fastnerf_leaf_table_read': (I, [P, P, L, P]),
+    'fastnerf_grid_points': (I, [L, L, P, L, P, L, P, L, P, P]),
+    'fastnerf_grid_sigma': (I, [L, P, P, P]),
+    'fastnerf_mc_ws_bytes': (L, [L, L, L]),
+    'fastnerf_mc_count': (I, [P, L, L, L, F, P, P, P]),
+    'fastnerf_mc_emit': (I, [P, L, L, L, F, P, P, P, P]),
+    'fastnerf_mc_tables': (I, [P, P]),
 }
 
 _lib = None

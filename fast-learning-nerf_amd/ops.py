@@ -632,3 +632,45 @@ def pp_gen_rays(H, W, intrinsics, c2w, device='cuda'):
     check(lib().fastnerf_pp_gen_rays(int(H), int(W), K.ctypes.data, M.ctypes.data, ptr(ro), ptr(rd), stream()),
           'fastnerf_pp_gen_rays')
     return ro, rd
+
+
+MC_TRI_STRIDE = 16   # FASTNERF_MC_TRI_STRIDE
+
+
+def grid_points(p0, xs, ys, zs, rays11):
+    """Rows p0 .. p0 + len(rays11) - 1 of the (xs, ys, zs) point grid (meshgrid 'ij' order) as rays11 rows o = point, rest 0."""
+    require_gpu(xs, ys, zs, rays11)
+    check(lib().fastnerf_grid_points(int(p0), rays11.shape[0], ptr(xs), xs.numel(), ptr(ys), ys.numel(), ptr(zs), zs.numel(),
+                                     ptr(rays11), stream()), 'fastnerf_grid_points')
+
+
+def grid_sigma(raw, out):
+    """out[q] = relu(raw[q, .., 3]) for the len(out) rows of an MLP output [n, 1, 4]."""
+    require_gpu(raw, out)
+    assert raw.numel() == 4 * out.numel()
+    check(lib().fastnerf_grid_sigma(out.numel(), ptr(raw), ptr(out), stream()), 'fastnerf_grid_sigma')
+
+
+def mc_tables():
+    """(tri [256, MC_TRI_STRIDE] int8, edge [256] uint16): the marching-cubes tables the kernels use (host call, no GPU)."""
+    tri = np.zeros((256, MC_TRI_STRIDE), np.int8)
+    edge = np.zeros(256, np.uint16)
+    check(lib().fastnerf_mc_tables(tri.ctypes.data, edge.ctypes.data), 'fastnerf_mc_tables')
+    return tri, edge
+
+
+def marching_cubes(vol, threshold):
+    """vol: contiguous float32 [nx, ny, nz] cuda tensor -> (verts [V, 3] float32, tris [T, 3] int32), the contract of
+    include/fastnerf.h.  One host synchronisation (the counts)."""
+    require_gpu(vol)
+    nx, ny, nz = vol.shape
+    ws = torch.empty(int(check(lib().fastnerf_mc_ws_bytes(nx, ny, nz), 'fastnerf_mc_ws_bytes')), device=vol.device, dtype=torch.uint8)
+    counts = np.zeros(2, np.int64)
+    check(lib().fastnerf_mc_count(ptr(vol), nx, ny, nz, float(threshold), ptr(ws), counts.ctypes.data, stream()), 'fastnerf_mc_count')
+    V, T = int(counts[0]), int(counts[1])
+    verts = torch.empty(V, 3, device=vol.device, dtype=torch.float32)
+    tris = torch.empty(T, 3, device=vol.device, dtype=torch.int32)
+    if V > 0:
+        check(lib().fastnerf_mc_emit(ptr(vol), nx, ny, nz, float(threshold), ptr(ws), ptr(verts), ptr(tris), stream()),
+              'fastnerf_mc_emit')
+    return verts, tris

@@ -431,6 +431,34 @@ int fastnerf_allreduce_leaf_sumcount(fn_comm* comm, double* sum, int32_t* count,
 int fastnerf_leaf_table_reset(uint32_t* table, int64_t n, fn_stream_t stream);
 int fastnerf_leaf_table_read(const uint32_t* table, float* host_out, int64_t n, fn_stream_t stream);
 
+/* ---- mesh extraction (extract_mesh.py:38-74: dense density query + mcubes.marching_cubes) ------------------------------
+ * fastnerf_grid_points: rows p0 .. p0+n-1 of the point grid (xs[i], ys[j], zs[k]), p = (i*ny + j)*nz + k (torch.meshgrid
+ * 'ij' order), written as rays11 [n,11] with o = the point and everything else 0 -- what run_network builds for explicit
+ * points, so fastnerf_mlp_*_fwd with z = 0 evaluates the network there.  fastnerf_grid_sigma: out[q] = relu(raw[q*4+3]).
+ * Marching cubes over vol [nx,ny,nz] float32 (C order, every dimension >= 2, finite values), inside = value > thr:
+ *   vertices  one per grid edge whose endpoints lie on different sides, ordered by the lower endpoint's linear index, then
+ *             axis i, j, k; position in index coordinates = lower endpoint + t along the edge's axis,
+ *             t = (thr - v_a) / (v_b - v_a) in fp32 (the other two coordinates are exact integers).  float verts [V,3].
+ *   triangles int32 tris [T,3] of vertex indices, ordered by cell ((nx-1)(ny-1)(nz-1) cells, C order), then table order;
+ *             (v1-v0) x (v2-v0) points from inside to outside.  The table (fastnerf_mc_tables) closes every mesh: ambiguous
+ *             faces separate the inside corners.
+ * Protocol: ws = fastnerf_mc_ws_bytes(nx, ny, nz) bytes of device memory; fastnerf_mc_count writes counts_host[0] = V,
+ * counts_host[1] = T and, an exception to the convention above, SYNCHRONISES (it waits for `stream`); it returns -1 when V or T
+ * exceeds 2^31-1.  fastnerf_mc_emit, with the same vol / thr / ws and nothing in between, fills verts and tris.  No
+ * atomics: the output is bit-identical from run to run.
+ * fastnerf_mc_tables: tri_host [256*FASTNERF_MC_TRI_STRIDE] int8 (edge triples, -1 terminated), edge_host [256] uint16
+ * (crossing-edge mask per case); host only. */
+#define FASTNERF_MC_TRI_STRIDE 16
+int fastnerf_grid_points(int64_t p0, int64_t n, const float* xs, int64_t nx, const float* ys, int64_t ny, const float* zs,
+                         int64_t nz, float* rays11, fn_stream_t stream);
+int fastnerf_grid_sigma(int64_t n, const float* raw, float* out, fn_stream_t stream);
+int64_t fastnerf_mc_ws_bytes(int64_t nx, int64_t ny, int64_t nz);
+int fastnerf_mc_count(const float* vol, int64_t nx, int64_t ny, int64_t nz, float thr, void* ws, int64_t* counts_host,
+                      fn_stream_t stream);
+int fastnerf_mc_emit(const float* vol, int64_t nx, int64_t ny, int64_t nz, float thr, void* ws, float* verts, int32_t* tris,
+                     fn_stream_t stream);
+int fastnerf_mc_tables(int8_t* tri_host, uint16_t* edge_host);
+
 #ifdef __cplusplus
 }
 #endif
