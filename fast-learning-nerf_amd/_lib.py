@@ -34,6 +34,11 @@ class StepArgs(C.Structure):
                             'fwd_flags', 'max_leaves', 'adam_t')])
 
 
+class OccGrid(C.Structure):
+    """fn_occ_grid of include/fastnerf.h, field for field."""
+    _fields_ = [('words', P), ('lo', F * 3), ('inv', F * 3), ('n', C.c_int32 * 3), ('outside_occupied', C.c_int32)]
+
+
 STEP_FORWARD, STEP_BWD_FINE, STEP_BWD_COARSE, STEP_UPDATE = 1, 2, 4, 8
 
 # name -> (restype, argtypes); mirrors include/fastnerf.h one to one
@@ -127,6 +132,15 @@ SIGNATURES = {
     'fastnerf_mc_count': (I, [P, L, L, L, F, P, P, P]),
     'fastnerf_mc_emit': (I, [P, L, L, L, F, P, P, P, P]),
     'fastnerf_mc_tables': (I, [P, P]),
+    'fastnerf_occ_words': (L, [L, L, L]),
+    'fastnerf_occ_build': (I, [P, L, L, L, F, I, P, P, P]),
+    'fastnerf_occ_from_mask': (I, [P, L, L, L, P, P]),
+    'fastnerf_occ_query': (I, [C.POINTER(OccGrid), L, P, P, P]),
+    'fastnerf_occ_classify': (I, [C.POINTER(OccGrid), L, I, P, P, P, P, P, P, P]),
+    'fastnerf_mlp_fwd_list_ex': (I, [I, L, I, P, P, P, P, P, P, P, I, P]),
+    'fastnerf_mlp_bf16_fwd_list': (I, [I, L, I, P, P, P, P, P, P, P, I, P]),
+    'fastnerf_mlp_x6_fwd_list': (I, [I, L, I, P, P, P, P, P, P, P, I, P]),
+    'fastnerf_render_rays_fwd_occ': (I, [I, L, I, I, P, I, I, I, I, P, P, U64, U64, P, P, P, P, C.POINTER(OccGrid), P, P] + [P] * 16 + [I, P]),
 }
 
 _lib = None

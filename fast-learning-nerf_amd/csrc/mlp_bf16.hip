@@ -570,7 +570,9 @@ __device__ __forceinline__ void b_bg_point(const float* __restrict__ o, const fl
 // BG == true : nerf++ background net: inverted-sphere points (4-D), samples consumed far -> near
 //              (ddp_model.py:118-124), 84 channels = 64 in E + 20 (padded to 32) in the X2 block that borrows the
 //              top 8 KiB of Hhi while H is free (layer 0) or after layer 5 has consumed h4 (re-encoded from registers).
-template <bool SAVE, bool BG>
+// LIST (SAVE == false, BG == false): the live-list mode without saving, row j's logits go to raw[live_idx[j]] (occupancy.hip);
+// a separate instantiation: the others come out instruction-identical.
+template <bool SAVE, bool BG, bool LIST = false>
 __global__ void __launch_bounds__(BNTHR, 2)
 mlp_fwd_bf16_kernel(int64_t P, int S, const float* __restrict__ rays, const float* __restrict__ zv,
                     const float* __restrict__ params, const uint4* __restrict__ pk, float* __restrict__ raw,
@@ -792,7 +794,7 @@ mlp_fwd_bf16_kernel(int64_t P, int S, const float* __restrict__ rays, const floa
       skip_tail = (slot[0] | slot[1] | slot[2] | slot[3]) == 0;
     }
     if (skip_tail) {
-      if (pq == 0 && pm < valid && raw) *reinterpret_cast<float4*>(raw + (p0 + pm) * 4) = make_float4(0.f, 0.f, 0.f, alpha_val);
+      if (pq == 0 && pm < valid && raw) *reinterpret_cast<float4*>(raw + (LIST ? pp : p0 + pm) * 4) = make_float4(0.f, 0.f, 0.f, alpha_val);
     } else {
     // feature layer (no ReLU)
     ea.bias = params + lay.FB;
@@ -844,7 +846,7 @@ mlp_fwd_bf16_kernel(int64_t P, int S, const float* __restrict__ rays, const floa
       if (pq == 0 && pm < valid && raw) {
         float4 o;
         o.x = s0 + params[lay.RB]; o.y = s1 + params[lay.RB + 1]; o.z = s2 + params[lay.RB + 2]; o.w = alpha_val;
-        *reinterpret_cast<float4*>(raw + (p0 + pm) * 4) = o;
+        *reinterpret_cast<float4*>(raw + (LIST ? pp : p0 + pm) * 4) = o;
       }
     }
     }   // !skip_tail
@@ -872,6 +874,8 @@ static int b_fwd_launch(int kind, int64_t n, int S, const float* rays11, const f
                                hipFuncAttributeMaxDynamicSharedMemorySize, BLDS_BYTES));
     FN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fwd_bf16_kernel<true, true>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, BLDS_BYTES));
+    FN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fwd_bf16_kernel<false, false, true>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, BLDS_BYTES));
     attr_done = true;
   }
   const uint4* pk = reinterpret_cast<const uint4*>(packed_fwd);
@@ -880,7 +884,9 @@ static int b_fwd_launch(int kind, int64_t n, int S, const float* rays11, const f
   hipStream_t st = fn::S(stream);
   unsigned* sched = b_sched_pair();
   FN_CHECK_ARG(sched != nullptr, "scheduler counters (hipMalloc failed?)");
-  if (kind == 2) {
+  if (live_idx && !act) {   // the list form without saving (kind 0 only: the entry point checks)
+    hipLaunchKernelGGL((mlp_fwd_bf16_kernel<false, false, true>), g, b, BLDS_BYTES, st, P, S, rays11, z, params, pk, raw, a4, lay, O, sched, live_idx, live_cnt, flags);
+  } else if (kind == 2) {
     if (act) hipLaunchKernelGGL((mlp_fwd_bf16_kernel<true, true>), g, b, BLDS_BYTES, st, P, S, rays11, z, params, pk, raw, a4, lay, O, sched, live_idx, live_cnt, 0);
     else hipLaunchKernelGGL((mlp_fwd_bf16_kernel<false, true>), g, b, BLDS_BYTES, st, P, S, rays11, z, params, pk, raw, a4, lay, O, sched, live_idx, live_cnt, 0);
   } else {
@@ -909,6 +915,16 @@ extern "C" int fastnerf_mlp_bf16_fwd_flags(int kind, int64_t n, int S, const flo
   FN_CHECK_ARG(n == 0 || (rays11 && z && params && packed_fwd && raw), "null pointer");
   if (n == 0) return 0;
   return b_fwd_launch(kind, n, S, rays11, z, params, packed_fwd, raw, nullptr, nullptr, nullptr, stream, flags);
+}
+
+// Inference over a point list (see fastnerf.h): logits of the points live_idx[0 .. *live_cnt) -> raw[live_idx[j]], nothing saved.
+extern "C" int fastnerf_mlp_bf16_fwd_list(int kind, int64_t n, int S, const float* rays11, const float* z, const float* params,
+                                          const float* packed_fwd, float* raw, const int32_t* live_idx, const int32_t* live_cnt,
+                                          int flags, fn_stream_t stream) {
+  FN_CHECK_ARG(kind == 0 && n > 0 && S >= 1, "kind == 0, n>0, S>=1");
+  FN_CHECK_ARG(rays11 && z && params && packed_fwd && raw && live_idx && live_cnt, "null pointer");
+  FN_CHECK_ARG(n * (int64_t)S < ((int64_t)1 << 31), "lists index points with int32");
+  return b_fwd_launch(kind, n, S, rays11, z, params, packed_fwd, raw, nullptr, live_idx, live_cnt, stream, flags);
 }
 
 // Training forward over a live-point list (see fastnerf.h): activations of the points live_idx[0 .. *live_cnt) are saved

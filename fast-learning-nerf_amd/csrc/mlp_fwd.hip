@@ -46,7 +46,9 @@ __device__ __forceinline__ int x2idx(int m, int k) { return m * 32 + ((((k >> 2)
 //              borrows the first 8 KiB of H while H is free (L0) or after it has been consumed (L5).
 #define FN_SIN(a) (ABL_NOPE ? (a) : sinf(a))
 #define FN_COS(a) (ABL_NOPE ? (a) : cosf(a))
-template <bool SAVE, bool BG, int MM = MM_F32>
+// LIST (inference over a point list, SAVE == false, BG == false): as the live-list mode below, but nothing is saved and row j's
+// logits go to raw[live_idx[j]] -- the occupancy-grid render (occupancy.hip); a separate instantiation: the others come out instruction-identical.
+template <bool SAVE, bool BG, int MM = MM_F32, bool LIST = false>
 __global__ void __launch_bounds__(NTHR, 2 * NTHR / 512 * WG_PER_CU)
 mlp_fwd_kernel(int64_t P, int S, const float* __restrict__ rays, const float* __restrict__ zv,
                const float* __restrict__ params, const float* __restrict__ packed, float* __restrict__ raw,
@@ -227,7 +229,7 @@ mlp_fwd_kernel(int64_t P, int S, const float* __restrict__ rays, const float* __
       skip_tail = any == 0;
     }
     if (skip_tail) {
-      if (pq == 0 && pm < valid && raw) *reinterpret_cast<float4*>(raw + (p0 + pm) * 4) = make_float4(0.f, 0.f, 0.f, alpha_val);
+      if (pq == 0 && pm < valid && raw) *reinterpret_cast<float4*>(raw + (LIST ? pp : p0 + pm) * 4) = make_float4(0.f, 0.f, 0.f, alpha_val);
     } else {
     // ---- feature layer (no ReLU) ------------------------------------------------------
     load_bias<2>(bv2, params + lay.FB, wn, lane);
@@ -287,7 +289,7 @@ mlp_fwd_kernel(int64_t P, int S, const float* __restrict__ rays, const float* __
       if (pq == 0 && pm < valid && raw) {
         float4 o;
         o.x = s0 + params[lay.RB]; o.y = s1 + params[lay.RB + 1]; o.z = s2 + params[lay.RB + 2]; o.w = alpha_val;
-        *reinterpret_cast<float4*>(raw + (p0 + pm) * 4) = o;
+        *reinterpret_cast<float4*>(raw + (LIST ? pp : p0 + pm) * 4) = o;
       }
     }
     }   // !skip_tail
@@ -296,11 +298,11 @@ mlp_fwd_kernel(int64_t P, int S, const float* __restrict__ rays, const float* __
   b_sched_exit(sched, tid);
 }
 
-template <bool SAVE, bool BG, int MM>
+template <bool SAVE, bool BG, int MM, bool LIST = false>
 static int fwd_launch_t(int grid, hipStream_t st, int64_t P, int S, const float* rays11, const float* z, const float* params,
                         const float* packed_fwd, float* raw, float* act, const NetLayout& lay, unsigned* sched, const int* live_idx,
                         const int* live_cnt, int flags) {
-  auto kern = mlp_fwd_kernel<SAVE, BG, MM>;
+  auto kern = mlp_fwd_kernel<SAVE, BG, MM, LIST>;
   static bool attr = false;
   if (!attr) {
     FN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
@@ -323,7 +325,10 @@ static int fwd_launch(int kind, int64_t n, int S, const float* rays11, const flo
   hipStream_t st = fn::S(stream);
   unsigned* sched = b_sched_pair();
   FN_CHECK_ARG(sched != nullptr, "scheduler counters (hipMalloc failed?)");
-  const int fl = (kind == 0 && !live_idx && !act) ? flags : 0;
+  const int fl = (kind == 0 && !act && (!live_idx || raw)) ? flags : 0;
+  if (live_idx && !act)   // the list form without saving: logits scattered to raw[live_idx[j]]
+    return mm == MM_X6 ? fwd_launch_t<false, false, MM_X6, true>(grid, st, P, S, rays11, z, params, packed_fwd, raw, nullptr, lay, sched, live_idx, live_cnt, fl)
+                       : fwd_launch_t<false, false, MM_F32, true>(grid, st, P, S, rays11, z, params, packed_fwd, raw, nullptr, lay, sched, live_idx, live_cnt, fl);
 #define FN_FWD(SAVE_, BG_, MM_) \
   fwd_launch_t<SAVE_, BG_, MM_>(grid, st, P, S, rays11, z, params, packed_fwd, raw, act, lay, sched, live_idx, live_cnt, fl)
   if (mm == MM_X6) {
@@ -380,4 +385,23 @@ extern "C" int fastnerf_mlp_x6_fwd_live(int kind, int64_t n, int S, const float*
   FN_CHECK_ARG(rays11 && z && params && packed_fwd && act && live_idx && live_cnt, "null pointer");
   FN_CHECK_ARG(n * (int64_t)S < ((int64_t)1 << 31), "live lists index points with int32");
   return fwd_launch(kind, n, S, rays11, z, params, packed_fwd, nullptr, act, live_idx, live_cnt, stream, 0, MM_X6);
+}
+
+// Inference over a point list (see fastnerf.h): logits of the points live_idx[0 .. *live_cnt) -> raw[live_idx[j]], nothing saved,
+// nothing else written.  flags as fastnerf_mlp_fwd_flags_ex (a tile here is 64 consecutive list entries).
+extern "C" int fastnerf_mlp_fwd_list_ex(int kind, int64_t n, int S, const float* rays11, const float* z, const float* params,
+                                        const float* packed_fwd, float* raw, const int32_t* live_idx, const int32_t* live_cnt,
+                                        int flags, fn_stream_t stream) {
+  FN_CHECK_ARG(kind == 0 && n > 0 && S >= 1, "kind == 0, n>0, S>=1");
+  FN_CHECK_ARG(rays11 && z && params && packed_fwd && raw && live_idx && live_cnt, "null pointer");
+  FN_CHECK_ARG(n * (int64_t)S < ((int64_t)1 << 31), "lists index points with int32");
+  return fwd_launch(kind, n, S, rays11, z, params, packed_fwd, raw, nullptr, live_idx, live_cnt, stream, flags);
+}
+extern "C" int fastnerf_mlp_x6_fwd_list(int kind, int64_t n, int S, const float* rays11, const float* z, const float* params,
+                                        const float* packed_fwd, float* raw, const int32_t* live_idx, const int32_t* live_cnt,
+                                        int flags, fn_stream_t stream) {
+  FN_CHECK_ARG(kind == 0 && n > 0 && S >= 1, "kind == 0, n>0, S>=1");
+  FN_CHECK_ARG(rays11 && z && params && packed_fwd && raw && live_idx && live_cnt, "null pointer");
+  FN_CHECK_ARG(n * (int64_t)S < ((int64_t)1 << 31), "lists index points with int32");
+  return fwd_launch(kind, n, S, rays11, z, params, packed_fwd, raw, nullptr, live_idx, live_cnt, stream, flags, MM_X6);
 }

@@ -1,0 +1,260 @@
+// occupancy.hip -- the occupancy grid of the inference path (include/fastnerf.h, "occupancy grid"): one bit per cell of a box
+// [lo, hi) cut into nx x ny x nz cells, and the kernels that build it, look points up in it and sort the samples of a render
+// pass by it, for gfx950.
+//
+// Bit layout (opaque to callers): cell (i, j, k) has the linear index c = (i * ny + j) * nz + k, bit c & 31 of word c >> 5.
+// 256^3 cells are 2 MiB: the whole grid stays in an XCD's L2 while a pass is classified.
+//
+// The cell of a point x along one axis is floor((x - lo) * inv) with the subtraction and the product each rounded to fp32
+// (fsub / fmul: no contraction), inv = n / (hi - lo) rounded once on the host.  An index outside 0 .. n-1 on any axis -- which
+// is where every non-finite coordinate ends up, a NaN failing both comparisons -- takes the grid's `outside_occupied`.
+//
+// Kernels
+//   occ_pack_kernel      cell predicate -> packed words, 64 cells per wave through one ballot.  Predicate: any of the cell's 8
+//                        corner values of a point volume [nx+1, ny+1, nz+1] is > threshold (= their maximum is, for a volume
+//                        without NaNs), or a byte mask [nx, ny, nz].
+//   occ_dilate_kernel    OR over +-d cells along ONE axis; three launches (k, j, i) give the Chebyshev ball, clipped at the box
+//   occ_query_kernel     [n, 3] points -> one byte each
+//   occ_count / scatter  the samples o + d * z of a pass: per-block counts -> (the scan of train.hip) -> ascending list of the
+//                        occupied sample indices; the others get raw = (0, 0, 0, 0).  The shape of fastnerf_compact_live with
+//                        another predicate: deterministic, no atomics, the list length stays on the device.
+// All of them are memory bound and small next to the MLP they spare: one lane per cell / point / four consecutive samples, a
+// ray's 44 bytes come through the cache for all its samples.
+#include "common.h"
+
+namespace fn {
+void cp_scan_launch(int nb, int32_t* blk, int32_t* count_out, int n_points, hipStream_t st);   // train.hip
+}
+
+#define OCC_BLOCK 256
+#define OCC_PTS 1024   // samples per block of the classify passes (256 threads x 4) = CP_PTS of train.hip, whose scan and
+                       // fastnerf_compact_ws_ints this file reuses
+
+namespace {
+
+struct OccDev {
+  const uint32_t* words;
+  float lo[3], inv[3];
+  int n[3];
+  int outside;
+};
+
+struct OccDims {
+  int nx, ny, nz;
+  int64_t ncells, nwords;
+};
+
+__device__ __forceinline__ bool occ_bit(const uint32_t* __restrict__ words, uint32_t c) { return (words[c >> 5] >> (c & 31u)) & 1u; }
+
+__device__ __forceinline__ bool occ_point(const OccDev& g, float x, float y, float z) {
+  const float fi = floorf(fmul(fsub(x, g.lo[0]), g.inv[0]));
+  const float fj = floorf(fmul(fsub(y, g.lo[1]), g.inv[1]));
+  const float fk = floorf(fmul(fsub(z, g.lo[2]), g.inv[2]));
+  const bool inside = fi >= 0.f && fi < (float)g.n[0] && fj >= 0.f && fj < (float)g.n[1] && fk >= 0.f && fk < (float)g.n[2];
+  if (!inside) return g.outside != 0;
+  return occ_bit(g.words, ((uint32_t)fi * (uint32_t)g.n[1] + (uint32_t)fj) * (uint32_t)g.n[2] + (uint32_t)fk);
+}
+
+// the block's 256 predicate bits -> 8 words; every thread of the block calls it (c is the thread's cell, b false beyond the grid)
+__device__ __forceinline__ void occ_store_bits(bool b, int64_t c, uint32_t* __restrict__ words, int64_t nwords) {
+  const unsigned long long m = __ballot(b);
+  const int lane = threadIdx.x & 63;
+  const int64_t w = c >> 5;   // lanes 0 and 32 sit on word boundaries: a block starts at a multiple of 256 cells
+  if (lane == 0 && w < nwords) words[w] = (uint32_t)m;
+  if (lane == 32 && w < nwords) words[w] = (uint32_t)(m >> 32);
+}
+
+__device__ __forceinline__ void occ_ijk(int64_t c, const OccDims& d, int& i, int& j, int& k) {
+  const uint32_t q = (uint32_t)c, r = q / (uint32_t)d.nz;   // ncells < 2^31
+  k = (int)(q - r * (uint32_t)d.nz);
+  i = (int)(r / (uint32_t)d.ny);
+  j = (int)(r - (uint32_t)i * (uint32_t)d.ny);
+}
+
+template <bool FROM_MASK>
+__global__ void __launch_bounds__(OCC_BLOCK) occ_pack_kernel(const float* __restrict__ vol, const uint8_t* __restrict__ mask, OccDims d,
+                                                             float thr, uint32_t* __restrict__ words) {
+  const int64_t c = (int64_t)blockIdx.x * OCC_BLOCK + threadIdx.x;
+  bool b = false;
+  if (c < d.ncells) {
+    if (FROM_MASK) {
+      b = mask[c] != 0;
+    } else {
+      int i, j, k;
+      occ_ijk(c, d, i, j, k);
+      const int64_t sy = d.nz + 1, sx = (int64_t)(d.ny + 1) * (d.nz + 1);
+      const float* p = vol + i * sx + j * sy + k;
+      b = (p[0] > thr) | (p[1] > thr) | (p[sy] > thr) | (p[sy + 1] > thr) | (p[sx] > thr) | (p[sx + 1] > thr) |
+          (p[sx + sy] > thr) | (p[sx + sy + 1] > thr);
+    }
+  }
+  occ_store_bits(b, c, words, d.nwords);
+}
+
+__global__ void __launch_bounds__(OCC_BLOCK) occ_dilate_kernel(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, OccDims d,
+                                                               int axis, int r) {
+  const int64_t c = (int64_t)blockIdx.x * OCC_BLOCK + threadIdx.x;
+  bool b = false;
+  if (c < d.ncells) {
+    int ijk[3];
+    occ_ijk(c, d, ijk[0], ijk[1], ijk[2]);
+    const int len = axis == 0 ? d.nx : (axis == 1 ? d.ny : d.nz);
+    const int64_t stride = axis == 0 ? (int64_t)d.ny * d.nz : (axis == 1 ? d.nz : 1);
+    const int pos = ijk[axis];
+    const int a = pos - r < 0 ? 0 : pos - r, e = pos + r > len - 1 ? len - 1 : pos + r;
+    for (int q = a; q <= e && !b; ++q) b = occ_bit(src, (uint32_t)(c + (q - pos) * stride));
+  }
+  occ_store_bits(b, c, dst, d.nwords);
+}
+
+__global__ void __launch_bounds__(OCC_BLOCK) occ_query_kernel(OccDev g, int64_t n, const float* __restrict__ pts, uint8_t* __restrict__ out) {
+  for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n; q += (int64_t)gridDim.x * blockDim.x)
+    out[q] = occ_point(g, pts[q * 3], pts[q * 3 + 1], pts[q * 3 + 2]) ? 1 : 0;
+}
+
+// bits 0..3: samples p0 .. p0+3 of the pass are occupied (x = o + d * z as the MLP kernels compute it)
+__device__ __forceinline__ unsigned occ_flags(const OccDev& g, const float* __restrict__ rays, const float* __restrict__ zv, uint32_t S,
+                                              int64_t p0, int64_t n) {
+  unsigned f = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int64_t p = p0 + k;
+    if (p < n) {
+      const float* rr = rays + (int64_t)((uint32_t)p / S) * 11;   // n < 2^31
+      const float zz = zv[p];
+      if (occ_point(g, fadd(rr[0], fmul(rr[3], zz)), fadd(rr[1], fmul(rr[4], zz)), fadd(rr[2], fmul(rr[5], zz)))) f |= 1u << k;
+    }
+  }
+  return f;
+}
+
+__global__ void __launch_bounds__(OCC_BLOCK) occ_count_kernel(OccDev g, int64_t n, int S, const float* __restrict__ rays,
+                                                              const float* __restrict__ zv, int* __restrict__ blk) {
+  __shared__ int red[4];
+  const unsigned f = occ_flags(g, rays, zv, (uint32_t)S, (int64_t)blockIdx.x * OCC_PTS + threadIdx.x * 4, n);
+  int c = __popc(f);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) blk[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+
+__global__ void __launch_bounds__(OCC_BLOCK) occ_scatter_kernel(OccDev g, int64_t n, int S, const float* __restrict__ rays,
+                                                                const float* __restrict__ zv, const int* __restrict__ blk,
+                                                                int* __restrict__ live_idx, float* __restrict__ raw) {
+  __shared__ int wsum[4];
+  const int64_t p0 = (int64_t)blockIdx.x * OCC_PTS + threadIdx.x * 4;
+  const unsigned f = occ_flags(g, rays, zv, (uint32_t)S, p0, n);
+  const int c = __popc(f);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int x = c;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(x, o, 64); if (lane >= o) x += t; }
+  if (lane == 63) wsum[w] = x;
+  __syncthreads();
+  int pos = blk[blockIdx.x] + x - c;
+  for (int k = 0; k < w; ++k) pos += wsum[k];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (f & (1u << k)) live_idx[pos++] = (int)(p0 + k);
+    else if (raw && p0 + k < n) *reinterpret_cast<float4*>(raw + (p0 + k) * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------
+bool occ_dims(int64_t nx, int64_t ny, int64_t nz, OccDims* d) {
+  if (nx < 1 || ny < 1 || nz < 1 || nx > (1 << 24) || ny > (1 << 24) || nz > (1 << 24)) return false;
+  if (nx > (((int64_t)1 << 31) - 1) / ny / nz) return false;
+  d->nx = (int)nx;
+  d->ny = (int)ny;
+  d->nz = (int)nz;
+  d->ncells = nx * ny * nz;
+  d->nwords = (d->ncells + 31) / 32;
+  return true;
+}
+
+bool occ_dev(const fn_occ_grid* g, OccDev* o) {
+  OccDims d;
+  if (!g || !g->words || !occ_dims(g->n[0], g->n[1], g->n[2], &d)) return false;
+  o->words = g->words;
+  for (int c = 0; c < 3; ++c) {
+    if (!(g->inv[c] > 0.f) || !(g->inv[c] <= 3.0e38f) || !(g->lo[c] == g->lo[c])) return false;
+    o->lo[c] = g->lo[c];
+    o->inv[c] = g->inv[c];
+    o->n[c] = g->n[c];
+  }
+  o->outside = g->outside_occupied ? 1 : 0;
+  return true;
+}
+
+inline unsigned occ_blocks(int64_t ncells) { return (unsigned)((ncells + OCC_BLOCK - 1) / OCC_BLOCK); }
+
+}  // namespace
+
+extern "C" int64_t fastnerf_occ_words(int64_t nx, int64_t ny, int64_t nz) {
+  OccDims d;
+  if (!occ_dims(nx, ny, nz, &d)) {
+    fn::set_error("fastnerf_occ_words: bad argument: 1 <= nx, ny, nz <= 2^24 cells, fewer than 2^31 in all");
+    return -1;
+  }
+  return d.nwords;
+}
+
+extern "C" int fastnerf_occ_build(const float* vol, int64_t nx, int64_t ny, int64_t nz, float threshold, int dilate, uint32_t* words,
+                                  uint32_t* ws, fn_stream_t stream) {
+  OccDims d;
+  FN_CHECK_ARG(occ_dims(nx, ny, nz, &d), "1 <= nx, ny, nz <= 2^24 cells, fewer than 2^31 in all");
+  FN_CHECK_ARG(vol && words && dilate >= 0 && (dilate == 0 || ws), "non-null vol / words, dilate >= 0, ws when dilate > 0");
+  FN_CHECK_ARG(threshold == threshold, "threshold is a NaN");
+  hipStream_t s = fn::S(stream);
+  const dim3 g(occ_blocks(d.ncells)), b(OCC_BLOCK);
+  uint32_t* a0 = ws;
+  uint32_t* a1 = ws ? ws + d.nwords : nullptr;
+  hipLaunchKernelGGL(occ_pack_kernel<false>, g, b, 0, s, vol, (const uint8_t*)nullptr, d, threshold, dilate ? a0 : words);
+  if (dilate) {
+    hipLaunchKernelGGL(occ_dilate_kernel, g, b, 0, s, (const uint32_t*)a0, a1, d, 2, dilate);
+    hipLaunchKernelGGL(occ_dilate_kernel, g, b, 0, s, (const uint32_t*)a1, a0, d, 1, dilate);
+    hipLaunchKernelGGL(occ_dilate_kernel, g, b, 0, s, (const uint32_t*)a0, words, d, 0, dilate);
+  }
+  FN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fastnerf_occ_from_mask(const uint8_t* mask, int64_t nx, int64_t ny, int64_t nz, uint32_t* words, fn_stream_t stream) {
+  OccDims d;
+  FN_CHECK_ARG(occ_dims(nx, ny, nz, &d), "1 <= nx, ny, nz <= 2^24 cells, fewer than 2^31 in all");
+  FN_CHECK_ARG(mask && words, "non-null pointers");
+  hipLaunchKernelGGL(occ_pack_kernel<true>, dim3(occ_blocks(d.ncells)), dim3(OCC_BLOCK), 0, fn::S(stream), (const float*)nullptr, mask, d,
+                     0.f, words);
+  FN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fastnerf_occ_query(const fn_occ_grid* grid, int64_t n, const float* pts, uint8_t* out, fn_stream_t stream) {
+  OccDev g;
+  FN_CHECK_ARG(occ_dev(grid, &g), "grid: non-null words, 1 <= n[i] <= 2^24, fewer than 2^31 cells, finite lo, finite inv > 0");
+  FN_CHECK_ARG(n >= 0, "n >= 0");
+  if (n == 0) return 0;
+  FN_CHECK_ARG(pts && out, "non-null pointers");
+  const int64_t blocks = (n + OCC_BLOCK - 1) / OCC_BLOCK;
+  hipLaunchKernelGGL(occ_query_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(OCC_BLOCK), 0, fn::S(stream), g, n, pts, out);
+  FN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fastnerf_occ_classify(const fn_occ_grid* grid, int64_t n, int S, const float* rays11, const float* z, int32_t* live_idx,
+                                     int32_t* count_out, float* raw, int32_t* ws, fn_stream_t stream) {
+  OccDev g;
+  FN_CHECK_ARG(occ_dev(grid, &g), "grid: non-null words, 1 <= n[i] <= 2^24, fewer than 2^31 cells, finite lo, finite inv > 0");
+  FN_CHECK_ARG(n > 0 && S >= 1 && n * (int64_t)S < ((int64_t)1 << 31), "n > 0, S >= 1, n * S < 2^31");
+  FN_CHECK_ARG(rays11 && z && live_idx && count_out && ws, "non-null pointers");
+  const int64_t P = n * (int64_t)S;
+  const int nb = (int)((P + OCC_PTS - 1) / OCC_PTS);
+  hipStream_t s = fn::S(stream);
+  hipLaunchKernelGGL(occ_count_kernel, dim3(nb), dim3(OCC_BLOCK), 0, s, g, P, S, rays11, z, ws);
+  fn::cp_scan_launch(nb, ws, count_out, (int)P, s);
+  hipLaunchKernelGGL(occ_scatter_kernel, dim3(nb), dim3(OCC_BLOCK), 0, s, g, P, S, rays11, z, (const int*)ws, live_idx, raw);
+  FN_LAUNCH_CHECK();
+  return 0;
+}

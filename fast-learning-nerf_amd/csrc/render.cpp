@@ -55,6 +55,58 @@ extern "C" int fastnerf_render_rays_fwd_ex(int math_mode, int64_t n, int N_sampl
   return fastnerf_raw2outputs_fwd(n, S1, raw1, z1, rays11, noise1, white_bkgd, rgb1, disp1, acc1, w1, depth1, stream);
 }
 
+// The same chain through an occupancy grid (inference): per pass, the samples are sorted by the grid (fastnerf_occ_classify:
+// list of the occupied ones, zero logits for the others) and the network runs over the list only.
+extern "C" int fastnerf_render_rays_fwd_occ(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11, int lindisp,
+                                            int perturb, int det, int white_bkgd, const float* t_rand, const float* u, uint64_t seed0,
+                                            uint64_t seed1, const float* params_c, const float* packed_c, const float* params_f,
+                                            const float* packed_f, const fn_occ_grid* grid, int32_t* live_ws, int32_t* counts_out,
+                                            float* z0, float* raw0, float* rgb0, float* disp0, float* acc0, float* w0, float* depth0,
+                                            float* z1, float* z_samples, float* z_std, float* raw1, float* rgb1, float* disp1,
+                                            float* acc1, float* w1, float* depth1, int flags, fn_stream_t stream) {
+  if (math_mode < 0 || math_mode > 2 || n < 0 || N_samples < 2 || N_importance < 0) {
+    fn::set_error("fastnerf_render_rays_fwd_occ: bad argument: math_mode in {0,1,2}, n>=0, N_samples>=2, N_importance>=0");
+    return -1;
+  }
+  if (N_importance > 0 && N_samples < 3) {
+    fn::set_error("fastnerf_render_rays_fwd_occ: hierarchical sampling needs N_samples >= 3 (the inner weights of 2 samples are empty)");
+    return -1;
+  }
+  if (n == 0) return 0;
+  const int S1 = N_samples + N_importance;
+  if (n * (int64_t)S1 >= ((int64_t)1 << 31)) {
+    fn::set_error("fastnerf_render_rays_fwd_occ: bad argument: n * (N_samples + N_importance) < 2^31 (lists index points with int32)");
+    return -1;
+  }
+  if (!rays11 || !params_c || !packed_c || !grid || !live_ws || !counts_out || !z0 || !raw0 || !rgb0 || !disp0 || !acc0 || !w0 ||
+      !depth0) {
+    fn::set_error("fastnerf_render_rays_fwd_occ: null pointer (coarse pass)");
+    return -1;
+  }
+  int32_t* idx = live_ws;
+  int32_t* cws = live_ws + n * (int64_t)S1;
+  int rc;
+  auto mlp = [&](int S, const float* z, const float* params, const float* packed, float* raw, int32_t* cnt) -> int {
+    if ((rc = fastnerf_occ_classify(grid, n, S, rays11, z, idx, cnt, raw, cws, stream))) return rc;
+    if (math_mode == 2) return fastnerf_mlp_x6_fwd_list(0, n, S, rays11, z, params, packed, raw, idx, cnt, flags, stream);
+    return math_mode ? fastnerf_mlp_bf16_fwd_list(0, n, S, rays11, z, params, packed, raw, idx, cnt, flags, stream)
+                     : fastnerf_mlp_fwd_list_ex(0, n, S, rays11, z, params, packed, raw, idx, cnt, flags, stream);
+  };
+  if ((rc = fastnerf_sample_coarse(n, N_samples, rays11, lindisp, perturb, t_rand, seed0, z0, stream))) return rc;
+  if ((rc = mlp(N_samples, z0, params_c, packed_c, raw0, counts_out))) return rc;
+  if ((rc = fastnerf_raw2outputs_fwd(n, N_samples, raw0, z0, rays11, nullptr, white_bkgd, rgb0, disp0, acc0, w0, depth0, stream)))
+    return rc;
+  if (N_importance == 0) return 0;
+  if (!params_f || !packed_f || !z1 || !z_samples || !z_std || !raw1 || !rgb1 || !disp1 || !acc1 || !w1 || !depth1) {
+    fn::set_error("fastnerf_render_rays_fwd_occ: null pointer (fine pass)");
+    return -1;
+  }
+  if ((rc = fastnerf_sample_pdf_merge(n, N_samples, N_importance, z0, w0, det, u, seed1, z1, z_samples, z_std, stream)))
+    return rc;
+  if ((rc = mlp(S1, z1, params_f, packed_f, raw1, counts_out + 2))) return rc;
+  return fastnerf_raw2outputs_fwd(n, S1, raw1, z1, rays11, nullptr, white_bkgd, rgb1, disp1, acc1, w1, depth1, stream);
+}
+
 // Backward of the same chain (autograd of render.py:238-299 w.r.t. the network parameters; sample positions are
 // detached in the reference, so the coarse net only sees d(loss)/d(rgb0)): compositing backward -> MLP backward for the
 // fine pass (into grads_f) and the coarse pass (into grads_c).  draw_ws: n * (N_samples + N_importance) * 4 floats.

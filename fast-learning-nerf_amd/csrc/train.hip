@@ -249,6 +249,13 @@ __global__ void __launch_bounds__(256) cp_scatter_kernel(int64_t n, const float*
 
 extern "C" int64_t fastnerf_compact_ws_ints(int64_t n_points) { return (n_points + CP_PTS - 1) / CP_PTS; }
 
+// the scan step for other predicates over the same block size (occupancy.hip: occupied samples of a render pass)
+namespace fn {
+void cp_scan_launch(int nb, int32_t* blk, int32_t* count_out, int n_points, hipStream_t st) {
+  hipLaunchKernelGGL(cp_scan_kernel, dim3(1), dim3(1024), 0, st, nb, blk, count_out, n_points);
+}
+}  // namespace fn
+
 extern "C" int fastnerf_compact_live(int64_t n_points, const float* draw, int32_t* live_idx, int32_t* count_out,
                                      int32_t* ws, fn_stream_t stream) {
   FN_CHECK_ARG(n_points > 0 && n_points < ((int64_t)1 << 31) && draw && live_idx && count_out && ws,

@@ -674,3 +674,113 @@ def marching_cubes(vol, threshold):
         check(lib().fastnerf_mc_emit(ptr(vol), nx, ny, nz, float(threshold), ptr(ws), ptr(verts), ptr(tris), stream()),
               'fastnerf_mc_emit')
     return verts, tris
+
+
+# ---- occupancy grid (csrc/occupancy.hip) ---------------------------------------------------------------------------
+def occ_words(nx, ny, nz):
+    """Number of uint32 words (held as int32) of the packed bits of an nx x ny x nz grid."""
+    return int(check(lib().fastnerf_occ_words(int(nx), int(ny), int(nz)), 'fastnerf_occ_words'))
+
+
+def occ_build(vol, threshold=0., dilate=1):
+    """Point volume [nx+1, ny+1, nz+1] -> packed bits: corner maximum > threshold, then dilation by `dilate` cells."""
+    require_gpu(vol)
+    if vol.dim() != 3 or min(vol.shape) < 2:
+        raise ValueError('an occupancy grid needs a point volume [nx+1, ny+1, nz+1] with every dimension >= 2, got %s' % (tuple(vol.shape),))
+    if int(dilate) < 0:
+        raise ValueError('dilate must be >= 0')
+    vol = _f32(vol)
+    nx, ny, nz = (int(s) - 1 for s in vol.shape)
+    nw = occ_words(nx, ny, nz)
+    words = torch.empty(nw, device=vol.device, dtype=torch.int32)
+    ws = torch.empty(2 * nw, device=vol.device, dtype=torch.int32) if int(dilate) > 0 else None
+    check(lib().fastnerf_occ_build(ptr(vol), nx, ny, nz, float(threshold), int(dilate), ptr(words), ptr(ws), stream()), 'fastnerf_occ_build')
+    return words
+
+
+def occ_from_mask(mask):
+    """Bool / byte mask [nx, ny, nz] -> packed bits."""
+    require_gpu(mask)
+    if mask.dim() != 3 or min(mask.shape) < 1:
+        raise ValueError('an occupancy mask is [nx, ny, nz] with every dimension >= 1, got %s' % (tuple(mask.shape),))
+    m = (mask != 0).to(torch.uint8).contiguous()
+    nx, ny, nz = (int(s) for s in m.shape)
+    words = torch.empty(occ_words(nx, ny, nz), device=m.device, dtype=torch.int32)
+    check(lib().fastnerf_occ_from_mask(ptr(m), nx, ny, nz, ptr(words), stream()), 'fastnerf_occ_from_mask')
+    return words
+
+
+def occ_query(cgrid, pts):
+    """cgrid: _lib.OccGrid; pts [n, 3] -> uint8 [n]."""
+    require_gpu(pts)
+    pts = _f32(pts).reshape(-1, 3)
+    out = torch.empty(pts.shape[0], device=pts.device, dtype=torch.uint8)
+    check(lib().fastnerf_occ_query(cgrid, pts.shape[0], ptr(pts), ptr(out), stream()), 'fastnerf_occ_query')
+    return out
+
+
+def occ_classify(cgrid, rays11, z, raw=None):
+    """The samples o + d * z of a pass sorted by the grid: (live_idx int32 [n*S], counts int32 [2] = (occupied, n*S)), both on
+    the device; live_idx[:occupied] ascends.  raw ([n, S, 4], optional) is zeroed at the other samples, untouched elsewhere."""
+    require_gpu(rays11, z, raw)
+    n, S = z.shape
+    P = n * S
+    assert rays11.shape == (n, 11) and rays11.is_contiguous() and z.is_contiguous() and z.dtype == torch.float32
+    assert raw is None or (raw.numel() == P * 4 and raw.is_contiguous() and raw.dtype == torch.float32)
+    idx = torch.empty(P, device=z.device, dtype=torch.int32)
+    cnt = torch.empty(2, device=z.device, dtype=torch.int32)
+    ws = torch.empty(int(lib().fastnerf_compact_ws_ints(P)), device=z.device, dtype=torch.int32)
+    check(lib().fastnerf_occ_classify(cgrid, n, S, ptr(rays11), ptr(z), ptr(idx), ptr(cnt), ptr(raw), ptr(ws), stream()),
+          'fastnerf_occ_classify')
+    return idx, cnt
+
+
+def mlp_fwd_list(rays11, z, params, packed_fwd, raw, live_idx, live_cnt, flags=0):
+    """Inference forward over a point list (current math mode): raw[live_idx[j]] = logits of point live_idx[j], j < live_cnt[0]."""
+    require_gpu(rays11, z, params, packed_fwd, raw, live_idx, live_cnt)
+    n, S = z.shape
+    assert raw.numel() == n * S * 4 and raw.is_contiguous() and live_idx.dtype == torch.int32 and live_cnt.dtype == torch.int32
+    assert packed_fwd.numel() == packed_floats(0, 1) and packed_tag(packed_fwd) == _MATH, \
+        'packed weights were not produced by mlp_pack under the current math mode'
+    fn = lib().fastnerf_mlp_bf16_fwd_list if _split(0) else (lib().fastnerf_mlp_x6_fwd_list if _x6() else lib().fastnerf_mlp_fwd_list_ex)
+    check(fn(0, n, S, ptr(rays11), ptr(z), ptr(params), ptr(packed_fwd), ptr(raw), ptr(live_idx), ptr(live_cnt), int(flags), stream()),
+          'fastnerf_mlp_fwd_list')
+    return raw
+
+
+def render_rays_fwd_occ(rays11, params_c, packed_c, params_f, packed_f, N_samples, N_importance, cgrid, lindisp=False, perturb=False,
+                        det=True, white_bkgd=False, t_rand=None, u=None, seed0=0, seed1=0, skip_dead_rgb=False):
+    """render_rays_fwd (inference, no sigma noise) through an occupancy grid: one C-ABI call.  Same dict, without act0 / act1,
+    plus 'counts': int32 [4] on the device = (occupied, total) samples of the coarse pass, then of the fine pass."""
+    require_gpu(rays11, params_c, packed_c, params_f, packed_f, t_rand, u)
+    n = rays11.shape[0]
+    dev = rays11.device
+    f32 = dict(device=dev, dtype=torch.float32)
+    assert packed_tag(packed_c) == _MATH and (packed_f is None or packed_tag(packed_f) == _MATH), \
+        'packed weights were not produced by mlp_pack under the current math mode'
+    if t_rand is not None:
+        t_rand = _f32(t_rand)
+        assert t_rand.shape == (n, N_samples)
+    if u is not None:
+        u = _f32(u)
+        assert u.shape == (n, N_importance)
+    S1 = N_samples + N_importance
+    o = {'z0': torch.empty(n, N_samples, **f32), 'raw0': torch.empty(n, N_samples, 4, **f32), 'act0': None,
+         'rgb0': torch.empty(n, 3, **f32), 'disp0': torch.empty(n, **f32), 'acc0': torch.empty(n, **f32),
+         'w0': torch.empty(n, N_samples, **f32), 'depth0': torch.empty(n, **f32),
+         'counts': torch.zeros(4, device=dev, dtype=torch.int32)}
+    if N_importance > 0:
+        o.update({'z1': torch.empty(n, S1, **f32), 'z_samples': torch.empty(n, N_importance, **f32), 'z_std': torch.empty(n, **f32),
+                  'raw1': torch.empty(n, S1, 4, **f32), 'act1': None,
+                  'rgb1': torch.empty(n, 3, **f32), 'disp1': torch.empty(n, **f32), 'acc1': torch.empty(n, **f32),
+                  'w1': torch.empty(n, S1, **f32), 'depth1': torch.empty(n, **f32)})
+    live_ws = torch.empty(max(1, n * S1 + int(lib().fastnerf_compact_ws_ints(max(1, n * S1)))), device=dev, dtype=torch.int32)
+    g = o.get
+    check(lib().fastnerf_render_rays_fwd_occ(
+        mode_id(), n, int(N_samples), int(N_importance), ptr(rays11), int(bool(lindisp)),
+        int(bool(perturb) or t_rand is not None), int(bool(det)), int(bool(white_bkgd)), ptr(t_rand), ptr(u), int(seed0), int(seed1),
+        ptr(params_c), ptr(packed_c), ptr(params_f), ptr(packed_f), cgrid, ptr(live_ws), ptr(o['counts']),
+        ptr(o['z0']), ptr(o['raw0']), ptr(o['rgb0']), ptr(o['disp0']), ptr(o['acc0']), ptr(o['w0']), ptr(o['depth0']),
+        ptr(g('z1')), ptr(g('z_samples')), ptr(g('z_std')), ptr(g('raw1')), ptr(g('rgb1')), ptr(g('disp1')), ptr(g('acc1')),
+        ptr(g('w1')), ptr(g('depth1')), 1 if skip_dead_rgb else 0, stream()), 'fastnerf_render_rays_fwd_occ')
+    return o

@@ -190,6 +190,28 @@ def _forward_core(rays11, net_c, net_f, N_samples, N_importance, lindisp, pertur
     return out, saved
 
 
+def _forward_occ(rays11, net_c, net_f, N_samples, N_importance, lindisp, perturb, white_bkgd, t_rand, u, occupancy, skip_dead_rgb=False):
+    """The fused inference forward through an occupancy grid (fastnerf_render_rays_fwd_occ): _forward_core(save=False) with the
+    networks run on the occupied samples only.  Returns the outputs dict, plus 'counts' (device int32 [4])."""
+    pc = net_c.packed()
+    fine = pf = None
+    if N_importance > 0:
+        fine = net_f if net_f is not None else net_c
+        pf = fine.packed() if fine is not net_c else pc
+    o = ops.render_rays_fwd_occ(rays11, net_c.flat, pc[0], None if fine is None else fine.flat, None if pf is None else pf[0],
+                                N_samples, N_importance, occupancy._c, lindisp=lindisp, perturb=perturb, det=(perturb == 0.),
+                                white_bkgd=white_bkgd, t_rand=t_rand, u=u,
+                                seed0=_next_seed() if (perturb and t_rand is None) else 0,
+                                seed1=_next_seed() if (N_importance > 0 and perturb and u is None) else 0,
+                                skip_dead_rgb=bool(skip_dead_rgb and net_c.use_viewdirs))
+    if N_importance > 0:
+        return dict(rgb_map=o['rgb1'], disp_map=o['disp1'], acc_map=o['acc1'], raw=o['raw1'], rgb0=o['rgb0'], disp0=o['disp0'],
+                    acc0=o['acc0'], z_std=o['z_std'], weights=o['w1'], z_vals=o['z1'], depth_map=o['depth1'],
+                    z_samples=o['z_samples'], weights0=o['w0'], z0=o['z0'], raw0=o['raw0'], counts=o['counts'])
+    return dict(rgb_map=o['rgb0'], disp_map=o['disp0'], acc_map=o['acc0'], raw=o['raw0'], weights=o['w0'], z_vals=o['z0'],
+                depth_map=o['depth0'], z0=o['z0'], raw0=o['raw0'], counts=o['counts'])
+
+
 def _backward_core(saved, g_rgb, g_rgb0, out_c=None, out_f=None, counts=None):
     """Writes d(loss)/d(params) of the coarse (and fine) net, given d(loss)/d(rgb maps), into
     out_c / out_f (flat, parameter order; default: the nets' flat_grad buffers).  A forward that saved no activations
@@ -319,8 +341,25 @@ def _composite(raw, z, rays11, noise, white_bkgd):
     return ops.raw2outputs_fwd(raw4, z, rays11, noise, white_bkgd)
 
 
+def _query_occupied(network_query_fn, net, rays11, z, viewdirs, occupancy):
+    """The closure route's network call through an occupancy grid: the samples are sorted by the grid on the device
+    (fastnerf_occ_classify), `network_query_fn` sees the occupied points only -- pts [L, 1, 3], viewdirs [L, 3] gathered per
+    point -- and its rows are scattered into a zero raw [n, S, C].  One host read: the list length sizes the gather."""
+    n, S = z.shape
+    idx, cnt = occupancy.classify(rays11, z)
+    L = int(cnt[0].item())
+    live = idx[:L].long()
+    ray = torch.div(live, S, rounding_mode='floor')
+    pts = (rays11[ray, 0:3] + rays11[ray, 3:6] * z.reshape(-1)[live][:, None])[:, None, :]      # render.py:268, per point
+    rows = network_query_fn(pts, None if viewdirs is None else viewdirs[ray], net)
+    C = rows.shape[-1]      # (an empty list is an ordinary input: the network is still asked, with 0 points, for its channel count)
+    raw = torch.zeros(n * S, C, device=z.device, dtype=rows.dtype)
+    raw[live] = rows.reshape(L, C)
+    return raw.reshape(n, S, C)
+
+
 def _render_rays_closure(ray_batch, rays11, network_fn, network_fine, network_query_fn, N_samples, N_importance, retraw, lindisp,
-                         perturb, white_bkgd, t_rand, u, noise0, noise1):
+                         perturb, white_bkgd, t_rand, u, noise0, noise1, occupancy=None):
     """render.py:195-305 for any torch network: sampling, inverse-CDF + merge and compositing run on the HIP kernels, the
     network runs as `network_query_fn(pts, viewdirs, net)` in torch, and autograd reaches its parameters through
     raw2outputs_full.  Random draws follow the fused route (same injected tensors, same host-RNG seed draws)."""
@@ -330,8 +369,11 @@ def _render_rays_closure(ray_batch, rays11, network_fn, network_fine, network_qu
     seed0 = _next_seed() if (perturb and t_rand is None) else 0
     z = ops.sample_coarse(rays11, N_samples, lindisp=lindisp, perturb=bool(perturb), t_rand=t_rand, seed=seed0)
     rays_o, rays_d = rays11[:, 0:3], rays11[:, 3:6]
-    pts = rays_o[..., None, :] + rays_d[..., None, :] * z[..., :, None]      # render.py:268
-    raw = network_query_fn(pts, viewdirs, network_fn)
+    if occupancy is not None:
+        raw = _query_occupied(network_query_fn, network_fn, rays11, z, viewdirs, occupancy)
+    else:
+        pts = rays_o[..., None, :] + rays_d[..., None, :] * z[..., :, None]      # render.py:268
+        raw = network_query_fn(pts, viewdirs, network_fn)
     rgb, disp, acc, weights, _ = _composite(raw, z, rays11, noise0, white_bkgd)
     ret = {}
     if N_importance > 0:
@@ -340,8 +382,12 @@ def _render_rays_closure(ray_batch, rays11, network_fn, network_fine, network_qu
         # sample_pdf(mid(z), weights[1:-1]) on the detached weights (render.py:279-283) + sort(cat)
         z1, _, z_std = ops.sample_pdf_merge(z, weights.detach().contiguous(), N_importance, det=(perturb == 0.), u=u, seed=seed1,
                                             want_samples=False)
-        pts = rays_o[..., None, :] + rays_d[..., None, :] * z1[..., :, None]
-        raw = network_query_fn(pts, viewdirs, network_fine if network_fine is not None else network_fn)
+        if occupancy is not None:
+            raw = _query_occupied(network_query_fn, network_fine if network_fine is not None else network_fn, rays11, z1, viewdirs,
+                                  occupancy)
+        else:
+            pts = rays_o[..., None, :] + rays_d[..., None, :] * z1[..., :, None]
+            raw = network_query_fn(pts, viewdirs, network_fine if network_fine is not None else network_fn)
         rgb, disp, acc, _, _ = _composite(raw, z1, rays11, noise1, white_bkgd)
         ret['z_std'] = z_std
     out = {'rgb_map': rgb, 'disp_map': disp, 'acc_map': acc}
@@ -352,7 +398,7 @@ def _render_rays_closure(ray_batch, rays11, network_fn, network_fine, network_qu
 
 
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
-                N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False):
+                N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False, occupancy=None):
     """render.py:195-305.  Two routes, chosen by the networks (after `.module` unwrapping):
 
     * fastnerf NeRF modules (8 x 256): positional encoding + MLP run fused inside the HIP kernels; `network_query_fn` is
@@ -361,7 +407,12 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
       points of both passes, as the reference does; sampling and compositing still run on the HIP kernels, and every map is
       differentiable w.r.t. the network's parameters.
 
-    A NeRF paired with another kind of network raises TypeError (the fused route would not train the other one)."""
+    A NeRF paired with another kind of network raises TypeError (the fused route would not train the other one).
+
+    `occupancy` (an occupancy.OccupancyGrid; inference only): a sample in a cell whose bit is clear gets raw = 0 without the
+    network being evaluated, in both passes; every other sample gets the logits it gets without the grid.  ValueError with
+    raw_noise_std > 0 (noise is added to sigma before the relu: a zero sigma is not a dead sample) and when gradients are
+    wanted (the training step must not silently change its gradients)."""
     net_c = _unwrap(network_fn)
     net_f = _unwrap(network_fine)
     fused = isinstance(net_c, NeRF)
@@ -375,6 +426,14 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     if fused and ray_batch.shape[-1] == 8 and net_c.use_viewdirs:
         raise ValueError('networks built with use_viewdirs=True need ray batches with view directions [N,11]')
     ops.require_gpu(ray_batch)
+    if occupancy is not None:
+        if raw_noise_std > 0.:
+            raise ValueError('render_rays: an occupancy grid cannot be combined with raw_noise_std > 0 (sigma noise is added before '
+                             'the relu, so a sample with zero sigma is not dead)')
+        nets = [m for m in (net_c, net_f) if isinstance(m, torch.nn.Module)]
+        if torch.is_grad_enabled() and any(p.requires_grad for m in nets for p in m.parameters()):
+            raise ValueError('render_rays: an occupancy grid is an inference feature; call it under torch.no_grad() (or with '
+                             'parameters that do not require grad)')
     rays11 = ray_batch.contiguous().float()
     if rays11.shape[-1] == 8:      # no view directions: the kernels' direction slots stay zero (their weights are zero too)
         rays11 = torch.cat([rays11, torch.zeros(rays11.shape[0], 3, device=rays11.device)], -1)
@@ -393,7 +452,16 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             noise0, noise1 = ops.sigma_noise(n, N_samples, N_samples + N_importance if N_importance > 0 else 0, raw_noise_std, _next_seed(), dev)
     if not fused:
         return _render_rays_closure(ray_batch, rays11, network_fn, network_fine, network_query_fn, N_samples, N_importance, retraw,
-                                    lindisp, perturb, white_bkgd, t_rand, u, noise0, noise1)
+                                    lindisp, perturb, white_bkgd, t_rand, u, noise0, noise1, occupancy=occupancy)
+    if occupancy is not None:
+        out = _forward_occ(rays11, net_c, net_f, N_samples, N_importance, lindisp, perturb, white_bkgd, t_rand, u, occupancy,
+                           skip_dead_rgb=not retraw)
+        ret = {'rgb_map': out['rgb_map'], 'disp_map': out['disp_map'], 'acc_map': out['acc_map']}
+        if retraw:
+            ret['raw'] = out['raw']
+        if N_importance > 0:
+            ret['rgb0'], ret['disp0'], ret['acc0'], ret['z_std'] = out['rgb0'], out['disp0'], out['acc0'], out['z_std']
+        return ret
     cfg = dict(rays11=rays11, net_c=net_c, net_f=net_f, N_samples=N_samples, N_importance=N_importance,
                lindisp=lindisp, perturb=perturb, white_bkgd=white_bkgd, t_rand=t_rand, u=u, noise0=noise0,
                noise1=noise1,

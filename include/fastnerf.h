@@ -459,6 +459,66 @@ int fastnerf_mc_emit(const float* vol, int64_t nx, int64_t ny, int64_t nz, float
                      fn_stream_t stream);
 int fastnerf_mc_tables(int8_t* tri_host, uint16_t* edge_host);
 
+
+/* ---- occupancy grid: rendering that does not evaluate the network in empty space (inference only) -----------------------
+ * The grid: a box [lo, hi) in the network's input space (world space, or NDC space for LLFF scenes) cut into
+ * n[0] x n[1] x n[2] cells, one bit per cell (fastnerf_occ_words() uint32 words; the bit layout is the library's), and
+ * `outside_occupied`.  The cell index of a point x along an axis is floor((x - lo) * inv), subtraction and product each
+ * rounded to fp32, inv = n / (hi - lo) rounded to fp32 once by the caller.  A point whose index lies outside 0 .. n-1 on any
+ * axis, a non-finite point included, takes `outside_occupied`.  The struct lives on the HOST; `words` is a device pointer.
+ *   fastnerf_occ_build      vol: point volume [nx+1, ny+1, nz+1] float32 (what the dense density query of extract_mesh.py:38-61
+ *                           gives).  A cell is occupied when one of its 8 corners is > threshold (the corners' maximum, for a
+ *                           volume without NaNs); then every cell within `dilate` cells (Chebyshev distance, clipped at the box)
+ *                           of an occupied one becomes occupied.  ws: 2 * fastnerf_occ_words() uint32 of scratch (NULL allowed
+ *                           when dilate == 0).
+ *   fastnerf_occ_from_mask  mask: [nx, ny, nz] bytes (C order), non-zero = occupied
+ *   fastnerf_occ_query      pts [n,3] -> out [n] bytes, 1 = occupied
+ *   fastnerf_occ_classify   the n * S samples x = o + d * z of a pass (rays11 [n,11], z [n,S]; one rounded multiply, one rounded
+ *                           add, as the MLP kernels compute the point): live_idx[0 .. count) = ascending indices n_ray * S + s of
+ *                           the occupied samples, count_out[0] = count, count_out[1] = n * S (device values, no host round
+ *                           trip), and raw[p*4 .. p*4+3] = 0 for every other sample (raw may be NULL).  ws:
+ *                           fastnerf_compact_ws_ints(n * S) int32.  The three launches of fastnerf_compact_live with another
+ *                           predicate: deterministic, no atomics. */
+typedef struct fn_occ_grid {
+  const uint32_t* words; /* device */
+  float lo[3], inv[3];
+  int32_t n[3];
+  int32_t outside_occupied;
+} fn_occ_grid;
+int64_t fastnerf_occ_words(int64_t nx, int64_t ny, int64_t nz);
+int fastnerf_occ_build(const float* vol, int64_t nx, int64_t ny, int64_t nz, float threshold, int dilate, uint32_t* words,
+                       uint32_t* ws, fn_stream_t stream);
+int fastnerf_occ_from_mask(const uint8_t* mask, int64_t nx, int64_t ny, int64_t nz, uint32_t* words, fn_stream_t stream);
+int fastnerf_occ_query(const fn_occ_grid* grid, int64_t n, const float* pts, uint8_t* out, fn_stream_t stream);
+int fastnerf_occ_classify(const fn_occ_grid* grid, int64_t n, int S, const float* rays11, const float* z, int32_t* live_idx,
+                          int32_t* count_out, float* raw, int32_t* ws, fn_stream_t stream);
+/* NeRF.forward + Embedder.embed (model.py:38-63) of the points live_idx[0 .. *live_cnt) only, inference (nothing saved):
+ * raw[live_idx[j]*4 .. +3] = the logits the plain forward gives that point; no other element of raw is written.  kind 0 only.
+ * flags as fastnerf_mlp_fwd_flags_ex, a tile being 64 consecutive list entries.  _ex: exact fp32, bf16: split-bf16 (x3),
+ * x6: bf16x6. */
+int fastnerf_mlp_fwd_list_ex(int kind, int64_t n, int S, const float* rays11, const float* z, const float* params,
+                             const float* packed_fwd, float* raw, const int32_t* live_idx, const int32_t* live_cnt, int flags,
+                             fn_stream_t stream);
+int fastnerf_mlp_bf16_fwd_list(int kind, int64_t n, int S, const float* rays11, const float* z, const float* params,
+                               const float* packed_fwd, float* raw, const int32_t* live_idx, const int32_t* live_cnt, int flags,
+                               fn_stream_t stream);
+int fastnerf_mlp_x6_fwd_list(int kind, int64_t n, int S, const float* rays11, const float* z, const float* params,
+                             const float* packed_fwd, float* raw, const int32_t* live_idx, const int32_t* live_cnt, int flags,
+                             fn_stream_t stream);
+/* render_rays (render.py:195-305) through an occupancy grid, inference only: what fastnerf_render_rays_fwd_ex enqueues with
+ * act0 == act1 == NULL and no sigma noise, except that each MLP launch becomes fastnerf_occ_classify + the list forward: a
+ * sample in a cell whose bit is clear gets raw = (0, 0, 0, 0) without the network being evaluated, in both passes (the coarse
+ * weights that feed the inverse-CDF sampler come from the masked logits).  An occupied sample gets exactly the logits of the
+ * plain forward.  live_ws: n * (N_samples + N_importance) + fastnerf_compact_ws_ints(n * (N_samples + N_importance)) int32 of
+ * scratch; counts_out: 4 int32 = (occupied, total) of the coarse pass, then of the fine pass. */
+int fastnerf_render_rays_fwd_occ(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11, int lindisp,
+                                 int perturb, int det, int white_bkgd, const float* t_rand, const float* u, uint64_t seed0,
+                                 uint64_t seed1, const float* params_c, const float* packed_c, const float* params_f,
+                                 const float* packed_f, const fn_occ_grid* grid, int32_t* live_ws, int32_t* counts_out, float* z0,
+                                 float* raw0, float* rgb0, float* disp0, float* acc0, float* w0, float* depth0, float* z1,
+                                 float* z_samples, float* z_std, float* raw1, float* rgb1, float* disp1, float* acc1, float* w1,
+                                 float* depth1, int flags, fn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
