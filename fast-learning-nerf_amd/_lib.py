@@ -31,7 +31,8 @@ class StepArgs(C.Structure):
         + [(k, D) for k in ('focal', 'lr', 'beta1', 'beta2', 'eps')]
         + [(k, F) for k in ('near_plane', 'far_plane', 'grad_scale')]
         + [(k, I) for k in ('math_mode', 'N_samples', 'N_importance', 'lindisp', 'perturb', 'white_bkgd', 'ndc', 'H', 'W', 'live',
-                            'fwd_flags', 'max_leaves', 'adam_t')])
+                            'fwd_flags', 'max_leaves', 'adam_t')]
+        + [('occ', P), ('occ_counts', P)])
 
 
 class OccGrid(C.Structure):
@@ -137,6 +138,8 @@ SIGNATURES = {
     'fastnerf_occ_from_mask': (I, [P, L, L, L, P, P]),
     'fastnerf_occ_query': (I, [C.POINTER(OccGrid), L, P, P, P]),
     'fastnerf_occ_classify': (I, [C.POINTER(OccGrid), L, I, P, P, P, P, P, P, P]),
+    'fastnerf_occ_cell_points': (I, [C.POINTER(OccGrid), L, L, U64, P, P]),
+    'fastnerf_occ_update': (I, [P, P, L, L, L, L, L, F, F, I, P, P, P, P]),
     'fastnerf_mlp_fwd_list_ex': (I, [I, L, I, P, P, P, P, P, P, P, I, P]),
     'fastnerf_mlp_bf16_fwd_list': (I, [I, L, I, P, P, P, P, P, P, P, I, P]),
     'fastnerf_mlp_x6_fwd_list': (I, [I, L, I, P, P, P, P, P, P, P, I, P]),

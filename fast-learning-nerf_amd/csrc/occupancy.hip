@@ -15,6 +15,10 @@
 //                        without NaNs), or a byte mask [nx, ny, nz].
 //   occ_dilate_kernel    OR over +-d cells along ONE axis; three launches (k, j, i) give the Chebyshev ball, clipped at the box
 //   occ_query_kernel     [n, 3] points -> one byte each
+//   occ_cell_points      training grid: one (jittered) point inside each cell of a cell range, as rays11 rows
+//   occ_update_kernel    training grid: dens = max(dens * decay, relu(sigma)) on a cell range and, in the same launch, the
+//                        bit dens > threshold of EVERY cell: one lane per cell, a wave's 64 consecutive cells are one ballot =
+//                        two words, each stored by the one lane that owns it (no atomics)
 //   occ_count / scatter  the samples o + d * z of a pass: per-block counts -> (the scan of train.hip) -> ascending list of the
 //                        occupied sample indices; the others get raw = (0, 0, 0, 0).  The shape of fastnerf_compact_live with
 //                        another predicate: deterministic, no atomics, the list length stays on the device.
@@ -112,6 +116,70 @@ __global__ void __launch_bounds__(OCC_BLOCK) occ_query_kernel(OccDev g, int64_t 
     out[q] = occ_point(g, pts[q * 3], pts[q * 3 + 1], pts[q * 3 + 2]) ? 1 : 0;
 }
 
+__device__ __forceinline__ int occ_axis_cell(float x, float lo, float inv) { return (int)floorf(fmul(fsub(x, lo), inv)); }
+
+// One point inside each of the cells c0 .. c0+n-1: x = lo + (index + jitter) / inv per axis, each operation rounded to fp32,
+// jitter = 0.5 (seed == 0) or a Philox draw in [0, 1) keyed by (seed, cell).  Where fp32 rounding puts that point into a
+// neighbouring cell (index + jitter rounds up to index + 1, or the sum lands on a face), the jitter is clamped towards the
+// cell's centre -- halved distance to 0.5 per attempt, 0.5 itself at the end -- until occ_point's arithmetic gives the cell back.
+__global__ void __launch_bounds__(OCC_BLOCK) occ_cell_points_kernel(OccDev g, int64_t c0, int64_t n, uint32_t k0, uint32_t k1, int jit,
+                                                                    float* __restrict__ rays11) {
+  const int64_t q = (int64_t)blockIdx.x * OCC_BLOCK + threadIdx.x;
+  if (q >= n) return;
+  const uint32_t c = (uint32_t)(c0 + q);
+  const uint32_t r = c / (uint32_t)g.n[2];
+  int idx[3];
+  idx[2] = (int)(c - r * (uint32_t)g.n[2]);
+  idx[0] = (int)(r / (uint32_t)g.n[1]);
+  idx[1] = (int)(r - (uint32_t)idx[0] * (uint32_t)g.n[1]);
+  float u[3] = {0.5f, 0.5f, 0.5f};
+  if (jit) {
+    uint32_t o[4];
+    philox4x32(c, 0u, 0x6f636367u, 0u, k0, k1, o);
+    u[0] = u01(o[0]);
+    u[1] = u01(o[1]);
+    u[2] = u01(o[2]);
+  }
+  float* row = rays11 + q * 11;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    float j = u[a], x = 0.f;
+    for (int it = 0; it < 26; ++it) {
+      x = fadd(g.lo[a], __fdiv_rn(fadd((float)idx[a], j), g.inv[a]));
+      if (occ_axis_cell(x, g.lo[a], g.inv[a]) == idx[a]) break;
+      j = it < 24 ? fadd(0.5f, fmul(fsub(j, 0.5f), 0.5f)) : 0.5f;
+    }
+    row[a] = x;
+  }
+#pragma unroll
+  for (int a = 3; a < 11; ++a) row[a] = 0.f;
+}
+
+// sigma of cell c0 + q is raw_c[q * 4 + 3] (and raw_f's, the larger of the two counts); relu maps a NaN to 0.
+__global__ void __launch_bounds__(OCC_BLOCK) occ_update_kernel(const float* __restrict__ raw_c, const float* __restrict__ raw_f, int64_t c0,
+                                                               int64_t n, OccDims d, float decay, float thr, float* __restrict__ dens,
+                                                               uint32_t* __restrict__ words) {
+  const int64_t c = (int64_t)blockIdx.x * OCC_BLOCK + threadIdx.x;
+  bool b = false;
+  if (c < d.ncells) {
+    float v = dens[c];
+    const int64_t q = c - c0;
+    if (q >= 0 && q < n) {
+      float s = raw_c[q * 4 + 3];
+      s = s > 0.f ? s : 0.f;
+      if (raw_f) {
+        const float t = raw_f[q * 4 + 3];
+        s = t > s ? t : s;
+      }
+      const float old = fmul(v, decay);
+      v = s > old ? s : old;
+      dens[c] = v;
+    }
+    b = v > thr;
+  }
+  if (words) occ_store_bits(b, c, words, d.nwords);   // (uniform: words == NULL updates the density only)
+}
+
 // bits 0..3: samples p0 .. p0+3 of the pass are occupied (x = o + d * z as the MLP kernels compute it)
 __device__ __forceinline__ unsigned occ_flags(const OccDev& g, const float* __restrict__ rays, const float* __restrict__ zv, uint32_t S,
                                               int64_t p0, int64_t n) {
@@ -174,9 +242,10 @@ bool occ_dims(int64_t nx, int64_t ny, int64_t nz, OccDims* d) {
   return true;
 }
 
-bool occ_dev(const fn_occ_grid* g, OccDev* o) {
+// the grid's geometry without its bits (o->words = g->words, which may be NULL)
+bool occ_geom(const fn_occ_grid* g, OccDev* o) {
   OccDims d;
-  if (!g || !g->words || !occ_dims(g->n[0], g->n[1], g->n[2], &d)) return false;
+  if (!g || !occ_dims(g->n[0], g->n[1], g->n[2], &d)) return false;
   o->words = g->words;
   for (int c = 0; c < 3; ++c) {
     if (!(g->inv[c] > 0.f) || !(g->inv[c] <= 3.0e38f) || !(g->lo[c] == g->lo[c])) return false;
@@ -188,7 +257,19 @@ bool occ_dev(const fn_occ_grid* g, OccDev* o) {
   return true;
 }
 
+bool occ_dev(const fn_occ_grid* g, OccDev* o) { return g && g->words && occ_geom(g, o); }
+
 inline unsigned occ_blocks(int64_t ncells) { return (unsigned)((ncells + OCC_BLOCK - 1) / OCC_BLOCK); }
+
+// the three dilation passes (k, j, i) of a grid whose undilated bits are in ws[0 .. nwords): -> words.  ws: 2 * nwords.
+void occ_dilate_launch(const OccDims& d, int dilate, uint32_t* ws, uint32_t* words, hipStream_t s) {
+  const dim3 g(occ_blocks(d.ncells)), b(OCC_BLOCK);
+  uint32_t* a0 = ws;
+  uint32_t* a1 = ws + d.nwords;
+  hipLaunchKernelGGL(occ_dilate_kernel, g, b, 0, s, (const uint32_t*)a0, a1, d, 2, dilate);
+  hipLaunchKernelGGL(occ_dilate_kernel, g, b, 0, s, (const uint32_t*)a1, a0, d, 1, dilate);
+  hipLaunchKernelGGL(occ_dilate_kernel, g, b, 0, s, (const uint32_t*)a0, words, d, 0, dilate);
+}
 
 }  // namespace
 
@@ -209,14 +290,8 @@ extern "C" int fastnerf_occ_build(const float* vol, int64_t nx, int64_t ny, int6
   FN_CHECK_ARG(threshold == threshold, "threshold is a NaN");
   hipStream_t s = fn::S(stream);
   const dim3 g(occ_blocks(d.ncells)), b(OCC_BLOCK);
-  uint32_t* a0 = ws;
-  uint32_t* a1 = ws ? ws + d.nwords : nullptr;
-  hipLaunchKernelGGL(occ_pack_kernel<false>, g, b, 0, s, vol, (const uint8_t*)nullptr, d, threshold, dilate ? a0 : words);
-  if (dilate) {
-    hipLaunchKernelGGL(occ_dilate_kernel, g, b, 0, s, (const uint32_t*)a0, a1, d, 2, dilate);
-    hipLaunchKernelGGL(occ_dilate_kernel, g, b, 0, s, (const uint32_t*)a1, a0, d, 1, dilate);
-    hipLaunchKernelGGL(occ_dilate_kernel, g, b, 0, s, (const uint32_t*)a0, words, d, 0, dilate);
-  }
+  hipLaunchKernelGGL(occ_pack_kernel<false>, g, b, 0, s, vol, (const uint8_t*)nullptr, d, threshold, dilate ? ws : words);
+  if (dilate) occ_dilate_launch(d, dilate, ws, words, s);
   FN_LAUNCH_CHECK();
   return 0;
 }
@@ -239,6 +314,37 @@ extern "C" int fastnerf_occ_query(const fn_occ_grid* grid, int64_t n, const floa
   FN_CHECK_ARG(pts && out, "non-null pointers");
   const int64_t blocks = (n + OCC_BLOCK - 1) / OCC_BLOCK;
   hipLaunchKernelGGL(occ_query_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(OCC_BLOCK), 0, fn::S(stream), g, n, pts, out);
+  FN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fastnerf_occ_cell_points(const fn_occ_grid* grid, int64_t c0, int64_t n, uint64_t seed, float* rays11, fn_stream_t stream) {
+  OccDev g;
+  FN_CHECK_ARG(occ_geom(grid, &g), "grid: 1 <= n[i] <= 2^24, fewer than 2^31 cells, finite lo, finite inv > 0 (the bits are not read)");
+  const int64_t ncells = (int64_t)g.n[0] * g.n[1] * g.n[2];
+  FN_CHECK_ARG(c0 >= 0 && n >= 0 && c0 <= ncells && n <= ncells - c0, "0 <= c0, c0 + n <= number of cells");
+  if (n == 0) return 0;
+  FN_CHECK_ARG(rays11, "non-null pointers");
+  hipLaunchKernelGGL(occ_cell_points_kernel, dim3(occ_blocks(n)), dim3(OCC_BLOCK), 0, fn::S(stream), g, c0, n, (uint32_t)seed,
+                     (uint32_t)(seed >> 32), seed != 0 ? 1 : 0, rays11);
+  FN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fastnerf_occ_update(const float* raw_c, const float* raw_f, int64_t c0, int64_t n, int64_t nx, int64_t ny, int64_t nz,
+                                   float decay, float threshold, int dilate, float* dens, uint32_t* words, uint32_t* ws,
+                                   fn_stream_t stream) {
+  OccDims d;
+  FN_CHECK_ARG(occ_dims(nx, ny, nz, &d), "1 <= nx, ny, nz <= 2^24 cells, fewer than 2^31 in all");
+  FN_CHECK_ARG(c0 >= 0 && n >= 0 && c0 <= d.ncells && n <= d.ncells - c0, "0 <= c0, c0 + n <= number of cells");
+  FN_CHECK_ARG(dens && (n == 0 || raw_c) && dilate >= 0 && (dilate == 0 || ws || !words),
+               "non-null dens, raw_c when n > 0, dilate >= 0, ws when dilate > 0 and words are wanted");
+  FN_CHECK_ARG(decay >= 0.f && decay <= 1.f && threshold == threshold, "0 <= decay <= 1, threshold is not a NaN");
+  if (!words && n == 0) return 0;
+  hipStream_t s = fn::S(stream);
+  hipLaunchKernelGGL(occ_update_kernel, dim3(occ_blocks(d.ncells)), dim3(OCC_BLOCK), 0, s, raw_c, raw_f, c0, n, d, decay, threshold, dens,
+                     !words ? (uint32_t*)nullptr : (dilate ? ws : words));
+  if (words && dilate) occ_dilate_launch(d, dilate, ws, words, s);
   FN_LAUNCH_CHECK();
   return 0;
 }

@@ -274,6 +274,22 @@ extern "C" int fastnerf_train_step(const fn_step_args* a, int phases, fn_stream_
     fn::set_error("fastnerf_train_step: null network buffer");
     return -1;
   }
+  if (a->occ) {
+    // the grid removes samples from the FIRST forward of a compacted step; the plain backward has no list to run over, and sigma
+    // noise is added before the relu: a sample with zero sigma is not dead then
+    if (!a->live) {
+      fn::set_error("fastnerf_train_step: an occupancy grid needs the compacted step (live != 0): the plain backward has no list");
+      return -1;
+    }
+    if (a->noise0 || a->noise1) {
+      fn::set_error("fastnerf_train_step: an occupancy grid cannot be combined with sigma noise (it is added before the relu)");
+      return -1;
+    }
+    if (!a->live_ws) {
+      fn::set_error("fastnerf_train_step: an occupancy grid needs live_ws");
+      return -1;
+    }
+  }
   const float* params_c = a->params;
   const float* params_f = two ? a->params + a->net_floats : nullptr;
   float* grads_c = a->grads;
@@ -288,7 +304,17 @@ extern "C" int fastnerf_train_step(const fn_step_args* a, int phases, fn_stream_
     if ((rc = fastnerf_pack_rays(a->n, a->rays_o, a->rays_d, a->near_plane, a->far_plane, a->ndc, a->H, a->W, a->focal, a->rays11,
                                  stream))) return rc;
     const bool save = !a->live;
-    if ((rc = fastnerf_render_rays_fwd_ex(a->math_mode, a->n, a->N_samples, a->N_importance, a->rays11, a->lindisp,
+    if (a->occ) {
+      // live_ws: [4] counters of the backward | list | scan scratch -- the forward's list and scratch are dead before the backward
+      // writes its own; without occ_counts the forward's counters land in the backward's (which overwrites them)
+      if ((rc = fastnerf_render_rays_fwd_occ(a->math_mode, a->n, a->N_samples, a->N_importance, a->rays11, a->lindisp,
+                                             (a->perturb || a->t_rand) ? 1 : 0, a->perturb ? 0 : 1, a->white_bkgd, a->t_rand, a->u,
+                                             a->seed0, a->seed1, params_c, a->packed_fwd_c, params_f, a->packed_fwd_f, a->occ,
+                                             a->live_ws + 4, a->occ_counts ? a->occ_counts : a->live_ws, a->z0, a->raw0, a->rgb0,
+                                             a->disp0, a->acc0, a->w0, a->depth0, a->z1, a->z_samples, a->z_std, a->raw1, a->rgb1,
+                                             a->disp1, a->acc1, a->w1, a->depth1, a->fwd_flags, stream)))
+        return rc;
+    } else if ((rc = fastnerf_render_rays_fwd_ex(a->math_mode, a->n, a->N_samples, a->N_importance, a->rays11, a->lindisp,
                                           (a->perturb || a->t_rand) ? 1 : 0, a->perturb ? 0 : 1, a->white_bkgd, a->t_rand, a->u,
                                           a->noise0, a->noise1, a->seed0, a->seed1, params_c, a->packed_fwd_c, params_f,
                                           a->packed_fwd_f, a->z0, a->raw0, save ? a->act0 : nullptr, a->rgb0, a->disp0, a->acc0,

@@ -1,4 +1,4 @@
-"""Occupancy grid: rendering that does not evaluate the networks in empty space (inference only).
+"""Occupancy grid: rendering -- and, opted into, training -- that does not evaluate the networks in empty space.
 
     grid = fastnerf.occupancy.OccupancyGrid.from_network(render_kwargs_test)
     render_kwargs_test['occupancy'] = grid          # render / render_path / render_rays pass it through
@@ -7,7 +7,12 @@ The contract (include/fastnerf.h): a box [lo, hi) in the networks' in
 bit per cell, and `outside_occupied`.  A sample x = o + d * z lies in cell floor((x - lo) * inv) per axis (fp32, each operation
 rounded, inv = n / (hi - lo) rounded once); an index outside 0 .. n-1, a non-finite point included, takes `outside_occupied`.
 A sample whose bit is clear gets raw = (0, 0, 0, 0) without the network being evaluated, in the coarse and the fine pass; a
-sample whose bit is set gets exactly the logits of the plain forward.  The kernels are csrc/occupancy.hip."""
+sample whose bit is set gets exactly the logits of the plain forward.  The kernels are csrc/occupancy.hip.
+
+Training (opt-in): a grid made by `OccupancyGrid.for_training` starts fully occupied and carries a per-cell density `dens`;
+`run_nerf.Trainer(..., occupancy=grid)` runs the first forward of its compacted step over the occupied samples only and calls
+`grid.update` as training goes: dens = max(dens * decay, relu(sigma)) at a jittered point INSIDE each cell, bit = dens >
+threshold, dilated.  render_rays(..., occupancy=grid) with gradients enabled still raises: the autograd route has no grid."""
 import ctypes as C
 
 import numpy as np
@@ -17,9 +22,11 @@ from . import _lib, ops
 
 
 class OccupancyGrid:
-    """Bits of an nx x ny x nz grid over [lo, hi) on the GPU.  Build one with from_mask / from_density / from_network / load."""
+    """Bits of an nx x ny x nz grid over [lo, hi) on the GPU.  Build one with from_mask / from_density / from_network / load,
+    or for_training (a grid with a density that `update` maintains)."""
+    CHUNK = 1 << 19      # cells per network launch of update()
 
-    def __init__(self, words, shape, lo, hi, outside_occupied=True):
+    def __init__(self, words, shape, lo, hi, outside_occupied=True, dens=None, decay=None, threshold=0., dilate=1):
         ops.require_gpu(words)
         self.shape = tuple(int(s) for s in shape)
         if len(self.shape) != 3:
@@ -35,6 +42,25 @@ class OccupancyGrid:
         self.outside_occupied = bool(outside_occupied)
         self._c = _lib.OccGrid(words.data_ptr(), (C.c_float * 3)(*self.lo.tolist()), (C.c_float * 3)(*self.inv.tolist()),
                                (C.c_int32 * 3)(*self.shape), int(self.outside_occupied))
+        # the training grid's state (None / unused for an inference grid)
+        self.dens = None
+        self.decay = None if decay is None else float(decay)
+        self.threshold, self.dilate = float(threshold), int(dilate)
+        self.updates = 0        # update() calls so far: the default seed of the next one
+        self.cursor = 0         # first cell of the next slice (cells_per_call)
+        self.primed = False     # every cell has been sampled at least once
+        if dens is not None:
+            ops.require_gpu(dens)
+            assert dens.dtype == torch.float32 and dens.is_contiguous() and dens.numel() == self.ncells
+            if not 0. <= self.decay <= 1.:
+                raise ValueError('decay lies in [0, 1]')
+            if self.dilate < 0:
+                raise ValueError('dilate must be >= 0')
+            self.dens = dens.reshape(-1)
+
+    @property
+    def ncells(self):
+        return self.shape[0] * self.shape[1] * self.shape[2]
 
     # ---- constructors -----------------------------------------------------------------------------------------------
     @classmethod
@@ -77,16 +103,95 @@ class OccupancyGrid:
         return cls.from_density(vol, -bound, bound, threshold, dilate, outside_occupied)
 
     @classmethod
+    def for_training(cls, N=128, bound=1.2, threshold=0., dilate=1, decay=0.95, outside_occupied=True, device='cuda'):
+        """A grid to train through (run_nerf.Trainer(..., occupancy=grid)): N^3 cells (or N = (nx, ny, nz)) over
+        [-bound, bound)^3, every bit set, and a zero density that the first `update` fills from the networks.  A cell closes
+        once dens * decay^k <= threshold: with the default threshold = 0 that is never in practice (fp32 underflow, some 2000
+        refreshes), so the grid then only loses cells whose sigma was never positive at any sampled point; threshold > 0
+        lets cells close again."""
+        shape = (int(N),) * 3 if np.ndim(N) == 0 else tuple(int(s) for s in N)
+        if len(shape) != 3 or min(shape) < 1:
+            raise ValueError('N is a cell count or (nx, ny, nz), every one >= 1')
+        dev = torch.device(device)
+        words = ops.occ_from_mask(torch.ones(shape, dtype=torch.bool, device=dev))
+        dens = torch.zeros(shape[0] * shape[1] * shape[2], device=dev, dtype=torch.float32)
+        return cls(words, shape, -bound, bound, outside_occupied, dens=dens, decay=decay, threshold=threshold, dilate=dilate)
+
+    @classmethod
     def load(cls, path, device='cuda'):
         with np.load(path) as f:
             words = torch.from_numpy(f['words'].astype(np.uint32).view(np.int32)).to(device)
-            return cls(words, f['shape'].tolist(), f['lo'], f['hi'], bool(f['outside_occupied']))
+            if 'dens' not in f.files:
+                return cls(words, f['shape'].tolist(), f['lo'], f['hi'], bool(f['outside_occupied']))
+            g = cls(words, f['shape'].tolist(), f['lo'], f['hi'], bool(f['outside_occupied']),
+                    dens=torch.from_numpy(f['dens'].astype(np.float32)).to(device), decay=float(f['decay']),
+                    threshold=float(f['threshold']), dilate=int(f['dilate']))
+            g.updates, g.cursor, g.primed = int(f['updates']), int(f['cursor']), bool(f['primed'])
+            return g
 
     def save(self, path):
-        """.npz: words (uint32; cell (i,j,k) = bit c & 31 of word c >> 5, c = (i*ny + j)*nz + k), shape, lo, hi, outside_occupied."""
+        """.npz: words (uint32; cell (i,j,k) = bit c & 31 of word c >> 5, c = (i*ny + j)*nz + k), shape, lo, hi, outside_occupied;
+        a training grid adds dens (float32 [nx*ny*nz], cell order c), decay, threshold, dilate, updates, cursor, primed."""
+        fields = dict(words=self.words.cpu().numpy().view(np.uint32), shape=np.asarray(self.shape, np.int64), lo=self.lo,
+                      hi=self.hi, outside_occupied=np.asarray(self.outside_occupied))
+        if self.dens is not None:
+            fields.update(dens=self.dens.cpu().numpy(), decay=np.asarray(self.decay, np.float64),
+                          threshold=np.asarray(self.threshold, np.float64), dilate=np.asarray(self.dilate, np.int64),
+                          updates=np.asarray(self.updates, np.int64), cursor=np.asarray(self.cursor, np.int64),
+                          primed=np.asarray(self.primed))
         with open(path, 'wb') as fh:      # (a file object: numpy appends no suffix)
-            np.savez(fh, words=self.words.cpu().numpy().view(np.uint32), shape=np.asarray(self.shape, np.int64), lo=self.lo,
-                     hi=self.hi, outside_occupied=np.asarray(self.outside_occupied))
+            np.savez(fh, **fields)
+
+    # ---- training ---------------------------------------------------------------------------------------------------
+    def update(self, render_kwargs, seed=None, cells_per_call=None, _packed=None):
+        """Refresh the density and the bits from the networks of `render_kwargs` (fastnerf NeRF modules): a point inside each
+        cell (fastnerf_occ_cell_points: Philox jitter keyed by (seed, cell); seed 0 = cell centres; default = 1 + the number
+        of updates so far, so that every rank of a data-parallel run draws the same points), the non-saving forward of the
+        coarse and of the fine network there, then dens = max(dens * decay, relu(sigma_coarse), relu(sigma_fine)) and
+        bit = dens > threshold, dilated (fastnerf_occ_update).  Everything is enqueued on the current stream: no host round trip.
+
+        cells_per_call: refresh only that many cells, a slice that rotates through the grid from call to call, so that the cost
+        per call is bounded; a cell decays once per refresh of its own.  The first call always takes every cell: a cell that
+        was never sampled has no density to stand on."""
+        from .model import NeRF
+        if self.dens is None:
+            raise ValueError('update() needs a grid with a density: OccupancyGrid.for_training(...)')
+        nets = [getattr(render_kwargs['network_fn'], 'module', render_kwargs['network_fn'])]
+        fine = render_kwargs.get('network_fine')
+        fine = getattr(fine, 'module', fine)
+        if fine is not None and fine is not nets[0]:
+            nets.append(fine)
+        if not all(isinstance(m, NeRF) for m in nets):
+            raise TypeError('OccupancyGrid.update runs the fused HIP forward: it needs fastnerf NeRF networks')
+        packed = _packed if _packed is not None else [m.packed()[0] for m in nets]
+        seed = self.updates + 1 if seed is None else int(seed)
+        total = self.ncells
+        if cells_per_call is None or not self.primed or int(cells_per_call) >= total:
+            ranges = [(0, total)]
+            self.primed = True
+        else:
+            k = max(1, int(cells_per_call))
+            a, b = self.cursor, self.cursor + k
+            ranges = [(a, min(b, total))] + ([(0, b - total)] if b > total else [])
+            self.cursor = b % total
+        dev = self.dens.device
+        n0 = min(self.CHUNK, max(r[1] - r[0] for r in ranges))
+        rays11 = torch.empty(n0, 11, device=dev, dtype=torch.float32)
+        z = torch.zeros(n0, 1, device=dev, dtype=torch.float32)
+        raws = [torch.empty(n0, 1, 4, device=dev, dtype=torch.float32) for _ in nets]
+        ws = torch.empty(2 * self.words.numel(), device=dev, dtype=torch.int32) if self.dilate > 0 else None
+        with torch.no_grad():
+            for lo, hi in ranges:
+                for c0 in range(lo, hi, n0):
+                    n = min(n0, hi - c0)
+                    ops.occ_cell_points(self._c, c0, rays11[:n], seed)
+                    for m, pk, raw in zip(nets, packed, raws):
+                        ops.mlp_fwd(rays11[:n], z[:n], m.flat, pk, raw=raw[:n])
+                    ops.occ_update(raws[0], raws[1] if len(raws) > 1 else None, c0, n, self.shape, self.decay, self.threshold,
+                                   self.dilate, self.dens, None)
+            # the bits of every cell and their dilation once, after the density of the last chunk
+            ops.occ_update(None, None, 0, 0, self.shape, self.decay, self.threshold, self.dilate, self.dens, self.words, ws)
+        self.updates += 1
 
     # ---- inspection -------------------------------------------------------------------------------------------------
     def to_mask(self):

@@ -735,6 +735,33 @@ def occ_classify(cgrid, rays11, z, raw=None):
     return idx, cnt
 
 
+def occ_cell_points(cgrid, c0, rays11, seed=0):
+    """One point inside each of the cells c0 .. c0 + len(rays11) - 1 of the grid as rays11 rows (o = point, rest 0): the cell's
+    centre (seed 0) or a Philox-jittered point keyed by (seed, cell)."""
+    require_gpu(rays11)
+    assert rays11.dim() == 2 and rays11.shape[1] == 11 and rays11.is_contiguous() and rays11.dtype == torch.float32
+    check(lib().fastnerf_occ_cell_points(cgrid, int(c0), rays11.shape[0], int(seed), ptr(rays11), stream()), 'fastnerf_occ_cell_points')
+    return rays11
+
+
+def occ_update(raw_c, raw_f, c0, n, shape, decay, threshold, dilate, dens, words, ws=None):
+    """dens = max(dens * decay, relu(sigma of raw_c), relu(sigma of raw_f)) on the cells c0 .. c0 + n - 1, then words = dens >
+    threshold over the whole grid, dilated by `dilate` cells.  words=None: the density only; n=0: the bits only.  In place; no host
+    round trip."""
+    require_gpu(raw_c, raw_f, dens, words, ws)
+    nx, ny, nz = (int(s) for s in shape)
+    nw = occ_words(nx, ny, nz)
+    assert dens.dtype == torch.float32 and dens.is_contiguous() and dens.numel() == nx * ny * nz
+    assert words is None or (words.dtype == torch.int32 and words.is_contiguous() and words.numel() == nw)
+    for r in (raw_c, raw_f):
+        assert r is None or (r.dtype == torch.float32 and r.is_contiguous() and r.numel() >= 4 * int(n))
+    if int(dilate) > 0 and ws is None and words is not None:
+        ws = torch.empty(2 * nw, device=dens.device, dtype=torch.int32)
+    assert ws is None or (ws.dtype == torch.int32 and ws.numel() >= 2 * nw)
+    check(lib().fastnerf_occ_update(ptr(raw_c), ptr(raw_f), int(c0), int(n), nx, ny, nz, float(decay), float(threshold), int(dilate),
+                                    ptr(dens), ptr(words), ptr(ws), stream()), 'fastnerf_occ_update')
+
+
 def mlp_fwd_list(rays11, z, params, packed_fwd, raw, live_idx, live_cnt, flags=0):
     """Inference forward over a point list (current math mode): raw[live_idx[j]] = logits of point live_idx[j], j < live_cnt[0]."""
     require_gpu(rays11, z, params, packed_fwd, raw, live_idx, live_cnt)

@@ -18,7 +18,7 @@ import torch
 
 from . import _lib, ops, parallel
 from .model import NeRF, noview_slices
-from .render import LivePolicy, _Workspace, _backward_core, _burn_seeds, _forward_core, _next_seed, render, render_path  # noqa: F401
+from .render import LivePolicy, _Workspace, get_compact, _backward_core, _burn_seeds, _forward_core, _next_seed, render, render_path  # noqa: F401
 from .run_nerf_helpers import get_embedder, img2mse, mse2psnr
 from .tree import QuadTreeManager
 
@@ -217,11 +217,23 @@ class Trainer:
     step(): render (perturbed, hierarchical) -> loss = mse(fine) + mse(coarse) -> analytic backward
     -> RCCL all-reduce(SUM) of the flat gradient (grads are pre-scaled by n_local/N_global, so the
     sum is the gradient of the global-batch mean) -> Adam over both nets in one launch -> LR decay
-    with the reference's pre-increment rule (run_nerf.py:498-508)."""
+    with the reference's pre-increment rule (run_nerf.py:498-508).
+
+    occupancy (opt-in; an occupancy.OccupancyGrid, usually OccupancyGrid.for_training()): the first forward of each pass
+    evaluates the networks on the samples in occupied cells only; a sample in an empty cell gets raw = (0, 0, 0, 0), whose
+    d(loss)/d(raw) is exactly zero, so the compacted backward needs no change.  The first `occupancy_warmup` steps leave the
+    grid untouched; from then on a grid with a density is refreshed (`grid.update`) every `occupancy_every` steps, by at most
+    `occupancy_cells` cells per refresh when that is set.  While a grid is set the step ALWAYS takes the compacted route:
+    LivePolicy still measures the live fraction but may not switch to the plain backward, which has no list to run over
+    (FASTNERF_COMPACT=0, one network shared by both passes and FASTNERF_FUSED_STEP=0 are ValueErrors), and
+    raw_noise_std > 0 is a ValueError (noise is added before the relu: a zero sigma is not a dead sample).
+    `occupancy_counts`: device int32 [4] = (occupied, total) samples of the coarse pass, then of the fine pass, of the last step
+    (None without a grid).  A step on an empty batch (a data-parallel tail) neither renders nor refreshes the grid."""
 
     def __init__(self, render_kwargs_train, H, W, K, near, far, lrate=5e-4, lrate_decay=250, decay=True,
-                 beta1=0.9, beta2=0.999, eps=1e-8):
+                 beta1=0.9, beta2=0.999, eps=1e-8, occupancy=None, occupancy_every=16, occupancy_warmup=256, occupancy_cells=None):
         kw = render_kwargs_train
+        self._kw = kw
         self.net_c = kw['network_fn']
         self.net_f = kw['network_fine']
         self.N_samples, self.N_importance = kw['N_samples'], kw['N_importance']
@@ -253,7 +265,26 @@ class Trainer:
         self.overlap_allreduce = os.environ.get('FASTNERF_OVERLAP_ALLREDUCE', '1') != '0'
         self._sa = None          # fn_step_args of the fused path
         self._sa_key = None
+        self.occupancy = occupancy
+        self.occupancy_every, self.occupancy_warmup = max(1, int(occupancy_every)), int(occupancy_warmup)
+        self.occupancy_cells = occupancy_cells
+        self.occupancy_counts = None if occupancy is None else torch.zeros(4, device=self.flat.device, dtype=torch.int32)
+        self.occupancy_steps = 0     # steps taken with the grid set
+        self._check_occupancy()
         self.repack()
+
+    def _check_occupancy(self):
+        if self.occupancy is None:
+            return
+        if self.raw_noise_std > 0.:
+            raise ValueError('Trainer: an occupancy grid cannot be combined with raw_noise_std > 0 (sigma noise is added before the '
+                             'relu, so a sample with zero sigma is not dead)')
+        if not self.fused:
+            raise ValueError('Trainer: an occupancy grid needs the fused step (two distinct networks with view directions, or a '
+                             'single pass; FASTNERF_FUSED_STEP unset)')
+        if get_compact() == '0' or not self.live.available(self.net_c, self.net_f, self.N_importance):
+            raise ValueError('Trainer: an occupancy grid needs the compacted step (FASTNERF_COMPACT=0 or one network shared by '
+                             'both passes rules it out): the plain backward has no list')
 
     def repack(self):
         self.pc = self.net_c.packed(refresh=True)
@@ -261,6 +292,8 @@ class Trainer:
 
     def forward_backward(self, rays_o, rays_d, target, leaf_tag=None, table=None, max_leaves=0, t_rand=None, u=None,
                          n_global=None):
+        if self.occupancy is not None:
+            raise ValueError('Trainer.forward_backward: the call-by-call route has no occupancy grid; use step()')
         n = rays_o.shape[0]
         dev = rays_o.device
         rays11 = ops.pack_rays(rays_o, rays_d, self.near, self.far, ndc=self.ndc, H=self.H, W=self.W,
@@ -301,6 +334,9 @@ class Trainer:
             self.repack()           # the math mode changed under this trainer
             self._sa_key = None
         live = self.live.use_live(self.net_c, self.net_f, Ni)
+        if self.occupancy is not None:
+            self._check_occupancy()
+            live = True             # the grid's first forward feeds the compacted backward only
         key = (n, str(dev), torch.cuda.current_stream(dev).cuda_stream, tag)
         a = self._sa
         if a is None or self._sa_key != key:
@@ -378,10 +414,27 @@ class Trainer:
         a.grad_scale = 1.0 if n_global is None else float(n) / float(n_global)
         a.live = int(live)
         a.fwd_flags = 1 if (live and self.skip_dead_rgb and noise0 is None) else 0
+        occ = self.occupancy
+        if occ is not None and self.occupancy_counts is None:      # a grid set after construction
+            self.occupancy_counts = torch.zeros(4, device=self.flat.device, dtype=torch.int32)
+        a.occ = None if occ is None else ctypes.addressof(occ._c)
+        a.occ_counts = None if occ is None else self.occupancy_counts.data_ptr()
+        hold.append(occ)
         self._hold = hold       # inputs stay referenced until the next step is prepared (the launches are asynchronous)
         out = _StepOut(block, self._regions, _OUT_NAMES_2 if Ni > 0 else _OUT_NAMES_1)
         loss2 = block[self._regions['loss2'][0]:self._regions['loss2'][0] + 2]
         return a, out, loss2, live
+
+    def _occupancy_tick(self):
+        """Before a step with the grid set: refresh it when its turn has come (a grid without a density is never touched)."""
+        k = self.occupancy_steps - self.occupancy_warmup
+        if self.occupancy.dens is not None and k >= 0 and k % self.occupancy_every == 0:
+            if ops.packed_tag(self.pc[0]) != ops.get_math():
+                self.repack()
+                self._sa_key = None
+            self.occupancy.update(self._kw, cells_per_call=self.occupancy_cells,
+                                  _packed=[self.pc[0]] + ([self.pf[0]] if (self.pf is not None and self.net_f is not self.net_c) else []))
+        self.occupancy_steps += 1
 
     def _fused_call(self, a, phases):
         _lib.check(_lib.lib().fastnerf_train_step(ctypes.byref(a), int(phases), _lib.stream()), 'fastnerf_train_step')
@@ -400,6 +453,8 @@ class Trainer:
         overlap = self.world > 1 and two and self.overlap_allreduce and self.grad.numel() == 2 * Nn
         fused = self.fused and n > 0
         self.adam_t += 1
+        if self.occupancy is not None and n > 0:
+            self._occupancy_tick()
         if fused:
             a, out, loss2, live = self._fused_prepare(rays_o, rays_d, target, leaf_tag, table, max_leaves, t_rand, u, n_global)
             a.lr, a.adam_t = float(self.lr), int(self.adam_t)
@@ -580,7 +635,13 @@ def train(images, poses, H, W, focal, args, near=2., far=6., device='cuda', log=
     bds_dict = {'near': near, 'far': far}   # run_nerf.py:267-272: the bounds travel in both kwargs dicts
     kw_train.update(bds_dict)
     kw_test.update(bds_dict)
-    trainer = Trainer(kw_train, H, W, K, near, far, lrate=args.lrate, lrate_decay=args.lrate_decay)
+    occ_kw = {}
+    if getattr(args, 'occupancy_train', False):     # opt-in (no such flag in the reference's parser): train through an occupancy grid
+        from .occupancy import OccupancyGrid
+        occ_kw = dict(occupancy=OccupancyGrid.for_training(N=getattr(args, 'occupancy_N', 128), bound=getattr(args, 'occupancy_bound', 1.2),
+                                                           device=dev),
+                      occupancy_every=getattr(args, 'occupancy_every', 16), occupancy_warmup=getattr(args, 'occupancy_warmup', 256))
+    trainer = Trainer(kw_train, H, W, K, near, far, lrate=args.lrate, lrate_decay=args.lrate_decay, **occ_kw)
     trainer.global_iter = global_iter
     if len(optimizer.state_dict()['state']) > 0:   # create_nerf restored a checkpoint (ours or the reference's)
         trainer.load_torch_optimizer(optimizer)

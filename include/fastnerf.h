@@ -369,11 +369,15 @@ int fastnerf_mlp_x6_bwd_live(int kind, int64_t n, int S, const float* draw, cons
  * (grads + net_floats) on a side stream, FN_STEP_BWD_COARSE runs beside it, all-reduce of the coarse half, FN_STEP_UPDATE.
  * Two distinct NeRF nets with view directions (or one net when N_importance == 0); coarse net first in params / grads /
  * adam_m / adam_v (the order of `grad_vars`, run_nerf.py:87-97).  Buffer shapes are those of the individual entry points;
- * act0 / act1 are used by the plain backward (live == 0), act_ws / live_ws / counts by the compacted one (live != 0). */
+ * act0 / act1 are used by the plain backward (live == 0), act_ws / live_ws / counts by the compacted one (live != 0).
+ * With `occ` set (a compacted step only: -1 with live == 0, whose backward has no list, and with sigma noise, which is added
+ * before the relu so that a zero sigma is not a dead sample) a sample in a cell whose bit is clear gets raw = (0,0,0,0) without
+ * the network being run; d(loss)/d(raw) of such a sample is exactly zero, so the live list is a subset of the occupied list. */
 #define FN_STEP_FORWARD 1     /* pack rays, forward, loss + d(loss)/d(rgb maps) + leaf table */
 #define FN_STEP_BWD_FINE 2    /* backward of the fine pass -> grads + net_floats (no-op when N_importance == 0) */
 #define FN_STEP_BWD_COARSE 4  /* backward of the coarse pass -> grads */
 #define FN_STEP_UPDATE 8      /* Adam over both nets + re-pack of their weights */
+struct fn_occ_grid; /* the occupancy grid, declared below */
 typedef struct fn_step_args {
   /* the batch */
   int64_t n;
@@ -399,6 +403,11 @@ typedef struct fn_step_args {
   int32_t live;                                     /* != 0: forward without saving + compacted backward */
   int32_t fwd_flags;                                /* FN_FWD_* of the first forward of a compacted step */
   int32_t max_leaves, adam_t;
+  /* training through an occupancy grid (declared below; live != 0 and no sigma noise): the first forward of each pass runs over
+   * the occupied samples only, as fastnerf_render_rays_fwd_occ does; occ_counts: NULL or 4 int32 = (occupied, total) of the
+   * coarse pass, then of the fine pass.  NULL / NULL: the step without a grid. */
+  const struct fn_occ_grid* occ;
+  int32_t* occ_counts;
 } fn_step_args;
 int64_t fastnerf_step_args_size(void);              /* sizeof(fn_step_args): binding sanity check */
 int fastnerf_train_step(const fn_step_args* args, int phases, fn_stream_t stream);
@@ -460,7 +469,7 @@ int fastnerf_mc_emit(const float* vol, int64_t nx, int64_t ny, int64_t nz, float
 int fastnerf_mc_tables(int8_t* tri_host, uint16_t* edge_host);
 
 
-/* ---- occupancy grid: rendering that does not evaluate the network in empty space (inference only) -----------------------
+/* ---- occupancy grid: rendering (and, opted into, training) that does not evaluate the network in empty space -----------------------
  * The grid: a box [lo, hi) in the network's input space (world space, or NDC space for LLFF scenes) cut into
  * n[0] x n[1] x n[2] cells, one bit per cell (fastnerf_occ_words() uint32 words; the bit layout is the library's), and
  * `outside_occupied`.  The cell index of a point x along an axis is floor((x - lo) * inv), subtraction and product each
@@ -492,6 +501,24 @@ int fastnerf_occ_from_mask(const uint8_t* mask, int64_t nx, int64_t ny, int64_t 
 int fastnerf_occ_query(const fn_occ_grid* grid, int64_t n, const float* pts, uint8_t* out, fn_stream_t stream);
 int fastnerf_occ_classify(const fn_occ_grid* grid, int64_t n, int S, const float* rays11, const float* z, int32_t* live_idx,
                           int32_t* count_out, float* raw, int32_t* ws, fn_stream_t stream);
+/* A grid that is kept while the networks train (fn_step_args.occ): a persistent density dens[nx*ny*nz] (fp32, cell order
+ * c = (i*ny + j)*nz + k) beside the bits.
+ *   fastnerf_occ_cell_points  one point inside each of the cells c0 .. c0+n-1, as rays11 rows [n,11] in the layout of
+ *                           fastnerf_grid_points (o = point, everything else 0).  Per axis x = lo + (index + jitter) / inv, each
+ *                           operation rounded to fp32; jitter = 0.5 when seed == 0, else a Philox4x32-10 draw in [0,1) keyed by
+ *                           (seed, cell): the same seed gives the same bits.  Where rounding would put x into a neighbouring cell
+ *                           the jitter is clamped towards 0.5, so that fastnerf_occ_query of the point names the cell (for every
+ *                           grid whose cells are wider than a few fp32 steps of their coordinates).  grid->words is not read.
+ *   fastnerf_occ_update     raw_c / raw_f: [n,4] logits of the coarse / fine network (raw_f may be NULL) at the points of the
+ *                           cells c0 .. c0+n-1.  dens[c] = max(dens[c] * decay, relu(sigma_c), relu(sigma_f)) for those cells
+ *                           (a NaN sigma counts as 0), every other cell keeps its value; then, in the same launch, the bit of
+ *                           EVERY cell becomes dens > threshold, and the dilation of fastnerf_occ_build follows.  ws: 2 *
+ *                           fastnerf_occ_words() uint32 (NULL allowed when dilate == 0).  n == 0 re-derives the bits only;
+ *                           words == NULL updates the density only (a refresh in several chunks derives the bits once, at its
+ *                           end). */
+int fastnerf_occ_cell_points(const fn_occ_grid* grid, int64_t c0, int64_t n, uint64_t seed, float* rays11, fn_stream_t stream);
+int fastnerf_occ_update(const float* raw_c, const float* raw_f, int64_t c0, int64_t n, int64_t nx, int64_t ny, int64_t nz,
+                        float decay, float threshold, int dilate, float* dens, uint32_t* words, uint32_t* ws, fn_stream_t stream);
 /* NeRF.forward + Embedder.embed (model.py:38-63) of the points live_idx[0 .. *live_cnt) only, inference (nothing saved):
  * raw[live_idx[j]*4 .. +3] = the logits the plain forward gives that point; no other element of raw is written.  kind 0 only.
  * flags as fastnerf_mlp_fwd_flags_ex, a tile being 64 consecutive list entries.  _ex: exact fp32, bf16: split-bf16 (x3),
