@@ -40,6 +40,14 @@ class OccGrid(C.Structure):
     _fields_ = [('words', P), ('lo', F * 3), ('inv', F * 3), ('n', C.c_int32 * 3), ('outside_occupied', C.c_int32)]
 
 
+OCC_MAX_LEVELS = 8      # FN_OCC_MAX_LEVELS
+
+
+class OccCascade(C.Structure):
+    """fn_occ_cascade of include/fastnerf.h, field for field."""
+    _fields_ = [('levels', C.c_int32), ('reserved', C.c_int32), ('level', OccGrid * OCC_MAX_LEVELS)]
+
+
 STEP_FORWARD, STEP_BWD_FINE, STEP_BWD_COARSE, STEP_UPDATE = 1, 2, 4, 8
 
 # name -> (restype, argtypes); mirrors include/fastnerf.h one to one
@@ -138,12 +146,15 @@ SIGNATURES = {
     'fastnerf_occ_from_mask': (I, [P, L, L, L, P, P]),
     'fastnerf_occ_query': (I, [C.POINTER(OccGrid), L, P, P, P]),
     'fastnerf_occ_classify': (I, [C.POINTER(OccGrid), L, I, P, P, P, P, P, P, P]),
+    'fastnerf_occ_query_cascade': (I, [C.POINTER(OccCascade), L, P, P, P]),
+    'fastnerf_occ_classify_cascade': (I, [C.POINTER(OccCascade), L, I, P, P, P, P, P, P, P]),
     'fastnerf_occ_cell_points': (I, [C.POINTER(OccGrid), L, L, U64, P, P]),
     'fastnerf_occ_update': (I, [P, P, L, L, L, L, L, F, F, I, P, P, P, P]),
     'fastnerf_mlp_fwd_list_ex': (I, [I, L, I, P, P, P, P, P, P, P, I, P]),
     'fastnerf_mlp_bf16_fwd_list': (I, [I, L, I, P, P, P, P, P, P, P, I, P]),
     'fastnerf_mlp_x6_fwd_list': (I, [I, L, I, P, P, P, P, P, P, P, I, P]),
     'fastnerf_render_rays_fwd_occ': (I, [I, L, I, I, P, I, I, I, I, P, P, U64, U64, P, P, P, P, C.POINTER(OccGrid), P, P] + [P] * 16 + [I, P]),
+    'fastnerf_render_rays_fwd_occ_cascade': (I, [I, L, I, I, P, I, I, I, I, P, P, U64, U64, P, P, P, P, C.POINTER(OccCascade), P, P] + [P] * 16 + [I, P]),
 }
 
 _lib = None

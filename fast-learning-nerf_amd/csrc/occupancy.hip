@@ -22,6 +22,11 @@
 //   occ_count / scatter  the samples o + d * z of a pass: per-block counts -> (the scan of train.hip) -> ascending list of the
 //                        occupied sample indices; the others get raw = (0, 0, 0, 0).  The shape of fastnerf_compact_live with
 //                        another predicate: deterministic, no atomics, the list length stays on the device.
+//   occ_*_cascade       the query / count / scatter kernels over a cascade of up to 8 grids: a point takes the bit of the FIRST
+//                        level whose box contains it, `outside` when none does.  The descriptors travel by value in the kernel
+//                        argument (8 x 40 bytes of geometry, 8 pointers) and are read through scalar loads: the level loop's
+//                        bounds and counter are wave-uniform, each lane leaves it at its own level.  Separate kernels: the
+//                        single-grid ones above keep their instructions.
 // All of them are memory bound and small next to the MLP they spare: one lane per cell / point / four consecutive samples, a
 // ray's 44 bytes come through the cache for all its samples.
 #include "common.h"
@@ -43,6 +48,20 @@ struct OccDev {
   int outside;
 };
 
+// a cascade (fn_occ_cascade): per level the geometry of OccDev (40 bytes) and, apart from it, the pointer to its bits
+struct OccLevel {
+  float lo[3], inv[3];
+  int n[3];
+  int pad;
+};
+
+struct OccCascadeDev {
+  OccLevel g[FN_OCC_MAX_LEVELS];
+  const uint32_t* words[FN_OCC_MAX_LEVELS];
+  int levels;
+  int outside;
+};
+
 struct OccDims {
   int nx, ny, nz;
   int64_t ncells, nwords;
@@ -57,6 +76,20 @@ __device__ __forceinline__ bool occ_point(const OccDev& g, float x, float y, flo
   const bool inside = fi >= 0.f && fi < (float)g.n[0] && fj >= 0.f && fj < (float)g.n[1] && fk >= 0.f && fk < (float)g.n[2];
   if (!inside) return g.outside != 0;
   return occ_bit(g.words, ((uint32_t)fi * (uint32_t)g.n[1] + (uint32_t)fj) * (uint32_t)g.n[2] + (uint32_t)fk);
+}
+
+// first level whose box contains the point decides; l and c.levels are uniform, so g[l] and words[l] are scalar loads
+__device__ __forceinline__ bool occ_point(const OccCascadeDev& c, float x, float y, float z) {
+  for (int l = 0; l < c.levels; ++l) {
+    const OccLevel& g = c.g[l];
+    const float fi = floorf(fmul(fsub(x, g.lo[0]), g.inv[0]));
+    const float fj = floorf(fmul(fsub(y, g.lo[1]), g.inv[1]));
+    const float fk = floorf(fmul(fsub(z, g.lo[2]), g.inv[2]));
+    // (& not &&: one straight-line test per level, its 40 bytes of geometry fetched by one batch of scalar loads)
+    if ((fi >= 0.f) & (fi < (float)g.n[0]) & (fj >= 0.f) & (fj < (float)g.n[1]) & (fk >= 0.f) & (fk < (float)g.n[2]))
+      return occ_bit(c.words[l], ((uint32_t)fi * (uint32_t)g.n[1] + (uint32_t)fj) * (uint32_t)g.n[2] + (uint32_t)fk);
+  }
+  return c.outside != 0;
 }
 
 // the block's 256 predicate bits -> 8 words; every thread of the block calls it (c is the thread's cell, b false beyond the grid)
@@ -112,6 +145,12 @@ __global__ void __launch_bounds__(OCC_BLOCK) occ_dilate_kernel(const uint32_t* _
 }
 
 __global__ void __launch_bounds__(OCC_BLOCK) occ_query_kernel(OccDev g, int64_t n, const float* __restrict__ pts, uint8_t* __restrict__ out) {
+  for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n; q += (int64_t)gridDim.x * blockDim.x)
+    out[q] = occ_point(g, pts[q * 3], pts[q * 3 + 1], pts[q * 3 + 2]) ? 1 : 0;
+}
+
+__global__ void __launch_bounds__(OCC_BLOCK) occ_query_cascade_kernel(OccCascadeDev g, int64_t n, const float* __restrict__ pts,
+                                                                      uint8_t* __restrict__ out) {
   for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n; q += (int64_t)gridDim.x * blockDim.x)
     out[q] = occ_point(g, pts[q * 3], pts[q * 3 + 1], pts[q * 3 + 2]) ? 1 : 0;
 }
@@ -181,7 +220,8 @@ __global__ void __launch_bounds__(OCC_BLOCK) occ_update_kernel(const float* __re
 }
 
 // bits 0..3: samples p0 .. p0+3 of the pass are occupied (x = o + d * z as the MLP kernels compute it)
-__device__ __forceinline__ unsigned occ_flags(const OccDev& g, const float* __restrict__ rays, const float* __restrict__ zv, uint32_t S,
+template <class G>
+__device__ __forceinline__ unsigned occ_flags(const G& g, const float* __restrict__ rays, const float* __restrict__ zv, uint32_t S,
                                               int64_t p0, int64_t n) {
   unsigned f = 0;
 #pragma unroll
@@ -230,6 +270,44 @@ __global__ void __launch_bounds__(OCC_BLOCK) occ_scatter_kernel(OccDev g, int64_
   }
 }
 
+// The cascade's count and scatter: the bodies above, word for word, over occ_flags<OccCascadeDev>.  Written out a second time
+// on purpose: routing both through one templated body reorders a few instructions of the single-grid kernels, which the training step
+// launches and which stay instruction-identical; so do forceinline helpers for the block reduce and the block scan alone.  A fix
+// to one body goes into the other too.
+__global__ void __launch_bounds__(OCC_BLOCK) occ_count_cascade_kernel(OccCascadeDev g, int64_t n, int S, const float* __restrict__ rays,
+                                                                      const float* __restrict__ zv, int* __restrict__ blk) {
+  __shared__ int red[4];
+  const unsigned f = occ_flags(g, rays, zv, (uint32_t)S, (int64_t)blockIdx.x * OCC_PTS + threadIdx.x * 4, n);
+  int c = __popc(f);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) blk[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+
+__global__ void __launch_bounds__(OCC_BLOCK) occ_scatter_cascade_kernel(OccCascadeDev g, int64_t n, int S, const float* __restrict__ rays,
+                                                                        const float* __restrict__ zv, const int* __restrict__ blk,
+                                                                        int* __restrict__ live_idx, float* __restrict__ raw) {
+  __shared__ int wsum[4];
+  const int64_t p0 = (int64_t)blockIdx.x * OCC_PTS + threadIdx.x * 4;
+  const unsigned f = occ_flags(g, rays, zv, (uint32_t)S, p0, n);
+  const int c = __popc(f);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int x = c;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(x, o, 64); if (lane >= o) x += t; }
+  if (lane == 63) wsum[w] = x;
+  __syncthreads();
+  int pos = blk[blockIdx.x] + x - c;
+  for (int k = 0; k < w; ++k) pos += wsum[k];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (f & (1u << k)) live_idx[pos++] = (int)(p0 + k);
+    else if (raw && p0 + k < n) *reinterpret_cast<float4*>(raw + (p0 + k) * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------
 bool occ_dims(int64_t nx, int64_t ny, int64_t nz, OccDims* d) {
   if (nx < 1 || ny < 1 || nz < 1 || nx > (1 << 24) || ny > (1 << 24) || nz > (1 << 24)) return false;
@@ -258,6 +336,25 @@ bool occ_geom(const fn_occ_grid* g, OccDev* o) {
 }
 
 bool occ_dev(const fn_occ_grid* g, OccDev* o) { return g && g->words && occ_geom(g, o); }
+
+// every level passes occ_dev's checks; the cascade's `outside` is the LAST level's outside_occupied
+bool occ_cascade_dev(const fn_occ_cascade* c, OccCascadeDev* o) {
+  if (!c || c->levels < 1 || c->levels > FN_OCC_MAX_LEVELS) return false;
+  *o = OccCascadeDev{};
+  for (int l = 0; l < c->levels; ++l) {
+    OccDev d;
+    if (!occ_dev(&c->level[l], &d)) return false;
+    for (int a = 0; a < 3; ++a) {
+      o->g[l].lo[a] = d.lo[a];
+      o->g[l].inv[a] = d.inv[a];
+      o->g[l].n[a] = d.n[a];
+    }
+    o->words[l] = d.words;
+    o->outside = d.outside;
+  }
+  o->levels = c->levels;
+  return true;
+}
 
 inline unsigned occ_blocks(int64_t ncells) { return (unsigned)((ncells + OCC_BLOCK - 1) / OCC_BLOCK); }
 
@@ -361,6 +458,45 @@ extern "C" int fastnerf_occ_classify(const fn_occ_grid* grid, int64_t n, int S, 
   hipLaunchKernelGGL(occ_count_kernel, dim3(nb), dim3(OCC_BLOCK), 0, s, g, P, S, rays11, z, ws);
   fn::cp_scan_launch(nb, ws, count_out, (int)P, s);
   hipLaunchKernelGGL(occ_scatter_kernel, dim3(nb), dim3(OCC_BLOCK), 0, s, g, P, S, rays11, z, (const int*)ws, live_idx, raw);
+  FN_LAUNCH_CHECK();
+  return 0;
+}
+
+#define OCC_CASCADE_ARG "cascade: 1 <= levels <= 8; every level: non-null words, 1 <= n[i] <= 2^24, fewer than 2^31 cells, finite lo, finite inv > 0"
+
+// render.cpp checks a cascade before it enqueues anything: NULL when every level is usable, else what is asked of one
+namespace fn {
+const char* occ_cascade_fault(const fn_occ_cascade* c) {
+  OccCascadeDev d;
+  return occ_cascade_dev(c, &d) ? nullptr : OCC_CASCADE_ARG;
+}
+}  // namespace fn
+
+extern "C" int fastnerf_occ_query_cascade(const fn_occ_cascade* cascade, int64_t n, const float* pts, uint8_t* out, fn_stream_t stream) {
+  OccCascadeDev g;
+  FN_CHECK_ARG(occ_cascade_dev(cascade, &g), OCC_CASCADE_ARG);
+  FN_CHECK_ARG(n >= 0, "n >= 0");
+  if (n == 0) return 0;
+  FN_CHECK_ARG(pts && out, "non-null pointers");
+  const int64_t blocks = (n + OCC_BLOCK - 1) / OCC_BLOCK;
+  hipLaunchKernelGGL(occ_query_cascade_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(OCC_BLOCK), 0, fn::S(stream), g, n, pts,
+                     out);
+  FN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fastnerf_occ_classify_cascade(const fn_occ_cascade* cascade, int64_t n, int S, const float* rays11, const float* z,
+                                             int32_t* live_idx, int32_t* count_out, float* raw, int32_t* ws, fn_stream_t stream) {
+  OccCascadeDev g;
+  FN_CHECK_ARG(occ_cascade_dev(cascade, &g), OCC_CASCADE_ARG);
+  FN_CHECK_ARG(n > 0 && S >= 1 && n * (int64_t)S < ((int64_t)1 << 31), "n > 0, S >= 1, n * S < 2^31");
+  FN_CHECK_ARG(rays11 && z && live_idx && count_out && ws, "non-null pointers");
+  const int64_t P = n * (int64_t)S;
+  const int nb = (int)((P + OCC_PTS - 1) / OCC_PTS);
+  hipStream_t s = fn::S(stream);
+  hipLaunchKernelGGL(occ_count_cascade_kernel, dim3(nb), dim3(OCC_BLOCK), 0, s, g, P, S, rays11, z, ws);
+  fn::cp_scan_launch(nb, ws, count_out, (int)P, s);
+  hipLaunchKernelGGL(occ_scatter_cascade_kernel, dim3(nb), dim3(OCC_BLOCK), 0, s, g, P, S, rays11, z, (const int*)ws, live_idx, raw);
   FN_LAUNCH_CHECK();
   return 0;
 }

@@ -4,7 +4,10 @@
 #include <stdint.h>
 #include "../../include/fastnerf.h"
 
-namespace fn { void set_error(const char* fmt, ...); }
+namespace fn {
+void set_error(const char* fmt, ...);
+const char* occ_cascade_fault(const fn_occ_cascade* c);   // occupancy.hip
+}
 
 extern "C" int fastnerf_render_rays_fwd_ex(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11,
                                         int lindisp, int perturb, int det, int white_bkgd, const float* t_rand, const float* u,
@@ -55,39 +58,46 @@ extern "C" int fastnerf_render_rays_fwd_ex(int math_mode, int64_t n, int N_sampl
   return fastnerf_raw2outputs_fwd(n, S1, raw1, z1, rays11, noise1, white_bkgd, rgb1, disp1, acc1, w1, depth1, stream);
 }
 
-// The same chain through an occupancy grid (inference): per pass, the samples are sorted by the grid (fastnerf_occ_classify:
-// list of the occupied ones, zero logits for the others) and the network runs over the list only.
-extern "C" int fastnerf_render_rays_fwd_occ(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11, int lindisp,
-                                            int perturb, int det, int white_bkgd, const float* t_rand, const float* u, uint64_t seed0,
-                                            uint64_t seed1, const float* params_c, const float* packed_c, const float* params_f,
-                                            const float* packed_f, const fn_occ_grid* grid, int32_t* live_ws, int32_t* counts_out,
-                                            float* z0, float* raw0, float* rgb0, float* disp0, float* acc0, float* w0, float* depth0,
-                                            float* z1, float* z_samples, float* z_std, float* raw1, float* rgb1, float* disp1,
-                                            float* acc1, float* w1, float* depth1, int flags, fn_stream_t stream) {
+// The same chain through an occupancy grid or a cascade of them (inference): per pass, the samples are sorted by it
+// (fastnerf_occ_classify / _cascade: list of the occupied ones, zero logits for the others) and the network runs over the list only.
+// One body for both entry points: exactly one of grid / cascade is set, `fname` names the caller in the error texts.
+static int rr_fwd_occ(const char* fname, int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11, int lindisp,
+                      int perturb, int det, int white_bkgd, const float* t_rand, const float* u, uint64_t seed0, uint64_t seed1,
+                      const float* params_c, const float* packed_c, const float* params_f, const float* packed_f,
+                      const fn_occ_grid* grid, const fn_occ_cascade* cascade, int32_t* live_ws, int32_t* counts_out, float* z0,
+                      float* raw0, float* rgb0, float* disp0, float* acc0, float* w0, float* depth0, float* z1, float* z_samples,
+                      float* z_std, float* raw1, float* rgb1, float* disp1, float* acc1, float* w1, float* depth1, int flags,
+                      fn_stream_t stream) {
   if (math_mode < 0 || math_mode > 2 || n < 0 || N_samples < 2 || N_importance < 0) {
-    fn::set_error("fastnerf_render_rays_fwd_occ: bad argument: math_mode in {0,1,2}, n>=0, N_samples>=2, N_importance>=0");
+    fn::set_error("%s: bad argument: math_mode in {0,1,2}, n>=0, N_samples>=2, N_importance>=0", fname);
     return -1;
   }
   if (N_importance > 0 && N_samples < 3) {
-    fn::set_error("fastnerf_render_rays_fwd_occ: hierarchical sampling needs N_samples >= 3 (the inner weights of 2 samples are empty)");
+    fn::set_error("%s: hierarchical sampling needs N_samples >= 3 (the inner weights of 2 samples are empty)", fname);
     return -1;
   }
   if (n == 0) return 0;
   const int S1 = N_samples + N_importance;
   if (n * (int64_t)S1 >= ((int64_t)1 << 31)) {
-    fn::set_error("fastnerf_render_rays_fwd_occ: bad argument: n * (N_samples + N_importance) < 2^31 (lists index points with int32)");
+    fn::set_error("%s: bad argument: n * (N_samples + N_importance) < 2^31 (lists index points with int32)", fname);
     return -1;
   }
-  if (!rays11 || !params_c || !packed_c || !grid || !live_ws || !counts_out || !z0 || !raw0 || !rgb0 || !disp0 || !acc0 || !w0 ||
-      !depth0) {
-    fn::set_error("fastnerf_render_rays_fwd_occ: null pointer (coarse pass)");
+  if (!rays11 || !params_c || !packed_c || (!grid && !cascade) || !live_ws || !counts_out || !z0 || !raw0 || !rgb0 || !disp0 || !acc0 ||
+      !w0 || !depth0) {
+    fn::set_error("%s: null pointer (coarse pass)", fname);
+    return -1;
+  }
+  if (const char* fault = cascade ? fn::occ_cascade_fault(cascade) : nullptr) {   // before anything is enqueued
+    fn::set_error("%s: bad argument: %s", fname, fault);
     return -1;
   }
   int32_t* idx = live_ws;
   int32_t* cws = live_ws + n * (int64_t)S1;
   int rc;
   auto mlp = [&](int S, const float* z, const float* params, const float* packed, float* raw, int32_t* cnt) -> int {
-    if ((rc = fastnerf_occ_classify(grid, n, S, rays11, z, idx, cnt, raw, cws, stream))) return rc;
+    if ((rc = cascade ? fastnerf_occ_classify_cascade(cascade, n, S, rays11, z, idx, cnt, raw, cws, stream)
+                      : fastnerf_occ_classify(grid, n, S, rays11, z, idx, cnt, raw, cws, stream)))
+      return rc;
     if (math_mode == 2) return fastnerf_mlp_x6_fwd_list(0, n, S, rays11, z, params, packed, raw, idx, cnt, flags, stream);
     return math_mode ? fastnerf_mlp_bf16_fwd_list(0, n, S, rays11, z, params, packed, raw, idx, cnt, flags, stream)
                      : fastnerf_mlp_fwd_list_ex(0, n, S, rays11, z, params, packed, raw, idx, cnt, flags, stream);
@@ -98,13 +108,38 @@ extern "C" int fastnerf_render_rays_fwd_occ(int math_mode, int64_t n, int N_samp
     return rc;
   if (N_importance == 0) return 0;
   if (!params_f || !packed_f || !z1 || !z_samples || !z_std || !raw1 || !rgb1 || !disp1 || !acc1 || !w1 || !depth1) {
-    fn::set_error("fastnerf_render_rays_fwd_occ: null pointer (fine pass)");
+    fn::set_error("%s: null pointer (fine pass)", fname);
     return -1;
   }
   if ((rc = fastnerf_sample_pdf_merge(n, N_samples, N_importance, z0, w0, det, u, seed1, z1, z_samples, z_std, stream)))
     return rc;
   if ((rc = mlp(S1, z1, params_f, packed_f, raw1, counts_out + 2))) return rc;
   return fastnerf_raw2outputs_fwd(n, S1, raw1, z1, rays11, nullptr, white_bkgd, rgb1, disp1, acc1, w1, depth1, stream);
+}
+
+extern "C" int fastnerf_render_rays_fwd_occ(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11, int lindisp,
+                                            int perturb, int det, int white_bkgd, const float* t_rand, const float* u, uint64_t seed0,
+                                            uint64_t seed1, const float* params_c, const float* packed_c, const float* params_f,
+                                            const float* packed_f, const fn_occ_grid* grid, int32_t* live_ws, int32_t* counts_out,
+                                            float* z0, float* raw0, float* rgb0, float* disp0, float* acc0, float* w0, float* depth0,
+                                            float* z1, float* z_samples, float* z_std, float* raw1, float* rgb1, float* disp1,
+                                            float* acc1, float* w1, float* depth1, int flags, fn_stream_t stream) {
+  return rr_fwd_occ("fastnerf_render_rays_fwd_occ", math_mode, n, N_samples, N_importance, rays11, lindisp, perturb, det, white_bkgd,
+                    t_rand, u, seed0, seed1, params_c, packed_c, params_f, packed_f, grid, nullptr, live_ws, counts_out, z0, raw0, rgb0,
+                    disp0, acc0, w0, depth0, z1, z_samples, z_std, raw1, rgb1, disp1, acc1, w1, depth1, flags, stream);
+}
+
+extern "C" int fastnerf_render_rays_fwd_occ_cascade(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11,
+                                                    int lindisp, int perturb, int det, int white_bkgd, const float* t_rand,
+                                                    const float* u, uint64_t seed0, uint64_t seed1, const float* params_c,
+                                                    const float* packed_c, const float* params_f, const float* packed_f,
+                                                    const fn_occ_cascade* cascade, int32_t* live_ws, int32_t* counts_out, float* z0,
+                                                    float* raw0, float* rgb0, float* disp0, float* acc0, float* w0, float* depth0,
+                                                    float* z1, float* z_samples, float* z_std, float* raw1, float* rgb1, float* disp1,
+                                                    float* acc1, float* w1, float* depth1, int flags, fn_stream_t stream) {
+  return rr_fwd_occ("fastnerf_render_rays_fwd_occ_cascade", math_mode, n, N_samples, N_importance, rays11, lindisp, perturb, det,
+                    white_bkgd, t_rand, u, seed0, seed1, params_c, packed_c, params_f, packed_f, nullptr, cascade, live_ws, counts_out,
+                    z0, raw0, rgb0, disp0, acc0, w0, depth0, z1, z_samples, z_std, raw1, rgb1, disp1, acc1, w1, depth1, flags, stream);
 }
 
 // Backward of the same chain (autograd of render.py:238-299 w.r.t. the network parameters; sample positions are

@@ -12,13 +12,42 @@ sample whose bit is set gets exactly the logits of the plain forward.  The kerne
 Training (opt-in): a grid made by `OccupancyGrid.for_training` starts fully occupied and carries a per-cell density `dens`;
 `run_nerf.Trainer(..., occupancy=grid)` runs the first forward of its compacted step over the occupied samples only and calls
 `grid.update` as training goes: dens = max(dens * decay, relu(sigma)) at a jittered point INSIDE each cell, bit = dens >
-threshold, dilated.  render_rays(..., occupancy=grid) with gradients enabled still raises: the autograd route has no grid."""
+threshold, dilated.  render_rays(..., occupancy=grid) with gradients enabled still raises: the autograd route has no grid.
+
+Cascade (rendering only): `OccupancyCascade` is an ordered list of 1 to 8 such grids, innermost first -- usually the fine grid
+over the object and coarser grids over larger boxes around it.  A sample takes the bit of the FIRST grid whose box contains it
+(each grid's own index arithmetic), and `outside_occupied` of the cascade when none does.  Space outside the inner box is then
+skipped because it was looked at and found empty, not because it was assumed empty.
+
+    cascade = fastnerf.occupancy.OccupancyCascade.from_network(render_kwargs_test, levels=3)
+    render_kwargs_test['occupancy'] = cascade"""
 import ctypes as C
 
 import numpy as np
 import torch
 
 from . import _lib, ops
+
+
+def _network_volume(render_kwargs, N, bound, which='both', chunk=1024 * 64):
+    """relu(sigma) of the networks of `render_kwargs` on linspace(-bound, bound, N+1)^3 (mesh.density_grid): the point volume that
+    OccupancyGrid.from_network and every level of OccupancyCascade.from_network are built from.  which: 'both' = the element-wise
+    maximum of the coarse and the fine network's volumes, or 'fine' / 'coarse'."""
+    from . import mesh
+    if which not in ('both', 'fine', 'coarse'):
+        raise ValueError("which is 'both', 'fine' or 'coarse'")
+    nets = []
+    if which in ('both', 'coarse') or render_kwargs.get('network_fine') is None:
+        nets.append(render_kwargs['network_fn'])
+    if which in ('both', 'fine') and render_kwargs.get('network_fine') is not None:
+        nets.append(render_kwargs['network_fine'])
+    t = torch.linspace(-bound, bound, N + 1, device='cuda')
+    vol = None
+    for net in nets:
+        v = mesh.density_grid(net, t, t, t, chunk=chunk, network_query_fn=render_kwargs.get('network_query_fn'),
+                              use_viewdirs=render_kwargs.get('use_viewdirs'))
+        vol = v if vol is None else torch.maximum(vol, v)
+    return vol
 
 
 class OccupancyGrid:
@@ -86,21 +115,7 @@ class OccupancyGrid:
         """N^3 cells over [-bound, bound)^3 from relu(sigma) on linspace(-bound, bound, N+1)^3 (mesh.density_grid).  which:
         'both' (default) = the element-wise maximum of the coarse and the fine network's volumes -- the coarse pass is masked
         by the same grid -- or 'fine' / 'coarse'."""
-        from . import mesh
-        if which not in ('both', 'fine', 'coarse'):
-            raise ValueError("which is 'both', 'fine' or 'coarse'")
-        nets = []
-        if which in ('both', 'coarse') or render_kwargs.get('network_fine') is None:
-            nets.append(render_kwargs['network_fn'])
-        if which in ('both', 'fine') and render_kwargs.get('network_fine') is not None:
-            nets.append(render_kwargs['network_fine'])
-        t = torch.linspace(-bound, bound, N + 1, device='cuda')
-        vol = None
-        for net in nets:
-            v = mesh.density_grid(net, t, t, t, chunk=chunk, network_query_fn=render_kwargs.get('network_query_fn'),
-                                  use_viewdirs=render_kwargs.get('use_viewdirs'))
-            vol = v if vol is None else torch.maximum(vol, v)
-        return cls.from_density(vol, -bound, bound, threshold, dilate, outside_occupied)
+        return cls.from_density(_network_volume(render_kwargs, N, bound, which, chunk), -bound, bound, threshold, dilate, outside_occupied)
 
     @classmethod
     def for_training(cls, N=128, bound=1.2, threshold=0., dilate=1, decay=0.95, outside_occupied=True, device='cuda'):
@@ -120,18 +135,24 @@ class OccupancyGrid:
     @classmethod
     def load(cls, path, device='cuda'):
         with np.load(path) as f:
-            words = torch.from_numpy(f['words'].astype(np.uint32).view(np.int32)).to(device)
-            if 'dens' not in f.files:
-                return cls(words, f['shape'].tolist(), f['lo'], f['hi'], bool(f['outside_occupied']))
-            g = cls(words, f['shape'].tolist(), f['lo'], f['hi'], bool(f['outside_occupied']),
-                    dens=torch.from_numpy(f['dens'].astype(np.float32)).to(device), decay=float(f['decay']),
-                    threshold=float(f['threshold']), dilate=int(f['dilate']))
-            g.updates, g.cursor, g.primed = int(f['updates']), int(f['cursor']), bool(f['primed'])
-            return g
+            if 'levels' in f.files:
+                raise ValueError('%s holds an occupancy cascade of %d levels: load it with OccupancyCascade.load' % (path, int(f['levels'])))
+            return cls._from_fields(f, '', device)
 
-    def save(self, path):
-        """.npz: words (uint32; cell (i,j,k) = bit c & 31 of word c >> 5, c = (i*ny + j)*nz + k), shape, lo, hi, outside_occupied;
-        a training grid adds dens (float32 [nx*ny*nz], cell order c), decay, threshold, dilate, updates, cursor, primed."""
+    @classmethod
+    def _from_fields(cls, f, prefix, device):
+        """The grid whose save() fields are f[prefix + name]."""
+        get = lambda k: f[prefix + k]      # noqa: E731
+        words = torch.from_numpy(get('words').astype(np.uint32).view(np.int32)).to(device)
+        if prefix + 'dens' not in f.files:
+            return cls(words, get('shape').tolist(), get('lo'), get('hi'), bool(get('outside_occupied')))
+        g = cls(words, get('shape').tolist(), get('lo'), get('hi'), bool(get('outside_occupied')),
+                dens=torch.from_numpy(get('dens').astype(np.float32)).to(device), decay=float(get('decay')),
+                threshold=float(get('threshold')), dilate=int(get('dilate')))
+        g.updates, g.cursor, g.primed = int(get('updates')), int(get('cursor')), bool(get('primed'))
+        return g
+
+    def _fields(self):
         fields = dict(words=self.words.cpu().numpy().view(np.uint32), shape=np.asarray(self.shape, np.int64), lo=self.lo,
                       hi=self.hi, outside_occupied=np.asarray(self.outside_occupied))
         if self.dens is not None:
@@ -139,8 +160,13 @@ class OccupancyGrid:
                           threshold=np.asarray(self.threshold, np.float64), dilate=np.asarray(self.dilate, np.int64),
                           updates=np.asarray(self.updates, np.int64), cursor=np.asarray(self.cursor, np.int64),
                           primed=np.asarray(self.primed))
+        return fields
+
+    def save(self, path):
+        """.npz: words (uint32; cell (i,j,k) = bit c & 31 of word c >> 5, c = (i*ny + j)*nz + k), shape, lo, hi, outside_occupied;
+        a training grid adds dens (float32 [nx*ny*nz], cell order c), decay, threshold, dilate, updates, cursor, primed."""
         with open(path, 'wb') as fh:      # (a file object: numpy appends no suffix)
-            np.savez(fh, **fields)
+            np.savez(fh, **self._fields())
 
     # ---- training ---------------------------------------------------------------------------------------------------
     def update(self, render_kwargs, seed=None, cells_per_call=None, _packed=None):
@@ -210,6 +236,109 @@ class OccupancyGrid:
 
     def occupied_fraction(self):
         return float(self.to_mask().float().mean())
+
+    def classify(self, rays11, z, raw=None):
+        """(live_idx, counts) of ops.occ_classify for the samples o + d * z of a pass."""
+        return ops.occ_classify(self._c, rays11, z, raw)
+
+
+class OccupancyCascade:
+    """An ordered list of 1 to 8 OccupancyGrids, innermost first (the cascade keeps references to them).  A point is looked up
+    level by level with each grid's own index arithmetic; the first grid whose box contains it decides, and the sample takes that
+    cell's bit.  A point that no box contains -- every non-finite point -- takes `outside_occupied` (None = the last grid's); the
+    grids' own `outside_occupied` flags are not read.  The boxes need not be nested or concentric.  A cascade of one grid is that
+    grid, bit for bit.  render / render_path / render_rays take it wherever they take a grid; training does not
+    (run_nerf.Trainer raises)."""
+    MAX_LEVELS = _lib.OCC_MAX_LEVELS
+
+    def __init__(self, grids, outside_occupied=None):
+        grids = list(grids)
+        if not 1 <= len(grids) <= self.MAX_LEVELS:
+            raise ValueError('an occupancy cascade has 1 to %d levels, got %d' % (self.MAX_LEVELS, len(grids)))
+        if not all(isinstance(g, OccupancyGrid) for g in grids):
+            raise TypeError('an occupancy cascade is made of OccupancyGrids')
+        if len({g.words.device for g in grids}) != 1:
+            raise ValueError('the levels of an occupancy cascade live on one device')
+        self.grids = grids
+        self.outside_occupied = grids[-1].outside_occupied if outside_occupied is None else bool(outside_occupied)
+        self._c = _lib.OccCascade()
+        self._c.levels = len(grids)
+        for l, g in enumerate(grids):      # copies of the levels' descriptors: the words stay the grids' own
+            C.memmove(C.byref(self._c.level[l]), C.byref(g._c), C.sizeof(_lib.OccGrid))
+        self._c.level[len(grids) - 1].outside_occupied = int(self.outside_occupied)
+
+    @property
+    def levels(self):
+        return len(self.grids)
+
+    @classmethod
+    def from_network(cls, render_kwargs, levels=3, N=256, bound=1.2, growth=2.0, threshold=0., dilate=1, which='both',
+                     outside_occupied=True, chunk=1024 * 64):
+        """Level l is exactly OccupancyGrid.from_network(render_kwargs, N=N_l, bound=bound * growth**l, ...): N_l^3 cells over
+        [-bound * growth^l, bound * growth^l)^3, N a scalar or one value per level.  Each level is built over its WHOLE box,
+        independently of the others, so level l alone equals the single grid of that box bit for bit (its cells that lie inside
+        an inner level's box are built too, and never read).
+
+        At the seams: dilation is per level and clipped at the level's box.  Outwards the coarser level's own dilation covers
+        the face, because its cells over the inner box carry the inner density.  Inwards, density just outside an inner box does
+        NOT open the inner level's boundary cells: a level sees only the density at its own cells' corners."""
+        levels = int(levels)
+        if not 1 <= levels <= cls.MAX_LEVELS:
+            raise ValueError('an occupancy cascade has 1 to %d levels, got %d' % (cls.MAX_LEVELS, levels))
+        Ns = [int(N)] * levels if np.ndim(N) == 0 else [int(n) for n in N]
+        if len(Ns) != levels:
+            raise ValueError('N is a cell count or one per level: got %d values for %d levels' % (len(Ns), levels))
+        if not float(growth) > 0.:
+            raise ValueError('growth must be > 0')
+        grids = [OccupancyGrid.from_network(render_kwargs, N=Ns[l], bound=bound * float(growth) ** l, threshold=threshold, dilate=dilate,
+                                            which=which, outside_occupied=outside_occupied, chunk=chunk) for l in range(levels)]
+        return cls(grids, outside_occupied)
+
+    @classmethod
+    def load(cls, path, device='cuda'):
+        with np.load(path) as f:
+            if 'levels' not in f.files:
+                raise ValueError('%s holds a single occupancy grid: load it with OccupancyGrid.load' % path)
+            grids = [OccupancyGrid._from_fields(f, 'l%d_' % l, device) for l in range(int(f['levels']))]
+            return cls(grids, bool(f['outside_occupied']))
+
+    def save(self, path):
+        """.npz: levels (int64), outside_occupied (of the cascade), and per level i the fields of OccupancyGrid.save prefixed
+        `l{i}_`: l0_words (uint32; cell (i,j,k) = bit c & 31 of word c >> 5, c = (i*ny + j)*nz + k), l0_shape, l0_lo, l0_hi,
+        l0_outside_occupied, l1_words, ...  OccupancyGrid.load refuses such a file."""
+        fields = dict(levels=np.asarray(self.levels, np.int64), outside_occupied=np.asarray(self.outside_occupied))
+        for l, g in enumerate(self.grids):
+            fields.update({'l%d_%s' % (l, k): v for k, v in g._fields().items()})
+        with open(path, 'wb') as fh:
+            np.savez(fh, **fields)
+
+    # ---- inspection -------------------------------------------------------------------------------------------------
+    def query(self, points):
+        """points [..., 3] (cuda) -> bool [...]: the bit a sample at that point takes."""
+        if not torch.is_tensor(points):
+            raise RuntimeError('fastnerf ops run on the GPU only (no CPU fallback): got a host array')
+        ops.require_gpu(points)
+        return ops.occ_query(self._c, points).bool().reshape(points.shape[:-1])
+
+    def decided_by(self, points):
+        """points [..., 3] (cuda) -> int8 [...]: the index of the level that decides the point, -1 when no box contains it.
+        Torch arithmetic with the levels' own fp32 lo and inv (subtraction and product each rounded), for inspection."""
+        if not torch.is_tensor(points):
+            raise RuntimeError('fastnerf ops run on the GPU only (no CPU fallback): got a host array')
+        ops.require_gpu(points)
+        x = points.float()
+        out = torch.full(x.shape[:-1], -1, device=x.device, dtype=torch.int8)
+        for l in reversed(range(self.levels)):
+            g = self.grids[l]
+            lo, inv = (torch.from_numpy(a).to(x.device) for a in (g.lo, g.inv))
+            f = torch.floor((x - lo) * inv)
+            inside = ((f >= 0) & (f < torch.tensor(g.shape, device=x.device, dtype=torch.float32))).all(-1)
+            out[inside] = l
+        return out
+
+    def occupied_fraction(self):
+        """One fraction per level, each over the level's whole box."""
+        return [g.occupied_fraction() for g in self.grids]
 
     def classify(self, rays11, z, raw=None):
         """(live_idx, counts) of ops.occ_classify for the samples o + d * z of a pass."""

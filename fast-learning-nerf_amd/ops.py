@@ -710,17 +710,29 @@ def occ_from_mask(mask):
     return words
 
 
+def _occ_entry(cgrid, name):
+    """The entry point `name` for a _lib.OccGrid, its `_cascade` form for a _lib.OccCascade: (function, its name).  The
+    descriptor itself is wanted (OccupancyGrid._c / OccupancyCascade._c): a ctypes.byref() or POINTER() of one, which ctypes
+    alone would convert, does not say which entry point it is for and raises TypeError."""
+    if isinstance(cgrid, _lib.OccCascade):
+        name += '_cascade'
+    elif not isinstance(cgrid, _lib.OccGrid):
+        raise TypeError('expected a _lib.OccGrid or a _lib.OccCascade, got %s' % type(cgrid).__name__)
+    return getattr(lib(), name), name
+
+
 def occ_query(cgrid, pts):
-    """cgrid: _lib.OccGrid; pts [n, 3] -> uint8 [n]."""
+    """cgrid: _lib.OccGrid or _lib.OccCascade; pts [n, 3] -> uint8 [n]."""
     require_gpu(pts)
     pts = _f32(pts).reshape(-1, 3)
     out = torch.empty(pts.shape[0], device=pts.device, dtype=torch.uint8)
-    check(lib().fastnerf_occ_query(cgrid, pts.shape[0], ptr(pts), ptr(out), stream()), 'fastnerf_occ_query')
+    fn, name = _occ_entry(cgrid, 'fastnerf_occ_query')
+    check(fn(cgrid, pts.shape[0], ptr(pts), ptr(out), stream()), name)
     return out
 
 
 def occ_classify(cgrid, rays11, z, raw=None):
-    """The samples o + d * z of a pass sorted by the grid: (live_idx int32 [n*S], counts int32 [2] = (occupied, n*S)), both on
+    """The samples o + d * z of a pass sorted by the grid (or the cascade): (live_idx int32 [n*S], counts int32 [2] = (occupied, n*S)), both on
     the device; live_idx[:occupied] ascends.  raw ([n, S, 4], optional) is zeroed at the other samples, untouched elsewhere."""
     require_gpu(rays11, z, raw)
     n, S = z.shape
@@ -730,8 +742,8 @@ def occ_classify(cgrid, rays11, z, raw=None):
     idx = torch.empty(P, device=z.device, dtype=torch.int32)
     cnt = torch.empty(2, device=z.device, dtype=torch.int32)
     ws = torch.empty(int(lib().fastnerf_compact_ws_ints(P)), device=z.device, dtype=torch.int32)
-    check(lib().fastnerf_occ_classify(cgrid, n, S, ptr(rays11), ptr(z), ptr(idx), ptr(cnt), ptr(raw), ptr(ws), stream()),
-          'fastnerf_occ_classify')
+    fn, name = _occ_entry(cgrid, 'fastnerf_occ_classify')
+    check(fn(cgrid, n, S, ptr(rays11), ptr(z), ptr(idx), ptr(cnt), ptr(raw), ptr(ws), stream()), name)
     return idx, cnt
 
 
@@ -777,7 +789,8 @@ def mlp_fwd_list(rays11, z, params, packed_fwd, raw, live_idx, live_cnt, flags=0
 
 def render_rays_fwd_occ(rays11, params_c, packed_c, params_f, packed_f, N_samples, N_importance, cgrid, lindisp=False, perturb=False,
                         det=True, white_bkgd=False, t_rand=None, u=None, seed0=0, seed1=0, skip_dead_rgb=False):
-    """render_rays_fwd (inference, no sigma noise) through an occupancy grid: one C-ABI call.  Same dict, without act0 / act1,
+    """render_rays_fwd (inference, no sigma noise) through an occupancy grid (cgrid a _lib.OccGrid) or a cascade (a
+    _lib.OccCascade: fastnerf_render_rays_fwd_occ_cascade): one C-ABI call.  Same dict, without act0 / act1,
     plus 'counts': int32 [4] on the device = (occupied, total) samples of the coarse pass, then of the fine pass."""
     require_gpu(rays11, params_c, packed_c, params_f, packed_f, t_rand, u)
     n = rays11.shape[0]
@@ -803,11 +816,12 @@ def render_rays_fwd_occ(rays11, params_c, packed_c, params_f, packed_f, N_sample
                   'w1': torch.empty(n, S1, **f32), 'depth1': torch.empty(n, **f32)})
     live_ws = torch.empty(max(1, n * S1 + int(lib().fastnerf_compact_ws_ints(max(1, n * S1)))), device=dev, dtype=torch.int32)
     g = o.get
-    check(lib().fastnerf_render_rays_fwd_occ(
+    fn, name = _occ_entry(cgrid, 'fastnerf_render_rays_fwd_occ')
+    check(fn(
         mode_id(), n, int(N_samples), int(N_importance), ptr(rays11), int(bool(lindisp)),
         int(bool(perturb) or t_rand is not None), int(bool(det)), int(bool(white_bkgd)), ptr(t_rand), ptr(u), int(seed0), int(seed1),
         ptr(params_c), ptr(packed_c), ptr(params_f), ptr(packed_f), cgrid, ptr(live_ws), ptr(o['counts']),
         ptr(o['z0']), ptr(o['raw0']), ptr(o['rgb0']), ptr(o['disp0']), ptr(o['acc0']), ptr(o['w0']), ptr(o['depth0']),
         ptr(g('z1')), ptr(g('z_samples')), ptr(g('z_std')), ptr(g('raw1')), ptr(g('rgb1')), ptr(g('disp1')), ptr(g('acc1')),
-        ptr(g('w1')), ptr(g('depth1')), 1 if skip_dead_rgb else 0, stream()), 'fastnerf_render_rays_fwd_occ')
+        ptr(g('w1')), ptr(g('depth1')), 1 if skip_dead_rgb else 0, stream()), name)
     return o

@@ -191,7 +191,8 @@ def _forward_core(rays11, net_c, net_f, N_samples, N_importance, lindisp, pertur
 
 
 def _forward_occ(rays11, net_c, net_f, N_samples, N_importance, lindisp, perturb, white_bkgd, t_rand, u, occupancy, skip_dead_rgb=False):
-    """The fused inference forward through an occupancy grid (fastnerf_render_rays_fwd_occ): _forward_core(save=False) with the
+    """The fused inference forward through an occupancy grid or cascade (fastnerf_render_rays_fwd_occ / _occ_cascade, chosen by
+    the type of `occupancy._c`): _forward_core(save=False) with the
     networks run on the occupied samples only.  Returns the outputs dict, plus 'counts' (device int32 [4])."""
     pc = net_c.packed()
     fine = pf = None
@@ -342,8 +343,8 @@ def _composite(raw, z, rays11, noise, white_bkgd):
 
 
 def _query_occupied(network_query_fn, net, rays11, z, viewdirs, occupancy):
-    """The closure route's network call through an occupancy grid: the samples are sorted by the grid on the device
-    (fastnerf_occ_classify), `network_query_fn` sees the occupied points only -- pts [L, 1, 3], viewdirs [L, 3] gathered per
+    """The closure route's network call through an occupancy grid or cascade: the samples are sorted by it on the device
+    (fastnerf_occ_classify / _cascade), `network_query_fn` sees the occupied points only -- pts [L, 1, 3], viewdirs [L, 3] gathered per
     point -- and its rows are scattered into a zero raw [n, S, C].  One host read: the list length sizes the gather."""
     n, S = z.shape
     idx, cnt = occupancy.classify(rays11, z)
@@ -409,8 +410,9 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
 
     A NeRF paired with another kind of network raises TypeError (the fused route would not train the other one).
 
-    `occupancy` (an occupancy.OccupancyGrid; inference only): a sample in a cell whose bit is clear gets raw = 0 without the
-    network being evaluated, in both passes; every other sample gets the logits it gets without the grid.  ValueError with
+    `occupancy` (an occupancy.OccupancyGrid or an occupancy.OccupancyCascade, whose first level that contains a sample decides;
+    inference only): a sample in a cell whose bit is clear gets raw = 0 without the network being evaluated, in both passes; every
+    other sample gets the logits it gets without the grid.  ValueError with
     raw_noise_std > 0 (noise is added to sigma before the relu: a zero sigma is not a dead sample) and when gradients are
     wanted (the training step must not silently change its gradients)."""
     net_c = _unwrap(network_fn)

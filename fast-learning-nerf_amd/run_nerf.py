@@ -219,7 +219,8 @@ class Trainer:
     sum is the gradient of the global-batch mean) -> Adam over both nets in one launch -> LR decay
     with the reference's pre-increment rule (run_nerf.py:498-508).
 
-    occupancy (opt-in; an occupancy.OccupancyGrid, usually OccupancyGrid.for_training()): the first forward of each pass
+    occupancy (opt-in; an occupancy.OccupancyGrid, usually OccupancyGrid.for_training(); an OccupancyCascade raises
+    ValueError: it is for rendering): the first forward of each pass
     evaluates the networks on the samples in occupied cells only; a sample in an empty cell gets raw = (0, 0, 0, 0), whose
     d(loss)/d(raw) is exactly zero, so the compacted backward needs no change.  The first `occupancy_warmup` steps leave the
     grid untouched; from then on a grid with a density is refreshed (`grid.update`) every `occupancy_every` steps, by at most
@@ -276,6 +277,11 @@ class Trainer:
     def _check_occupancy(self):
         if self.occupancy is None:
             return
+        from .occupancy import OccupancyCascade
+        if isinstance(self.occupancy, OccupancyCascade):
+            raise ValueError('Trainer: training takes a single OccupancyGrid, not an OccupancyCascade: the fused step has room for one '
+                             'grid (fn_step_args.occ), and refreshing a cascade would evaluate both networks on levels x N^3 cells per '
+                             'refresh, more than the first forward it could shorten; build the cascade for rendering after training')
         if self.raw_noise_std > 0.:
             raise ValueError('Trainer: an occupancy grid cannot be combined with raw_noise_std > 0 (sigma noise is added before the '
                              'relu, so a sample with zero sigma is not dead)')

@@ -501,6 +501,26 @@ int fastnerf_occ_from_mask(const uint8_t* mask, int64_t nx, int64_t ny, int64_t 
 int fastnerf_occ_query(const fn_occ_grid* grid, int64_t n, const float* pts, uint8_t* out, fn_stream_t stream);
 int fastnerf_occ_classify(const fn_occ_grid* grid, int64_t n, int S, const float* rays11, const float* z, int32_t* live_idx,
                           int32_t* count_out, float* raw, int32_t* ws, fn_stream_t stream);
+/* ---- cascade: an ordered list of 1 to 8 such grids g_0 .. g_{L-1} (usually the fine grid over the object, then coarser grids over
+ * boxes around it; the boxes need not be nested or concentric), each with its own box, cell counts and bits.  A point is looked up
+ * level by level, with each level's own index arithmetic as above: the FIRST level whose index lies in 0 .. n-1 on all three axes
+ * decides, and the sample takes that cell's bit.  A point no level contains -- every non-finite point -- takes `outside_occupied` of
+ * the LAST level; the `outside_occupied` of the other levels is not read.  A cascade of one level is that grid, bit for bit.  The
+ * struct lives on the HOST; level[l].words are device pointers.  fn_occ_grid and fn_step_args keep their sizes: the cascade has
+ * entry points of its own (rendering only; fn_step_args.occ stays a single grid).
+ *   fastnerf_occ_query_cascade     the arguments and the result of fastnerf_occ_query
+ *   fastnerf_occ_classify_cascade  the contract of fastnerf_occ_classify: ascending list, device count, zero logits for the other
+ *                                  samples, the same ws, the same three launches without atomics
+ * -1 unless 1 <= levels <= FN_OCC_MAX_LEVELS and every level passes the checks fastnerf_occ_query makes of its grid. */
+#define FN_OCC_MAX_LEVELS 8
+typedef struct fn_occ_cascade {
+  int32_t levels;
+  int32_t reserved;
+  fn_occ_grid level[FN_OCC_MAX_LEVELS];
+} fn_occ_cascade;
+int fastnerf_occ_query_cascade(const fn_occ_cascade* cascade, int64_t n, const float* pts, uint8_t* out, fn_stream_t stream);
+int fastnerf_occ_classify_cascade(const fn_occ_cascade* cascade, int64_t n, int S, const float* rays11, const float* z,
+                                  int32_t* live_idx, int32_t* count_out, float* raw, int32_t* ws, fn_stream_t stream);
 /* A grid that is kept while the networks train (fn_step_args.occ): a persistent density dens[nx*ny*nz] (fp32, cell order
  * c = (i*ny + j)*nz + k) beside the bits.
  *   fastnerf_occ_cell_points  one point inside each of the cells c0 .. c0+n-1, as rays11 rows [n,11] in the layout of
@@ -545,6 +565,15 @@ int fastnerf_render_rays_fwd_occ(int math_mode, int64_t n, int N_samples, int N_
                                  float* raw0, float* rgb0, float* disp0, float* acc0, float* w0, float* depth0, float* z1,
                                  float* z_samples, float* z_std, float* raw1, float* rgb1, float* disp1, float* acc1, float* w1,
                                  float* depth1, int flags, fn_stream_t stream);
+/* The same through a cascade: every argument as above, each pass sorted by fastnerf_occ_classify_cascade.  The two functions share
+ * one body; with levels == 1 the outputs equal fastnerf_render_rays_fwd_occ's with that grid bit for bit. */
+int fastnerf_render_rays_fwd_occ_cascade(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11, int lindisp,
+                                         int perturb, int det, int white_bkgd, const float* t_rand, const float* u, uint64_t seed0,
+                                         uint64_t seed1, const float* params_c, const float* packed_c, const float* params_f,
+                                         const float* packed_f, const fn_occ_cascade* cascade, int32_t* live_ws, int32_t* counts_out,
+                                         float* z0, float* raw0, float* rgb0, float* disp0, float* acc0, float* w0, float* depth0,
+                                         float* z1, float* z_samples, float* z_std, float* raw1, float* rgb1, float* disp1,
+                                         float* acc1, float* w1, float* depth1, int flags, fn_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,8 @@ outside_occupied=False: samples outside the box count as empty, for a scene know
 
 --plain-only renders without the grid and uses only calls that older checkouts have: run it there for the comparator.
 
-usage: python tools/time_occupancy.py [--steps 600] [--views 4] [--size 800] [--plain-only] [--outside-occupied 0|1] [--out FILE]"""
+usage: python tools/time_occupancy.py [--steps 600] [--views 4] [--size 800] [--plain-only] [--outside-occupied 0|1] [--levels K [--growth 2.0]]
+       [--N 256 | --N 256,128,128] [--out FILE]"""
 import argparse
 import json
 import os
@@ -34,8 +35,20 @@ def main():
     ap.add_argument('--chunk', type=int, default=32768)
     ap.add_argument('--plain-only', action='store_true')
     ap.add_argument('--outside-occupied', type=int, default=1, help='0: samples outside the grid box count as empty (a scene known to lie inside it)')
+    ap.add_argument('--levels', type=int, default=0, help='K >= 1: an OccupancyCascade of K levels instead of the single grid')
+    ap.add_argument('--growth', type=float, default=2.0, help='box of level l = bound * growth^l (with --levels)')
+    ap.add_argument('--N', default='256', help='cells per axis; with --levels also one value per level, comma separated')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
+    if a.levels < 0 or a.levels > 8:
+        ap.error('--levels is 1 .. 8 (0: the single grid)')
+    n_values = len(a.N.split(','))
+    if a.levels == 0 and (n_values != 1 or a.growth != 2.0):
+        ap.error('--growth and one --N per level go with --levels K')
+    if a.levels > 0 and n_values not in (1, a.levels):
+        ap.error('--N is one value or one per level: got %d for --levels %d' % (n_values, a.levels))
+    if a.plain_only and (a.levels or n_values != 1):
+        ap.error('--plain-only renders without a grid: --levels / --N do not apply')
     import fastnerf
     from fastnerf import ops, synthetic
     dev = torch.device('cuda')
@@ -91,8 +104,13 @@ def main():
            'samples': [N_SAMPLES, N_IMPORTANCE], 'chunk': a.chunk, 'scene': 'three solid bodies, density zero beyond %.1f sigma' % CUTOFF,
            'ms_per_view_plain': ms_plain, 'psnr_plain': psnr(plain, gts)}
     if not a.plain_only:
-        G = fastnerf.occupancy.OccupancyGrid
-        gkw = dict(N=256, bound=1.2, threshold=0., dilate=1, which='both', outside_occupied=bool(a.outside_occupied))
+        Ns = [int(v) for v in a.N.split(',')]
+        gkw = dict(N=Ns[0], bound=1.2, threshold=0., dilate=1, which='both', outside_occupied=bool(a.outside_occupied))
+        if a.levels > 0:
+            G = fastnerf.occupancy.OccupancyCascade
+            gkw.update(levels=a.levels, growth=a.growth, N=Ns[0] if len(Ns) == 1 else Ns)
+        else:
+            G = fastnerf.occupancy.OccupancyGrid
         G.from_network(kte, **gkw)      # warm-up
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -101,6 +119,7 @@ def main():
         torch.cuda.synchronize()
         masked, ms_grid = timed_views({'occupancy': grid})
         counts = torch.zeros(4, dtype=torch.int64)
+        decided = torch.zeros(2, a.levels + 1, dtype=torch.int64)      # cascade: samples per deciding level (last: none), coarse / fine
         ms_classify = 0.0
         with torch.no_grad():      # untimed: the occupied share of the samples of the same views
             for c2w in views:
@@ -119,12 +138,19 @@ def main():
                     e3.record()
                     torch.cuda.synchronize()
                     ms_classify += e2.elapsed_time(e3)
+                    if a.levels > 0:
+                        for k, z in enumerate((o['z0'], o['z_vals'])):
+                            who = grid.decided_by(r11[:, None, 0:3] + r11[:, None, 3:6] * z[..., None]).long()
+                            decided[k] += torch.bincount((who % (a.levels + 1)).reshape(-1), minlength=a.levels + 1).cpu()
         d = torch.stack([(m - p).abs() for m, p in zip(masked, plain)])
         res.update({'grid': gkw, 'classify_ms_per_view': ms_classify / a.views,
                     'grid_build_ms': e0.elapsed_time(e1), 'grid_occupied_fraction': grid.occupied_fraction(),
                     'occupied_share_coarse': float(counts[0]) / float(counts[1]), 'occupied_share_fine': float(counts[2]) / float(counts[3]),
                     'ms_per_view_grid': ms_grid, 'speedup': ms_plain['mean'] / ms_grid['mean'], 'psnr_grid': psnr(masked, gts),
                     'max_abs_drgb': float(d.max()), 'mean_abs_drgb': float(d.mean())})
+        if a.levels > 0:
+            res.update({'decided_share_coarse': (decided[0].double() / decided[0].sum()).tolist(),
+                        'decided_share_fine': (decided[1].double() / decided[1].sum()).tolist()})
     line = json.dumps(res)
     print(line)
     if a.out:
