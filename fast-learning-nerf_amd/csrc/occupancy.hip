@@ -22,11 +22,12 @@
 //   occ_count / scatter  the samples o + d * z of a pass: per-block counts -> (the scan of train.hip) -> ascending list of the
 //                        occupied sample indices; the others get raw = (0, 0, 0, 0).  The shape of fastnerf_compact_live with
 //                        another predicate: deterministic, no atomics, the list length stays on the device.
-//   occ_*_cascade       the query / count / scatter kernels over a cascade of up to 8 grids: a point takes the bit of the FIRST
-//                        level whose box contains it, `outside` when none does.  The descriptors travel by value in the kernel
-//                        argument (8 x 40 bytes of geometry, 8 pointers) and are read through scalar loads: the level loop's
-//                        bounds and counter are wave-uniform, each lane leaves it at its own level.  Separate kernels: the
-//                        single-grid ones above keep their instructions.
+//   The query / count / scatter kernels have ONE body each, instantiated for OccDev (one grid) and OccCascadeDev (a cascade of up
+//   to 8 grids); the two occ_point overloads are all that differs.  In a cascade a point takes the bit of the FIRST level whose box
+//   contains it, `outside` when none does.  The descriptors travel by value in the kernel argument (8 x 40 bytes of geometry, 8
+//   pointers) and are read through scalar loads: the level loop's bounds and counter are wave-uniform, each lane leaves it at its
+//   own level.  The six instantiations compile to the instructions of the kernels once written out per form (hipcc -S listings
+//   compared with tools/isa_funcs.py: 11 kernels identical, 0 differ); timings: profiles/occupancy_render.md.
 // All of them are memory bound and small next to the MLP they spare: one lane per cell / point / four consecutive samples, a
 // ray's 44 bytes come through the cache for all its samples.
 #include "common.h"
@@ -144,13 +145,9 @@ __global__ void __launch_bounds__(OCC_BLOCK) occ_dilate_kernel(const uint32_t* _
   occ_store_bits(b, c, dst, d.nwords);
 }
 
-__global__ void __launch_bounds__(OCC_BLOCK) occ_query_kernel(OccDev g, int64_t n, const float* __restrict__ pts, uint8_t* __restrict__ out) {
-  for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n; q += (int64_t)gridDim.x * blockDim.x)
-    out[q] = occ_point(g, pts[q * 3], pts[q * 3 + 1], pts[q * 3 + 2]) ? 1 : 0;
-}
-
-__global__ void __launch_bounds__(OCC_BLOCK) occ_query_cascade_kernel(OccCascadeDev g, int64_t n, const float* __restrict__ pts,
-                                                                      uint8_t* __restrict__ out) {
+// G: OccDev or OccCascadeDev (occ_point picks the lookup)
+template <class G>
+__global__ void __launch_bounds__(OCC_BLOCK) occ_query_kernel(G g, int64_t n, const float* __restrict__ pts, uint8_t* __restrict__ out) {
   for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n; q += (int64_t)gridDim.x * blockDim.x)
     out[q] = occ_point(g, pts[q * 3], pts[q * 3 + 1], pts[q * 3 + 2]) ? 1 : 0;
 }
@@ -236,7 +233,8 @@ __device__ __forceinline__ unsigned occ_flags(const G& g, const float* __restric
   return f;
 }
 
-__global__ void __launch_bounds__(OCC_BLOCK) occ_count_kernel(OccDev g, int64_t n, int S, const float* __restrict__ rays,
+template <class G>
+__global__ void __launch_bounds__(OCC_BLOCK) occ_count_kernel(G g, int64_t n, int S, const float* __restrict__ rays,
                                                               const float* __restrict__ zv, int* __restrict__ blk) {
   __shared__ int red[4];
   const unsigned f = occ_flags(g, rays, zv, (uint32_t)S, (int64_t)blockIdx.x * OCC_PTS + threadIdx.x * 4, n);
@@ -248,47 +246,10 @@ __global__ void __launch_bounds__(OCC_BLOCK) occ_count_kernel(OccDev g, int64_t 
   if (threadIdx.x == 0) blk[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
-__global__ void __launch_bounds__(OCC_BLOCK) occ_scatter_kernel(OccDev g, int64_t n, int S, const float* __restrict__ rays,
+template <class G>
+__global__ void __launch_bounds__(OCC_BLOCK) occ_scatter_kernel(G g, int64_t n, int S, const float* __restrict__ rays,
                                                                 const float* __restrict__ zv, const int* __restrict__ blk,
                                                                 int* __restrict__ live_idx, float* __restrict__ raw) {
-  __shared__ int wsum[4];
-  const int64_t p0 = (int64_t)blockIdx.x * OCC_PTS + threadIdx.x * 4;
-  const unsigned f = occ_flags(g, rays, zv, (uint32_t)S, p0, n);
-  const int c = __popc(f);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int x = c;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(x, o, 64); if (lane >= o) x += t; }
-  if (lane == 63) wsum[w] = x;
-  __syncthreads();
-  int pos = blk[blockIdx.x] + x - c;
-  for (int k = 0; k < w; ++k) pos += wsum[k];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    if (f & (1u << k)) live_idx[pos++] = (int)(p0 + k);
-    else if (raw && p0 + k < n) *reinterpret_cast<float4*>(raw + (p0 + k) * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-}
-
-// The cascade's count and scatter: the bodies above, word for word, over occ_flags<OccCascadeDev>.  Written out a second time
-// on purpose: routing both through one templated body reorders a few instructions of the single-grid kernels, which the training step
-// launches and which stay instruction-identical; so do forceinline helpers for the block reduce and the block scan alone.  A fix
-// to one body goes into the other too.
-__global__ void __launch_bounds__(OCC_BLOCK) occ_count_cascade_kernel(OccCascadeDev g, int64_t n, int S, const float* __restrict__ rays,
-                                                                      const float* __restrict__ zv, int* __restrict__ blk) {
-  __shared__ int red[4];
-  const unsigned f = occ_flags(g, rays, zv, (uint32_t)S, (int64_t)blockIdx.x * OCC_PTS + threadIdx.x * 4, n);
-  int c = __popc(f);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) blk[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-
-__global__ void __launch_bounds__(OCC_BLOCK) occ_scatter_cascade_kernel(OccCascadeDev g, int64_t n, int S, const float* __restrict__ rays,
-                                                                        const float* __restrict__ zv, const int* __restrict__ blk,
-                                                                        int* __restrict__ live_idx, float* __restrict__ raw) {
   __shared__ int wsum[4];
   const int64_t p0 = (int64_t)blockIdx.x * OCC_PTS + threadIdx.x * 4;
   const unsigned f = occ_flags(g, rays, zv, (uint32_t)S, p0, n);
@@ -368,6 +329,24 @@ void occ_dilate_launch(const OccDims& d, int dilate, uint32_t* ws, uint32_t* wor
   hipLaunchKernelGGL(occ_dilate_kernel, g, b, 0, s, (const uint32_t*)a0, words, d, 0, dilate);
 }
 
+// the launches of fastnerf_occ_query / _cascade and fastnerf_occ_classify / _cascade (G: OccDev or OccCascadeDev); the callers
+// keep the argument checks and FN_LAUNCH_CHECK, whose texts carry their own names
+template <class G>
+void occ_query_launch(const G& g, int64_t n, const float* pts, uint8_t* out, hipStream_t s) {
+  const int64_t blocks = (n + OCC_BLOCK - 1) / OCC_BLOCK;
+  hipLaunchKernelGGL(occ_query_kernel<G>, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(OCC_BLOCK), 0, s, g, n, pts, out);
+}
+
+template <class G>
+void occ_classify_launch(const G& g, int64_t n, int S, const float* rays11, const float* z, int32_t* live_idx, int32_t* count_out,
+                         float* raw, int32_t* ws, hipStream_t s) {
+  const int64_t P = n * (int64_t)S;
+  const int nb = (int)((P + OCC_PTS - 1) / OCC_PTS);
+  hipLaunchKernelGGL(occ_count_kernel<G>, dim3(nb), dim3(OCC_BLOCK), 0, s, g, P, S, rays11, z, ws);
+  fn::cp_scan_launch(nb, ws, count_out, (int)P, s);
+  hipLaunchKernelGGL(occ_scatter_kernel<G>, dim3(nb), dim3(OCC_BLOCK), 0, s, g, P, S, rays11, z, (const int*)ws, live_idx, raw);
+}
+
 }  // namespace
 
 extern "C" int64_t fastnerf_occ_words(int64_t nx, int64_t ny, int64_t nz) {
@@ -409,8 +388,7 @@ extern "C" int fastnerf_occ_query(const fn_occ_grid* grid, int64_t n, const floa
   FN_CHECK_ARG(n >= 0, "n >= 0");
   if (n == 0) return 0;
   FN_CHECK_ARG(pts && out, "non-null pointers");
-  const int64_t blocks = (n + OCC_BLOCK - 1) / OCC_BLOCK;
-  hipLaunchKernelGGL(occ_query_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(OCC_BLOCK), 0, fn::S(stream), g, n, pts, out);
+  occ_query_launch(g, n, pts, out, fn::S(stream));
   FN_LAUNCH_CHECK();
   return 0;
 }
@@ -452,12 +430,7 @@ extern "C" int fastnerf_occ_classify(const fn_occ_grid* grid, int64_t n, int S, 
   FN_CHECK_ARG(occ_dev(grid, &g), "grid: non-null words, 1 <= n[i] <= 2^24, fewer than 2^31 cells, finite lo, finite inv > 0");
   FN_CHECK_ARG(n > 0 && S >= 1 && n * (int64_t)S < ((int64_t)1 << 31), "n > 0, S >= 1, n * S < 2^31");
   FN_CHECK_ARG(rays11 && z && live_idx && count_out && ws, "non-null pointers");
-  const int64_t P = n * (int64_t)S;
-  const int nb = (int)((P + OCC_PTS - 1) / OCC_PTS);
-  hipStream_t s = fn::S(stream);
-  hipLaunchKernelGGL(occ_count_kernel, dim3(nb), dim3(OCC_BLOCK), 0, s, g, P, S, rays11, z, ws);
-  fn::cp_scan_launch(nb, ws, count_out, (int)P, s);
-  hipLaunchKernelGGL(occ_scatter_kernel, dim3(nb), dim3(OCC_BLOCK), 0, s, g, P, S, rays11, z, (const int*)ws, live_idx, raw);
+  occ_classify_launch(g, n, S, rays11, z, live_idx, count_out, raw, ws, fn::S(stream));
   FN_LAUNCH_CHECK();
   return 0;
 }
@@ -478,9 +451,7 @@ extern "C" int fastnerf_occ_query_cascade(const fn_occ_cascade* cascade, int64_t
   FN_CHECK_ARG(n >= 0, "n >= 0");
   if (n == 0) return 0;
   FN_CHECK_ARG(pts && out, "non-null pointers");
-  const int64_t blocks = (n + OCC_BLOCK - 1) / OCC_BLOCK;
-  hipLaunchKernelGGL(occ_query_cascade_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(OCC_BLOCK), 0, fn::S(stream), g, n, pts,
-                     out);
+  occ_query_launch(g, n, pts, out, fn::S(stream));
   FN_LAUNCH_CHECK();
   return 0;
 }
@@ -491,12 +462,7 @@ extern "C" int fastnerf_occ_classify_cascade(const fn_occ_cascade* cascade, int6
   FN_CHECK_ARG(occ_cascade_dev(cascade, &g), OCC_CASCADE_ARG);
   FN_CHECK_ARG(n > 0 && S >= 1 && n * (int64_t)S < ((int64_t)1 << 31), "n > 0, S >= 1, n * S < 2^31");
   FN_CHECK_ARG(rays11 && z && live_idx && count_out && ws, "non-null pointers");
-  const int64_t P = n * (int64_t)S;
-  const int nb = (int)((P + OCC_PTS - 1) / OCC_PTS);
-  hipStream_t s = fn::S(stream);
-  hipLaunchKernelGGL(occ_count_cascade_kernel, dim3(nb), dim3(OCC_BLOCK), 0, s, g, P, S, rays11, z, ws);
-  fn::cp_scan_launch(nb, ws, count_out, (int)P, s);
-  hipLaunchKernelGGL(occ_scatter_cascade_kernel, dim3(nb), dim3(OCC_BLOCK), 0, s, g, P, S, rays11, z, (const int*)ws, live_idx, raw);
+  occ_classify_launch(g, n, S, rays11, z, live_idx, count_out, raw, ws, fn::S(stream));
   FN_LAUNCH_CHECK();
   return 0;
 }

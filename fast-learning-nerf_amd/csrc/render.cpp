@@ -1,12 +1,112 @@
 // render.cpp -- host-side sequencing of the fused forward of render_rays (render.py:238-299): one C-ABI call
 // enqueues  coarse sampler -> coarse MLP -> compositing -> [inverse-CDF + merge -> fine MLP -> compositing]
-// on the caller's stream.  No kernels here; every stage is one of the library's own entry points.
+// on the caller's stream.  No kernels here; every stage is one of the library's own entry points.  The chain is written once
+// (rr_fwd_chain) and every MLP call goes through one table of entry points indexed by the math mode (modes[]).
 #include <stdint.h>
 #include "../../include/fastnerf.h"
 
 namespace fn {
 void set_error(const char* fmt, ...);
 const char* occ_cascade_fault(const fn_occ_cascade* c);   // occupancy.hip
+}
+
+// ---- the math modes: one row of MLP entry points per math_mode (0 exact fp32, 1 split-bf16 "bf16x3", 2 "bf16x6") -----------------
+// A further mode is a further row.  The three families have one signature per operation except the plain forward, where only
+// fastnerf_mlp_x6_fwd takes both `act` and `flags`: the other two get an adapter with that signature.
+struct MlpMode {
+  int (*pack)(int kind, const float* params, float* packed_fwd, float* packed_bwd, fn_stream_t);
+  int (*fwd)(int kind, int64_t n, int S, const float* rays11, const float* z, const float* params, const float* packed_fwd, float* raw,
+             float* act, int flags, fn_stream_t);
+  int (*fwd_list)(int kind, int64_t n, int S, const float* rays11, const float* z, const float* params, const float* packed_fwd,
+                  float* raw, const int32_t* live_idx, const int32_t* live_cnt, int flags, fn_stream_t);
+  int (*fwd_live)(int kind, int64_t n, int S, const float* rays11, const float* z, const float* params, const float* packed_fwd,
+                  float* act, const int32_t* live_idx, const int32_t* live_cnt, fn_stream_t);
+  int (*bwd)(int kind, int64_t n, int S, const float* draw, const float* act, const float* params, const float* packed_bwd, float* dact,
+             float* partial, float* grads, fn_stream_t);
+  int (*bwd_live)(int kind, int64_t n, int S, const float* draw, const float* act, const float* params, const float* packed_bwd,
+                  float* dact, float* partial, float* grads, const int32_t* live_idx, const int32_t* live_cnt, fn_stream_t);
+};
+
+// a training launch (act != NULL) has no options; an inference launch with flags == 0 is the plain forward with act == NULL
+static int fwd_fp32(int kind, int64_t n, int S, const float* rays11, const float* z, const float* params, const float* packed_fwd,
+                    float* raw, float* act, int flags, fn_stream_t stream) {
+  return act ? fastnerf_mlp_fwd_ex(kind, n, S, rays11, z, params, packed_fwd, raw, act, stream)
+             : fastnerf_mlp_fwd_flags_ex(kind, n, S, rays11, z, params, packed_fwd, raw, flags, stream);
+}
+
+static int fwd_bf16(int kind, int64_t n, int S, const float* rays11, const float* z, const float* params, const float* packed_fwd,
+                    float* raw, float* act, int flags, fn_stream_t stream) {
+  return act ? fastnerf_mlp_bf16_fwd(kind, n, S, rays11, z, params, packed_fwd, raw, act, stream)
+             : fastnerf_mlp_bf16_fwd_flags(kind, n, S, rays11, z, params, packed_fwd, raw, flags, stream);
+}
+
+static const MlpMode modes[3] = {
+    {fastnerf_mlp_pack_ex, fwd_fp32, fastnerf_mlp_fwd_list_ex, fastnerf_mlp_fwd_live_ex, fastnerf_mlp_bwd_ex, fastnerf_mlp_bwd_live_ex},
+    {fastnerf_mlp_bf16_pack, fwd_bf16, fastnerf_mlp_bf16_fwd_list, fastnerf_mlp_bf16_fwd_live, fastnerf_mlp_bf16_bwd,
+     fastnerf_mlp_bf16_bwd_live},
+    {fastnerf_mlp_x6_pack, fastnerf_mlp_x6_fwd, fastnerf_mlp_x6_fwd_list, fastnerf_mlp_x6_fwd_live, fastnerf_mlp_x6_bwd,
+     fastnerf_mlp_x6_bwd_live},
+};
+
+// ---- the forward ------------------------------------------------------------------------------------------------------------
+// What the forward entry points share: `fname` names the caller in the error texts, noise0 / noise1 are NULL through a grid.
+struct RrFwd {
+  const char* fname;
+  int math_mode;
+  int64_t n;
+  int N_samples, N_importance;
+  const float* rays11;
+  int lindisp, perturb, det, white_bkgd;
+  const float *t_rand, *u, *noise0, *noise1;
+  uint64_t seed0, seed1;
+  const float *params_c, *packed_c, *params_f, *packed_f;
+  float *z0, *raw0, *rgb0, *disp0, *acc0, *w0, *depth0, *z1, *z_samples, *z_std, *raw1, *rgb1, *disp1, *acc1, *w1, *depth1;
+  int flags;
+  fn_stream_t stream;
+};
+
+// the checks that come before the n == 0 return
+static bool rr_fwd_scalars(const RrFwd& a) {
+  if (a.math_mode < 0 || a.math_mode > 2 || a.n < 0 || a.N_samples < 2 || a.N_importance < 0) {
+    fn::set_error("%s: bad argument: math_mode in {0,1,2}, n>=0, N_samples>=2, N_importance>=0", a.fname);
+    return false;
+  }
+  if (a.N_importance > 0 && a.N_samples < 3) {
+    // the reference fails here too: weights[..., 1:-1] is empty and sample_pdf indexes an empty cdf (run_nerf_helpers.py:147)
+    fn::set_error("%s: hierarchical sampling needs N_samples >= 3 (the inner weights of 2 samples are empty)", a.fname);
+    return false;
+  }
+  return true;
+}
+
+static bool rr_fwd_coarse_ptrs(const RrFwd& a) {
+  return a.rays11 && a.params_c && a.packed_c && a.z0 && a.raw0 && a.rgb0 && a.disp0 && a.acc0 && a.w0 && a.depth0;
+}
+
+// The chain, once: sampler -> net -> compositing [-> inverse-CDF + merge -> net -> compositing].  net(pass, S, z, params, packed,
+// raw, noise) enqueues whatever fills raw [n, S, 4] for pass 0 (coarse) / 1 (fine); the caller has made the checks up to the
+// coarse pass.
+template <class Net>
+static int rr_fwd_chain(const RrFwd& a, Net&& net) {
+  int rc;
+  if ((rc = fastnerf_sample_coarse(a.n, a.N_samples, a.rays11, a.lindisp, a.perturb, a.t_rand, a.seed0, a.z0, a.stream))) return rc;
+  if ((rc = net(0, a.N_samples, a.z0, a.params_c, a.packed_c, a.raw0, a.noise0))) return rc;
+  if ((rc = fastnerf_raw2outputs_fwd(a.n, a.N_samples, a.raw0, a.z0, a.rays11, a.noise0, a.white_bkgd, a.rgb0, a.disp0, a.acc0, a.w0,
+                                     a.depth0, a.stream)))
+    return rc;
+  if (a.N_importance == 0) return 0;
+  if (!a.params_f || !a.packed_f || !a.z1 || !a.z_samples || !a.z_std || !a.raw1 || !a.rgb1 || !a.disp1 || !a.acc1 || !a.w1 ||
+      !a.depth1) {
+    fn::set_error("%s: null pointer (fine pass)", a.fname);
+    return -1;
+  }
+  const int S1 = a.N_samples + a.N_importance;
+  if ((rc = fastnerf_sample_pdf_merge(a.n, a.N_samples, a.N_importance, a.z0, a.w0, a.det, a.u, a.seed1, a.z1, a.z_samples, a.z_std,
+                                      a.stream)))
+    return rc;
+  if ((rc = net(1, S1, a.z1, a.params_f, a.packed_f, a.raw1, a.noise1))) return rc;
+  return fastnerf_raw2outputs_fwd(a.n, S1, a.raw1, a.z1, a.rays11, a.noise1, a.white_bkgd, a.rgb1, a.disp1, a.acc1, a.w1, a.depth1,
+                                  a.stream);
 }
 
 extern "C" int fastnerf_render_rays_fwd_ex(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11,
@@ -17,104 +117,50 @@ extern "C" int fastnerf_render_rays_fwd_ex(int math_mode, int64_t n, int N_sampl
                                         float* disp0, float* acc0, float* w0, float* depth0, float* z1,
                                         float* z_samples, float* z_std, float* raw1, float* act1, float* rgb1,
                                         float* disp1, float* acc1, float* w1, float* depth1, int flags, fn_stream_t stream) {
-  if (math_mode < 0 || math_mode > 2 || n < 0 || N_samples < 2 || N_importance < 0) {
-    fn::set_error("fastnerf_render_rays_fwd: bad argument: math_mode in {0,1,2}, n>=0, N_samples>=2, N_importance>=0");
-    return -1;
-  }
-  if (N_importance > 0 && N_samples < 3) {
-    // the reference fails here too: weights[..., 1:-1] is empty and sample_pdf indexes an empty cdf (run_nerf_helpers.py:147)
-    fn::set_error("fastnerf_render_rays_fwd: hierarchical sampling needs N_samples >= 3 (the inner weights of 2 samples are empty)");
-    return -1;
-  }
+  const RrFwd a = {"fastnerf_render_rays_fwd", math_mode, n, N_samples, N_importance, rays11, lindisp, perturb, det, white_bkgd, t_rand,
+                   u, noise0, noise1, seed0, seed1, params_c, packed_c, params_f, packed_f, z0, raw0, rgb0, disp0, acc0, w0, depth0, z1,
+                   z_samples, z_std, raw1, rgb1, disp1, acc1, w1, depth1, flags, stream};
+  if (!rr_fwd_scalars(a)) return -1;
   if (n == 0) return 0;
-  if (!rays11 || !params_c || !packed_c || !z0 || !raw0 || !rgb0 || !disp0 || !acc0 || !w0 || !depth0) {
-    fn::set_error("fastnerf_render_rays_fwd: null pointer (coarse pass)");
+  if (!rr_fwd_coarse_ptrs(a)) {
+    fn::set_error("%s: null pointer (coarse pass)", a.fname);
     return -1;
   }
-  int rc;
   // (options only where their precondition holds: an inference launch, no sigma noise in that pass)
-  auto mlp = [&](int64_t nn, int S, const float* z, const float* params, const float* packed, float* raw, float* act,
-                 const float* noise) {
-    if (math_mode == 2) return fastnerf_mlp_x6_fwd(0, nn, S, rays11, z, params, packed, raw, act, (!act && !noise) ? flags : 0, stream);
-    if (!act && !noise && flags)
-      return math_mode ? fastnerf_mlp_bf16_fwd_flags(0, nn, S, rays11, z, params, packed, raw, flags, stream)
-                       : fastnerf_mlp_fwd_flags_ex(0, nn, S, rays11, z, params, packed, raw, flags, stream);
-    return math_mode ? fastnerf_mlp_bf16_fwd(0, nn, S, rays11, z, params, packed, raw, act, stream)
-                     : fastnerf_mlp_fwd_ex(0, nn, S, rays11, z, params, packed, raw, act, stream);
-  };
-  if ((rc = fastnerf_sample_coarse(n, N_samples, rays11, lindisp, perturb, t_rand, seed0, z0, stream))) return rc;
-  if ((rc = mlp(n, N_samples, z0, params_c, packed_c, raw0, act0, noise0))) return rc;
-  if ((rc = fastnerf_raw2outputs_fwd(n, N_samples, raw0, z0, rays11, noise0, white_bkgd, rgb0, disp0, acc0, w0, depth0, stream)))
-    return rc;
-  if (N_importance == 0) return 0;
-  if (!params_f || !packed_f || !z1 || !z_samples || !z_std || !raw1 || !rgb1 || !disp1 || !acc1 || !w1 || !depth1) {
-    fn::set_error("fastnerf_render_rays_fwd: null pointer (fine pass)");
-    return -1;
-  }
-  const int S1 = N_samples + N_importance;
-  if ((rc = fastnerf_sample_pdf_merge(n, N_samples, N_importance, z0, w0, det, u, seed1, z1, z_samples, z_std, stream)))
-    return rc;
-  if ((rc = mlp(n, S1, z1, params_f, packed_f, raw1, act1, noise1))) return rc;
-  return fastnerf_raw2outputs_fwd(n, S1, raw1, z1, rays11, noise1, white_bkgd, rgb1, disp1, acc1, w1, depth1, stream);
+  return rr_fwd_chain(a, [&](int pass, int S, const float* z, const float* params, const float* packed, float* raw, const float* noise) {
+    float* act = pass ? act1 : act0;
+    return modes[math_mode].fwd(0, n, S, rays11, z, params, packed, raw, act, (!act && !noise) ? flags : 0, stream);
+  });
 }
 
 // The same chain through an occupancy grid or a cascade of them (inference): per pass, the samples are sorted by it
 // (fastnerf_occ_classify / _cascade: list of the occupied ones, zero logits for the others) and the network runs over the list only.
-// One body for both entry points: exactly one of grid / cascade is set, `fname` names the caller in the error texts.
-static int rr_fwd_occ(const char* fname, int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11, int lindisp,
-                      int perturb, int det, int white_bkgd, const float* t_rand, const float* u, uint64_t seed0, uint64_t seed1,
-                      const float* params_c, const float* packed_c, const float* params_f, const float* packed_f,
-                      const fn_occ_grid* grid, const fn_occ_cascade* cascade, int32_t* live_ws, int32_t* counts_out, float* z0,
-                      float* raw0, float* rgb0, float* disp0, float* acc0, float* w0, float* depth0, float* z1, float* z_samples,
-                      float* z_std, float* raw1, float* rgb1, float* disp1, float* acc1, float* w1, float* depth1, int flags,
-                      fn_stream_t stream) {
-  if (math_mode < 0 || math_mode > 2 || n < 0 || N_samples < 2 || N_importance < 0) {
-    fn::set_error("%s: bad argument: math_mode in {0,1,2}, n>=0, N_samples>=2, N_importance>=0", fname);
+// One body for both entry points: exactly one of grid / cascade is set.  counts_out: (occupied, total) coarse, then fine.
+static int rr_fwd_occ(const RrFwd& a, const fn_occ_grid* grid, const fn_occ_cascade* cascade, int32_t* live_ws, int32_t* counts_out) {
+  if (!rr_fwd_scalars(a)) return -1;
+  if (a.n == 0) return 0;
+  const int64_t P1 = a.n * (int64_t)(a.N_samples + a.N_importance);
+  if (P1 >= ((int64_t)1 << 31)) {
+    fn::set_error("%s: bad argument: n * (N_samples + N_importance) < 2^31 (lists index points with int32)", a.fname);
     return -1;
   }
-  if (N_importance > 0 && N_samples < 3) {
-    fn::set_error("%s: hierarchical sampling needs N_samples >= 3 (the inner weights of 2 samples are empty)", fname);
-    return -1;
-  }
-  if (n == 0) return 0;
-  const int S1 = N_samples + N_importance;
-  if (n * (int64_t)S1 >= ((int64_t)1 << 31)) {
-    fn::set_error("%s: bad argument: n * (N_samples + N_importance) < 2^31 (lists index points with int32)", fname);
-    return -1;
-  }
-  if (!rays11 || !params_c || !packed_c || (!grid && !cascade) || !live_ws || !counts_out || !z0 || !raw0 || !rgb0 || !disp0 || !acc0 ||
-      !w0 || !depth0) {
-    fn::set_error("%s: null pointer (coarse pass)", fname);
+  if (!rr_fwd_coarse_ptrs(a) || (!grid && !cascade) || !live_ws || !counts_out) {
+    fn::set_error("%s: null pointer (coarse pass)", a.fname);
     return -1;
   }
   if (const char* fault = cascade ? fn::occ_cascade_fault(cascade) : nullptr) {   // before anything is enqueued
-    fn::set_error("%s: bad argument: %s", fname, fault);
+    fn::set_error("%s: bad argument: %s", a.fname, fault);
     return -1;
   }
   int32_t* idx = live_ws;
-  int32_t* cws = live_ws + n * (int64_t)S1;
-  int rc;
-  auto mlp = [&](int S, const float* z, const float* params, const float* packed, float* raw, int32_t* cnt) -> int {
-    if ((rc = cascade ? fastnerf_occ_classify_cascade(cascade, n, S, rays11, z, idx, cnt, raw, cws, stream)
-                      : fastnerf_occ_classify(grid, n, S, rays11, z, idx, cnt, raw, cws, stream)))
+  int32_t* cws = live_ws + P1;
+  return rr_fwd_chain(a, [&](int pass, int S, const float* z, const float* params, const float* packed, float* raw, const float*) {
+    int32_t* cnt = counts_out + 2 * pass;
+    if (int rc = cascade ? fastnerf_occ_classify_cascade(cascade, a.n, S, a.rays11, z, idx, cnt, raw, cws, a.stream)
+                         : fastnerf_occ_classify(grid, a.n, S, a.rays11, z, idx, cnt, raw, cws, a.stream))
       return rc;
-    if (math_mode == 2) return fastnerf_mlp_x6_fwd_list(0, n, S, rays11, z, params, packed, raw, idx, cnt, flags, stream);
-    return math_mode ? fastnerf_mlp_bf16_fwd_list(0, n, S, rays11, z, params, packed, raw, idx, cnt, flags, stream)
-                     : fastnerf_mlp_fwd_list_ex(0, n, S, rays11, z, params, packed, raw, idx, cnt, flags, stream);
-  };
-  if ((rc = fastnerf_sample_coarse(n, N_samples, rays11, lindisp, perturb, t_rand, seed0, z0, stream))) return rc;
-  if ((rc = mlp(N_samples, z0, params_c, packed_c, raw0, counts_out))) return rc;
-  if ((rc = fastnerf_raw2outputs_fwd(n, N_samples, raw0, z0, rays11, nullptr, white_bkgd, rgb0, disp0, acc0, w0, depth0, stream)))
-    return rc;
-  if (N_importance == 0) return 0;
-  if (!params_f || !packed_f || !z1 || !z_samples || !z_std || !raw1 || !rgb1 || !disp1 || !acc1 || !w1 || !depth1) {
-    fn::set_error("%s: null pointer (fine pass)", fname);
-    return -1;
-  }
-  if ((rc = fastnerf_sample_pdf_merge(n, N_samples, N_importance, z0, w0, det, u, seed1, z1, z_samples, z_std, stream)))
-    return rc;
-  if ((rc = mlp(S1, z1, params_f, packed_f, raw1, counts_out + 2))) return rc;
-  return fastnerf_raw2outputs_fwd(n, S1, raw1, z1, rays11, nullptr, white_bkgd, rgb1, disp1, acc1, w1, depth1, stream);
+    return modes[a.math_mode].fwd_list(0, a.n, S, a.rays11, z, params, packed, raw, idx, cnt, a.flags, a.stream);
+  });
 }
 
 extern "C" int fastnerf_render_rays_fwd_occ(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11, int lindisp,
@@ -124,9 +170,10 @@ extern "C" int fastnerf_render_rays_fwd_occ(int math_mode, int64_t n, int N_samp
                                             float* z0, float* raw0, float* rgb0, float* disp0, float* acc0, float* w0, float* depth0,
                                             float* z1, float* z_samples, float* z_std, float* raw1, float* rgb1, float* disp1,
                                             float* acc1, float* w1, float* depth1, int flags, fn_stream_t stream) {
-  return rr_fwd_occ("fastnerf_render_rays_fwd_occ", math_mode, n, N_samples, N_importance, rays11, lindisp, perturb, det, white_bkgd,
-                    t_rand, u, seed0, seed1, params_c, packed_c, params_f, packed_f, grid, nullptr, live_ws, counts_out, z0, raw0, rgb0,
-                    disp0, acc0, w0, depth0, z1, z_samples, z_std, raw1, rgb1, disp1, acc1, w1, depth1, flags, stream);
+  return rr_fwd_occ({"fastnerf_render_rays_fwd_occ", math_mode, n, N_samples, N_importance, rays11, lindisp, perturb, det, white_bkgd,
+                     t_rand, u, nullptr, nullptr, seed0, seed1, params_c, packed_c, params_f, packed_f, z0, raw0, rgb0, disp0, acc0, w0,
+                     depth0, z1, z_samples, z_std, raw1, rgb1, disp1, acc1, w1, depth1, flags, stream},
+                    grid, nullptr, live_ws, counts_out);
 }
 
 extern "C" int fastnerf_render_rays_fwd_occ_cascade(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11,
@@ -137,14 +184,12 @@ extern "C" int fastnerf_render_rays_fwd_occ_cascade(int math_mode, int64_t n, in
                                                     float* raw0, float* rgb0, float* disp0, float* acc0, float* w0, float* depth0,
                                                     float* z1, float* z_samples, float* z_std, float* raw1, float* rgb1, float* disp1,
                                                     float* acc1, float* w1, float* depth1, int flags, fn_stream_t stream) {
-  return rr_fwd_occ("fastnerf_render_rays_fwd_occ_cascade", math_mode, n, N_samples, N_importance, rays11, lindisp, perturb, det,
-                    white_bkgd, t_rand, u, seed0, seed1, params_c, packed_c, params_f, packed_f, nullptr, cascade, live_ws, counts_out,
-                    z0, raw0, rgb0, disp0, acc0, w0, depth0, z1, z_samples, z_std, raw1, rgb1, disp1, acc1, w1, depth1, flags, stream);
+  return rr_fwd_occ({"fastnerf_render_rays_fwd_occ_cascade", math_mode, n, N_samples, N_importance, rays11, lindisp, perturb, det,
+                     white_bkgd, t_rand, u, nullptr, nullptr, seed0, seed1, params_c, packed_c, params_f, packed_f, z0, raw0, rgb0,
+                     disp0, acc0, w0, depth0, z1, z_samples, z_std, raw1, rgb1, disp1, acc1, w1, depth1, flags, stream},
+                    nullptr, cascade, live_ws, counts_out);
 }
 
-// Backward of the same chain (autograd of render.py:238-299 w.r.t. the network parameters; sample positions are
-// detached in the reference, so the coarse net only sees d(loss)/d(rgb0)): compositing backward -> MLP backward for the
-// fine pass (into grads_f) and the coarse pass (into grads_c).  draw_ws: n * (N_samples + N_importance) * 4 floats.
 extern "C" int fastnerf_render_rays_fwd(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11,
                                         int lindisp, int perturb, int det, int white_bkgd, const float* t_rand, const float* u,
                                         const float* noise0, const float* noise1, uint64_t seed0, uint64_t seed1,
@@ -159,6 +204,9 @@ extern "C" int fastnerf_render_rays_fwd(int math_mode, int64_t n, int N_samples,
                                      stream);
 }
 
+// Backward of the same chain (autograd of render.py:238-299 w.r.t. the network parameters; sample positions are
+// detached in the reference, so the coarse net only sees d(loss)/d(rgb0)): compositing backward -> MLP backward for the
+// fine pass (into grads_f) and the coarse pass (into grads_c).  draw_ws: n * (N_samples + N_importance) * 4 floats.
 // passes: bit 0 = the fine pass (N_importance > 0 only), bit 1 = the coarse pass (the only one when N_importance == 0)
 static int rr_bwd(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11,
                   int white_bkgd, const float* g_rgb, const float* g_rgb0, const float* noise0,
@@ -177,9 +225,7 @@ static int rr_bwd(int math_mode, int64_t n, int N_samples, int N_importance, con
   }
   int rc;
   auto mlp = [&](int S, const float* act, const float* params, const float* packed, float* grads) {
-    if (math_mode == 2) return fastnerf_mlp_x6_bwd(0, n, S, draw_ws, act, params, packed, dact_ws, partial_ws, grads, stream);
-    return math_mode ? fastnerf_mlp_bf16_bwd(0, n, S, draw_ws, act, params, packed, dact_ws, partial_ws, grads, stream)
-                     : fastnerf_mlp_bwd_ex(0, n, S, draw_ws, act, params, packed, dact_ws, partial_ws, grads, stream);
+    return modes[math_mode].bwd(0, n, S, draw_ws, act, params, packed, dact_ws, partial_ws, grads, stream);
   };
   const float* g_coarse = g_rgb;
   if (N_importance > 0) {
@@ -246,16 +292,8 @@ static int rr_bwd_live(int math_mode, int64_t n, int N_samples, int N_importance
                   const float* pf, const float* pb, float* grads, int32_t* cnt_out) -> int {
     if ((rc = fastnerf_raw2outputs_bwd(n, S, raw, z, rays11, noise, white_bkgd, g, draw_ws, stream))) return rc;
     if ((rc = fastnerf_compact_live(n * (int64_t)S, draw_ws, idx, cnt_out, cws, stream))) return rc;
-    if (math_mode == 2) {
-      if ((rc = fastnerf_mlp_x6_fwd_live(0, n, S, rays11, z, params, pf, act_ws, idx, cnt_out, stream))) return rc;
-      return fastnerf_mlp_x6_bwd_live(0, n, S, draw_ws, act_ws, params, pb, dact_ws, partial_ws, grads, idx, cnt_out, stream);
-    }
-    if (math_mode) {
-      if ((rc = fastnerf_mlp_bf16_fwd_live(0, n, S, rays11, z, params, pf, act_ws, idx, cnt_out, stream))) return rc;
-      return fastnerf_mlp_bf16_bwd_live(0, n, S, draw_ws, act_ws, params, pb, dact_ws, partial_ws, grads, idx, cnt_out, stream);
-    }
-    if ((rc = fastnerf_mlp_fwd_live_ex(0, n, S, rays11, z, params, pf, act_ws, idx, cnt_out, stream))) return rc;
-    return fastnerf_mlp_bwd_live_ex(0, n, S, draw_ws, act_ws, params, pb, dact_ws, partial_ws, grads, idx, cnt_out, stream);
+    if ((rc = modes[math_mode].fwd_live(0, n, S, rays11, z, params, pf, act_ws, idx, cnt_out, stream))) return rc;
+    return modes[math_mode].bwd_live(0, n, S, draw_ws, act_ws, params, pb, dact_ws, partial_ws, grads, idx, cnt_out, stream);
   };
   const float* g_coarse = g_rgb;
   int32_t* c_fine = counts_out ? counts_out : cnt;
@@ -383,12 +421,8 @@ extern "C" int fastnerf_train_step(const fn_step_args* a, int phases, fn_stream_
     const int64_t total = a->net_floats * (two ? 2 : 1);
     if ((rc = fastnerf_adam_step(total, a->params, a->grads, a->adam_m, a->adam_v, a->lr, a->beta1, a->beta2, a->eps, a->adam_t,
                                  stream))) return rc;
-    auto pack = [&](const float* p, float* pf, float* pb) {
-      if (a->math_mode == 2) return fastnerf_mlp_x6_pack(0, p, pf, pb, stream);
-      return a->math_mode ? fastnerf_mlp_bf16_pack(0, p, pf, pb, stream) : fastnerf_mlp_pack_ex(0, p, pf, pb, stream);
-    };
-    if ((rc = pack(params_c, a->packed_fwd_c, a->packed_bwd_c))) return rc;
-    if (two && (rc = pack(params_f, a->packed_fwd_f, a->packed_bwd_f))) return rc;
+    if ((rc = modes[a->math_mode].pack(0, params_c, a->packed_fwd_c, a->packed_bwd_c, stream))) return rc;
+    if (two && (rc = modes[a->math_mode].pack(0, params_f, a->packed_fwd_f, a->packed_bwd_f, stream))) return rc;
   }
   return 0;
 }

@@ -22,13 +22,12 @@ DACT_FLOATS = 2432
 # ---- matrix-core math mode of the 8x256 MLP kernels ---------------------------------------------
 # 'fp32'   : v_mfma_f32_32x32x2_f32 (csrc/mlp_*.hip), every kind: the products and sums of an fp32 FMA chain
 # 'bf16x6' : csrc/mlp_*.hip MM_X6 -- every fp32 operand decomposed EXACTLY into three bf16 pieces, a product = its six piece
-#            products of weight >= 2^-16, fp32 accumulation on v_mfma_f32_32x32x16_bf16: fp32-WIDTH products (the dropped terms
+#            products of weight >= 2^-16, fp32 accumulation on v_mfma_f32_16x16x32_bf16: fp32-WIDTH products (the dropped terms
 #            are <= 2^-24 of the product) at 2.67x the matrix rate of the fp32 instruction; same buffers as 'fp32' except the
 #            packed weights (three bf16 planes)
 # 'bf16x3' : 3-term split-bf16 (two pieces, 16 significand bits) on the same instruction (csrc/mlp_bf16.hip): NARROWER than
 #            fp32 (products ~2^-17 relative), ~2.5x the rate of 'fp32'; rendered RGB still within 1e-6 of the fp32 kernels
 # (the two-fp16-piece 'f16x3' experiment of round 4 was deleted in round 6: unguarded fp16 range; its record is profiles/r04_f16x3_*)
-import os
 MATH_MODES = ('fp32', 'bf16x3', 'bf16x6')
 _MODE_ID = {'fp32': 0, 'bf16x3': 1, 'bf16x6': 2}
 _MATH = os.environ.get('FASTNERF_MATH', 'bf16x6')   # default: the reference's arithmetic width
@@ -50,10 +49,6 @@ def set_math(mode):
 def mode_id():
     """math_mode argument of the fused C-ABI entry points (fastnerf_render_rays_*, fastnerf_train_step)."""
     return _MODE_ID[_MATH]
-
-
-def _x6():
-    return _MATH == 'bf16x6'
 
 
 # math mode a packed-weight buffer was produced under: a Python attribute on the tensor object AND a registry by storage
@@ -95,29 +90,52 @@ def packed_tag(t):
     return entry[0] if entry else None
 
 
-def _split(kind):
-    return _MATH == 'bf16x3' and int(kind) in (0, 1, 2)
+# The MLP entry points of each family (include/fastnerf.h), by operation: the one place that knows their names.  The plain
+# forward is the odd one out: only fastnerf_mlp_x6_fwd takes `flags` (after `act`).
+_MLP = {
+    'fp32': dict(pack='fastnerf_mlp_pack_ex', fwd='fastnerf_mlp_fwd_ex', bwd='fastnerf_mlp_bwd_ex', fwd_live='fastnerf_mlp_fwd_live_ex',
+                 bwd_live='fastnerf_mlp_bwd_live_ex', fwd_list='fastnerf_mlp_fwd_list_ex'),
+    'bf16x3': dict(pack='fastnerf_mlp_bf16_pack', fwd='fastnerf_mlp_bf16_fwd', bwd='fastnerf_mlp_bf16_bwd',
+                   fwd_live='fastnerf_mlp_bf16_fwd_live', bwd_live='fastnerf_mlp_bf16_bwd_live', fwd_list='fastnerf_mlp_bf16_fwd_list'),
+    'bf16x6': dict(pack='fastnerf_mlp_x6_pack', fwd='fastnerf_mlp_x6_fwd', bwd='fastnerf_mlp_x6_bwd', fwd_live='fastnerf_mlp_x6_fwd_live',
+                   bwd_live='fastnerf_mlp_x6_bwd_live', fwd_list='fastnerf_mlp_x6_fwd_list'),
+}
+
+
+def _family(kind):
+    """The kernel family that serves a net of this kind under the current math mode: the split-bf16 kernels exist for kinds
+    0 to 2 only, any other kind runs on the exact-fp32 ones under 'bf16x3'."""
+    if _MATH == 'bf16x3' and int(kind) not in (0, 1, 2):
+        return 'fp32'
+    return _MATH
+
+
+def _mlp(op, kind):
+    """(ctypes function, its name) of the MLP operation `op` for a net of this kind under the current math mode."""
+    name = _MLP[_family(kind)][op]
+    return getattr(lib(), name), name
 
 
 def act_floats(P, kind=0):
     """Size (floats) of the saved-activation buffer for P points of a net of the given kind."""
-    if _split(kind):
+    if _family(kind) == 'bf16x3':
         return int(lib().fastnerf_mlp_bf16_floats(int(kind), 3, int(P)))
     return int(lib().fastnerf_mlp_act_floats(int(kind), int(P)))
 
 
 def dact_floats(P, kind=0):
     """Size (floats) of the pre-activation-gradient workspace for P points."""
-    if _split(kind):
+    if _family(kind) == 'bf16x3':
         return int(lib().fastnerf_mlp_bf16_floats(int(kind), 4, int(P)))
     return int(P) * DACT_FLOATS
 
 
 def packed_floats(kind, which):
     """which: 1 forward, 2 backward packed-weight buffer (floats) under the current math mode."""
-    if _split(kind):
+    family = _family(kind)
+    if family == 'bf16x3':
         return int(lib().fastnerf_mlp_bf16_floats(int(kind), int(which), 0))
-    if _x6():
+    if family == 'bf16x6':
         return int(lib().fastnerf_mlp_x6_packed_floats(int(kind), int(which)))
     return net_floats(kind, which)
 
@@ -207,15 +225,8 @@ def mlp_pack(params, packed_fwd=None, packed_bwd=None, kind=0):
     # the two modes' buffers can have the same size: tag them so that a mix-up is an error, not garbage
     for t in (packed_fwd, packed_bwd):
         _tag_packed(t, _MATH)
-    if _split(kind):
-        check(lib().fastnerf_mlp_bf16_pack(int(kind), ptr(params), ptr(packed_fwd), ptr(packed_bwd), stream()),
-              'fastnerf_mlp_bf16_pack')
-        return packed_fwd, packed_bwd
-    if _x6():
-        check(lib().fastnerf_mlp_x6_pack(int(kind), ptr(params), ptr(packed_fwd), ptr(packed_bwd), stream()), 'fastnerf_mlp_x6_pack')
-        return packed_fwd, packed_bwd
-    check(lib().fastnerf_mlp_pack_ex(int(kind), ptr(params), ptr(packed_fwd), ptr(packed_bwd), stream()),
-          'fastnerf_mlp_pack_ex')
+    fn, name = _mlp('pack', kind)
+    check(fn(int(kind), ptr(params), ptr(packed_fwd), ptr(packed_bwd), stream()), name)
     return packed_fwd, packed_bwd
 
 
@@ -230,16 +241,9 @@ def mlp_fwd(rays11, z, params, packed_fwd, act=None, raw=None, kind=0):
         assert act.numel() >= act_floats(n * S, kind)
     assert packed_fwd.numel() == packed_floats(kind, 1) and packed_tag(packed_fwd) == _MATH, \
         'packed weights were not produced by mlp_pack under the current math mode'
-    if _split(kind):
-        check(lib().fastnerf_mlp_bf16_fwd(int(kind), n, S, ptr(rays11), ptr(z), ptr(params), ptr(packed_fwd), ptr(raw),
-                                          ptr(act), stream()), 'fastnerf_mlp_bf16_fwd')
-        return raw
-    if _x6():
-        check(lib().fastnerf_mlp_x6_fwd(int(kind), n, S, ptr(rays11), ptr(z), ptr(params), ptr(packed_fwd), ptr(raw), ptr(act), 0,
-                                        stream()), 'fastnerf_mlp_x6_fwd')
-        return raw
-    check(lib().fastnerf_mlp_fwd_ex(int(kind), n, S, ptr(rays11), ptr(z), ptr(params), ptr(packed_fwd), ptr(raw),
-                                    ptr(act), stream()), 'fastnerf_mlp_fwd_ex')
+    fn, name = _mlp('fwd', kind)
+    flags = (0,) if name == 'fastnerf_mlp_x6_fwd' else ()
+    check(fn(int(kind), n, S, ptr(rays11), ptr(z), ptr(params), ptr(packed_fwd), ptr(raw), ptr(act), *flags, stream()), name)
     return raw
 
 
@@ -253,16 +257,8 @@ def mlp_bwd(draw, act, params, packed_bwd, dact, partial, grads, kind=0):
     assert dact.numel() >= dact_floats(n * S, kind) and grads.numel() == net_floats(kind, 0)
     assert packed_bwd.numel() == packed_floats(kind, 2) and packed_tag(packed_bwd) == _MATH, \
         'packed weights were not produced by mlp_pack under the current math mode'
-    if _split(kind):
-        check(lib().fastnerf_mlp_bf16_bwd(int(kind), n, S, ptr(draw), ptr(act), ptr(params), ptr(packed_bwd), ptr(dact),
-                                          ptr(partial), ptr(grads), stream()), 'fastnerf_mlp_bf16_bwd')
-        return grads
-    if _x6():
-        check(lib().fastnerf_mlp_x6_bwd(int(kind), n, S, ptr(draw), ptr(act), ptr(params), ptr(packed_bwd), ptr(dact), ptr(partial),
-                                        ptr(grads), stream()), 'fastnerf_mlp_x6_bwd')
-        return grads
-    check(lib().fastnerf_mlp_bwd_ex(int(kind), n, S, ptr(draw), ptr(act), ptr(params), ptr(packed_bwd), ptr(dact),
-                                    ptr(partial), ptr(grads), stream()), 'fastnerf_mlp_bwd_ex')
+    fn, name = _mlp('bwd', kind)
+    check(fn(int(kind), n, S, ptr(draw), ptr(act), ptr(params), ptr(packed_bwd), ptr(dact), ptr(partial), ptr(grads), stream()), name)
     return grads
 
 
@@ -281,18 +277,12 @@ def raw2outputs_fwd(raw, z, rays11, noise=None, white_bkgd=False):
     return rgb, disp, acc, weights, depth
 
 
-def render_rays_fwd(rays11, params_c, packed_c, params_f, packed_f, N_samples, N_importance, lindisp=False, perturb=False,
-                    det=True, white_bkgd=False, t_rand=None, u=None, noise0=None, noise1=None, seed0=0, seed1=0, save=False, skip_dead_rgb=False, act_bufs=None):
-    """One C-ABI call for the whole forward of render_rays (render.py:238-299).  Returns a dict of the tensors the
-    step-by-step ops would have produced (same kernels, same results).  params_f / packed_f may be None when
-    N_importance == 0."""
-    require_gpu(rays11, params_c, packed_c, params_f, packed_f, t_rand, u, noise0, noise1)
+def _rr_fwd_outputs(rays11, packed_c, packed_f, N_samples, N_importance, t_rand, u, act_buf=lambda k, P: None):
+    """What render_rays_fwd and render_rays_fwd_occ do before their call: the packed-weight and random-draw checks, and the dict of
+    output tensors (act0 / act1 from act_buf(pass, points)).  Returns (outputs, t_rand, u)."""
     n = rays11.shape[0]
-    dev = rays11.device
-    f32 = dict(device=dev, dtype=torch.float32)
-    split = _split(0)
-    tag = _MATH
-    assert packed_tag(packed_c) == tag and (packed_f is None or packed_tag(packed_f) == tag), \
+    f32 = dict(device=rays11.device, dtype=torch.float32)
+    assert packed_tag(packed_c) == _MATH and (packed_f is None or packed_tag(packed_f) == _MATH), \
         'packed weights were not produced by mlp_pack under the current math mode'
     if t_rand is not None:
         t_rand = _f32(t_rand)
@@ -300,35 +290,55 @@ def render_rays_fwd(rays11, params_c, packed_c, params_f, packed_f, N_samples, N
     if u is not None:
         u = _f32(u)
         assert u.shape == (n, N_importance)
-    # act_bufs = (buffer for the coarse pass, buffer for the fine pass): caller-owned scratch for the saved activations (11 GB at
-    # the bench size) instead of fresh allocations -- for callers whose backward follows before the next forward
-    def act_buf(k, count):
-        if not save:
-            return None
-        if act_bufs is not None and act_bufs[k] is not None:
-            assert act_bufs[k].numel() >= count and act_bufs[k].dtype == torch.float32 and act_bufs[k].device == dev
-            return act_bufs[k]
-        return torch.empty(count, **f32)
     o = {'z0': torch.empty(n, N_samples, **f32), 'raw0': torch.empty(n, N_samples, 4, **f32),
-         'act0': act_buf(0, act_floats(n * N_samples)),
+         'act0': act_buf(0, n * N_samples),
          'rgb0': torch.empty(n, 3, **f32), 'disp0': torch.empty(n, **f32), 'acc0': torch.empty(n, **f32),
          'w0': torch.empty(n, N_samples, **f32), 'depth0': torch.empty(n, **f32)}
     S1 = N_samples + N_importance
     if N_importance > 0:
         o.update({'z1': torch.empty(n, S1, **f32), 'z_samples': torch.empty(n, N_importance, **f32), 'z_std': torch.empty(n, **f32),
-                  'raw1': torch.empty(n, S1, 4, **f32), 'act1': act_buf(1, act_floats(n * S1)),
+                  'raw1': torch.empty(n, S1, 4, **f32), 'act1': act_buf(1, n * S1),
                   'rgb1': torch.empty(n, 3, **f32), 'disp1': torch.empty(n, **f32), 'acc1': torch.empty(n, **f32),
                   'w1': torch.empty(n, S1, **f32), 'depth1': torch.empty(n, **f32)})
-    g = o.get
+    return o, t_rand, u
+
+
+def _rr_fwd_ptrs(o, rays11, params_c, packed_c, params_f, packed_f, N_samples, N_importance, lindisp, perturb, det, white_bkgd, t_rand,
+                 u, seed0, seed1, with_act):
+    """The arguments the forward entry points have in common, in their order: (mode .. u, seed0 .. packed_f, the outputs); the
+    plain entry point has noise0 / noise1 between the first two and takes act0 / act1 among the outputs (with_act)."""
+    head = [mode_id(), rays11.shape[0], int(N_samples), int(N_importance), ptr(rays11), int(bool(lindisp)),
+            int(bool(perturb) or t_rand is not None), int(bool(det)), int(bool(white_bkgd)), ptr(t_rand), ptr(u)]
+    nets = [int(seed0), int(seed1), ptr(params_c), ptr(packed_c), ptr(params_f), ptr(packed_f)]
+    keys = ['z0', 'raw0', 'act0', 'rgb0', 'disp0', 'acc0', 'w0', 'depth0', 'z1', 'z_samples', 'z_std', 'raw1', 'act1', 'rgb1', 'disp1',
+            'acc1', 'w1', 'depth1']
+    return head, nets, [ptr(o.get(k)) for k in keys if with_act or not k.startswith('act')]
+
+
+def render_rays_fwd(rays11, params_c, packed_c, params_f, packed_f, N_samples, N_importance, lindisp=False, perturb=False,
+                    det=True, white_bkgd=False, t_rand=None, u=None, noise0=None, noise1=None, seed0=0, seed1=0, save=False, skip_dead_rgb=False, act_bufs=None):
+    """One C-ABI call for the whole forward of render_rays (render.py:238-299).  Returns a dict of the tensors the
+    step-by-step ops would have produced (same kernels, same results).  params_f / packed_f may be None when
+    N_importance == 0."""
+    require_gpu(rays11, params_c, packed_c, params_f, packed_f, t_rand, u, noise0, noise1)
+    dev = rays11.device
+    # act_bufs = (buffer for the coarse pass, buffer for the fine pass): caller-owned scratch for the saved activations (11 GB at
+    # the bench size) instead of fresh allocations -- for callers whose backward follows before the next forward
+    def act_buf(k, P):
+        if not save:
+            return None
+        count = act_floats(P)
+        if act_bufs is not None and act_bufs[k] is not None:
+            assert act_bufs[k].numel() >= count and act_bufs[k].dtype == torch.float32 and act_bufs[k].device == dev
+            return act_bufs[k]
+        return torch.empty(count, device=dev, dtype=torch.float32)
+    o, t_rand, u = _rr_fwd_outputs(rays11, packed_c, packed_f, N_samples, N_importance, t_rand, u, act_buf)
+    head, nets, outs = _rr_fwd_ptrs(o, rays11, params_c, packed_c, params_f, packed_f, N_samples, N_importance, lindisp, perturb, det,
+                                    white_bkgd, t_rand, u, seed0, seed1, with_act=True)
     # skip_dead_rgb (FN_FWD_SKIP_DEAD_RGB): the inference launches may leave the colour logits of tiles without a live sample at
     # zero -- every other output is bit-identical; only callers that never expose `raw0` / `raw1` ask for it
-    check(lib().fastnerf_render_rays_fwd_ex(
-        mode_id(), n, int(N_samples), int(N_importance), ptr(rays11), int(bool(lindisp)),
-        int(bool(perturb) or t_rand is not None), int(bool(det)), int(bool(white_bkgd)), ptr(t_rand), ptr(u), ptr(noise0), ptr(noise1),
-        int(seed0), int(seed1), ptr(params_c), ptr(packed_c), ptr(params_f), ptr(packed_f),
-        ptr(o['z0']), ptr(o['raw0']), ptr(o['act0']), ptr(o['rgb0']), ptr(o['disp0']), ptr(o['acc0']), ptr(o['w0']), ptr(o['depth0']),
-        ptr(g('z1')), ptr(g('z_samples')), ptr(g('z_std')), ptr(g('raw1')), ptr(g('act1')), ptr(g('rgb1')), ptr(g('disp1')),
-        ptr(g('acc1')), ptr(g('w1')), ptr(g('depth1')), 1 if skip_dead_rgb else 0, stream()), 'fastnerf_render_rays_fwd_ex')
+    check(lib().fastnerf_render_rays_fwd_ex(*head, ptr(noise0), ptr(noise1), *nets, *outs, 1 if skip_dead_rgb else 0, stream()),
+          'fastnerf_render_rays_fwd_ex')
     return o
 
 
@@ -369,9 +379,8 @@ def mlp_fwd_live(rays11, z, params, packed_fwd, act, live_idx, live_cnt, kind=0)
     tag = _MATH
     assert act.numel() >= act_floats(n * S, kind) and live_idx.dtype == torch.int32 and live_cnt.dtype == torch.int32
     assert packed_fwd.numel() == packed_floats(kind, 1) and packed_tag(packed_fwd) == tag
-    fn = lib().fastnerf_mlp_bf16_fwd_live if _split(kind) else (lib().fastnerf_mlp_x6_fwd_live if _x6() else lib().fastnerf_mlp_fwd_live_ex)
-    check(fn(int(kind), n, S, ptr(rays11), ptr(z), ptr(params), ptr(packed_fwd), ptr(act), ptr(live_idx), ptr(live_cnt), stream()),
-          'fastnerf_mlp_fwd_live')
+    fn, name = _mlp('fwd_live', kind)
+    check(fn(int(kind), n, S, ptr(rays11), ptr(z), ptr(params), ptr(packed_fwd), ptr(act), ptr(live_idx), ptr(live_cnt), stream()), name)
 
 
 def mlp_bwd_live(draw, act, params, packed_bwd, dact, partial, grads, live_idx, live_cnt, kind=0):
@@ -380,9 +389,9 @@ def mlp_bwd_live(draw, act, params, packed_bwd, dact, partial, grads, live_idx, 
     tag = _MATH
     assert dact.numel() >= dact_floats(n * S, kind) and grads.numel() == net_floats(kind, 0)
     assert packed_bwd.numel() == packed_floats(kind, 2) and packed_tag(packed_bwd) == tag
-    fn = lib().fastnerf_mlp_bf16_bwd_live if _split(kind) else (lib().fastnerf_mlp_x6_bwd_live if _x6() else lib().fastnerf_mlp_bwd_live_ex)
+    fn, name = _mlp('bwd_live', kind)
     check(fn(int(kind), n, S, ptr(draw), ptr(act), ptr(params), ptr(packed_bwd), ptr(dact), ptr(partial), ptr(grads), ptr(live_idx),
-             ptr(live_cnt), stream()), 'fastnerf_mlp_bwd_live')
+             ptr(live_cnt), stream()), name)
     return grads
 
 
@@ -781,47 +790,24 @@ def mlp_fwd_list(rays11, z, params, packed_fwd, raw, live_idx, live_cnt, flags=0
     assert raw.numel() == n * S * 4 and raw.is_contiguous() and live_idx.dtype == torch.int32 and live_cnt.dtype == torch.int32
     assert packed_fwd.numel() == packed_floats(0, 1) and packed_tag(packed_fwd) == _MATH, \
         'packed weights were not produced by mlp_pack under the current math mode'
-    fn = lib().fastnerf_mlp_bf16_fwd_list if _split(0) else (lib().fastnerf_mlp_x6_fwd_list if _x6() else lib().fastnerf_mlp_fwd_list_ex)
-    check(fn(0, n, S, ptr(rays11), ptr(z), ptr(params), ptr(packed_fwd), ptr(raw), ptr(live_idx), ptr(live_cnt), int(flags), stream()),
-          'fastnerf_mlp_fwd_list')
+    fn, name = _mlp('fwd_list', 0)
+    check(fn(0, n, S, ptr(rays11), ptr(z), ptr(params), ptr(packed_fwd), ptr(raw), ptr(live_idx), ptr(live_cnt), int(flags), stream()), name)
     return raw
 
 
 def render_rays_fwd_occ(rays11, params_c, packed_c, params_f, packed_f, N_samples, N_importance, cgrid, lindisp=False, perturb=False,
                         det=True, white_bkgd=False, t_rand=None, u=None, seed0=0, seed1=0, skip_dead_rgb=False):
     """render_rays_fwd (inference, no sigma noise) through an occupancy grid (cgrid a _lib.OccGrid) or a cascade (a
-    _lib.OccCascade: fastnerf_render_rays_fwd_occ_cascade): one C-ABI call.  Same dict, without act0 / act1,
+    _lib.OccCascade: fastnerf_render_rays_fwd_occ_cascade): one C-ABI call.  Same dict, act0 / act1 None,
     plus 'counts': int32 [4] on the device = (occupied, total) samples of the coarse pass, then of the fine pass."""
     require_gpu(rays11, params_c, packed_c, params_f, packed_f, t_rand, u)
-    n = rays11.shape[0]
     dev = rays11.device
-    f32 = dict(device=dev, dtype=torch.float32)
-    assert packed_tag(packed_c) == _MATH and (packed_f is None or packed_tag(packed_f) == _MATH), \
-        'packed weights were not produced by mlp_pack under the current math mode'
-    if t_rand is not None:
-        t_rand = _f32(t_rand)
-        assert t_rand.shape == (n, N_samples)
-    if u is not None:
-        u = _f32(u)
-        assert u.shape == (n, N_importance)
-    S1 = N_samples + N_importance
-    o = {'z0': torch.empty(n, N_samples, **f32), 'raw0': torch.empty(n, N_samples, 4, **f32), 'act0': None,
-         'rgb0': torch.empty(n, 3, **f32), 'disp0': torch.empty(n, **f32), 'acc0': torch.empty(n, **f32),
-         'w0': torch.empty(n, N_samples, **f32), 'depth0': torch.empty(n, **f32),
-         'counts': torch.zeros(4, device=dev, dtype=torch.int32)}
-    if N_importance > 0:
-        o.update({'z1': torch.empty(n, S1, **f32), 'z_samples': torch.empty(n, N_importance, **f32), 'z_std': torch.empty(n, **f32),
-                  'raw1': torch.empty(n, S1, 4, **f32), 'act1': None,
-                  'rgb1': torch.empty(n, 3, **f32), 'disp1': torch.empty(n, **f32), 'acc1': torch.empty(n, **f32),
-                  'w1': torch.empty(n, S1, **f32), 'depth1': torch.empty(n, **f32)})
-    live_ws = torch.empty(max(1, n * S1 + int(lib().fastnerf_compact_ws_ints(max(1, n * S1)))), device=dev, dtype=torch.int32)
-    g = o.get
+    o, t_rand, u = _rr_fwd_outputs(rays11, packed_c, packed_f, N_samples, N_importance, t_rand, u)
+    o['counts'] = torch.zeros(4, device=dev, dtype=torch.int32)
+    P1 = rays11.shape[0] * (N_samples + N_importance)
+    live_ws = torch.empty(max(1, P1 + int(lib().fastnerf_compact_ws_ints(max(1, P1)))), device=dev, dtype=torch.int32)
+    head, nets, outs = _rr_fwd_ptrs(o, rays11, params_c, packed_c, params_f, packed_f, N_samples, N_importance, lindisp, perturb, det,
+                                    white_bkgd, t_rand, u, seed0, seed1, with_act=False)
     fn, name = _occ_entry(cgrid, 'fastnerf_render_rays_fwd_occ')
-    check(fn(
-        mode_id(), n, int(N_samples), int(N_importance), ptr(rays11), int(bool(lindisp)),
-        int(bool(perturb) or t_rand is not None), int(bool(det)), int(bool(white_bkgd)), ptr(t_rand), ptr(u), int(seed0), int(seed1),
-        ptr(params_c), ptr(packed_c), ptr(params_f), ptr(packed_f), cgrid, ptr(live_ws), ptr(o['counts']),
-        ptr(o['z0']), ptr(o['raw0']), ptr(o['rgb0']), ptr(o['disp0']), ptr(o['acc0']), ptr(o['w0']), ptr(o['depth0']),
-        ptr(g('z1')), ptr(g('z_samples')), ptr(g('z_std')), ptr(g('raw1')), ptr(g('rgb1')), ptr(g('disp1')), ptr(g('acc1')),
-        ptr(g('w1')), ptr(g('depth1')), 1 if skip_dead_rgb else 0, stream()), name)
+    check(fn(*head, *nets, cgrid, ptr(live_ws), ptr(o['counts']), *outs, 1 if skip_dead_rgb else 0, stream()), name)
     return o

@@ -154,6 +154,16 @@ class LivePolicy:
         self.step += 1
 
 
+def _maps(o, N_importance):
+    """The outputs of ops.render_rays_fwd / _fwd_occ under the names of render_rays' maps."""
+    if N_importance > 0:
+        return dict(rgb_map=o['rgb1'], disp_map=o['disp1'], acc_map=o['acc1'], raw=o['raw1'], rgb0=o['rgb0'], disp0=o['disp0'],
+                    acc0=o['acc0'], z_std=o['z_std'], weights=o['w1'], z_vals=o['z1'], depth_map=o['depth1'],
+                    z_samples=o['z_samples'], weights0=o['w0'], z0=o['z0'])
+    return dict(rgb_map=o['rgb0'], disp_map=o['disp0'], acc_map=o['acc0'], raw=o['raw0'], weights=o['w0'], z_vals=o['z0'],
+                depth_map=o['depth0'])
+
+
 def _forward_core(rays11, net_c, net_f, N_samples, N_importance, lindisp, perturb, white_bkgd, t_rand, u, noise0,
                   noise1, save, packed_c=None, packed_f=None, skip_dead_rgb=False, act_ws=False):
     """The fused forward.  Returns (outputs dict, saved-for-backward dict)."""
@@ -176,18 +186,11 @@ def _forward_core(rays11, net_c, net_f, N_samples, N_importance, lindisp, pertur
                             seed0=_next_seed() if (perturb and t_rand is None) else 0,
                             seed1=_next_seed() if (N_importance > 0 and perturb and u is None) else 0, save=save,
                             skip_dead_rgb=bool(skip_dead_rgb and not save and net_c.use_viewdirs), act_bufs=act_bufs)
-    out = {}
     saved = {'rays11': rays11, 'z0': o['z0'], 'raw0': o['raw0'], 'act0': o['act0'], 'noise0': noise0, 'white': white_bkgd,
              'net_c': net_c, 'net_f': None, 'pc': pc, 'live': not save}
     if N_importance > 0:
-        out.update(rgb_map=o['rgb1'], disp_map=o['disp1'], acc_map=o['acc1'], raw=o['raw1'], rgb0=o['rgb0'], disp0=o['disp0'],
-                   acc0=o['acc0'], z_std=o['z_std'], weights=o['w1'], z_vals=o['z1'], depth_map=o['depth1'],
-                   z_samples=o['z_samples'], weights0=o['w0'], z0=o['z0'])
         saved.update(z1=o['z1'], raw1=o['raw1'], act1=o['act1'], noise1=noise1, net_f=fine, pf=pf)
-    else:
-        out.update(rgb_map=o['rgb0'], disp_map=o['disp0'], acc_map=o['acc0'], raw=o['raw0'], weights=o['w0'], z_vals=o['z0'],
-                   depth_map=o['depth0'])
-    return out, saved
+    return _maps(o, N_importance), saved
 
 
 def _forward_occ(rays11, net_c, net_f, N_samples, N_importance, lindisp, perturb, white_bkgd, t_rand, u, occupancy, skip_dead_rgb=False):
@@ -205,12 +208,7 @@ def _forward_occ(rays11, net_c, net_f, N_samples, N_importance, lindisp, perturb
                                 seed0=_next_seed() if (perturb and t_rand is None) else 0,
                                 seed1=_next_seed() if (N_importance > 0 and perturb and u is None) else 0,
                                 skip_dead_rgb=bool(skip_dead_rgb and net_c.use_viewdirs))
-    if N_importance > 0:
-        return dict(rgb_map=o['rgb1'], disp_map=o['disp1'], acc_map=o['acc1'], raw=o['raw1'], rgb0=o['rgb0'], disp0=o['disp0'],
-                    acc0=o['acc0'], z_std=o['z_std'], weights=o['w1'], z_vals=o['z1'], depth_map=o['depth1'],
-                    z_samples=o['z_samples'], weights0=o['w0'], z0=o['z0'], raw0=o['raw0'], counts=o['counts'])
-    return dict(rgb_map=o['rgb0'], disp_map=o['disp0'], acc_map=o['acc0'], raw=o['raw0'], weights=o['w0'], z_vals=o['z0'],
-                depth_map=o['depth0'], z0=o['z0'], raw0=o['raw0'], counts=o['counts'])
+    return dict(_maps(o, N_importance), z0=o['z0'], raw0=o['raw0'], counts=o['counts'])
 
 
 def _backward_core(saved, g_rgb, g_rgb0, out_c=None, out_f=None, counts=None):
@@ -455,22 +453,16 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     if not fused:
         return _render_rays_closure(ray_batch, rays11, network_fn, network_fine, network_query_fn, N_samples, N_importance, retraw,
                                     lindisp, perturb, white_bkgd, t_rand, u, noise0, noise1, occupancy=occupancy)
-    if occupancy is not None:
-        out = _forward_occ(rays11, net_c, net_f, N_samples, N_importance, lindisp, perturb, white_bkgd, t_rand, u, occupancy,
-                           skip_dead_rgb=not retraw)
-        ret = {'rgb_map': out['rgb_map'], 'disp_map': out['disp_map'], 'acc_map': out['acc_map']}
-        if retraw:
-            ret['raw'] = out['raw']
-        if N_importance > 0:
-            ret['rgb0'], ret['disp0'], ret['acc0'], ret['z_std'] = out['rgb0'], out['disp0'], out['acc0'], out['z_std']
-        return ret
     cfg = dict(rays11=rays11, net_c=net_c, net_f=net_f, N_samples=N_samples, N_importance=N_importance,
                lindisp=lindisp, perturb=perturb, white_bkgd=white_bkgd, t_rand=t_rand, u=u, noise0=noise0,
                noise1=noise1,
                # nobody sees the colour logits of this call: tiles without a live sample may skip them (FN_FWD_SKIP_DEAD_RGB)
                skip_dead_rgb=not retraw)
     params = list(net_c.parameters()) + (list(net_f.parameters()) if (net_f is not None and net_f is not net_c) else [])
-    if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+    if occupancy is not None:
+        out = _forward_occ(rays11, net_c, net_f, N_samples, N_importance, lindisp, perturb, white_bkgd, t_rand, u, occupancy,
+                           skip_dead_rgb=not retraw)
+    elif torch.is_grad_enabled() and any(p.requires_grad for p in params):
         outs = _RenderRaysFn.apply(cfg, *params)
         keys = ['rgb_map', 'disp_map', 'acc_map', 'raw'] + (['rgb0', 'disp0', 'acc0', 'z_std'] if N_importance > 0 else [])
         out = dict(zip(keys, outs))

@@ -49,3 +49,29 @@ def test_build_freshness_is_by_source_content(monkeypatch):
     assert b._stale(extra=('-DSOMETHING',)), 'other flags are another build'
     monkeypatch.setattr(b, 'FLAGS', b.FLAGS + ['-O2'])
     assert b._stale()
+
+
+def _render_rays_fwd_calls(math_mode, n):
+    """The three forward entry points of render_rays with these scalars and NULL for every pointer, as (the prefix its error texts
+    carry, call): their scalar checks and the n == 0 return come before anything touches a pointer or the GPU."""
+    lib = _lib.lib()
+    head = [math_mode, n, 64, 128, None, 0, 0, 1, 0, None, None]      # .. rays11, lindisp, perturb, det, white_bkgd, t_rand, u
+    nets = [0, 0, None, None, None, None]                              # seed0, seed1, params_c .. packed_f
+    return [('fastnerf_render_rays_fwd:', lambda: lib.fastnerf_render_rays_fwd_ex(*head, None, None, *nets, *[None] * 18, 0, None)),
+            ('fastnerf_render_rays_fwd_occ:', lambda: lib.fastnerf_render_rays_fwd_occ(*head, *nets, None, None, None, *[None] * 16, 0, None)),
+            ('fastnerf_render_rays_fwd_occ_cascade:',
+             lambda: lib.fastnerf_render_rays_fwd_occ_cascade(*head, *nets, None, None, None, *[None] * 16, 0, None))]
+
+
+def test_render_rays_fwd_error_prefixes():
+    """A math mode outside {0, 1, 2} is refused by each forward entry point under its own name (fastnerf_render_rays_fwd_ex reports
+    as fastnerf_render_rays_fwd)."""
+    for prefix, call in _render_rays_fwd_calls(7, 4):
+        assert call() == -1
+        msg = _lib.lib().fastnerf_last_error().decode()
+        assert msg.startswith(prefix), msg
+
+
+def test_render_rays_fwd_no_rays_is_no_work():
+    for _, call in _render_rays_fwd_calls(2, 0):
+        assert call() == 0

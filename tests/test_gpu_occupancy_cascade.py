@@ -111,10 +111,16 @@ def test_query_equals_the_restatement(fn, outside):
     assert c.query(pts_t.reshape(-1, 1, 3)).shape == (pts.shape[0], 1) and c.decided_by(pts_t.reshape(-1, 1, 3)).shape == (pts.shape[0], 1)
 
 
-@pytest.mark.parametrize('S', [64, 192])
-def test_classify_equals_the_restatement(fn, S):
+# 169 rays: 169 * 64 and 169 * 192 are no multiples of the 1024-point block.  The tails: 37 x 13 = 481 points, one partial block, and
+# a thread's four consecutive samples straddle two rays (13 is no multiple of 4); 300 x 7 = 2100 points, three blocks, the last one
+# partial, so the scanned block offsets are used
+@pytest.mark.parametrize('n,S', [pytest.param(169, 64, id='64'), pytest.param(169, 192, id='192'), pytest.param(37, 13, id='37x13'),
+                                 pytest.param(300, 7, id='300x7')])
+def test_classify_equals_the_restatement(fn, n, S):
     rs = np.random.RandomState(S)
-    rays = R.scene_rays(O, side=13)      # 169 rays: 169 * 64 and 169 * 192 are no multiples of the 1024-point block
+    rays = R.scene_rays(O, side=13 if n <= 169 else 18)
+    rays = rays[np.round(np.linspace(0, rays.shape[0] - 1, n)).astype(int)]      # n rays spread over the image (all 169 of them)
+    assert rays.shape[0] == n
     z = np.sort(2.0 + 4.0 * rs.rand(rays.shape[0], S).astype(np.float32), -1)
     rays_t, z_t = torch.from_numpy(rays).cuda(), torch.from_numpy(z).cuda()
     cases = {k: (v, oo) for k, v in cascades_for_lookup().items() for oo in (True,)}
