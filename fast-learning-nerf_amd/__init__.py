@@ -7,7 +7,7 @@ The directory name contains '-', import it with
     importlib.import_module('fast-learning-nerf_amd')
 or through the `fastnerf` shim module at the repository root.
 """
-from . import _lib, ops  # noqa: F401
+from . import _lib, ops, flat_params  # noqa: F401
 from . import run_nerf_helpers, model, render, run_nerf, tree, parallel, synthetic, nerfpp, torch_ops, mesh, occupancy  # noqa: F401
 from .build import build  # noqa: F401
 

@@ -7,6 +7,9 @@ fp32 buffer laid out in `model.parameters()` order, so that
     checkpoint (with or without the DataParallel `module.` prefix) just works,
   * a data-parallel all-reduce is a single collective over `flat_grad`.
 
+What that layout means -- slice table, views, binding, packed-weight cache, checkpoint prefix -- is written once in
+flat_params.py; this module supplies the shapes.
+
 The kernels implement the configuration the reference's configs use (D=8, W=256, skips=[4], use_viewdirs=True,
 input_ch=63, input_ch_views=27).  `use_viewdirs=False` (model.py:35-36,60-61: one `output_linear` 256 -> output_ch on the
 trunk, no view branch) runs on the SAME kernels through an exactly equivalent view-branch network (`NeRF._sync_kernel_net`):
@@ -18,7 +21,7 @@ their names, order and gradients are the reference's (`views_linears.0` exists t
 import torch
 from torch import nn
 
-from . import ops
+from . import flat_params, ops
 
 SHAPES = (
     [(f'pts_linears.{i}', (256, 63 if i == 0 else (319 if i == 5 else 256))) for i in range(8)]
@@ -29,23 +32,12 @@ SHAPES = (
 
 def noview_shapes(output_ch):
     """Modules of the reference model without view directions in registration order (model.py:20-36, input_ch_views = 0)."""
-    return ([(f'pts_linears.{i}', (256, 63 if i == 0 else (319 if i == 5 else 256))) for i in range(8)]
-            + [('views_linears.0', (128, 256)), ('output_linear', (output_ch, 256))])
-
-
-def _slices(shapes):
-    out, off = [], 0
-    for name, (o, i) in shapes:
-        out.append((name + '.weight', off, (o, i)))
-        off += o * i
-        out.append((name + '.bias', off, (o,)))
-        off += o
-    return out, off
+    return SHAPES[:8] + [('views_linears.0', (128, 256)), ('output_linear', (output_ch, 256))]
 
 
 def noview_slices(output_ch):
     """[(name, offset, shape)], total floats -- parameters() order of the model without view directions."""
-    return _slices(noview_shapes(output_ch))
+    return flat_params.slices(noview_shapes(output_ch))
 
 
 PTS_FLOATS = sum(o * i + o for _, (o, i) in SHAPES[:8])   # the trunk comes first in both layouts
@@ -53,17 +45,12 @@ PTS_FLOATS = sum(o * i + o for _, (o, i) in SHAPES[:8])   # the trunk comes firs
 
 def param_slices():
     """[(name, offset, shape)] in model.parameters() order."""
-    out, off = [], 0
-    for name, (o, i) in SHAPES:
-        out.append((name + '.weight', off, (o, i)))
-        off += o * i
-        out.append((name + '.bias', off, (o,)))
-        off += o
+    out, off = flat_params.slices(SHAPES)
     assert off == ops.NET_PARAMS
     return out
 
 
-class NeRF(nn.Module):
+class NeRF(flat_params.FlatNet):
     def __init__(self, D=8, W=256, input_ch=63, input_ch_views=27, output_ch=4, skips=[4], use_viewdirs=True,
                  device='cuda', flat=None, flat_grad=None):
         super().__init__()
@@ -92,19 +79,7 @@ class NeRF(nn.Module):
         pflat = flat if flat is not None else torch.empty(total, device=dev, dtype=torch.float32)
         pgrad = flat_grad if flat_grad is not None else torch.zeros(total, device=dev, dtype=torch.float32)
         assert pflat.numel() == total and pgrad.numel() == total
-        mods = dict(self.named_modules())
-        for name, off, shape in slices:
-            mod_name, leaf = name.rsplit('.', 1)
-            mod = mods[mod_name]
-            n = 1
-            for s in shape:
-                n *= s
-            view = pflat[off:off + n].view(shape)
-            with torch.no_grad():
-                view.copy_(getattr(mod, leaf).detach().to(dev))
-            p = nn.Parameter(view)
-            p.grad = pgrad[off:off + n].view(shape)
-            setattr(mod, leaf, p)
+        flat_params.bind(self, slices, pflat, pgrad)
         self.param_flat, self.param_grad = pflat, pgrad      # the reference's parameters, parameters() order
         if use_viewdirs:
             self.flat, self.flat_grad = pflat, pgrad          # ... which is also what the kernels read / write
@@ -118,18 +93,11 @@ class NeRF(nn.Module):
                 k['rgb_linear.weight'][c, 2 * c] = 1.0
                 k['rgb_linear.weight'][c, 2 * c + 1] = -1.0
             self._sync_kernel_net()
-        self._packed = None
 
     # ---- no view directions: parameters <-> the equivalent view-branch network the kernels run -----------------
     @staticmethod
     def _kernel_views(flat):
-        out = {}
-        for name, off, shape in param_slices():
-            n = 1
-            for s in shape:
-                n *= s
-            out[name] = flat[off:off + n].view(shape)
-        return out
+        return flat_params.views(flat, param_slices())
 
     def _sync_kernel_net(self):
         if self.use_viewdirs:
@@ -177,21 +145,6 @@ class NeRF(nn.Module):
             for (name, off, shape), g in zip(noview_slices(self.output_ch)[0], self.param_grads_from(self.flat_grad)):
                 self.param_grad[off:off + g.numel()].view(shape).copy_(g)
 
-    # ---- packed weights for the MFMA kernels -----------------------------------------------
-    def packed(self, refresh=True):
-        """(packed_fwd, packed_bwd) fragment-ordered copies of the weights.  Re-packed from the
-        flat buffer on every call unless refresh=False (one ~5 MB launch; callers that update
-        the weights themselves, e.g. the fused Trainer, pass refresh=False between updates)."""
-        if self._packed is None or self._packed_mode != ops.get_math():
-            self._packed = (torch.empty(ops.packed_floats(0, 1), device=self.flat.device),
-                            torch.empty(ops.packed_floats(0, 2), device=self.flat.device))
-            self._packed_mode = ops.get_math()
-            refresh = True
-        if refresh:
-            self._sync_kernel_net()
-            ops.mlp_pack(self.flat, *self._packed)
-        return self._packed
-
     def forward(self, x):
         """Reference signature: x = [.., 63 + 27] already-embedded inputs (model.py:38-63).
         Convenience path for third-party callers (e.g. mesh extraction); the renderer never
@@ -211,5 +164,4 @@ class NeRF(nn.Module):
         return torch.cat([self.rgb_linear(h), alpha], -1)
 
     def load_state_dict(self, state_dict, strict=True):
-        sd = {(k[7:] if k.startswith('module.') else k): v for k, v in state_dict.items()}
-        return super().load_state_dict(sd, strict=strict)
+        return super().load_state_dict(flat_params.strip_prefix(state_dict), strict=strict)

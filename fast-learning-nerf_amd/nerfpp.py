@@ -12,7 +12,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import ops
+from . import flat_params, ops
 from .render import _Workspace, _burn_seeds, _next_seed
 
 TINY_NUMBER = 1e-6
@@ -22,21 +22,16 @@ HUGE_NUMBER = 1e10
 def mlpnet_slices(kind):
     """[(name, offset, shape)] in MLPNet.parameters() order (nerf_network.py:70-120)."""
     ic = 84 if kind == 2 else 63
-    out, off = [], 0
     dims = [ic] + [256] * 4 + [256 + ic] + [256] * 2
-    for i in range(8):
-        out.append((f'base_layers.{i}.0.weight', off, (256, dims[i]))); off += 256 * dims[i]
-        out.append((f'base_layers.{i}.0.bias', off, (256,))); off += 256
-    for name, shp in (('sigma_layers.0', (1, 256)), ('base_remap_layers.0', (256, 256)), ('rgb_layers.0', (128, 283)),
-                      ('rgb_layers.2', (3, 128))):
-        out.append((name + '.weight', off, shp)); off += shp[0] * shp[1]
-        out.append((name + '.bias', off, (shp[0],))); off += shp[0]
+    out, off = flat_params.slices([(f'base_layers.{i}.0', (256, dims[i])) for i in range(8)]
+                                  + [('sigma_layers.0', (1, 256)), ('base_remap_layers.0', (256, 256)),
+                                     ('rgb_layers.0', (128, 283)), ('rgb_layers.2', (3, 128))])
     assert off == ops.net_floats(kind, 0)
     return out
 
 
-class MLPNet(nn.Module):
-    """Parameters are views into a flat buffer in parameters() order; names match the reference."""
+class MLPNet(flat_params.FlatNet):
+    """Parameters are views into a flat buffer in parameters() order (flat_params.py); names match the reference."""
 
     def __init__(self, D=8, W=256, input_ch=63, input_ch_viewdirs=27, skips=[4], use_viewdirs=True, device='cuda',
                  flat=None, flat_grad=None):
@@ -62,28 +57,7 @@ class MLPNet(nn.Module):
         n = ops.net_floats(self.kind, 0)
         self.flat = flat if flat is not None else torch.empty(n, device=dev, dtype=torch.float32)
         self.flat_grad = flat_grad if flat_grad is not None else torch.zeros(n, device=dev, dtype=torch.float32)
-        mods = dict(self.named_modules())
-        for name, off, shape in mlpnet_slices(self.kind):
-            mod_name, leaf = name.rsplit('.', 1)
-            mod = mods[mod_name]
-            k = int(np.prod(shape))
-            view = self.flat[off:off + k].view(shape)
-            with torch.no_grad():
-                view.copy_(getattr(mod, leaf).detach().to(dev))
-            p = nn.Parameter(view)
-            p.grad = self.flat_grad[off:off + k].view(shape)
-            setattr(mod, leaf, p)
-        self._packed = None
-
-    def packed(self, refresh=True):
-        if self._packed is None or self._packed_mode != ops.get_math():
-            self._packed = (torch.empty(ops.packed_floats(self.kind, 1), device=self.flat.device),
-                            torch.empty(ops.packed_floats(self.kind, 2), device=self.flat.device))
-            self._packed_mode = ops.get_math()
-            refresh = True
-        if refresh:
-            ops.mlp_pack(self.flat, *self._packed, kind=self.kind)
-        return self._packed
+        flat_params.bind(self, mlpnet_slices(self.kind), self.flat, self.flat_grad)
 
     def forward(self, input):
         """Reference signature on already-embedded inputs (nerf_network.py:122-142); convenience
@@ -159,8 +133,7 @@ class _NerfNetFn(torch.autograd.Function):
         net = ctx.net
         out_f, out_b = torch.empty_like(net.fg_net.flat), torch.empty_like(net.bg_net.flat)
         _nerfnet_backward(net, ctx.saved, g_rgb.contiguous(), out_f, out_b)
-        grads = [out_f[o:o + int(np.prod(s))].view(s) for _, o, s in mlpnet_slices(1)] + \
-                [out_b[o:o + int(np.prod(s))].view(s) for _, o, s in mlpnet_slices(2)]
+        grads = [*flat_params.views(out_f, mlpnet_slices(1)).values(), *flat_params.views(out_b, mlpnet_slices(2)).values()]
         assert len(grads) == ctx.n_params
         return (None, None, None, None, None) + tuple(grads)
 
@@ -207,12 +180,11 @@ class NerfNetWithAutoExpo(nn.Module):
     def load_state_dict(self, state_dict, strict=True, **kwargs):
         """Accepts the reference's checkpoints: its nets are saved through nn.DataParallel (`module.` prefix, ddp_train_nerf.py:154).
         Further keywords of nn.Module.load_state_dict (`assign=`) are passed on."""
-        sd = {(k[7:] if k.startswith('module.') else k): v for k, v in state_dict.items()}
-        return super().load_state_dict(sd, strict=strict, **kwargs)
+        return super().load_state_dict(flat_params.strip_prefix(state_dict), strict=strict, **kwargs)
 
     def reference_state_dict(self):
         """state_dict under the names the reference saves and strictly loads (`module.nerf_net.fg_net. ...`)."""
-        return OrderedDict(('module.' + k, v) for k, v in self.state_dict().items())
+        return OrderedDict(flat_params.add_prefix(self.state_dict()))
 
 
 def intersect_sphere(ray_o, ray_d):
@@ -368,38 +340,12 @@ class CascadeTrainer:
     # ---- exchange with torch.optim.Adam (the reference's `optim_<m>` entries of model_*.pth, ddp_train_nerf.py:306-314) ----
     def torch_optimizer_state_dict(self, m):
         """Level m's Adam state in torch.optim.Adam's format over net.parameters() (= the flat buffer's order)."""
-        state, off = {}, 0
-        for i, p in enumerate(self.nets[m].parameters()):
-            k = p.numel()
-            state[i] = {'step': torch.tensor(float(self.t[m])), 'exp_avg': self.m[m][off:off + k].view(p.shape).clone(),
-                        'exp_avg_sq': self.v[m][off:off + k].view(p.shape).clone()}
-            off += k
-        assert off == self.nets[m].flat.numel()
-        group = {'lr': self.lrate, 'betas': (self.beta1, self.beta2), 'eps': self.eps, 'weight_decay': 0, 'amsgrad': False,
-                 'maximize': False, 'foreach': None, 'capturable': False, 'differentiable': False, 'fused': None,
-                 'decoupled_weight_decay': False, 'params': list(range(len(state)))}
-        return {'state': state if self.t[m] > 0 else {}, 'param_groups': [group]}
+        return flat_params.adam_state_to_torch(list(self.nets[m].parameters()), self.m[m], self.v[m], self.t[m], self.lrate,
+                                               (self.beta1, self.beta2), self.eps)
 
     def load_torch_optimizer(self, m, opt):
         """Take over level m's moments / step count from a torch.optim.Adam (or its state_dict) over the same parameters."""
-        sd = opt.state_dict() if hasattr(opt, 'state_dict') else opt
-        st = sd['state']
-        if len(st) == 0:
-            self.m[m].zero_(); self.v[m].zero_(); self.t[m] = 0
-            return
-        off, steps = 0, set()
-        for i, p in enumerate(self.nets[m].parameters()):
-            k = p.numel()
-            e = st.get(i)
-            if e is None:
-                self.m[m][off:off + k].zero_(); self.v[m][off:off + k].zero_()
-            else:
-                self.m[m][off:off + k].copy_(torch.as_tensor(e['exp_avg']).reshape(-1))
-                self.v[m][off:off + k].copy_(torch.as_tensor(e['exp_avg_sq']).reshape(-1))
-                steps.add(int(float(e['step'])))
-            off += k
-        assert off == self.nets[m].flat.numel() and len(steps) == 1, 'optimizer state does not match the parameter list'
-        self.t[m] = steps.pop()
+        self.t[m], _ = flat_params.adam_state_from_torch(list(self.nets[m].parameters()), self.m[m], self.v[m], opt)
 
 
 class QuadTreeManager:

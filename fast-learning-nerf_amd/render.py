@@ -16,7 +16,7 @@ import os
 import numpy as np
 import torch
 
-from . import ops
+from . import flat_params, ops
 from .model import NeRF, param_slices
 from .run_nerf_helpers import compute_ssim, get_rays, to8b
 
@@ -270,7 +270,7 @@ _POLICY = LivePolicy()   # the autograd route's policy (the fused Trainer keeps 
 
 
 def _grad_views(flat):
-    return [flat[off:off + int(np.prod(shape))].view(shape) for _, off, shape in param_slices()]
+    return list(flat_params.views(flat, param_slices()).values())
 
 
 class _RenderRaysFn(torch.autograd.Function):

@@ -16,7 +16,7 @@ import time
 import numpy as np
 import torch
 
-from . import _lib, ops, parallel
+from . import _lib, flat_params, ops, parallel
 from .model import NeRF, noview_slices
 from .render import LivePolicy, _Workspace, get_compact, _backward_core, _burn_seeds, _forward_core, _next_seed, render, render_path  # noqa: F401
 from .run_nerf_helpers import get_embedder, img2mse, mse2psnr
@@ -515,44 +515,13 @@ class Trainer:
     def torch_optimizer_state_dict(self):
         """State in torch.optim.Adam's format over grad_vars (coarse then fine parameters, parameters() order = the
         flat buffer's order): loadable by the reference's `optimizer.load_state_dict`."""
-        state, off = {}, 0
-        for i, p in enumerate(self._param_list()):
-            k = p.numel()
-            state[i] = {'step': torch.tensor(float(self.adam_t)),
-                        'exp_avg': self.m[off:off + k].view(p.shape).clone(),
-                        'exp_avg_sq': self.v[off:off + k].view(p.shape).clone()}
-            off += k
-        assert off == self.flat.numel()
-        group = {'lr': self.lr, 'betas': (self.beta1, self.beta2), 'eps': self.eps, 'weight_decay': 0, 'amsgrad': False,
-                 'maximize': False, 'foreach': None, 'capturable': False, 'differentiable': False, 'fused': None,
-                 'decoupled_weight_decay': False, 'params': list(range(len(state)))}
-        return {'state': state if self.adam_t > 0 else {}, 'param_groups': [group]}
+        return flat_params.adam_state_to_torch(self._param_list(), self.m, self.v, self.adam_t, self.lr, (self.beta1, self.beta2), self.eps)
 
     def load_torch_optimizer(self, opt):
         """Take over the moments / step count / lr of a torch.optim.Adam (or its state_dict) over the same
         parameters, e.g. the optimizer create_nerf restored from a reference checkpoint."""
-        sd = opt.state_dict() if hasattr(opt, 'state_dict') else opt
-        st = sd['state']
-        self.lr = float(sd['param_groups'][0]['lr'])
-        if len(st) == 0:
-            self.m.zero_(); self.v.zero_(); self.adam_t = 0
-            return
-        # a parameter that never received a gradient has NO entry in torch.optim.Adam's state (e.g. the unused views_linears.0 of
-        # a reference checkpoint trained without view directions, model.py:60-61): zero moments, step count from the others
-        off, steps = 0, set()
-        for i, p in enumerate(self._param_list()):
-            k = p.numel()
-            e = st.get(i)
-            if e is None:
-                self.m[off:off + k].zero_()
-                self.v[off:off + k].zero_()
-            else:
-                self.m[off:off + k].copy_(torch.as_tensor(e['exp_avg']).reshape(-1))
-                self.v[off:off + k].copy_(torch.as_tensor(e['exp_avg_sq']).reshape(-1))
-                steps.add(int(float(e['step'])))
-            off += k
-        assert off == self.flat.numel() and len(steps) == 1, 'optimizer state does not match the parameter list'
-        self.adam_t = steps.pop()
+        self.adam_t, lr = flat_params.adam_state_from_torch(self._param_list(), self.m, self.v, opt)
+        self.lr = float(lr)
 
     def load_state_dict(self, sd):
         self.m.copy_(sd['m']); self.v.copy_(sd['v'])
@@ -562,7 +531,7 @@ class Trainer:
 def reference_state_dict(net):
     """state_dict with the `module.` prefix of the nn.DataParallel wrapper the reference saves and strictly loads
     (run_nerf.py:82,90,124-126,535-536)."""
-    return {'module.' + k: v for k, v in net.state_dict().items()}
+    return flat_params.add_prefix(net.state_dict())
 
 
 def tree_pkl_path(args, epoch):
