@@ -155,6 +155,8 @@ SIGNATURES = {
     'fastnerf_mlp_x6_fwd_list': (I, [I, L, I, P, P, P, P, P, P, P, I, P]),
     'fastnerf_render_rays_fwd_occ': (I, [I, L, I, I, P, I, I, I, I, P, P, U64, U64, P, P, P, P, C.POINTER(OccGrid), P, P] + [P] * 16 + [I, P]),
     'fastnerf_render_rays_fwd_occ_cascade': (I, [I, L, I, I, P, I, I, I, I, P, P, U64, U64, P, P, P, P, C.POINTER(OccCascade), P, P] + [P] * 16 + [I, P]),
+    'fastnerf_mlp_sigma_grad_ws_floats': (L, [I, L]),
+    'fastnerf_mlp_sigma_grad': (I, [I, I, L, I, P, P, P, P, P, P, P, P, P]),
 }
 
 _lib = None

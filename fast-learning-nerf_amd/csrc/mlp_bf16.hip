@@ -1400,18 +1400,14 @@ static void b_add_seg(BRedTable& T, int64_t src, int64_t wg_stride, int nwg, int
   s.valid_cols = valid_cols; s.perm = perm; s.dw = dw;
 }
 
-static int b_bwd_launch(int kind, int64_t n, int S, const float* draw, const float* act_f, const float* params,
-                        const float* packed_bwd, float* dact_f, float* partial, float* grads, const int* live_idx,
-                        const int* live_cnt, fn_stream_t stream) {
+// The dX chain alone: what b_bwd_launch enqueues first, and all that a caller runs who wants the pre-activation gradients without any
+// dW (sigma_grad.hip).
+int fn_launch_dx_bf16(int kind, int64_t P, const float* draw, const float* act_f, const float* params, const float* packed_bwd,
+                      float* dact_f, const int* live_idx, const int* live_cnt, hipStream_t st) {
   const NetLayout& L = b_layout(kind);
   const BOff OB = b_offsets_bwd();
-  hipStream_t st = fn::S(stream);
-  const int64_t P = n * S;
   const int64_t nt = (P + BTM - 1) / BTM;
-  const int ncu = b_num_cus();
-  const uint4* act = reinterpret_cast<const uint4*>(act_f);
-  uint4* dact = reinterpret_cast<uint4*>(dact_f);
-  int grid = ncu * 2;
+  int grid = b_num_cus() * 2;
   if (nt < grid) grid = (int)nt;
   static bool attr_done = false;
   if (!attr_done) {
@@ -1421,9 +1417,30 @@ static int b_bwd_launch(int kind, int64_t n, int S, const float* draw, const flo
   }
   unsigned* sched = b_sched_pair();
   FN_CHECK_ARG(sched != nullptr, "scheduler counters (hipMalloc failed?)");
-  hipLaunchKernelGGL(mlp_bwd_dx_bf16_kernel, dim3(grid), dim3(BNTHR), BLDS_BYTES, st, P, draw, act, params,
-                     reinterpret_cast<const uint4*>(packed_bwd), dact, L, OB, sched, live_idx, live_cnt);
+  hipLaunchKernelGGL(mlp_bwd_dx_bf16_kernel, dim3(grid), dim3(BNTHR), BLDS_BYTES, st, P, draw, reinterpret_cast<const uint4*>(act_f), params,
+                     reinterpret_cast<const uint4*>(packed_bwd), reinterpret_cast<uint4*>(dact_f), L, OB, sched, live_idx, live_cnt);
   FN_LAUNCH_CHECK();
+  return 0;
+}
+// where the K-fragment tensors that sigma_grad.hip reads start (16-byte units from act / dact): the encoding, dY0, dY5
+void fn_bf16_sigma_grad_offsets(int64_t P, int64_t* pe, int64_t* dy0, int64_t* dy5) {
+  const int64_t nt = (P + BTM - 1) / BTM;
+  *pe = ba_pe(nt);
+  *dy0 = bd_y(nt, 0);
+  *dy5 = bd_y(nt, 5);
+}
+
+static int b_bwd_launch(int kind, int64_t n, int S, const float* draw, const float* act_f, const float* params,
+                        const float* packed_bwd, float* dact_f, float* partial, float* grads, const int* live_idx,
+                        const int* live_cnt, fn_stream_t stream) {
+  const NetLayout& L = b_layout(kind);
+  hipStream_t st = fn::S(stream);
+  const int64_t P = n * S;
+  const int64_t nt = (P + BTM - 1) / BTM;
+  const int ncu = b_num_cus();
+  const uint4* act = reinterpret_cast<const uint4*>(act_f);
+  uint4* dact = reinterpret_cast<uint4*>(dact_f);
+  if (int rc_dx = fn_launch_dx_bf16(kind, P, draw, act_f, params, packed_bwd, dact_f, live_idx, live_cnt, st)) return rc_dx;
 
   int nwg = ncu;
   // (always one workgroup per CU, also for batches of fewer tiles -- idle workgroups write zero partials: the order in

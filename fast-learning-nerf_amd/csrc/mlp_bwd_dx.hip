@@ -216,3 +216,12 @@ int fn_launch_dx(int mm, int grid, hipStream_t st, int64_t P, const float* draw,
   return mm == MM_X6 ? launch_dx_t<MM_X6>(grid, st, P, draw, act, params, packed_bwd, dact, L, live_idx, live_cnt)
                      : launch_dx_t<MM_F32>(grid, st, P, draw, act, params, packed_bwd, dact, L, live_idx, live_cnt);
 }
+// The chain alone, on the grid the backward entry points give it (mlp_bwd_dw.hip, bwd_launch_t): for a caller that wants the
+// pre-activation gradients and no dW (sigma_grad.hip).
+int fn_launch_dx_alone(int mm, int kind, int64_t P, const float* draw, const float* act, const float* params, const float* packed_bwd,
+                       float* dact, hipStream_t st) {
+  const int64_t ntiles = (P + TM - 1) / TM;
+  int grid = num_cus() * WG_PER_CU;
+  if (ntiles < grid) grid = (int)ntiles;
+  return fn_launch_dx(mm, grid, st, P, draw, act, params, packed_bwd, dact, layout_of(kind), nullptr, nullptr);
+}

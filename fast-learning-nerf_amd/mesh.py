@@ -3,7 +3,8 @@
 density_grid    the fine network's relu(sigma) on a dense point grid (extract_mesh.py:38-61); a fastnerf NeRF runs the
                 fused HIP forward chunk by chunk, with the points written straight into its ray rows (csrc/mesh.hip)
 marching_cubes  mcubes.marching_cubes (extract_mesh.py:74) as four HIP passes (csrc/mesh.hip); vertices in index coordinates
-extract_mesh    both, from a create_nerf render_kwargs, vertices in world coordinates
+extract_mesh    both, from a create_nerf render_kwargs, vertices in world coordinates; optionally with per-vertex normals
+vertex_normals  -grad(sigma) / |grad(sigma)| of the density field at given points (csrc/sigma_grad.hip)
 export_ply      trimesh's .ply export (extract_mesh.py:82-86): binary little-endian PLY, numpy only"""
 import numpy as np
 import torch
@@ -70,10 +71,28 @@ def marching_cubes(volume, threshold):
     return verts, tris.long()
 
 
-def extract_mesh(render_kwargs, N=256, bound=1.2, threshold=50., which='fine', chunk=1024 * 64):
+def vertex_normals(network, vertices, chunk=65536):
+    """[V,3] unit normals of the density field at `vertices` [V,3] (world coordinates, cuda): -grad / |grad| of the density logit
+    (NeRF.density_gradient: the fused forward, the dX chain and csrc/sigma_grad.hip), pointing from dense to empty space.  Exactly
+    (0, 0, 0) where the gradient is zero or not finite, never NaN.  Only a fastnerf NeRF has the kernels: anything else raises."""
+    net = getattr(network, 'module', network)
+    if not isinstance(net, NeRF):
+        raise TypeError('vertex_normals needs a fastnerf NeRF (the density gradient comes from its HIP kernels; there is no '
+                        'autograd fallback), got %s' % type(net).__name__)
+    _, g = net.density_gradient(vertices, chunk=chunk)
+    g = g.reshape(-1, 3)
+    big = g.abs().amax(-1, keepdim=True)                       # scale first: |g|^2 neither overflows nor underflows
+    ok = torch.isfinite(big) & (big > 0)
+    u = torch.where(ok, g / torch.where(ok, big, torch.ones_like(big)), torch.zeros_like(g))
+    length = torch.linalg.vector_norm(u, dim=-1, keepdim=True)
+    return torch.where(ok, -u / torch.where(ok, length, torch.ones_like(length)), torch.zeros_like(g))
+
+
+def extract_mesh(render_kwargs, N=256, bound=1.2, threshold=50., which='fine', chunk=1024 * 64, normals=False):
     """extract_mesh.py:38-74 from create_nerf's render_kwargs: density on the (N+1)^3 grid linspace(-bound, bound, N+1)^3 of
     the fine network (`which='fine'`; the coarse `network_fn` when there is no fine one or `which='coarse'`), marching
-    cubes at `threshold`.  -> (vertices [V,3] in world coordinates -bound + v * 2 bound / N, triangles [T,3] int64)."""
+    cubes at `threshold`.  -> (vertices [V,3] in world coordinates -bound + v * 2 bound / N, triangles [T,3] int64), and with
+    normals=True a third result: vertex_normals of the same network at those vertices [V,3]."""
     net = render_kwargs.get('network_fine') if which == 'fine' else None
     if net is None:
         net = render_kwargs['network_fn']
@@ -81,18 +100,29 @@ def extract_mesh(render_kwargs, N=256, bound=1.2, threshold=50., which='fine', c
     vol = density_grid(net, t, t, t, chunk=chunk, network_query_fn=render_kwargs.get('network_query_fn'),
                        use_viewdirs=render_kwargs.get('use_viewdirs'))
     verts, tris = marching_cubes(vol, threshold)
-    return -bound + verts * (2 * bound / N), tris
+    world = -bound + verts * (2 * bound / N)
+    if not normals:
+        return world, tris
+    return world, tris, vertex_normals(net, world, chunk=chunk)
 
 
-def export_ply(path, vertices, triangles):
-    """Binary little-endian PLY 1.0: `float x, y, z` per vertex, `list uchar int vertex_indices` per face."""
+def export_ply(path, vertices, triangles, normals=None):
+    """Binary little-endian PLY 1.0: `float x, y, z` per vertex (followed by `float nx, ny, nz` when `normals` [V,3] is given),
+    `list uchar int vertex_indices` per face."""
     v = np.ascontiguousarray(torch.as_tensor(vertices).detach().cpu().numpy(), dtype='<f4').reshape(-1, 3)
+    nprops = ''
+    if normals is not None:
+        nv = np.ascontiguousarray(torch.as_tensor(normals).detach().cpu().numpy(), dtype='<f4').reshape(-1, 3)
+        if nv.shape != v.shape:
+            raise ValueError('export_ply: %d normals for %d vertices' % (nv.shape[0], v.shape[0]))
+        v = np.ascontiguousarray(np.concatenate([v, nv], 1))
+        nprops = 'property float nx\nproperty float ny\nproperty float nz\n'
     f = np.asarray(torch.as_tensor(triangles).detach().cpu().numpy()).reshape(-1, 3)
     faces = np.empty(f.shape[0], dtype=[('n', 'u1'), ('i', '<i4', (3,))])
     faces['n'] = 3
     faces['i'] = f
-    head = ('ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n'
-            'element face %d\nproperty list uchar int vertex_indices\nend_header\n' % (v.shape[0], f.shape[0]))
+    head = ('ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n%s'
+            'element face %d\nproperty list uchar int vertex_indices\nend_header\n' % (v.shape[0], nprops, f.shape[0]))
     with open(path, 'wb') as fh:
         fh.write(head.encode('ascii'))
         fh.write(v.tobytes())

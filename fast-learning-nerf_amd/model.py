@@ -163,5 +163,39 @@ class NeRF(flat_params.FlatNet):
         h = F.relu(self.views_linears[0](h))
         return torch.cat([self.rgb_linear(h), alpha], -1)
 
+    def density_gradient(self, points, chunk=65536):
+        """(sigma [...], grad [..., 3]) at `points` [..., 3] (a cuda tensor): the density logit raw[..., 3] of the fused forward
+        under the current math mode and its gradient with respect to the point, both before the ReLU that turns the logit into a
+        density (ops.mlp_sigma_grad).  -grad / |grad| is the surface normal of the field (mesh.vertex_normals).
+
+        Runs under torch.no_grad(), `chunk` points at a time: the saved activations and pre-activation gradients of a chunk take
+        about 20 KB per point, 1.3 GB at the default.  A network without view directions runs on its equivalent kernel network
+        `self.flat`, whose sigma head is output row 3 (module docstring)."""
+        if not torch.is_tensor(points):
+            raise RuntimeError('fastnerf ops run on the GPU only (no CPU fallback): got a host array')
+        ops.require_gpu(points)
+        if points.shape[-1] != 3:
+            raise ValueError('density_gradient needs points [..., 3], got shape %s' % (tuple(points.shape),))
+        lead = tuple(points.shape[:-1])
+        pts = points.detach().reshape(-1, 3).float()
+        P = pts.shape[0]
+        dev = pts.device
+        sigma = torch.empty(P, device=dev, dtype=torch.float32)
+        grad = torch.empty(P, 3, device=dev, dtype=torch.float32)
+        if P == 0:
+            return sigma.reshape(lead), grad.reshape(lead + (3,))
+        n0 = min(max(1, int(chunk)), P)
+        with torch.no_grad():
+            pf, pb = self.packed()
+            ws = torch.empty(ops.sigma_grad_ws_floats(n0), device=dev, dtype=torch.float32)
+            rays11 = torch.zeros(n0, 11, device=dev, dtype=torch.float32)     # o = the point, d = 0: o + d * z is the point itself
+            z = torch.zeros(n0, 1, device=dev, dtype=torch.float32)
+            for p0 in range(0, P, n0):
+                n = min(n0, P - p0)
+                rays11[:n, 0:3] = pts[p0:p0 + n]
+                s, _ = ops.mlp_sigma_grad(rays11[:n], z[:n], self.flat, pf, pb, ws=ws, grad=grad[p0:p0 + n])
+                sigma[p0:p0 + n] = s[:, 0]
+        return sigma.reshape(lead), grad.reshape(lead + (3,))
+
     def load_state_dict(self, state_dict, strict=True):
         return super().load_state_dict(flat_params.strip_prefix(state_dict), strict=strict)

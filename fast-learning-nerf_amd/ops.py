@@ -262,6 +262,36 @@ def mlp_bwd(draw, act, params, packed_bwd, dact, partial, grads, kind=0):
     return grads
 
 
+def sigma_grad_ws_floats(P):
+    """Floats of scratch one mlp_sigma_grad call over P points needs under the current math mode (about 20 KB per point)."""
+    return int(check(lib().fastnerf_mlp_sigma_grad_ws_floats(mode_id(), int(P)), 'fastnerf_mlp_sigma_grad_ws_floats'))
+
+
+def mlp_sigma_grad(rays11, z, params, packed_fwd, packed_bwd, ws=None, grad=None, want_sigma=True):
+    """(sigma [n,S], grad [n,S,3]): the density logit raw[..., 3] of the current math mode's forward at the points o + d*z and its
+    gradient with respect to the point -- both BEFORE the ReLU of raw2outputs (fastnerf_mlp_sigma_grad, kind 0).  sigma equals
+    mlp_fwd(...)[..., 3] bit for bit; it is None with want_sigma=False.  ws: caller-owned scratch of >= sigma_grad_ws_floats(n*S)
+    floats (default: allocated here); grad: caller-owned output of >= n*S*3 floats, only its first n*S rows are written."""
+    require_gpu(rays11, z, params, packed_fwd, packed_bwd, ws, grad)
+    n, S = z.shape
+    P = n * S
+    assert rays11.shape == (n, 11) and z.dtype == torch.float32 and params.numel() == net_floats(0, 0)
+    assert packed_fwd.numel() == packed_floats(0, 1) and packed_bwd.numel() == packed_floats(0, 2) \
+        and packed_tag(packed_fwd) == _MATH and packed_tag(packed_bwd) == _MATH, \
+        'packed weights were not produced by mlp_pack under the current math mode'
+    dev = z.device
+    if ws is None:
+        ws = torch.empty(sigma_grad_ws_floats(P), device=dev, dtype=torch.float32)
+    assert ws.dtype == torch.float32 and ws.numel() >= sigma_grad_ws_floats(P)
+    if grad is None:
+        grad = torch.empty(P * 3, device=dev, dtype=torch.float32)
+    assert grad.dtype == torch.float32 and grad.numel() >= P * 3
+    sigma = torch.empty(n, S, device=dev, dtype=torch.float32) if want_sigma else None
+    check(lib().fastnerf_mlp_sigma_grad(mode_id(), 0, n, S, ptr(rays11), ptr(z), ptr(params), ptr(packed_fwd), ptr(packed_bwd), ptr(ws),
+                                        ptr(sigma), ptr(grad), stream()), 'fastnerf_mlp_sigma_grad')
+    return sigma, grad.reshape(-1)[:P * 3].view(n, S, 3)
+
+
 def raw2outputs_fwd(raw, z, rays11, noise=None, white_bkgd=False):
     require_gpu(raw, z, rays11, noise)
     n, S = z.shape

@@ -575,6 +575,25 @@ int fastnerf_render_rays_fwd_occ_cascade(int math_mode, int64_t n, int N_samples
                                          float* z1, float* z_samples, float* z_std, float* raw1, float* rgb1, float* disp1,
                                          float* acc1, float* w1, float* depth1, int flags, fn_stream_t stream);
 
+/* ---- density gradient: d(sigma)/d(x) through the fused MLP (csrc/sigma_grad.hip) -------------------------------------------------
+ * sigma[n,S] (may be NULL) = raw[..., 3] of the forward of `math_mode` (0 exact fp32, 1 split-bf16 "bf16x3", 2 "bf16x6") at the
+ * points o + d*z of fastnerf_mlp_fwd, and grad[n,S,3] = its gradient with respect to the point.  Both are taken BEFORE the ReLU
+ * that raw2outputs applies to the logit: where the logit is negative the density is zero and flat, the logit's gradient still
+ * points along the field.  One call enqueues the saving forward, a fill of the cotangent (0, 0, 0, 1), the dX chain alone (no dW,
+ * no reduction) and one kernel that multiplies the pre-activation gradients of layer 0 and of the skip layer by their input
+ * weights and applies the chain rule of the positional encoding with the saved sines and cosines.  No atomics: bit-identical from
+ * call to call, and a point's result does not depend on where it sits in the batch.  params / packed_fwd / packed_bwd: the flat
+ * parameters and the packed weights of the mode's pack entry point.  ws: fastnerf_mlp_sigma_grad_ws_floats(math_mode, n*S)
+ * floats of scratch (saved activations + pre-activation gradients + cotangent and logits of one call, about 20 KB per point).
+ * kind 0 only: -1 for kind 1 / 2 (the nerf++ nets), for a math_mode outside 0..2, n <= 0, S <= 0 or a NULL buffer other than
+ * sigma, before anything is enqueued.
+ * Differentiates model.py:38-63 (NeRF.forward, alpha_linear of the trunk) composed with run_nerf_helpers.py:15-46 (Embedder:
+ * [x, sin(2^k x), cos(2^k x)], k = 0..9). */
+int64_t fastnerf_mlp_sigma_grad_ws_floats(int math_mode, int64_t n_points);
+int fastnerf_mlp_sigma_grad(int math_mode, int kind, int64_t n, int S, const float* rays11, const float* z, const float* params,
+                            const float* packed_fwd, const float* packed_bwd, float* ws, float* sigma, float* grad,
+                            fn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,9 +2,10 @@
 (N+1)^3 grid over [-bound, bound]^3, run marching cubes at the threshold and write {basedir}/{expname}/lego_mesh.ply.
 No mcubes / trimesh: the grid query and marching cubes are HIP kernels (csrc/mesh.hip), the PLY writer is numpy.
 
-  python tools/extract_mesh.py --basedir ./logs --expname lego --N_importance 128 --use_viewdirs [--N 256] [--reference-scale]
+  python tools/extract_mesh.py --basedir ./logs --expname lego --N_importance 128 --use_viewdirs [--N 256] [--reference-scale] [--normals]
 
---reference-scale writes the reference's `vertices / N - .5` instead of world coordinates.  Prints the occupied fraction, V
+--reference-scale writes the reference's `vertices / N - .5` instead of world coordinates.  --normals adds per-vertex normals
+(nx, ny, nz) from the density field's own gradient at the world-coordinate vertices (fastnerf.mesh.vertex_normals).  Prints the occupied fraction, V
 and T, and the grid-query and marching-cubes times (device events, after one warm-up of each) as a JSON line."""
 import argparse
 import json
@@ -30,6 +31,7 @@ def parse_args(argv=None):
     p.add_argument('--bound', type=float, default=1.2)
     p.add_argument('--threshold', type=float, default=50.)
     p.add_argument('--reference-scale', action='store_true', help="write vertices / N - .5 (the reference's scaling)")
+    p.add_argument('--normals', action='store_true', help='write per-vertex normals -grad(sigma) / |grad(sigma)| (nx, ny, nz)')
     return p.parse_args(argv)
 
 
@@ -58,10 +60,14 @@ def main(argv=None):
     (verts, tris), ms_mc = timed(lambda: fastnerf.mesh.marching_cubes(vol, a.threshold))
     scale = (verts / a.N - .5) if a.reference_scale else (-a.bound + verts * (2 * a.bound / a.N))
     path = os.path.join(a.basedir, a.expname, 'lego_mesh.ply')
-    fastnerf.mesh.export_ply(path, scale, tris)
+    normals, ms_normals = None, None
+    if a.normals:   # always at the world-coordinate vertices: that is where the network lives
+        normals, ms_normals = timed(lambda: fastnerf.mesh.vertex_normals(net, -a.bound + verts * (2 * a.bound / a.N)))
+    fastnerf.mesh.export_ply(path, scale, tris, normals)
     print(json.dumps({'checkpoint': fastnerf.run_nerf.create_nerf.last_ckpt_path, 'grid': a.N + 1,
                       'fraction_occupied': float((vol > a.threshold).float().mean()), 'V': int(verts.shape[0]),
-                      'T': int(tris.shape[0]), 'density_grid_ms': ms_grid, 'marching_cubes_ms': ms_mc, 'ply': path}))
+                      'T': int(tris.shape[0]), 'density_grid_ms': ms_grid, 'marching_cubes_ms': ms_mc, 'normals_ms': ms_normals,
+                      'ply': path}))
     return scale, tris
 
 
