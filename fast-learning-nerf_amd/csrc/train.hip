@@ -275,6 +275,14 @@ extern "C" int fastnerf_compact_live(int64_t n_points, const float* draw, int32_
 // The values are N(0, std^2) draws of this library's own stream (the reference draws from torch's global generator: distribution parity, like
 // the jitter streams; the `pytest=True` hook of render_rays still injects the reference's deterministic numpy numbers).
 // ---------------------------------------------------------------------------------------------------------------------
+// ln(u1) of u1 = (m + 0.5) * 2^-24 = (2m + 1) * 2^-25, m < 2^24, in (0, 1).  For m >= 2^23 that u1 has 25 significant bits: formed in fp32
+// as (float)m + 0.5f it rounded to even -- off by 2^-25, exactly 1.0 (r = 0) for the largest m, and r = sqrt(-2 ln u1) off by 2^-25 / r
+// near u1 = 1 (1.4e-5 at r = 2e-3; found by tests/test_gpu_seeded_draws.py).  There 1 - u1 = (2^25 - 2m - 1) * 2^-25 is exact, so log1p takes it.
+__device__ __forceinline__ float log_u1(uint32_t m) {
+  if (m < (1u << 23)) return logf((float)(2u * m + 1u) * (1.0f / 33554432.0f));
+  return log1pf(-((float)((1u << 25) - 2u * m - 1u) * (1.0f / 33554432.0f)));
+}
+
 __global__ void __launch_bounds__(256) gauss_noise_kernel(int64_t n4, int64_t n, float sd, uint32_t k0, uint32_t k1, float* __restrict__ out) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
     uint32_t o[4];
@@ -282,9 +290,8 @@ __global__ void __launch_bounds__(256) gauss_noise_kernel(int64_t n4, int64_t n,
     float v[4];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      const float u1 = ((float)(o[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);      // (0, 1): the logarithm stays finite
       const float u2 = (float)(o[2 * h + 1] >> 8) * (1.0f / 16777216.0f);
-      const float r = sqrtf(-2.0f * logf(u1)) * sd;
+      const float r = sqrtf(-2.0f * log_u1(o[2 * h] >> 8)) * sd;      // u1 in (0, 1): the logarithm stays finite and below zero
       float sn, cs;
       sincosf(6.28318530717958647692f * u2, &sn, &cs);
       v[2 * h] = r * cs;
