@@ -220,7 +220,7 @@ __device__ __forceinline__ void dw6_body(const int64_t P, const float* __restric
   // the tiles this wave splits: tile t = k * NW + wave; t < CTO: channels t*32.. of dY, else channels (t - CTO)*32.. of X.
   // Rows are counted from the workgroup's first row.
   constexpr int CTI1 = CTI - CTI2, KI1 = CTI1 * 32, KI2 = CTI2 * 32;   // row widths of X and X2 (KI = KI1 + KI2 partial columns)
-  static_assert(!(RANK1 && CTI2), "the rank-1 row is taken over X only");
+  // (RANK1 with CTI2: the rank-1 row is taken over X only, KI1 columns -- the folded view job: X = h7, X2 = the encoded direction)
   constexpr int CTO1 = CTO - CTO2, NO1 = CTO1 * 32, NO2 = CTO2 * 32;   // row widths of dY and dY2 (NO = NO1 + NO2 partial rows)
   static_assert(!(RANK1 && CTO2) && !(CTI2 && CTO2), "one second tensor per job");
   const float* tsrc[TPW];
@@ -314,7 +314,7 @@ __device__ __forceinline__ void dw6_body(const int64_t P, const float* __restric
         split3_frag(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), h, m, l);
         d[0] = h; d[64] = m; d[128] = l;
         if (BIAS && (KNOWN ? (k * NW < CTO) : (t < CTO1))) ssum[k] += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-        if (RANK1 && (KNOWN ? (k * NW >= CTO) : (t >= CTO))) {
+        if (RANK1 && (KNOWN ? (k * NW >= CTO) : (t >= CTO && t < CTO + CTI1))) {
           const float4 d0 = *reinterpret_cast<const float4*>(DA + (st & 1) * 16 + half8);
           const float4 d1 = *reinterpret_cast<const float4*>(DA + (st & 1) * 16 + half8 + 4);
           const float da[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
@@ -426,7 +426,7 @@ __device__ __forceinline__ void dw6_body(const int64_t P, const float* __restric
         const float sv = ssum[k] + __shfl_xor(ssum[k], 32, 64);
         if (lane < 32) {
           if (BIAS && t < CTO1) partial_b[(int64_t)wg * NO1 + t * 32 + lane] = sv;
-          if (RANK1 && t >= CTO) partial_r[(int64_t)wg * KI + (t - CTO) * 32 + lane] = sv;
+          if (RANK1 && t >= CTO && t < CTO + CTI1) partial_r[(int64_t)wg * KI1 + (t - CTO) * 32 + lane] = sv;
         }
       }
     }
@@ -445,8 +445,8 @@ mlp_bwd_dw6_kernel(int64_t P, const float* __restrict__ dY, const float* __restr
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The eight 256 x 256 jobs of a pass (L1 .. L7 and the feature layer with the alpha head's rank-1 row) in ONE launch (round 6): grid =
-// (chunks, 8 jobs).  The number of split-K chunks per job is a function of the POINT COUNT ALONE (dw_trunk_chunks: an eighth of the chip per
+// The seven 256 x 256 jobs of a pass (L1 .. L7; the feature layer's job is gone with the fold, its rank-1 row rides the view job) in ONE launch:
+// grid = (chunks, 7 jobs).  The number of split-K chunks per job is a function of the POINT COUNT ALONE (dw_trunk_chunks: an eighth of the chip per
 // 256 k-steps of 16 points, between 1/8 of the CUs and all of them), so that
 //   * the partials and their reduction shrink with the batch: a 512-ray shard (the reference's configs train at 1024 - 1920 rays,
 //     lego.txt:16; an 8-way strong-scaling shard of BASELINE configs[1] is 512) writes 32 chunks per job instead of 256 -- 75 MB per
@@ -463,24 +463,21 @@ __host__ __device__ static inline int dw_trunk_chunks(int64_t P, int ncu) {
   k = k < 1 ? 1 : (k > 8 ? 8 : k);
   return unit * (int)k;
 }
+#define DW_TRUNK_JOBS 7
 struct DwTrunk {
-  const float* dY[8];
-  const float* X[8];
-  float* pw[8];
-  float* pb[8];
+  const float* dY[DW_TRUNK_JOBS];
+  const float* X[DW_TRUNK_JOBS];
+  float* pw[DW_TRUNK_JOBS];
+  float* pb[DW_TRUNK_JOBS];
 };
 __global__ void __launch_bounds__(512, 2)
-mlp_bwd_dw6_trunk_kernel(int64_t P, DwTrunk J, const float* __restrict__ draw, float* __restrict__ partial_r,
-                         const int* __restrict__ live_idx, const int* __restrict__ live_cnt, int ncu) {
+mlp_bwd_dw6_trunk_kernel(int64_t P, DwTrunk J, const int* __restrict__ live_idx, const int* __restrict__ live_cnt, int ncu) {
   if (live_idx) P = (int64_t)__builtin_amdgcn_readfirstlane(*live_cnt);
   const int nact = dw_trunk_chunks(P, ncu);
   if ((int)blockIdx.x >= nact) return;
   const int job = (int)blockIdx.y;
-  if (job == 7)
-    dw6_body<4, 2, 2, 4, true, true>(P, J.dY[7], J.X[7], draw, J.pw[7], J.pb[7], partial_r, live_idx, nullptr, nullptr, (int)blockIdx.x, nact);
-  else
-    dw6_body<4, 2, 2, 4, true, false>(P, J.dY[job], J.X[job], nullptr, J.pw[job], J.pb[job], nullptr, live_idx, nullptr, nullptr,
-                                      (int)blockIdx.x, nact);
+  dw6_body<4, 2, 2, 4, true, false>(P, J.dY[job], J.X[job], nullptr, J.pw[job], J.pb[job], nullptr, live_idx, nullptr, nullptr,
+                                    (int)blockIdx.x, nact);
 }
 
 // rgb head + alpha bias gradients (VALU reduction over points): per-workgroup partials
@@ -531,6 +528,8 @@ struct RedSeg {
   int64_t dst;        // offset into the flat gradient
   int nwg, rows, cols, ld, valid_cols;
   int dyn;            // 1: the segment's chunk count is dw_trunk_chunks(point count) (the trunk launch); nwg is its capacity
+  int sc_cols;        // > 0: columns < sc_cols do not go to the gradient but to scratch[sc_dst + r * sc_cols + c] (G = dL/dM of the folded view layer)
+  int64_t sc_dst;
 };
 #define MAX_SEGS 32
 struct RedTable {
@@ -538,8 +537,8 @@ struct RedTable {
   int n;
 };
 
-__global__ void __launch_bounds__(256) reduce_all_kernel(RedTable tab, const float* __restrict__ partial,
-                                                          float* __restrict__ grads, int64_t P, const int* __restrict__ live_cnt, int ncu) {
+__global__ void __launch_bounds__(256) reduce_all_kernel(RedTable tab, const float* __restrict__ partial, float* __restrict__ grads,
+                                                          float* __restrict__ scratch, int64_t P, const int* __restrict__ live_cnt, int ncu) {
   RedSeg sg = tab.s[blockIdx.y];
   if (sg.dyn) {
     if (live_cnt) P = (int64_t)*live_cnt;
@@ -569,8 +568,49 @@ __global__ void __launch_bounds__(256) reduce_all_kernel(RedTable tab, const flo
     for (int h = RS / 2; h >= 1; h >>= 1)
 #pragma unroll
       for (int i = 0; i < h; ++i) a[i] += a[i + h];
-    grads[sg.dst + (int64_t)r * sg.ld + c] = a[0];
+    if (c < sg.sc_cols) scratch[sg.sc_dst + (int64_t)r * sg.sc_cols + c] = a[0];
+    else grads[sg.dst + (int64_t)r * sg.ld + c] = a[0];
   }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The unfold: the gradients of the two layers that the kernels run as one (M = Wv_a Wf, Wv_a = Wv[:, :256]; mlp_pack.hip fold_kernel) from
+// G = dL/dM [128][256] (the view job's h7 columns, reduced into scratch), dbv (already in the flat gradient) and the current weights:
+//   dWf = Wv_a^T G  [256][256],   dbf = Wv_a^T dbv  [256],   dWv_a = G Wf^T + dbv bf^T  [128][256]
+// fp64 products and sums in ascending k, one rounding to fp32: parameter-sized work (2 x 8.4 M FMAs), one launch per pass behind reduce_all.
+// 16 x 16 output tiles, operands staged through LDS 16 k at a time; blocks 0..255 dWf, 256..383 dWv_a, 384 dbf.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) unfold_kernel(const float* __restrict__ G, const float* __restrict__ params, float* __restrict__ grads,
+                                                      int64_t VW, int64_t VB, int64_t FW, int64_t FB) {
+  __shared__ double As[16][17], Bs[16][17];
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+  const int b = blockIdx.x;
+  if (b == 384) {   // dbf[i] = sum_o Wv[o][i] dbv[o]
+    const int i = threadIdx.x;
+    double s = 0.0;
+    for (int o = 0; o < 128; ++o) s = fma((double)params[VW + (int64_t)o * 283 + i], (double)grads[VB + o], s);
+    grads[FB + i] = (float)s;
+    return;
+  }
+  const bool wf = b < 256;                       // dWf tile (i0, j0) / dWv_a tile (o0, i0)
+  const int r0 = wf ? (b >> 4) * 16 : ((b - 256) >> 4) * 16, c0 = (b & 15) * 16;
+  const int K = wf ? 128 : 256;
+  double s = 0.0;
+  for (int k0 = 0; k0 < K; k0 += 16) {
+    if (wf) {   // A[k][r] = Wv[k][r0 + r], B[k][c] = G[k][c0 + c]
+      As[ty][tx] = (double)params[VW + (int64_t)(k0 + ty) * 283 + r0 + tx];
+      Bs[ty][tx] = (double)G[(k0 + ty) * 256 + c0 + tx];
+    } else {    // A[k][r] = G[r0 + r][k], B[k][c] = Wf[c0 + c][k]
+      As[tx][ty] = (double)G[(r0 + ty) * 256 + k0 + tx];
+      Bs[tx][ty] = (double)params[FW + (int64_t)(c0 + ty) * 256 + k0 + tx];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 16; ++k) s = fma(As[k][ty], Bs[k][tx], s);
+    __syncthreads();
+  }
+  if (wf) grads[FW + (int64_t)(r0 + ty) * 256 + c0 + tx] = (float)s;
+  else grads[VW + (int64_t)(r0 + ty) * 283 + c0 + tx] = (float)fma((double)grads[VB + r0 + ty], (double)params[FB + c0 + tx], s);
 }
 
 // dW jobs of one net: NO, KI, bias?, rank1?   (KI of the two pe jobs = the layout's pe_pad)
@@ -579,8 +619,8 @@ static DwJobDesc dw_job(int j, int pe_pad) {
   switch (j) {
     case 0: return {256, pe_pad, 1, 0};     // L0 (pe)
     case 8: return {256, pe_pad, 0, 0};     // L5 (pe part)
-    case 9: return {256, 256, 1, 1};        // feature / remap (+ alpha / sigma row)
-    case 10: return {128, 256, 1, 0};       // view layer (feature part)
+    case 9: return {256, 256, 1, 1};        // (the feature / remap layer's job before the fold: its region now holds the view job's rank-1 partials and G)
+    case 10: return {128, 256, 1, 0};       // view layer (h7 part: G = dL/dM)
     case 11: return {128, 32, 0, 0};        // view layer (vpe part)
     default: return {256, 256, 1, 0};       // 1..7: L1..L7 (h part)
   }
@@ -608,11 +648,11 @@ extern "C" int64_t fastnerf_mlp_bwd_partial_floats(void) {
 template <int WO, int WI, int TO, int TI, bool BIAS, bool RANK1, int MM = MM_F32, int CTI2 = 0, int CTO2 = 0>
 static int launch_dw(int64_t P, const float* dY, int ldy, const float* X, int ldx, const float* draw, float* base,
                      int nwg, hipStream_t st, const int* live_idx = nullptr, const int* live_cnt = nullptr,
-                     const float* X2 = nullptr, const float* dY2 = nullptr) {
+                     const float* X2 = nullptr, const float* dY2 = nullptr, float* pr_at = nullptr) {
   constexpr int NO = WO * TO * 32, KI = WI * TI * 32;
   float* pw = base;
   float* pb = base + (int64_t)nwg * NO * KI;
-  float* pr = pb + (BIAS ? (int64_t)nwg * (NO - CTO2 * 32) : 0);
+  float* pr = pr_at ? pr_at : pb + (BIAS ? (int64_t)nwg * (NO - CTO2 * 32) : 0);   // pr_at: the rank-1 partials live elsewhere
   if constexpr (MM == MM_X6) {
     if (ldy != NO - CTO2 * 32 || ldx != KI - CTI2 * 32 || (CTI2 > 0) != (X2 != nullptr) || (CTO2 > 0) != (dY2 != nullptr)) {
       fn::set_error("launch_dw: the bf16x6 dW kernel needs ld == width (and X2 / dY2 exactly when CTI2 / CTO2 > 0)");
@@ -645,10 +685,10 @@ static int launch_dw(int64_t P, const float* dY, int ldy, const float* X, int ld
 }
 
 static void add_seg(RedTable& T, int64_t src, int64_t wg_stride, int nwg, int rows, int cols, int64_t dst, int ld,
-                    int valid_cols, int dyn = 0) {
+                    int valid_cols, int dyn = 0, int sc_cols = 0, int64_t sc_dst = 0) {
   RedSeg& s = T.s[T.n++];
   s.src = src; s.wg_stride = wg_stride; s.nwg = nwg; s.rows = rows; s.cols = cols; s.dst = dst; s.ld = ld;
-  s.valid_cols = valid_cols; s.dyn = dyn;
+  s.valid_cols = valid_cols; s.dyn = dyn; s.sc_cols = sc_cols; s.sc_dst = sc_dst;
 }
 
 template <int MM>
@@ -668,7 +708,7 @@ static int bwd_launch_t(int kind, int64_t n, int S, const float* draw, const flo
 
   // ---- dW jobs: every job writes per-chunk partials into its own region ------------------
   // (grids and chunk counts are functions of the point count alone -- one workgroup per CU and a fixed head-gradient grid for the jobs with
-  // their own launch, dw_trunk_chunks for the eight 256 x 256 jobs of the bf16x6 trunk launch -- so the order in which partial sums meet
+  // their own launch, dw_trunk_chunks for the seven 256 x 256 jobs of the bf16x6 trunk launch -- so the order in which partial sums meet
   // depends on the point count only: live-list backward == plain backward of the same points, bit for bit)
   const int nwg = ncu;
   RedTable T;
@@ -701,7 +741,7 @@ static int bwd_launch_t(int kind, int64_t n, int S, const float* draw, const flo
     if (rc) return rc;
     segs(0, L.LW[0], L.in_pe, L.in_pe, L.LB[0], 0);
   }
-  // L1..L7 (h part); MM_X6: together with the feature layer in the trunk launch below
+  // L1..L7 (h part); MM_X6: the trunk launch below
   if constexpr (MW != MM_X6) {
     for (int l = 1; l < 8; ++l) {
       if ((rc = launch_dw<4, 2, 2, 4, true, false, MW>(P, dact + dact_y(P, l), 256, act + act_h(P, PEP, l - 1), 256, nullptr, region(l), nwg, st, live_idx, live_cnt))) return rc;
@@ -715,47 +755,48 @@ static int bwd_launch_t(int kind, int64_t n, int S, const float* draw, const flo
     if (rc) return rc;
     segs(8, L.LW[5], 256 + L.in_pe, L.in_pe, 0, 0);
   }
-  // feature / remap layer (+bias) with the alpha / sigma head as a rank-1 row
+  // L1..L7 under MM_X6: the trunk launch; chunk w of a job writes where workgroup w of its own launch did
   if constexpr (MW == MM_X6) {
-    // the trunk launch: jobs 0..6 = L1..L7, job 7 = the feature layer; chunk w of a job writes where workgroup w of its own launch did
     DwTrunk J;
-    for (int l = 1; l <= 8; ++l) {
-      const int j = l < 8 ? l : 9;
-      J.dY[l - 1] = l < 8 ? dact + dact_y(P, l) : dact + dact_feat(P);
+    for (int l = 1; l < 8; ++l) {
+      J.dY[l - 1] = dact + dact_y(P, l);
       J.X[l - 1] = act + act_h(P, PEP, l - 1);
-      J.pw[l - 1] = region(j);
-      J.pb[l - 1] = region(j) + (int64_t)nwg * 256 * 256;
+      J.pw[l - 1] = region(l);
+      J.pb[l - 1] = region(l) + (int64_t)nwg * 256 * 256;
     }
-    float* pr = J.pb[7] + (int64_t)nwg * 256;
     constexpr int lds6 = 2 * 16 * 3 * 1024 + 128;
     static bool attr_t = false;
     if (!attr_t) {
       FN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_bwd_dw6_trunk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds6));
       attr_t = true;
     }
-    hipLaunchKernelGGL(mlp_bwd_dw6_trunk_kernel, dim3(dw_trunk_chunks(P, ncu), 8), dim3(512), lds6, st, P, J, draw, pr, live_idx, live_cnt, ncu);
+    hipLaunchKernelGGL(mlp_bwd_dw6_trunk_kernel, dim3(dw_trunk_chunks(P, ncu), DW_TRUNK_JOBS), dim3(512), lds6, st, P, J, live_idx, live_cnt, ncu);
     FN_LAUNCH_CHECK();
     for (int l = 1; l < 8; ++l) segs(l, L.LW[l] + (l == 5 ? L.in_pe : 0), l == 5 ? 256 + L.in_pe : 256, 256, L.LB[l], 0, 1);
-    segs(9, L.FW, 256, 256, L.FB, L.AW, 1);
-  } else {
-    if ((rc = launch_dw<4, 2, 2, 4, true, true, MW>(P, dact + dact_feat(P), 256, act + act_h(P, PEP, 7), 256, draw, region(9), nwg, st, live_idx, live_cnt))) return rc;
-    segs(9, L.FW, 256, 256, L.FB, L.AW);
   }
-  // view layer
+  // view layer on [h7 | vpe] (the folded feature / remap layer: mlp_pack.hip), with the alpha / sigma head as a rank-1 row over h7.
+  // The h7 columns of its dW are G = dL/dM: reduce_all leaves them in scratch (the former feature job's region, behind the rank-1
+  // partials), and unfold_kernel turns G into dWf, dbf and dWv[:, :256] below.
+  float* const pr_view = region(9);
+  const int64_t g_off = dw_job_base(9, ncu, PEP) + (int64_t)nwg * 256;
   if constexpr (MW == MM_X6) {
-    // one job for both inputs of the view layer (feature [P,256] | encoded direction [P,32]): dYv is read and split once; 12 waves,
+    // one job for both inputs of the view layer (h7 [P,256] | encoded direction [P,32]): dYv is read and split once; 12 waves,
     // partials [128][288] + bias [128] across the (adjacent) regions of jobs 10 and 11
-    if ((rc = launch_dw<4, 3, 1, 3, true, false, MW, 1, 0>(P, dact + dact_yv(P), 128, act + act_feat(P, PEP), 256, nullptr, region(10), nwg, st,
-                                                     live_idx, live_cnt, act + act_vpe(P, PEP), nullptr))) return rc;
+    if ((rc = launch_dw<4, 3, 1, 3, true, true, MW, 1, 0>(P, dact + dact_yv(P), 128, act + act_h(P, PEP, 7), 256, draw, region(10), nwg, st,
+                                                    live_idx, live_cnt, act + act_vpe(P, PEP), nullptr, pr_view))) return rc;
     const int64_t b10 = dw_job_base(10, ncu, PEP);
-    add_seg(T, b10, 128 * 288, nwg, 128, 288, L.VW, 283, 283);
+    add_seg(T, b10, 128 * 288, nwg, 128, 288, L.VW, 283, 283, 0, 256, g_off);
     add_seg(T, b10 + (int64_t)nwg * 128 * 288, 128, nwg, 1, 128, L.VB, 128, 128);
   } else {
-    if ((rc = launch_dw<2, 4, 2, 2, true, false, MW>(P, dact + dact_yv(P), 128, act + act_feat(P, PEP), 256, nullptr, region(10), nwg, st, live_idx, live_cnt))) return rc;
-    segs(10, L.VW, 283, 256, L.VB, 0);
+    if ((rc = launch_dw<2, 4, 2, 2, true, true, MW>(P, dact + dact_yv(P), 128, act + act_h(P, PEP, 7), 256, draw, region(10), nwg, st, live_idx, live_cnt,
+                                              nullptr, nullptr, pr_view))) return rc;
+    const int64_t b10 = dw_job_base(10, ncu, PEP);
+    add_seg(T, b10, 128 * 256, nwg, 128, 256, L.VW, 283, 256, 0, 256, g_off);
+    add_seg(T, b10 + (int64_t)nwg * 128 * 256, 128, nwg, 1, 128, L.VB, 128, 128);
     if ((rc = launch_dw<4, 1, 1, 1, false, false, MW>(P, dact + dact_yv(P), 128, act + act_vpe(P, PEP), 32, nullptr, region(11), nwg, st, live_idx, live_cnt))) return rc;
     segs(11, L.VW + 256, 283, 27, 0, 0);
   }
+  add_seg(T, dw_job_base(9, ncu, PEP), 256, nwg, 1, 256, L.AW, 256, 256);   // dWa: the rank-1 row
   // rgb head + alpha bias
   {
     const int hg = HEAD_MAX_WG;
@@ -765,7 +806,9 @@ static int bwd_launch_t(int kind, int64_t n, int S, const float* draw, const flo
     add_seg(T, hb, 388, hg, 1, 388, L.RW, 388, 387);   // dWr (384) + dbr (3), contiguous in every layout
     add_seg(T, hb + 387, 388, hg, 1, 1, L.AB, 1, 1);   // dba
   }
-  hipLaunchKernelGGL(reduce_all_kernel, dim3(256, T.n), dim3(256), 0, st, T, partial, grads, P, live_cnt, ncu);   // (256 x 256 threads: one element of a 256 x 256 segment per lane)
+  hipLaunchKernelGGL(reduce_all_kernel, dim3(256, T.n), dim3(256), 0, st, T, partial, grads, partial, P, live_cnt, ncu);   // (256 x 256 threads: one element of a 256 x 256 segment per lane)
+  FN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(unfold_kernel, dim3(385), dim3(256), 0, st, partial + g_off, params, grads, L.VW, L.VB, L.FW, L.FB);
   FN_LAUNCH_CHECK();
   return 0;
 }

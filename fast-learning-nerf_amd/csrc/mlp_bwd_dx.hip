@@ -151,20 +151,11 @@ mlp_bwd_dx_kernel(int64_t P, const float* __restrict__ draw, const float* __rest
     constexpr bool CHAIN = L16;
     AccT<L16, 2> acc;
     WRegsT<L16, 2> wch;
-    // ---- dfeat = dYv . Wv[:, :256]  (K = 128) ------------------------------------------
-    zero_acc<2>(acc);
-    gemm<MM, 2, 0>(acc, Hs, 0, 16, wblock<MM>(packed_t, lay.PB[0]), 16, 0, wn * 2, wm, lane);
-    __syncthreads();
-    wprefetch(wch, wblock<MM>(packed_t, lay.PB[1]), 32, 0, 32, wn * 2, lane);
-    epilogue_dx<false, false>(acc, Hs, Es, dx_preload<false, false, L16>(nullptr, nullptr, wn, lane), nullptr, wm, wn, lane,
-                              valid);
-    __syncthreads();
-    // ---- dY7 = (dfeat . Wf + dalpha x wa) * [h7 > 0] ------------------------------------
+    // ---- dY7 = (dYv . M + dalpha x wa) * [h7 > 0]  (K = 128; M = Wv[:, :256] Wf, the folded view layer: mlp_pack.hip) ----
     zero_acc<2>(acc);
     {
       const DxPre pre = dx_preload<true, true, L16>(maskw + (7 * NWAVES + wave) * 64, params + lay.AW, wn, lane);
-      gemm<MM, 2, 0, CHAIN>(acc, Hs, 0, 32, wblock<MM>(packed_t, lay.PB[1]), 32, 0, wn * 2, wm, lane, 0,
-                            dact + dact_feat(PL) + p0 * 256, valid, wave, wch);    // streams dfeat (what it reads) out
+      gemm<MM, 2, 0>(acc, Hs, 0, 16, wblock<MM>(packed_t, lay.PBM), 16, 0, wn * 2, wm, lane);
       __syncthreads();
       wprefetch(wch, wblock<MM>(packed_t, lay.PB[2]), 32, 0, 32, wn * 2, lane);
       epilogue_dx<true, true>(acc, Hs, Es, pre, nullptr, wm, wn, lane, valid);

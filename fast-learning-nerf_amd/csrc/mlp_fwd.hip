@@ -1,6 +1,8 @@
 // mlp_fwd.hip -- the fused forward of the 8 x 256 NeRF MLP (model.py:38-63; nerf++ MLPNet: nerf_network.py:70-120): positional encoding ->
-// 8 layers (skip at 5) -> alpha head -> feature -> view branch -> rgb, one persistent kernel, three math modes (mlp_common.h).
+// 8 layers (skip at 5) -> alpha head -> view branch (feature layer folded in) -> rgb, one persistent kernel, three math modes (mlp_common.h).
 #include "mlp_common.h"
+
+float* fn_fold_buffer(const float* packed_fwd, bool create);   // mlp_pack.hip
 
 // =========================================================================================
 // forward
@@ -51,8 +53,8 @@ __device__ __forceinline__ int x2idx(int m, int k) { return m * 32 + ((((k >> 2)
 template <bool SAVE, bool BG, int MM = MM_F32, bool LIST = false>
 __global__ void __launch_bounds__(NTHR, 2 * NTHR / 512 * WG_PER_CU)
 mlp_fwd_kernel(int64_t P, int S, const float* __restrict__ rays, const float* __restrict__ zv,
-               const float* __restrict__ params, const float* __restrict__ packed, float* __restrict__ raw,
-               float* __restrict__ act, NetLayout lay, unsigned* __restrict__ sched, const int* __restrict__ live_idx,
+               const float* __restrict__ params, const float* __restrict__ packed, const float* __restrict__ fold,
+               float* __restrict__ raw, float* __restrict__ act, NetLayout lay, unsigned* __restrict__ sched, const int* __restrict__ live_idx,
                const int* __restrict__ live_cnt, int flags) {
   // live-list mode (exact zero-gradient point compaction, see mlp_bf16.hip / train.hip): row j of the launch is point
   // live_idx[j], the row count is a device value; the saved tensors keep the strides of the capacity PL they were sized for
@@ -62,7 +64,7 @@ mlp_fwd_kernel(int64_t P, int S, const float* __restrict__ rays, const float* __
   float* Hs = smem;
   float* Es = smem + LDS_H;
   float* X2 = smem;   // [TM][32], aliases the head of H (BG only)
-  // tile scheduler word (sched.h): the last two floats of H = columns >= 128 of the last row, stale feature values at
+  // tile scheduler word (sched.h): the last two floats of H = columns >= 128 of the last row, stale h7 values at
   // the end of a tile and next written by the following tile's layer-0 epilogue, one barrier after everybody read it
   volatile int* sched_word = reinterpret_cast<volatile int*>(smem + LDS_H - 2);
   const int tid = threadIdx.x;
@@ -215,7 +217,7 @@ mlp_fwd_kernel(int64_t P, int S, const float* __restrict__ rays, const float* __
         Es[eidx(pm, 6 + 6 * k + dim)] = FN_COS(a);
       }
     }
-    // FN_FWD_SKIP_DEAD_RGB (see mlp_bf16.hip): a tile without a live sample skips the feature / view / colour layers.  One word
+    // FN_FWD_SKIP_DEAD_RGB (see mlp_bf16.hip): a tile without a live sample skips the view and colour layers.  One word
     // per wave in channels 56..63 of row 0 of the encoding tile (free since layer 5; the direction encoding uses 0..31).
     bool skip_tail = false;
     if (!SAVE && !BG && (flags & 1)) {
@@ -231,14 +233,10 @@ mlp_fwd_kernel(int64_t P, int S, const float* __restrict__ rays, const float* __
     if (skip_tail) {
       if (pq == 0 && pm < valid && raw) *reinterpret_cast<float4*>(raw + (LIST ? pp : p0 + pm) * 4) = make_float4(0.f, 0.f, 0.f, alpha_val);
     } else {
-    // ---- feature layer (no ReLU) ------------------------------------------------------
-    load_bias<2>(bv2, params + lay.FB, wn, lane);
-    init_acc<2, FOLD>(acc, bv2);
-    gemm<MM, 2, 0>(acc, Hs, 0, 32, wblock<MM>(packed, lay.PF[8]), 32, 0, wn * 2, wm, lane, dbg,
-                   SAVE ? act + act_h(PL, PEP, 7) + p0 * 256 : nullptr, valid, wave);
-    __syncthreads();
-    epilogue_fwd<2, false, false, FOLD>(acc, bv2, Hs, wm, wn, lane, nullptr, 256, valid);
-    __syncthreads();
+    // ---- view layer on h7: [h7 | vpe32] -> 128, ReLU -------------------------------------
+    // The feature / remap layer has no activation and feeds the view layer alone, so the two are ONE linear map of h7:
+    // zv = M h7 + Wv[:, 256:] vpe + b',  M = Wv[:, :256] Wf,  b' = bv + Wv[:, :256] bf, folded at every (re)pack (mlp_pack.hip fold_kernel).
+    __syncthreads();   // the direction encoding in Es is complete
     if (SAVE) {
       float* avp = act + act_vpe(PL, PEP) + p0 * 32;
       for (int i = tid; i < TM * 8; i += NTHR) {
@@ -247,15 +245,14 @@ mlp_fwd_kernel(int64_t P, int S, const float* __restrict__ rays, const float* __
           store_nt(avp + m * 32 + sl * 4, *reinterpret_cast<const float4*>(Es + m * 64 + ((sl ^ (m & 15)) << 2)));
       }
     }
-    // ---- view layer: [feat | vpe32] -> 128, ReLU ---------------------------------------
     {
       AccT<L16, 1> av;
       float bv1[L16 ? 2 : 1];
-      load_bias<1>(bv1, params + lay.VB, wn, lane);
+      load_bias<1>(bv1, fold + fold_plain(lay.PFB, L16), wn, lane);
       init_acc<1, FOLD>(av, bv1);
-      gemm<MM, 1, 0>(av, Hs, 0, 32, wblock<MM>(packed, lay.PF[9]), 36, 0, wn, wm, lane, dbg,
-                     SAVE ? act + act_feat(PL, PEP) + p0 * 256 : nullptr, valid, wave);
-      gemm<MM, 1, 1>(av, Es, 0, 4, wblock<MM>(packed, lay.PF[9]), 36, 32, wn, wm, lane, dbg);
+      gemm<MM, 1, 0>(av, Hs, 0, 32, wblock<MM>(fold, lay.PFM), 36, 0, wn, wm, lane, dbg,
+                     SAVE ? act + act_h(PL, PEP, 7) + p0 * 256 : nullptr, valid, wave);    // streams h7 (what it reads) out
+      gemm<MM, 1, 1>(av, Es, 0, 4, wblock<MM>(fold, lay.PFM), 36, 32, wn, wm, lane, dbg);
       __syncthreads();
       epilogue_fwd<1, true, false, FOLD>(av, bv1, Hs, wm, wn, lane, nullptr, 128, valid);
       __syncthreads();
@@ -308,7 +305,9 @@ static int fwd_launch_t(int grid, hipStream_t st, int64_t P, int S, const float*
     FN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
     attr = true;
   }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(NTHR), LDS_BYTES, st, P, S, rays11, z, params, packed_fwd, raw, act, lay, sched, live_idx,
+  const float* fold = fn_fold_buffer(packed_fwd, false);   // the folded view layer that the pack call left beside this buffer (mlp_pack.hip)
+  FN_CHECK_ARG(fold != nullptr, "packed_fwd was not filled by a pack call of this process (the folded view layer is kept by its address)");
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(NTHR), LDS_BYTES, st, P, S, rays11, z, params, packed_fwd, fold, raw, act, lay, sched, live_idx,
                      live_cnt, flags);
   FN_LAUNCH_CHECK();
   return 0;

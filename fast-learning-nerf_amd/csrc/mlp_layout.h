@@ -14,6 +14,12 @@ struct NetLayout {
   int64_t LW[8], LB[8];                    // trunk weights / biases (flat offsets, [out][in] row-major)
   int64_t VW, VB, FW, FB, AW, AB, RW, RB;  // view layer, feature/remap, alpha/sigma, rgb
   int64_t PF[10], PB[9];                   // packed (fragment order) offsets: fwd L0..L7,F,V ; bwd Vt,Ft,L7t..L1t
+  // the folded view layer (feature / remap layer multiplied into the view layer's first 256 columns: M = Wv[:, :256] Wf, b' = bv + Wv[:, :256] bf).
+  // PBM = M^T in the order of PB[0], appended to the backward buffer.  The forward's part lives in a buffer of its own beside packed_fwd
+  // (mlp_pack.hip fn_fold_buffer: the forward buffer's size is pinned), offsets into it: PFM = [M | Wv[:, 256:]] in the view layer's forward
+  // order, PFB = b' (128 plain floats), PFR = M as plain row-major fp32 [128][256] (what the two packings are made from).  PFB / PFR hold
+  // plain floats in every math mode: `fold_plain` gives their float offset in a buffer of that mode.
+  int64_t PFM, PFB, PFR, PBM, fold_total;
   int64_t n_params, pf_total, pb_total;
   int in_pe, pe_pad;                       // 63 -> 64, 84 -> 96
   int kind;
@@ -44,12 +50,21 @@ inline NetLayout make_layout(int kind) {
   }
   L.pf_total = p;
   p = 0;
+  L.PFM = p; p += (int64_t)288 * 128;
+  L.PFB = p; p += 128;
+  L.PFR = p; p += (int64_t)128 * 256;
+  L.fold_total = p;
+  p = 0;
   for (int j = 0; j < 9; ++j) { L.PB[j] = p; p += (int64_t)(j == 0 ? 128 : 256) * 256; }
+  L.PBM = p; p += (int64_t)128 * 256;
   L.pb_total = p;
   return L;
 }
 
-// ---- saved activations, SoA over P points: pe | h0..h7 | feat | vpe32 | hv128 | ReLU sign words ----
+// float offset of a plain-float region (PFB, PFR) in a packed buffer: the bf16x6 packing holds 3/2 floats per unit of the offsets above
+inline __host__ __device__ int64_t fold_plain(int64_t off, bool x6) { return x6 ? off * 3 / 2 : off; }
+
+// ---- saved activations, SoA over P points: pe | h0..h7 | (feat: a hole since the fold, nothing reads or writes it) | vpe32 | hv128 | ReLU sign words ----
 constexpr int ACT_REST = 8 * 256 + 256 + 32 + 128;   // 2464 floats per point after the pe block
 constexpr int ACT_MASK = 64;                         // 256 bytes of sign words per point (one 64-bit word per lane, layer and wave: mlp_common.h epilogue_fwd)
 inline __host__ __device__ int64_t act_pe(int64_t P, int pe_pad) { return 0; }
@@ -59,7 +74,7 @@ inline __host__ __device__ int64_t act_vpe(int64_t P, int pe_pad) { return P * (
 inline __host__ __device__ int64_t act_hv(int64_t P, int pe_pad) { return P * (pe_pad + 2048 + 256 + 32); }
 inline __host__ __device__ int64_t act_mask(int64_t P, int pe_pad) { return P * (pe_pad + ACT_REST); }  // uint64 words
 inline int64_t act_floats(int64_t P, int pe_pad) { return P * (pe_pad + ACT_REST + ACT_MASK) + 8192; }
-// ---- pre-activation gradients, SoA ----
+// ---- pre-activation gradients, SoA (dact_feat: a hole since the fold) ----
 constexpr int DACT_FLOATS = 8 * 256 + 256 + 128;
 inline __host__ __device__ int64_t dact_y(int64_t P, int l) { return (int64_t)l * P * 256; }
 inline __host__ __device__ int64_t dact_feat(int64_t P) { return 8 * P * 256; }

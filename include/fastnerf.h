@@ -349,6 +349,15 @@ int fastnerf_render_rays_bwd_live(int math_mode, int64_t n, int N_samples, int N
  * fastnerf_mlp_fwd_flags_ex (ignored when act != NULL). */
 int64_t fastnerf_mlp_x6_packed_floats(int kind, int which);
 int fastnerf_mlp_x6_pack(int kind, const float* params, float* packed_fwd, float* packed_bwd, fn_stream_t stream);
+/* The fp32 / bf16x6 kernels run the feature (remap) layer and the view layer as ONE linear map of h7: M = Wv[:, :256] Wf, b' = bv + Wv[:, :256] bf,
+ * folded in fp64 at every pack call.  M^T is appended to packed_bwd; the forward's part lives in a device buffer the library keeps beside
+ * packed_fwd, found by that buffer's ADDRESS: the forward entry points need the very packed_fwd a pack call of this process filled (a copy
+ * of it is an error, not garbage).  The backward writes the gradients of both layers as before (an fp64 unfold behind the reduction).
+ * fastnerf_mlp_fold_buffer: that device buffer (NULL: never packed); fastnerf_mlp_fold_offset(kind, what): what = 0 [M | Wv[:, 256:]] in the
+ * view layer's forward order, 1 b' (128 plain floats), 2 M row-major fp32 [128][256] -- offsets in floats of the fp32 packing (x 3/2 under
+ * bf16x6) --, 3 the offset of M^T in packed_bwd (same units), 4 the fold buffer's size. */
+const float* fastnerf_mlp_fold_buffer(const float* packed_fwd);
+int64_t fastnerf_mlp_fold_offset(int kind, int what);
 int fastnerf_mlp_x6_fwd(int kind, int64_t n, int S, const float* rays11, const float* z, const float* params,
                         const float* packed_fwd, float* raw, float* act, int flags, fn_stream_t stream);
 int fastnerf_mlp_x6_bwd(int kind, int64_t n, int S, const float* draw, const float* act, const float* params,
