@@ -159,6 +159,8 @@ SIGNATURES = {
     'fastnerf_render_rays_fwd_occ_cascade': (I, [I, L, I, I, P, I, I, I, I, P, P, U64, U64, P, P, P, P, C.POINTER(OccCascade), P, P] + [P] * 16 + [I, P]),
     'fastnerf_mlp_sigma_grad_ws_floats': (L, [I, L]),
     'fastnerf_mlp_sigma_grad': (I, [I, I, L, I, P, P, P, P, P, P, P, P, P]),
+    'fastnerf_ray_grad_ws_floats': (L, [I, L, I]),
+    'fastnerf_ray_grad': (I, [I, I, L, I, P, P, P, P, P, P, P, P, P, I, P, P]),
 }
 
 _lib = None

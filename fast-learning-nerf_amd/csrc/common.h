@@ -11,6 +11,10 @@ void set_error(const char* fmt, ...);
 inline hipStream_t S(fn_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 }  // namespace fn
 
+// sigma_grad.hip: sigma_grad_kernel on a caller's saved activations and pre-activation gradients of P points (also ray_grad.hip)
+int fn_launch_sigma_grad(int math_mode, int64_t P, const float* act, const float* dact, const float* raw, const float* params,
+                         float* sigma, float* grad, hipStream_t st);
+
 #define FN_CHECK_ARG(cond, msg)                          \
   do {                                                   \
     if (!(cond)) {                                       \

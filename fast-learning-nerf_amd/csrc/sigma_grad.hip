@@ -179,6 +179,30 @@ static int64_t sg_dact_floats(int math_mode, int64_t P) {
   return up4(math_mode == 1 ? fastnerf_mlp_bf16_floats(0, 4, P) : P * (int64_t)FASTNERF_DACT_FLOATS);
 }
 
+// sigma_grad_kernel on a caller's saved activations and pre-activation gradients of P points (the layouts of `math_mode`): what
+// fastnerf_mlp_sigma_grad runs on its own scratch, and fastnerf_ray_grad (ray_grad.hip) on the scratch a training backward left, whose
+// dY0 / dY5 then hold the cotangent of a loss instead of (0, 0, 0, 1).  raw is read only when sigma is wanted.
+int fn_launch_sigma_grad(int math_mode, int64_t P, const float* act, const float* dact, const float* raw, const float* params,
+                         float* sigma, float* grad, hipStream_t st) {
+  const NetLayout L = make_layout(0);
+  const unsigned grid = (unsigned)((P + SG_TM - 1) / SG_TM);
+  if (math_mode == 1) {
+    int64_t ope, oy0, oy5;
+    fn_bf16_sigma_grad_offsets(P, &ope, &oy0, &oy5);
+    const uint4* a4 = reinterpret_cast<const uint4*>(act);
+    const uint4* d4 = reinterpret_cast<const uint4*>(dact);
+    hipLaunchKernelGGL(sigma_grad_kernel<true>, dim3(grid), dim3(256), 0, st, P, static_cast<const void*>(d4 + oy0),
+                       static_cast<const void*>(d4 + oy5), static_cast<const void*>(a4 + ope), static_cast<const float*>(raw),
+                       params + L.LW[0], params + L.LW[5], sigma, grad);
+  } else {
+    hipLaunchKernelGGL(sigma_grad_kernel<false>, dim3(grid), dim3(256), 0, st, P, static_cast<const void*>(dact + dact_y(P, 0)),
+                       static_cast<const void*>(dact + dact_y(P, 5)), static_cast<const void*>(act + act_pe(P, L.pe_pad)),
+                       static_cast<const float*>(raw), params + L.LW[0], params + L.LW[5], sigma, grad);
+  }
+  FN_LAUNCH_CHECK();
+  return 0;
+}
+
 // act | dact | draw [P,4] | raw [P,4], each part 16-byte aligned
 extern "C" int64_t fastnerf_mlp_sigma_grad_ws_floats(int math_mode, int64_t n_points) {
   if (math_mode < 0 || math_mode > 2 || n_points < 0) {
@@ -213,21 +237,5 @@ extern "C" int fastnerf_mlp_sigma_grad(int math_mode, int kind, int64_t n, int S
   if (math_mode == 1) rc = fn_launch_dx_bf16(0, P, draw, act, params, packed_bwd, dact, nullptr, nullptr, st);
   else rc = fn_launch_dx_alone(math_mode == 2 ? 1 : 0, 0, P, draw, act, params, packed_bwd, dact, st);
   if (rc) return rc;
-  const NetLayout L = make_layout(0);
-  const unsigned grid = (unsigned)((P + SG_TM - 1) / SG_TM);
-  if (math_mode == 1) {
-    int64_t ope, oy0, oy5;
-    fn_bf16_sigma_grad_offsets(P, &ope, &oy0, &oy5);
-    const uint4* a4 = reinterpret_cast<const uint4*>(act);
-    const uint4* d4 = reinterpret_cast<const uint4*>(dact);
-    hipLaunchKernelGGL(sigma_grad_kernel<true>, dim3(grid), dim3(256), 0, st, P, static_cast<const void*>(d4 + oy0),
-                       static_cast<const void*>(d4 + oy5), static_cast<const void*>(a4 + ope), static_cast<const float*>(raw),
-                       params + L.LW[0], params + L.LW[5], sigma, grad);
-  } else {
-    hipLaunchKernelGGL(sigma_grad_kernel<false>, dim3(grid), dim3(256), 0, st, P, static_cast<const void*>(dact + dact_y(P, 0)),
-                       static_cast<const void*>(dact + dact_y(P, 5)), static_cast<const void*>(act + act_pe(P, L.pe_pad)),
-                       static_cast<const float*>(raw), params + L.LW[0], params + L.LW[5], sigma, grad);
-  }
-  FN_LAUNCH_CHECK();
-  return 0;
+  return fn_launch_sigma_grad(math_mode, P, act, dact, raw, params, sigma, grad, st);
 }

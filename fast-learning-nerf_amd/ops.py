@@ -292,6 +292,41 @@ def mlp_sigma_grad(rays11, z, params, packed_fwd, packed_bwd, ws=None, grad=None
     return sigma, grad.reshape(-1)[:P * 3].view(n, S, 3)
 
 
+def ray_grad_ws_floats(n, S):
+    """Floats of scratch one ray_grad call over n rays of S samples needs (the per-point gradient, 12 bytes per sample)."""
+    return int(check(lib().fastnerf_ray_grad_ws_floats(mode_id(), int(n), int(S)), 'fastnerf_ray_grad_ws_floats'))
+
+
+def ray_grad(rays11, z, raw, noise, draw, act, dact, params, d_rays=None, accumulate=False, ws=None, kind=0):
+    """d_rays [n,11]: the gradient of a loss with respect to the rays (o, d, near, far, viewdir) of ONE pass of render_rays
+    (fastnerf_ray_grad, kind 0, math modes fp32 and bf16x6).  Call it after raw2outputs_bwd (-> draw) and mlp_bwd on that draw,
+    with the same `act` and `dact`: it reads the pre-activation gradients the backward left there.  rays11, z, raw, noise: what the
+    pass's raw2outputs_bwd got.  Columns 6:8 (near, far) are exact zeros: they are constants of this gradient.
+    accumulate=True adds to `d_rays` (a second pass on top of the first); otherwise its n rows are overwritten (default: allocated
+    here).  bf16x3 raises NotImplementedError: its saved tensors have no ray-gradient kernel, and a partial gradient is worse than none."""
+    if _MATH == 'bf16x3':
+        raise NotImplementedError("ray gradients exist in the math modes 'fp32' and 'bf16x6' only (FASTNERF_MATH / ops.set_math), "
+                                  "not in 'bf16x3'")
+    require_gpu(rays11, z, raw, noise, draw, act, dact, params, d_rays, ws)
+    n, S = z.shape
+    P = n * S
+    f32 = torch.float32
+    assert rays11.shape == (n, 11) and rays11.dtype == f32 and z.dtype == f32 and params.numel() == net_floats(0, 0)
+    assert raw.numel() == P * 4 and draw.numel() == P * 4 and raw.dtype == f32 and draw.dtype == f32
+    assert noise is None or (noise.numel() == P and noise.dtype == f32)
+    assert act.dtype == f32 and dact.dtype == f32 and act.numel() >= act_floats(P) and dact.numel() >= dact_floats(P)
+    if d_rays is None:
+        assert not accumulate, 'accumulate=True needs the d_rays to add to'
+        d_rays = torch.empty(n, 11, device=z.device, dtype=f32)
+    assert d_rays.dtype == f32 and d_rays.numel() >= n * 11
+    if ws is None:
+        ws = torch.empty(ray_grad_ws_floats(n, S), device=z.device, dtype=f32)
+    assert ws.dtype == f32 and ws.numel() >= ray_grad_ws_floats(n, S)
+    check(lib().fastnerf_ray_grad(mode_id(), int(kind), n, S, ptr(rays11), ptr(z), ptr(raw), ptr(noise), ptr(draw), ptr(act), ptr(dact),
+                                  ptr(params), ptr(ws), int(bool(accumulate)), ptr(d_rays), stream()), 'fastnerf_ray_grad')
+    return d_rays.reshape(-1)[:n * 11].view(n, 11)
+
+
 def raw2outputs_fwd(raw, z, rays11, noise=None, white_bkgd=False):
     require_gpu(raw, z, rays11, noise)
     n, S = z.shape

@@ -10,6 +10,10 @@ raw2outputs_bwd + mlp_bwd for both nets and hands the flat gradients to the NeRF
 so the reference's `loss.backward(); optimizer.step()` loop works unchanged.  Networks that are not fastnerf
 NeRF modules take the closure route instead (`_render_rays_closure`): the caller's `network_query_fn` runs in torch
 between the same HIP sampling and compositing kernels, differentiable through torch.ops.fastnerf.raw2outputs_full.
+
+Ray and pose gradients: a `ray_batch` that requires grad gets `rgb_map` / `rgb0`'s gradient with respect to its columns o, d and
+viewdir on both routes (fused: ops.ray_grad after each pass's backward, `_RenderRaysRayGradFn`; near / far are constants and get
+zeros), and `render(..., c2w=pose)` with a pose that requires grad carries it on to the pose (`_PoseRaysFn`).
 """
 import os
 
@@ -252,18 +256,33 @@ def _backward_core(saved, g_rgb, g_rgb0, out_c=None, out_f=None, counts=None):
                             out_f if Ni > 0 else None, S0, Ni)
         return
     # one shared network for both passes (N_importance > 0 without network_fine): accumulate the two gradients
-    n, S1 = saved['z1'].shape
-    if g_rgb is None:
-        g_rgb = torch.zeros(n, 3, device=dev)
-    draw1 = ops.raw2outputs_bwd(saved['raw1'], saved['z1'], rays11, g_rgb, saved['noise1'], saved['white'])
-    dact = _Workspace.dact(dev, ops.dact_floats(n * S1))
-    gtmp = torch.empty_like(out_c)
-    ops.mlp_bwd(draw1, saved['act1'], net_f.flat, saved['pf'][1], dact, partial, gtmp)
-    g_c = g_rgb0 if g_rgb0 is not None else torch.zeros(n, 3, device=dev)
-    draw0 = ops.raw2outputs_bwd(saved['raw0'], saved['z0'], rays11, g_c, saved['noise0'], saved['white'])
-    dact = _Workspace.dact(dev, ops.dact_floats(n * S0))
-    ops.mlp_bwd(draw0, saved['act0'], net_c.flat, saved['pc'][1], dact, partial, out_c)
-    out_c.add_(gtmp)
+    _backward_passes(saved, g_rgb, g_rgb0, out_c, None)
+
+
+def _backward_passes(saved, g_rgb, g_rgb0, out_c, out_f, d_rays=None):
+    """The backward of a saving forward pass by pass -- raw2outputs_bwd -> mlp_bwd [-> ray_grad], the fine pass, then the coarse one --
+    for what the one-call ops.render_rays_bwd cannot do: one shared network (the fine pass's gradient is added to the coarse
+    pass's in out_c) and ray gradients (d_rays [n,11], overwritten: ops.ray_grad reads a pass's `dact` before the next pass
+    overwrites it).  Same kernels, inputs and order as the one call, so the parameter gradients are bit-identical to its."""
+    rays11 = saved['rays11']
+    dev = rays11.device
+    partial = _Workspace.partial(dev)
+    net_c, net_f = saved['net_c'], saved['net_f']
+    shared = net_f is net_c
+    passes = [('0', net_c, saved['pc'], g_rgb if net_f is None else g_rgb0, out_c)]
+    if net_f is not None:
+        passes.insert(0, ('1', net_f, saved['pf'], g_rgb, torch.empty_like(out_c) if shared else out_f))
+    for i, (k, net, packed, g, out) in enumerate(passes):
+        z, raw, noise, act = saved['z' + k], saved['raw' + k], saved['noise' + k], saved['act' + k]
+        if g is None:
+            g = torch.zeros(z.shape[0], 3, device=dev)
+        draw = ops.raw2outputs_bwd(raw, z, rays11, g, noise, saved['white'])
+        dact = _Workspace.dact(dev, ops.dact_floats(z.numel()))
+        ops.mlp_bwd(draw, act, net.flat, packed[1], dact, partial, out)
+        if d_rays is not None:
+            ops.ray_grad(rays11, z, raw, noise, draw, act, dact, net.flat, d_rays=d_rays, accumulate=i > 0)
+    if shared:
+        out_c.add_(passes[0][4])
 
 
 _POLICY = LivePolicy()   # the autograd route's policy (the fused Trainer keeps its own)
@@ -308,6 +327,39 @@ class _RenderRaysFn(torch.autograd.Function):
         return (None,) + tuple(grads)
 
 
+class _RenderRaysRayGradFn(torch.autograd.Function):
+    """_RenderRaysFn with the ray batch as a further input: the forward always saves its activations (the compacted backward has
+    no ray gradients), the backward runs pass by pass (_backward_passes) and returns d(loss)/d(ray_batch) beside the parameter
+    gradients, which equal the saving route's bit for bit.  Columns 6:8 (near, far) of the ray gradient are zeros: z is a constant of
+    the backward (render.py:281 detaches the fine samples; the coarse ones depend on near / far alone, which are not differentiated)."""
+
+    @staticmethod
+    def forward(ctx, cfg, ray_batch, *params):
+        out, saved = _forward_core(save=True, **cfg)
+        ctx.saved = saved
+        ctx.n_params = len(params)
+        ctx.ray_like = (ray_batch.shape[-1], ray_batch.dtype)
+        keys = ['rgb_map', 'disp_map', 'acc_map', 'raw'] + (['rgb0', 'disp0', 'acc0', 'z_std'] if 'rgb0' in out else [])
+        ctx.keys = keys
+        outs = tuple(out[k] for k in keys)
+        ctx.mark_non_differentiable(*[o for k, o in zip(keys, outs) if k not in ('rgb_map', 'rgb0')])
+        return outs
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        g = dict(zip(ctx.keys, gouts))
+        saved = ctx.saved
+        two = saved['net_f'] is not None and saved['net_f'] is not saved['net_c']
+        out_c = torch.empty_like(saved['net_c'].flat)      # (fresh buffers: see _RenderRaysFn.backward)
+        out_f = torch.empty_like(saved['net_f'].flat) if two else None
+        d_rays = torch.empty(saved['rays11'].shape[0], 11, device=out_c.device, dtype=torch.float32)
+        _backward_passes(saved, g.get('rgb_map'), g.get('rgb0'), out_c, out_f, d_rays=d_rays)
+        grads = saved['net_c'].param_grads_from(out_c) + (saved['net_f'].param_grads_from(out_f) if two else [])
+        assert len(grads) == ctx.n_params
+        width, dtype = ctx.ray_like
+        return (None, d_rays[:, :width].to(dtype)) + tuple(grads)
+
+
 def raw2outputs(raw, z_vals, rays_d, raw_noise_std=0, white_bkgd=False, pytest=False):
     """render.py:149-192 -> (rgb_map, disp_map, acc_map, weights, depth_map).  When `raw` requires grad, all five outputs are
     differentiable w.r.t. `raw` (torch.ops.fastnerf.raw2outputs_full, the reference's autograd formula); `z_vals` and `rays_d`
@@ -335,6 +387,15 @@ def _composite(raw, z, rays11, noise, white_bkgd):
     """Compositing of the closure route: the network's first four channels (a closure may return more, e.g. output_ch = 5),
     differentiable w.r.t. raw through every output when autograd records."""
     raw4 = raw[..., :4].float().contiguous()
+    if torch.is_grad_enabled() and rays11.requires_grad:
+        # rays that require grad: the op below does not differentiate rays11, and the points / view directions reach the rays
+        # through the network in torch.  What is left is dists = dz |d| (render.py:167): relu(sigma') dz |d| = relu(sigma' s) dz |d| with
+        # s = |d| / |d|.detach() = 1, so adding sigma' (s - 1) -- an exact zero -- to the logit gives d(loss)/d|d| its term
+        # sum_s draw[..., 3] sigma' / |d| (csrc/ray_grad.hip header) without changing a value.  Rays with d = 0: s = 1.
+        dn = torch.linalg.norm(rays11[:, 3:6], dim=-1, keepdim=True)
+        s1 = torch.where(dn > 0, dn / dn.detach(), torch.ones_like(dn)) - 1.0
+        sig = raw4[..., 3].detach() if noise is None else raw4[..., 3].detach() + noise
+        raw4 = torch.cat([raw4[..., :3], (raw4[..., 3] + sig * s1)[..., None]], -1)
     if torch.is_grad_enabled() and raw4.requires_grad:
         return torch.ops.fastnerf.raw2outputs_full(raw4, z, rays11, noise, white_bkgd)
     return ops.raw2outputs_fwd(raw4, z, rays11, noise, white_bkgd)
@@ -412,7 +473,12 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     inference only): a sample in a cell whose bit is clear gets raw = 0 without the network being evaluated, in both passes; every
     other sample gets the logits it gets without the grid.  ValueError with
     raw_noise_std > 0 (noise is added to sigma before the relu: a zero sigma is not a dead sample) and when gradients are
-    wanted (the training step must not silently change its gradients)."""
+    wanted (the training step must not silently change its gradients).
+
+    A `ray_batch` that requires grad receives d(rgb_map, rgb0)/d(ray_batch) as the reference's plain-torch render_rays gives it:
+    columns o, d (through the sample points and through dists * |d|) and viewdir; near / far (columns 6:8) get zeros on the
+    fused route (they are constants there: `render` passes Python floats).  Fused route: math modes 'fp32' and 'bf16x6'
+    (NotImplementedError under 'bf16x3'), always through the saving backward; disp_map / acc_map stay non-differentiable."""
     net_c = _unwrap(network_fn)
     net_f = _unwrap(network_fine)
     fused = isinstance(net_c, NeRF)
@@ -431,9 +497,9 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             raise ValueError('render_rays: an occupancy grid cannot be combined with raw_noise_std > 0 (sigma noise is added before '
                              'the relu, so a sample with zero sigma is not dead)')
         nets = [m for m in (net_c, net_f) if isinstance(m, torch.nn.Module)]
-        if torch.is_grad_enabled() and any(p.requires_grad for m in nets for p in m.parameters()):
+        if torch.is_grad_enabled() and (ray_batch.requires_grad or any(p.requires_grad for m in nets for p in m.parameters())):
             raise ValueError('render_rays: an occupancy grid is an inference feature; call it under torch.no_grad() (or with '
-                             'parameters that do not require grad)')
+                             'parameters and rays that do not require grad)')
     rays11 = ray_batch.contiguous().float()
     if rays11.shape[-1] == 8:      # no view directions: the kernels' direction slots stay zero (their weights are zero too)
         rays11 = torch.cat([rays11, torch.zeros(rays11.shape[0], 3, device=rays11.device)], -1)
@@ -462,6 +528,14 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     if occupancy is not None:
         out = _forward_occ(rays11, net_c, net_f, N_samples, N_importance, lindisp, perturb, white_bkgd, t_rand, u, occupancy,
                            skip_dead_rgb=not retraw)
+    elif torch.is_grad_enabled() and ray_batch.requires_grad:
+        if ops.get_math() == 'bf16x3':
+            raise NotImplementedError("render_rays: rays that require grad need the math mode 'fp32' or 'bf16x6' (FASTNERF_MATH / "
+                                      "ops.set_math): 'bf16x3' has no ray-gradient kernel")
+        cfg['rays11'] = rays11.detach()
+        outs = _RenderRaysRayGradFn.apply(cfg, ray_batch, *params)
+        keys = ['rgb_map', 'disp_map', 'acc_map', 'raw'] + (['rgb0', 'disp0', 'acc0', 'z_std'] if N_importance > 0 else [])
+        out = dict(zip(keys, outs))
     elif torch.is_grad_enabled() and any(p.requires_grad for p in params):
         outs = _RenderRaysFn.apply(cfg, *params)
         keys = ['rgb_map', 'disp_map', 'acc_map', 'raw'] + (['rgb0', 'disp0', 'acc0', 'z_std'] if N_importance > 0 else [])
@@ -486,24 +560,65 @@ def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
     return {k: (v[0] if len(v) == 1 else torch.cat(v, 0)) for k, v in all_ret.items()}
 
 
+class _PoseRaysFn(torch.autograd.Function):
+    """The ray batch [H*W, 11] of a pinhole camera (HIP get_rays + pack_rays, ndc=False) as a function of its pose c2w [3,4]:
+    o = t,  d = R dir,  viewdir v = d / |d|,  dir = ((col - cx) / fx, -(row - cy) / fy, -1)  (run_nerf_helpers.py:68-78, render.py:59-80).
+    Backward, from d_rays = (d_o, d_d, ., ., d_v):  d_t = sum d_o,  d_R = sum (d_d + (I - v v^T) d_v / |d|) (x) dir -- twelve
+    sums over the image, in torch: not a hot path."""
+
+    @staticmethod
+    def forward(ctx, c2w, H, W, K, near, far):
+        rays_o, rays_d = get_rays(H, W, K, c2w.detach())
+        ctx.cam = (H, W, float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2]))
+        ctx.save_for_backward(rays_d.reshape(-1, 3))
+        ctx.like = (c2w.device, c2w.dtype)
+        return ops.pack_rays(rays_o, rays_d, near, far)
+
+    @staticmethod
+    def backward(ctx, d_rays):
+        d, = ctx.saved_tensors
+        H, W, fx, fy, cx, cy = ctx.cam
+        dev = d.device
+        row, col = torch.meshgrid(torch.arange(H, device=dev, dtype=torch.float32), torch.arange(W, device=dev, dtype=torch.float32),
+                                  indexing='ij')
+        dirs = torch.stack([(col - cx) / fx, -(row - cy) / fy, -torch.ones_like(col)], -1).reshape(-1, 3)
+        d_rays = d_rays.float()
+        dn = torch.linalg.norm(d, dim=-1, keepdim=True)
+        v = d / dn
+        d_v = d_rays[:, 8:11]
+        g_d = d_rays[:, 3:6] + (d_v - v * (v * d_v).sum(-1, keepdim=True)) / dn
+        d_c2w = torch.cat([g_d.t() @ dirs, d_rays[:, 0:3].sum(0)[:, None]], -1)
+        return d_c2w.to(device=ctx.like[0], dtype=ctx.like[1]), None, None, None, None, None
+
+
 def render(H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far=1., use_viewdirs=False,
            c2w_staticcam=None, **kwargs):
-    """render.py:26-91 -> [rgb_map, disp_map, acc_map, extras]."""
-    if c2w is not None:
-        rays_o, rays_d = get_rays(H, W, K, c2w)
+    """render.py:26-91 -> [rgb_map, disp_map, acc_map, extras].  A tensor `c2w` that requires grad receives the gradient of
+    rgb_map (and rgb0) through the rays (_PoseRaysFn); with ndc=True or c2w_staticcam that raises NotImplementedError."""
+    if torch.is_tensor(c2w) and c2w.requires_grad and torch.is_grad_enabled():
+        if ndc or c2w_staticcam is not None:
+            raise NotImplementedError('render: a pose that requires grad is differentiated through plain pinhole rays only '
+                                      '(ndc=False, no c2w_staticcam)')
+        sh = (H, W, 3)
+        rays11 = _PoseRaysFn.apply(c2w[:3, :4], H, W, K, float(near), float(far))
+        if not use_viewdirs:
+            rays11 = rays11[:, :8]
     else:
-        rays_o, rays_d = rays
-    ops.require_gpu(rays_o, rays_d)
-    view_o, view_d = rays_o, rays_d
-    if use_viewdirs and c2w_staticcam is not None:   # (render.py:59-66: the static camera only exists inside this branch)
-        rays_o, rays_d = get_rays(H, W, K, c2w_staticcam)
-    sh = rays_d.shape
-    rays11 = ops.pack_rays(rays_o, rays_d, near, far, ndc=ndc, H=H, W=W, focal=float(K[0][0]))
-    if not use_viewdirs:
-        rays11 = rays11[:, :8].contiguous()           # [N,8]: o, d, near, far (render.py:74-78)
-    elif c2w_staticcam is not None:
-        # viewdirs come from the moving camera, origins/directions from the static one
-        rays11[:, 8:11] = ops.pack_rays(view_o, view_d, near, far)[:, 8:11]
+        if c2w is not None:
+            rays_o, rays_d = get_rays(H, W, K, c2w)
+        else:
+            rays_o, rays_d = rays
+        ops.require_gpu(rays_o, rays_d)
+        view_o, view_d = rays_o, rays_d
+        if use_viewdirs and c2w_staticcam is not None:   # (render.py:59-66: the static camera only exists inside this branch)
+            rays_o, rays_d = get_rays(H, W, K, c2w_staticcam)
+        sh = rays_d.shape
+        rays11 = ops.pack_rays(rays_o, rays_d, near, far, ndc=ndc, H=H, W=W, focal=float(K[0][0]))
+        if not use_viewdirs:
+            rays11 = rays11[:, :8].contiguous()           # [N,8]: o, d, near, far (render.py:74-78)
+        elif c2w_staticcam is not None:
+            # viewdirs come from the moving camera, origins/directions from the static one
+            rays11[:, 8:11] = ops.pack_rays(view_o, view_d, near, far)[:, 8:11]
     all_ret = batchify_rays(rays11, chunk, **kwargs)
     for k in all_ret:
         all_ret[k] = torch.reshape(all_ret[k], list(sh[:-1]) + list(all_ret[k].shape[1:]))

@@ -603,6 +603,28 @@ int fastnerf_mlp_sigma_grad(int math_mode, int kind, int64_t n, int S, const flo
                             const float* packed_fwd, const float* packed_bwd, float* ws, float* sigma, float* grad,
                             fn_stream_t stream);
 
+/* ---- ray gradient: d(loss)/d(ray batch) of one pass of render_rays (csrc/ray_grad.hip) -----------------------------------------------
+ * d_rays [n,11] = the gradient of a loss with respect to the pass's rays (o, d, near, far, viewdir), given what the pass's backward
+ * left behind.  Call it AFTER fastnerf_raw2outputs_bwd (draw [n,S,4] = d(loss)/d(raw)) and the MLP backward of `math_mode` on that draw
+ * (fastnerf_mlp_bwd_ex / fastnerf_mlp_x6_bwd), while `dact` (its pre-activation gradients) and `act` (the saving forward's
+ * activations) are still valid: with g[p] = d(loss)/d(point p) = the kernel of fastnerf_mlp_sigma_grad run on dact's dY0 / dY5,
+ *   d_o[r] = sum_s g[r,s]
+ *   d_d[r] = sum_s z[r,s] g[r,s] + c_r d_r / |d_r|^2,   c_r = sum_s draw[r,s,3] (raw[r,s,3] + noise[r,s])
+ *            (the second term: dists = dz |d| in raw2outputs, render.py:167; 0 for a ray with d = 0)
+ *   d_viewdir[r] = the PE(4) chain rule on (sum_s dYv[r,s]) Wv[:, 256:283], with the saved sines and cosines
+ *   columns 6:8 (near, far) = 0: z is a constant of the pass (render.py:244-266 and the detach of render.py:281), near / far are
+ *   not differentiated.
+ * This is autograd of render.py:195-305 for one pass with respect to ray_batch.  z, raw, noise (NULL = none), rays11: the inputs
+ * of the pass's fastnerf_raw2outputs_bwd.  params: the flat parameters.  ws: fastnerf_ray_grad_ws_floats(math_mode, n, S) floats of
+ * scratch (g).  accumulate != 0 adds to d_rays (a second pass on top of the first), 0 overwrites its n rows.  No atomics: bit-identical
+ * from call to call, and a ray's result does not depend on where it sits in the batch.
+ * -1 before anything is enqueued: math_mode outside 0..2, n < 0, S < 1; kind != 0 (the nerf++ nets); math_mode 1 (bf16x3: its
+ * K-fragment tensors have no ray-gradient kernel); a NULL buffer other than noise when n > 0.  n == 0 returns 0 at once. */
+int64_t fastnerf_ray_grad_ws_floats(int math_mode, int64_t n, int S);
+int fastnerf_ray_grad(int math_mode, int kind, int64_t n, int S, const float* rays11, const float* z, const float* raw,
+                      const float* noise, const float* draw, const float* act, const float* dact, const float* params, float* ws,
+                      int accumulate, float* d_rays, fn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
