@@ -1,6 +1,10 @@
 // mlp_bwd_dw.hip -- dW = dY^T X per layer (+ bias column sums, + the alpha head's rank-1 row), the head gradients, the ordered reduction of the
 // per-workgroup partials, and the backward entry points (which launch the dX kernel of mlp_bwd_dx.hip first).
 #include "mlp_common.h"
+#include "dw_pair.h"
+#include <atomic>
+#include <map>
+#include <utility>
 
 int fn_launch_dx(int mm, int grid, hipStream_t st, int64_t P, const float* draw, const float* act, const float* params, const float* packed_bwd,
                  float* dact, const NetLayout& L, const int* live_idx, const int* live_cnt);   // mlp_bwd_dx.hip
@@ -454,6 +458,8 @@ mlp_bwd_dw6_kernel(int64_t P, const float* __restrict__ dY, const float* __restr
 //   * the order in which partial sums meet depends on the point count only: the live-list backward (device-side count) chunks exactly like
 //     the plain backward of the same points -- bit-identical gradients (tests/test_gpu_compact.py).  The host sizes the grid for
 //     the capacity P_total; chunks beyond dw_trunk_chunks(P) exit and are not reduced.
+// The host checks dw_trunk_chunks(P) <= the chunks a partial region holds before every trunk launch (trunk_chunks_fit).  When one call runs
+// both passes of a two-net step, their 14 jobs go into ONE launch with the same chunking: mlp_bwd_dw6_trunk_pair_kernel below.
 // ---------------------------------------------------------------------------------------------------------------------
 #define DW_QMAX 256   // k-steps (of 16 points) a chunk grows to before the next eighth of the chip is added
 __host__ __device__ static inline int dw_trunk_chunks(int64_t P, int ncu) {
@@ -463,13 +469,7 @@ __host__ __device__ static inline int dw_trunk_chunks(int64_t P, int ncu) {
   k = k < 1 ? 1 : (k > 8 ? 8 : k);
   return unit * (int)k;
 }
-#define DW_TRUNK_JOBS 7
-struct DwTrunk {
-  const float* dY[DW_TRUNK_JOBS];
-  const float* X[DW_TRUNK_JOBS];
-  float* pw[DW_TRUNK_JOBS];
-  float* pb[DW_TRUNK_JOBS];
-};
+// (DW_TRUNK_JOBS = 7, struct DwTrunk: dw_pair.h)
 __global__ void __launch_bounds__(512, 2)
 mlp_bwd_dw6_trunk_kernel(int64_t P, DwTrunk J, const int* __restrict__ live_idx, const int* __restrict__ live_cnt, int ncu) {
   if (live_idx) P = (int64_t)__builtin_amdgcn_readfirstlane(*live_cnt);
@@ -478,6 +478,36 @@ mlp_bwd_dw6_trunk_kernel(int64_t P, DwTrunk J, const int* __restrict__ live_idx,
   const int job = (int)blockIdx.y;
   dw6_body<4, 2, 2, 4, true, false>(P, J.dY[job], J.X[job], nullptr, J.pw[job], J.pb[job], nullptr, live_idx, nullptr, nullptr,
                                     (int)blockIdx.x, nact);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The trunk jobs of BOTH passes of a two-net step in one launch (the paired backward: fn::x6_pair_* below, render.cpp rr_bwd).  A trunk workgroup
+// holds 96 KiB of LDS, a CU runs one at a time, so a launch costs whole rounds of ncu workgroups: at 4096 rays x (64 + 192) samples the passes
+// alone are 7 x 64 = 448 (1.75 rounds, costs 2) and 7 x 192 = 1344 workgroups (5.25 rounds, costs 6) of 256 k-steps each on 256 CUs; together they
+// are 1792 = exactly 7 rounds.  ceil(7 (c0 + c1) / ncu) <= ceil(7 c0 / ncu) + ceil(7 c1 / ncu): no shape takes more rounds than the two launches.
+// grid = 7 (c_fine + c_coarse) workgroups, flat, decoded to (pass, job, chunk) with the chunk fastest -- the dispatch order of the per-pass
+// grid (chunks, 7), the fine pass first; c = dw_trunk_chunks(the pass's own point count).  No dead workgroups (a (max chunks, 14) grid with
+// early exits would dispatch 896 of them at that shape).  Inside a job nothing differs from the per-pass launch: chunk count, k-step ranges and
+// partial regions are the same, so the partials, and every gradient reduced from them, are bit-identical.  No live list: the compacted backward
+// shares one act buffer between its passes and stays on the per-pass launch.
+// ---------------------------------------------------------------------------------------------------------------------
+struct DwTrunkPair {
+  DwTrunk J[2];     // [0] the fine pass, [1] the coarse pass
+  int64_t P[2];
+};
+__global__ void __launch_bounds__(512, 2)
+mlp_bwd_dw6_trunk_pair_kernel(DwTrunkPair A, int ncu) {
+  const int c0 = dw_trunk_chunks(A.P[0], ncu);
+  int b = (int)blockIdx.x;
+  const int pass = b >= DW_TRUNK_JOBS * c0 ? 1 : 0;
+  if (pass) b -= DW_TRUNK_JOBS * c0;
+  const int64_t P = A.P[pass];
+  const int nact = pass ? dw_trunk_chunks(P, ncu) : c0;
+  const int job = b / nact;
+  if (job >= DW_TRUNK_JOBS) return;   // never taken while host and device agree on ncu (the grid is exactly 7 (c0 + c1)): it keeps a mismatch inside the job tables
+  const DwTrunk& J = A.J[pass];
+  dw6_body<4, 2, 2, 4, true, false>(P, J.dY[job], J.X[job], nullptr, J.pw[job], J.pb[job], nullptr, nullptr, nullptr, nullptr, b - job * nact,
+                                    nact);
 }
 
 // rgb head + alpha bias gradients (VALU reduction over points): per-workgroup partials
@@ -522,20 +552,7 @@ __global__ void __launch_bounds__(128) head_grads_kernel(int64_t P, const float*
 }
 
 // ---- one launch reduces every job's per-workgroup partials into the flat gradient ------------
-struct RedSeg {
-  int64_t src;        // offset into the partial buffer
-  int64_t wg_stride;  // floats between consecutive workgroups' partials
-  int64_t dst;        // offset into the flat gradient
-  int nwg, rows, cols, ld, valid_cols;
-  int dyn;            // 1: the segment's chunk count is dw_trunk_chunks(point count) (the trunk launch); nwg is its capacity
-  int sc_cols;        // > 0: columns < sc_cols do not go to the gradient but to scratch[sc_dst + r * sc_cols + c] (G = dL/dM of the folded view layer)
-  int64_t sc_dst;
-};
-#define MAX_SEGS 32
-struct RedTable {
-  RedSeg s[MAX_SEGS];
-  int n;
-};
+// (struct RedSeg, MAX_SEGS, struct RedTable: dw_pair.h)
 
 __global__ void __launch_bounds__(256) reduce_all_kernel(RedTable tab, const float* __restrict__ partial, float* __restrict__ grads,
                                                           float* __restrict__ scratch, int64_t P, const int* __restrict__ live_cnt, int ncu) {
@@ -691,10 +708,45 @@ static void add_seg(RedTable& T, int64_t src, int64_t wg_stride, int nwg, int ro
   s.valid_cols = valid_cols; s.dyn = dyn; s.sc_cols = sc_cols; s.sc_dst = sc_dst;
 }
 
+// the trunk entries need 96 KiB of dynamic LDS: the attribute is set once per device (a process may drive several).  The flags are plain bools
+// written without a lock: two threads that race set the same attribute twice, which is harmless
+#define FN_MAX_DEV 64
+template <class K>
+static int trunk_lds_attr(K kern, bool (&done)[FN_MAX_DEV], int lds) {
+  int dev = 0;
+  FN_HIP(hipGetDevice(&dev));
+  if (dev < 0 || dev >= FN_MAX_DEV || !done[dev]) {
+    FN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    if (dev >= 0 && dev < FN_MAX_DEV) done[dev] = true;
+  }
+  return 0;
+}
+constexpr int DW_TRUNK_LDS = 2 * 16 * 3 * 1024 + 128;
+// a job's partial region holds nwg chunks: on a part with fewer than 8 CUs dw_trunk_chunks can ask for more
+static int trunk_chunks_fit(int64_t P, int ncu, int nwg) {
+  if (dw_trunk_chunks(P, ncu) > nwg) {
+    fn::set_error("mlp_bwd: the trunk launch needs %d chunks per job, the partial regions hold %d (a device with fewer than 8 CUs?)",
+                  dw_trunk_chunks(P, ncu), nwg);
+    return -1;
+  }
+  return 0;
+}
+
+// (struct DwDeferred -- what a pass of the paired backward leaves undone: dw_pair.h)
+// reduce_all + unfold of one pass: the partials of every job into the flat gradient, then G = dL/dM into the two folded layers' gradients
+static int bwd_reduce(const RedTable& T, const NetLayout& L, int64_t P, const float* params, float* partial, float* grads, int64_t g_off,
+                      const int* live_cnt, int ncu, hipStream_t st) {
+  hipLaunchKernelGGL(reduce_all_kernel, dim3(256, T.n), dim3(256), 0, st, T, partial, grads, partial, P, live_cnt, ncu);   // (256 x 256 threads: one element of a 256 x 256 segment per lane)
+  FN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(unfold_kernel, dim3(385), dim3(256), 0, st, partial + g_off, params, grads, L.VW, L.VB, L.FW, L.FB);
+  FN_LAUNCH_CHECK();
+  return 0;
+}
+
 template <int MM>
 static int bwd_launch_t(int kind, int64_t n, int S, const float* draw, const float* act, const float* params,
                       const float* packed_bwd, float* dact, float* partial, float* grads, const int* live_idx,
-                      const int* live_cnt, fn_stream_t stream) {
+                      const int* live_cnt, fn_stream_t stream, DwDeferred* defer = nullptr) {
   constexpr int MW = MM;
   const NetLayout& L = layout_of(kind);
   const int PEP = L.pe_pad;
@@ -764,14 +816,15 @@ static int bwd_launch_t(int kind, int64_t n, int S, const float* draw, const flo
       J.pw[l - 1] = region(l);
       J.pb[l - 1] = region(l) + (int64_t)nwg * 256 * 256;
     }
-    constexpr int lds6 = 2 * 16 * 3 * 1024 + 128;
-    static bool attr_t = false;
-    if (!attr_t) {
-      FN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_bwd_dw6_trunk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds6));
-      attr_t = true;
+    if ((rc = trunk_chunks_fit(P, ncu, nwg))) return rc;
+    if (defer) {
+      defer->J = J;   // (the paired backward: one launch for both passes, fn::x6_pair_finish)
+    } else {
+      static bool attr_t[FN_MAX_DEV] = {};
+      if ((rc = trunk_lds_attr(mlp_bwd_dw6_trunk_kernel, attr_t, DW_TRUNK_LDS))) return rc;
+      hipLaunchKernelGGL(mlp_bwd_dw6_trunk_kernel, dim3(dw_trunk_chunks(P, ncu), DW_TRUNK_JOBS), dim3(512), DW_TRUNK_LDS, st, P, J, live_idx, live_cnt, ncu);
+      FN_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(mlp_bwd_dw6_trunk_kernel, dim3(dw_trunk_chunks(P, ncu), DW_TRUNK_JOBS), dim3(512), lds6, st, P, J, live_idx, live_cnt, ncu);
-    FN_LAUNCH_CHECK();
     for (int l = 1; l < 8; ++l) segs(l, L.LW[l] + (l == 5 ? L.in_pe : 0), l == 5 ? 256 + L.in_pe : 256, 256, L.LB[l], 0, 1);
   }
   // view layer on [h7 | vpe] (the folded feature / remap layer: mlp_pack.hip), with the alpha / sigma head as a rank-1 row over h7.
@@ -806,12 +859,113 @@ static int bwd_launch_t(int kind, int64_t n, int S, const float* draw, const flo
     add_seg(T, hb, 388, hg, 1, 388, L.RW, 388, 387);   // dWr (384) + dbr (3), contiguous in every layout
     add_seg(T, hb + 387, 388, hg, 1, 1, L.AB, 1, 1);   // dba
   }
-  hipLaunchKernelGGL(reduce_all_kernel, dim3(256, T.n), dim3(256), 0, st, T, partial, grads, partial, P, live_cnt, ncu);   // (256 x 256 threads: one element of a 256 x 256 segment per lane)
+  if (defer) {
+    defer->T = T; defer->P = P; defer->g_off = g_off; defer->params = params; defer->partial = partial; defer->grads = grads; defer->kind = kind;
+    return 0;
+  }
+  return bwd_reduce(T, L, P, params, partial, grads, g_off, live_cnt, ncu, st);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The paired bf16x6 backward (render.cpp rr_bwd: one call runs both passes of a two-net step on the saving route).  Order on the stream:
+//   fine pass:   dX, pe job, view job, head gradients      (x6_pair_pass: the caller's dact / partial workspaces)
+//   coarse pass: the same                                   (x6_pair_pass: the SIDE dact / partial set below)
+//   ONE trunk launch over the 14 jobs of both passes        (x6_pair_finish)
+//   reduce_all + unfold of the fine net, then of the coarse net
+// The fine pass's dact and partials must survive the coarse pass, so the coarse pass gets a second dact + partial set that the library owns:
+// one per (device, stream), grown on demand, reused every step, alive as long as the process (the precedent: the fold buffer of mlp_pack.hip).
+// Its size is dact of the coarse pass's points (9.7 KB per point) + one partial buffer: 2.55 GB + 0.63 GB at 4096 x 64 coarse points on a 256-CU part.
+// It is never allocated inside a stream capture, and a failed allocation is no error: x6_pair_workspace returns false (once per size: the refused size is remembered, one line goes to stderr) and the caller takes the
+// unpaired route -- the same kernels on the same data, bit-identical gradients.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace fn {
+struct PairWs {
+  float *dact = nullptr, *partial = nullptr;
+  int64_t dact_cap = 0, partial_cap = 0;
+  int64_t refused = 0;   // > 0: an allocation of this many floats failed -- requests that large are not tried again (no hipMalloc per step)
+};
+static std::mutex g_pair_mu;   // held for the whole of x6_pair_workspace: the map and every buffer in it
+static std::map<std::pair<int, hipStream_t>, PairWs> g_pair;
+static std::atomic<int64_t> g_pair_launches{0};
+
+static bool pair_grow(PairWs& w, float*& p, int64_t& cap, int64_t need) {
+  if (cap >= need) return true;
+  if (w.refused > 0 && need >= w.refused) return false;
+  // (another stream of the process may be in a global-mode capture, which forbids allocation calls from other threads: relaxed mode for this
+  // thread while it allocates, as allocators that live beside captures do)
+  hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
+  (void)hipThreadExchangeStreamCaptureMode(&mode);
+  if (p) (void)hipFree(p);   // (waits for the device: no launch that uses the old buffer is still running)
+  p = nullptr;
+  cap = 0;
+  const bool ok = hipMalloc(reinterpret_cast<void**>(&p), sizeof(float) * (size_t)need) == hipSuccess;
+  (void)hipThreadExchangeStreamCaptureMode(&mode);
+  if (!ok) {
+    (void)hipGetLastError();
+    p = nullptr;
+    w.refused = need;
+    fprintf(stderr, "fastnerf: no memory for the side workspace of the paired bf16x6 backward (%.2f GB): this stream keeps the per-pass trunk launches\n",
+            4e-9 * (double)need);
+    return false;
+  }
+  cap = need;
+  return true;
+}
+
+// the side dact / partial set of this (device, stream) for a coarse pass of P_coarse points; false: take the unpaired route
+bool x6_pair_workspace(int64_t P_coarse, fn_stream_t stream, float** dact2, float** partial2) {
+  hipStream_t st = S(stream);
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cs) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  if (cs != hipStreamCaptureStatusNone) return false;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return false;
+  std::lock_guard<std::mutex> lk(g_pair_mu);
+  PairWs& w = g_pair[{dev, st}];
+  if (!pair_grow(w, w.dact, w.dact_cap, P_coarse * (int64_t)DACT_FLOATS) ||
+      !pair_grow(w, w.partial, w.partial_cap, fastnerf_mlp_bwd_partial_floats()))
+    return false;
+  *dact2 = w.dact;
+  *partial2 = w.partial;
+  return true;
+}
+
+// everything of fastnerf_mlp_x6_bwd but the trunk launch, the reduction and the unfold, which it records in *d (the caller's, one per pass)
+int x6_pair_pass(DwDeferred* d, int64_t n, int S, const float* draw, const float* act, const float* params, const float* packed_bwd,
+                 float* dact, float* partial, float* grads, fn_stream_t stream) {
+  FN_CHECK_ARG(d && n > 0 && S >= 1, "d != NULL, n>0, S>=1");
+  FN_CHECK_ARG(draw && act && params && packed_bwd && dact && partial && grads, "null pointer");
+  return bwd_launch_t<MM_X6>(0, n, S, draw, act, params, packed_bwd, dact, partial, grads, nullptr, nullptr, stream, d);
+}
+
+// ONE trunk launch over both passes, then each net's reduction and unfold
+int x6_pair_finish(const DwDeferred* fine, const DwDeferred* coarse, fn_stream_t stream) {
+  hipStream_t st = S(stream);
+  const int ncu = num_cus();
+  const DwDeferred* d[2] = {fine, coarse};
+  DwTrunkPair A;
+  int nwg = 0;
+  for (int k = 0; k < 2; ++k) {
+    A.J[k] = d[k]->J;
+    A.P[k] = d[k]->P;
+    nwg += DW_TRUNK_JOBS * dw_trunk_chunks(A.P[k], ncu);   // (each count fits its regions: bwd_launch_t has checked)
+  }
+  static bool attr_p[FN_MAX_DEV] = {};
+  if (int rc = trunk_lds_attr(mlp_bwd_dw6_trunk_pair_kernel, attr_p, DW_TRUNK_LDS)) return rc;
+  hipLaunchKernelGGL(mlp_bwd_dw6_trunk_pair_kernel, dim3(nwg), dim3(512), DW_TRUNK_LDS, st, A, ncu);
   FN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(unfold_kernel, dim3(385), dim3(256), 0, st, partial + g_off, params, grads, L.VW, L.VB, L.FW, L.FB);
-  FN_LAUNCH_CHECK();
+  g_pair_launches.fetch_add(1, std::memory_order_relaxed);
+  for (int k = 0; k < 2; ++k)
+    if (int rc = bwd_reduce(d[k]->T, layout_of(d[k]->kind), d[k]->P, d[k]->params, d[k]->partial, d[k]->grads, d[k]->g_off, nullptr, ncu, st)) return rc;
   return 0;
 }
+}  // namespace fn
+// paired trunk launches this process has enqueued: tells a caller (and tests/test_gpu_trunk_pair.py) which route its backward took
+extern "C" int64_t fastnerf_x6_pair_launches(void) { return fn::g_pair_launches.load(std::memory_order_relaxed); }
+
 static int bwd_launch(int kind, int64_t n, int S, const float* draw, const float* act, const float* params,
                       const float* packed_bwd, float* dact, float* partial, float* grads, const int* live_idx,
                       const int* live_cnt, fn_stream_t stream, int mm = MM_F32) {

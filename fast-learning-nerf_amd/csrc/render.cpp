@@ -4,10 +4,18 @@
 // (rr_fwd_chain) and every MLP call goes through one table of entry points indexed by the math mode (modes[]).
 #include <stdint.h>
 #include "../../include/fastnerf.h"
+#include "dw_pair.h"
 
 namespace fn {
 void set_error(const char* fmt, ...);
 const char* occ_cascade_fault(const fn_occ_cascade* c);   // occupancy.hip
+// mlp_bwd_dw.hip, the paired bf16x6 backward: workspace -> the side dact / partial set of this (device, stream) for the coarse pass, or false (a stream
+// capture, no memory: take the unpaired route); pass -> everything of fastnerf_mlp_x6_bwd but the trunk launch, the reduction and the unfold, which
+// it records in *d; finish -> ONE trunk launch over both passes, then each net's reduction and unfold
+bool x6_pair_workspace(int64_t P_coarse, fn_stream_t stream, float** dact2, float** partial2);
+int x6_pair_pass(DwDeferred* d, int64_t n, int S, const float* draw, const float* act, const float* params, const float* packed_bwd,
+                 float* dact, float* partial, float* grads, fn_stream_t stream);
+int x6_pair_finish(const DwDeferred* fine, const DwDeferred* coarse, fn_stream_t stream);
 }
 
 // ---- the math modes: one row of MLP entry points per math_mode (0 exact fp32, 1 split-bf16 "bf16x3", 2 "bf16x6") -----------------
@@ -208,6 +216,7 @@ extern "C" int fastnerf_render_rays_fwd(int math_mode, int64_t n, int N_samples,
 // detached in the reference, so the coarse net only sees d(loss)/d(rgb0)): compositing backward -> MLP backward for the
 // fine pass (into grads_f) and the coarse pass (into grads_c).  draw_ws: n * (N_samples + N_importance) * 4 floats.
 // passes: bit 0 = the fine pass (N_importance > 0 only), bit 1 = the coarse pass (the only one when N_importance == 0)
+// dact_ws / partial_ws hold the LAST pass's values on return -- the coarse pass's, or the fine pass's after the paired backward (below)
 static int rr_bwd(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11,
                   int white_bkgd, const float* g_rgb, const float* g_rgb0, const float* noise0,
                   const float* noise1, const float* z0, const float* raw0, const float* act0,
@@ -234,6 +243,19 @@ static int rr_bwd(int math_mode, int64_t n, int N_samples, int N_importance, con
       return -1;
     }
     const int S1 = N_samples + N_importance;
+    // Both passes in this call, bf16x6: the paired backward.  The trunk dW jobs of the two passes (7 jobs of 256 x 256 each) go into ONE
+    // launch behind both passes' other kernels, so the coarse pass runs on a second dact / partial set of the library's (the fine pass's must
+    // survive it); draw_ws is shared as before: the trunk jobs do not read it.  Same kernels on the same data as the two passes below, in another
+    // order: bit-identical gradients.  Phase-split calls, the other math modes and N_importance == 0 never come here.
+    float *dact2 = nullptr, *partial2 = nullptr;
+    if (passes == 3 && math_mode == 2 && fn::x6_pair_workspace(n * (int64_t)N_samples, stream, &dact2, &partial2)) {
+      DwDeferred d_fine, d_coarse;   // (this call's own: nothing of a call outlives it but the workspace)
+      if ((rc = fastnerf_raw2outputs_bwd(n, S1, raw1, z1, rays11, noise1, white_bkgd, g_rgb, draw_ws, stream))) return rc;
+      if ((rc = fn::x6_pair_pass(&d_fine, n, S1, draw_ws, act1, params_f, packed_bwd_f, dact_ws, partial_ws, grads_f, stream))) return rc;
+      if ((rc = fastnerf_raw2outputs_bwd(n, N_samples, raw0, z0, rays11, noise0, white_bkgd, g_rgb0, draw_ws, stream))) return rc;
+      if ((rc = fn::x6_pair_pass(&d_coarse, n, N_samples, draw_ws, act0, params_c, packed_bwd_c, dact2, partial2, grads_c, stream))) return rc;
+      return fn::x6_pair_finish(&d_fine, &d_coarse, stream);
+    }
     if (passes & 1) {
       if ((rc = fastnerf_raw2outputs_bwd(n, S1, raw1, z1, rays11, noise1, white_bkgd, g_rgb, draw_ws, stream))) return rc;
       if ((rc = mlp(S1, act1, params_f, packed_bwd_f, grads_f))) return rc;
@@ -332,7 +354,8 @@ extern "C" int fastnerf_render_rays_bwd_live(int math_mode, int64_t n, int N_sam
 // optimizer.step(); the leaf-error table of :505-506 is fed inside the loss launch) enqueued by ONE call -- or by one call
 // per phase when the caller interleaves its gradient all-reduce (data parallel: the fine net's gradient is final after
 // FN_STEP_BWD_FINE and travels while FN_STEP_BWD_COARSE runs).  Exactly the launches the entry points above make, in the same
-// order, on the caller's stream: results are bit-identical to calling them one by one.
+// order, on the caller's stream: results are bit-identical to calling them one by one.  (One exception to "the same order", not to the
+// results: a call with both backward phases in bf16x6 runs the paired backward of rr_bwd -- one trunk dW launch for both passes.)
 // ---------------------------------------------------------------------------------------------------------------------
 extern "C" int64_t fastnerf_step_args_size(void) { return (int64_t)sizeof(fn_step_args); }
 

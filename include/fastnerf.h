@@ -30,6 +30,9 @@ int fastnerf_version(void);
 const char* fastnerf_last_error(void);
 /* device properties used by bench/tests: returns CU count (or <0) */
 int fastnerf_device_cus(void);
+/* paired dW trunk launches (one launch for the trunk jobs of both passes of a bf16x6 step) this process has enqueued so far:
+ * tells which route a backward took; the unpaired route computes the same gradients */
+int64_t fastnerf_x6_pair_launches(void);
 
 /* ---- rays ------------------------------------------------------------- */
 /* get_rays (run_nerf_helpers.py:68-78): all H*W pixels of one camera.
