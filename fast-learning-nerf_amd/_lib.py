@@ -35,6 +35,18 @@ class StepArgs(C.Structure):
         + [('occ', P), ('occ_counts', P)])
 
 
+class MapGrads(C.Structure):
+    """fn_map_grads of include/fastnerf.h, field for field."""
+    _fields_ = [(k, P) for k in ('g_disp1', 'g_acc1', 'g_depth1', 'g_disp0', 'g_acc0', 'g_depth0')]
+
+
+class StepAux(C.Structure):
+    """fn_step_aux of include/fastnerf.h, field for field."""
+    _fields_ = ([(k, P) for k in ('depth_target', 'depth_weight', 'acc_target', 'acc_weight', 'g_depth1', 'g_acc1', 'g_depth0',
+                                  'g_acc0', 'loss4')]
+                + [('lambda_depth', F), ('lambda_acc', F)])
+
+
 class OccGrid(C.Structure):
     """fn_occ_grid of include/fastnerf.h, field for field."""
     _fields_ = [('words', P), ('lo', F * 3), ('inv', F * 3), ('n', C.c_int32 * 3), ('outside_occupied', C.c_int32)]
@@ -72,6 +84,7 @@ SIGNATURES = {
     'fastnerf_sample_pdf_merge': (I, [L, I, I, P, P, I, P, U64, P, P, P, P]),
     'fastnerf_sample_pdf': (I, [L, I, I, P, P, I, P, U64, P, P]),
     'fastnerf_mse_leafmax': (I, [L, P, P, P, F, P, P, P, P, I, P, P]),
+    'fastnerf_aux_loss': (I, [L] + [P] * 8 + [F, F, F] + [P] * 5 + [P]),
     'fastnerf_adam_step': (I, [L, P, P, P, P, D, D, D, D, I, P]),
     'fastnerf_net_floats': (L, [I, I]),
     'fastnerf_mlp_act_floats': (L, [I, L]),
@@ -88,6 +101,7 @@ SIGNATURES = {
     'fastnerf_mlp_bf16_fwd_flags': (I, [I, L, I, P, P, P, P, P, I, P]),
     'fastnerf_mlp_fwd_flags_ex': (I, [I, L, I, P, P, P, P, P, I, P]),
     'fastnerf_render_rays_bwd': (I, [I, L, I, I, P, I] + [P] * 20),
+    'fastnerf_render_rays_bwd_maps': (I, [I, L, I, I, P, I] + [P] * 19 + [P] * 4 + [C.POINTER(MapGrads), P]),
     'fastnerf_pp_intersect_sphere': (I, [L, P, P, P, P]),
     'fastnerf_pp_fg_depths': (I, [L, I, F, P, I, P, U64, P, P]),
     'fastnerf_pp_sample_pdf_merge': (I, [L, I, I, P, P, I, P, U64, P, P, P]),
@@ -120,6 +134,7 @@ SIGNATURES = {
     'fastnerf_mlp_fwd_live_ex': (I, [I, L, I, P, P, P, P, P, P, P, P]),
     'fastnerf_mlp_bwd_live_ex': (I, [I, L, I, P, P, P, P, P, P, P, P, P, P]),
     'fastnerf_render_rays_bwd_live': (I, [I, L, I, I, P, I] + [P] * 22 + [P]),
+    'fastnerf_render_rays_bwd_live_maps': (I, [I, L, I, I, P, I] + [P] * 22 + [P] * 4 + [C.POINTER(MapGrads), P]),
     'fastnerf_mlp_x6_packed_floats': (L, [I, I]),
     'fastnerf_mlp_x6_pack': (I, [I, P, P, P, P]),
     'fastnerf_mlp_fold_buffer': (P, [P]),
@@ -130,6 +145,8 @@ SIGNATURES = {
     'fastnerf_mlp_x6_bwd_live': (I, [I, L, I, P, P, P, P, P, P, P, P, P, P]),
     'fastnerf_step_args_size': (L, []),
     'fastnerf_train_step': (I, [C.POINTER(StepArgs), I, P]),
+    'fastnerf_step_aux_size': (L, []),
+    'fastnerf_train_step_aux': (I, [C.POINTER(StepArgs), C.POINTER(StepAux), I, P]),
     'fastnerf_comm_unique_id': (I, [C.c_char_p]),
     'fastnerf_comm_init': (I, [C.POINTER(P), C.c_char_p, I, I]),
     'fastnerf_comm_destroy': (I, [P]),
@@ -182,6 +199,8 @@ def lib():
             fn.argtypes = args
         if l.fastnerf_step_args_size() != C.sizeof(StepArgs):
             raise RuntimeError('fn_step_args: the ctypes mirror does not match the library (stale libfastnerf.so?)')
+        if l.fastnerf_step_aux_size() != C.sizeof(StepAux):
+            raise RuntimeError('fn_step_aux: the ctypes mirror does not match the library (stale libfastnerf.so?)')
         _lib = l
     return _lib
 

@@ -217,12 +217,34 @@ extern "C" int fastnerf_render_rays_fwd(int math_mode, int64_t n, int N_samples,
 // fine pass (into grads_f) and the coarse pass (into grads_c).  draw_ws: n * (N_samples + N_importance) * 4 floats.
 // passes: bit 0 = the fine pass (N_importance > 0 only), bit 1 = the coarse pass (the only one when N_importance == 0)
 // dact_ws / partial_ws hold the LAST pass's values on return -- the coarse pass's, or the fine pass's after the paired backward (below)
+//
+// Map gradients (fn_map_grads: every map of render.py:149-192 differentiable, as under the reference's autograd): what one pass's
+// compositing backward gets beside g_rgb.  A pass without any makes exactly the fastnerf_raw2outputs_bwd call it always made; a pass
+// with one goes through fastnerf_raw2outputs_bwd_full (g_rgb may then be NULL), at every site, the paired one included -- the trunk
+// jobs never read draw, so pairing is untouched.
+struct PassMaps {
+  const float *acc, *depth, *g_disp, *g_acc, *g_depth;
+  bool any() const { return g_disp || g_acc || g_depth; }
+};
+// pass 1 = the pass that produces the image (the only pass when N_importance == 0, where it runs on the coarse buffers), 0 = the coarse pass
+static PassMaps pass_maps(const fn_map_grads* m, int pass, const float* acc, const float* depth) {
+  if (!m) return {acc, depth, nullptr, nullptr, nullptr};
+  return pass ? PassMaps{acc, depth, m->g_disp1, m->g_acc1, m->g_depth1} : PassMaps{acc, depth, m->g_disp0, m->g_acc0, m->g_depth0};
+}
+static int comp_bwd(int64_t n, int S, const float* raw, const float* z, const float* rays11, const float* noise, int white_bkgd,
+                    const float* g_rgb, const PassMaps& m, float* draw, fn_stream_t stream) {
+  if (!m.any()) return fastnerf_raw2outputs_bwd(n, S, raw, z, rays11, noise, white_bkgd, g_rgb, draw, stream);
+  return fastnerf_raw2outputs_bwd_full(n, S, raw, z, rays11, noise, white_bkgd, m.acc, m.depth, g_rgb, m.g_disp, m.g_acc, nullptr,
+                                       m.g_depth, draw, stream);
+}
+
 static int rr_bwd(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11,
                   int white_bkgd, const float* g_rgb, const float* g_rgb0, const float* noise0,
                   const float* noise1, const float* z0, const float* raw0, const float* act0,
                   const float* z1, const float* raw1, const float* act1, const float* params_c,
                   const float* packed_bwd_c, const float* params_f, const float* packed_bwd_f,
                   float* draw_ws, float* dact_ws, float* partial_ws, float* grads_c, float* grads_f,
+                  const float* acc0, const float* depth0, const float* acc1, const float* depth1, const fn_map_grads* mg,
                   int passes, fn_stream_t stream) {
   if (math_mode < 0 || math_mode > 2 || n <= 0 || N_samples < 2 || N_importance < 0) {
     fn::set_error("fastnerf_render_rays_bwd: bad argument: math_mode in {0,1,2}, n>0, N_samples>=2, N_importance>=0");
@@ -237,9 +259,17 @@ static int rr_bwd(int math_mode, int64_t n, int N_samples, int N_importance, con
     return modes[math_mode].bwd(0, n, S, draw_ws, act, params, packed, dact_ws, partial_ws, grads, stream);
   };
   const float* g_coarse = g_rgb;
+  // the coarse buffers carry the image pass when there is one pass only: its map gradients are the *1 members then
+  PassMaps m_coarse = pass_maps(mg, 1, acc0, depth0);
   if (N_importance > 0) {
-    if (!g_rgb || !g_rgb0 || !z1 || !raw1 || !act1 || !params_f || !packed_bwd_f || !grads_f) {
+    const PassMaps m_fine = pass_maps(mg, 1, acc1, depth1);
+    m_coarse = pass_maps(mg, 0, acc0, depth0);
+    if ((!g_rgb && !m_fine.any()) || (!g_rgb0 && !m_coarse.any()) || !z1 || !raw1 || !act1 || !params_f || !packed_bwd_f || !grads_f) {
       fn::set_error("fastnerf_render_rays_bwd: null pointer (fine pass)");
+      return -1;
+    }
+    if ((m_fine.g_disp && (!acc1 || !depth1)) || (m_coarse.g_disp && (!acc0 || !depth0))) {
+      fn::set_error("fastnerf_render_rays_bwd: a disparity gradient needs the forward's acc and depth of its pass");
       return -1;
     }
     const int S1 = N_samples + N_importance;
@@ -250,24 +280,28 @@ static int rr_bwd(int math_mode, int64_t n, int N_samples, int N_importance, con
     float *dact2 = nullptr, *partial2 = nullptr;
     if (passes == 3 && math_mode == 2 && fn::x6_pair_workspace(n * (int64_t)N_samples, stream, &dact2, &partial2)) {
       DwDeferred d_fine, d_coarse;   // (this call's own: nothing of a call outlives it but the workspace)
-      if ((rc = fastnerf_raw2outputs_bwd(n, S1, raw1, z1, rays11, noise1, white_bkgd, g_rgb, draw_ws, stream))) return rc;
+      if ((rc = comp_bwd(n, S1, raw1, z1, rays11, noise1, white_bkgd, g_rgb, m_fine, draw_ws, stream))) return rc;
       if ((rc = fn::x6_pair_pass(&d_fine, n, S1, draw_ws, act1, params_f, packed_bwd_f, dact_ws, partial_ws, grads_f, stream))) return rc;
-      if ((rc = fastnerf_raw2outputs_bwd(n, N_samples, raw0, z0, rays11, noise0, white_bkgd, g_rgb0, draw_ws, stream))) return rc;
+      if ((rc = comp_bwd(n, N_samples, raw0, z0, rays11, noise0, white_bkgd, g_rgb0, m_coarse, draw_ws, stream))) return rc;
       if ((rc = fn::x6_pair_pass(&d_coarse, n, N_samples, draw_ws, act0, params_c, packed_bwd_c, dact2, partial2, grads_c, stream))) return rc;
       return fn::x6_pair_finish(&d_fine, &d_coarse, stream);
     }
     if (passes & 1) {
-      if ((rc = fastnerf_raw2outputs_bwd(n, S1, raw1, z1, rays11, noise1, white_bkgd, g_rgb, draw_ws, stream))) return rc;
+      if ((rc = comp_bwd(n, S1, raw1, z1, rays11, noise1, white_bkgd, g_rgb, m_fine, draw_ws, stream))) return rc;
       if ((rc = mlp(S1, act1, params_f, packed_bwd_f, grads_f))) return rc;
     }
     g_coarse = g_rgb0;
   }
-  if (!g_coarse) {
+  if (!g_coarse && !m_coarse.any()) {
     fn::set_error("fastnerf_render_rays_bwd: null gradient");
     return -1;
   }
+  if (m_coarse.g_disp && (!acc0 || !depth0)) {
+    fn::set_error("fastnerf_render_rays_bwd: a disparity gradient needs the forward's acc and depth of its pass");
+    return -1;
+  }
   if (!(passes & 2)) return 0;
-  if ((rc = fastnerf_raw2outputs_bwd(n, N_samples, raw0, z0, rays11, noise0, white_bkgd, g_coarse, draw_ws, stream))) return rc;
+  if ((rc = comp_bwd(n, N_samples, raw0, z0, rays11, noise0, white_bkgd, g_coarse, m_coarse, draw_ws, stream))) return rc;
   return mlp(N_samples, act0, params_c, packed_bwd_c, grads_c);
 }
 
@@ -279,7 +313,21 @@ extern "C" int fastnerf_render_rays_bwd(int math_mode, int64_t n, int N_samples,
                                         float* draw_ws, float* dact_ws, float* partial_ws, float* grads_c, float* grads_f,
                                         fn_stream_t stream) {
   return rr_bwd(math_mode, n, N_samples, N_importance, rays11, white_bkgd, g_rgb, g_rgb0, noise0, noise1, z0, raw0, act0, z1, raw1,
-                act1, params_c, packed_bwd_c, params_f, packed_bwd_f, draw_ws, dact_ws, partial_ws, grads_c, grads_f, 3, stream);
+                act1, params_c, packed_bwd_c, params_f, packed_bwd_f, draw_ws, dact_ws, partial_ws, grads_c, grads_f, nullptr, nullptr,
+                nullptr, nullptr, nullptr, 3, stream);
+}
+
+extern "C" int fastnerf_render_rays_bwd_maps(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11,
+                                             int white_bkgd, const float* g_rgb, const float* g_rgb0, const float* noise0,
+                                             const float* noise1, const float* z0, const float* raw0, const float* act0,
+                                             const float* z1, const float* raw1, const float* act1, const float* params_c,
+                                             const float* packed_bwd_c, const float* params_f, const float* packed_bwd_f,
+                                             float* draw_ws, float* dact_ws, float* partial_ws, float* grads_c, float* grads_f,
+                                             const float* acc0, const float* depth0, const float* acc1, const float* depth1,
+                                             const fn_map_grads* maps, fn_stream_t stream) {
+  return rr_bwd(math_mode, n, N_samples, N_importance, rays11, white_bkgd, g_rgb, g_rgb0, noise0, noise1, z0, raw0, act0, z1, raw1,
+                act1, params_c, packed_bwd_c, params_f, packed_bwd_f, draw_ws, dact_ws, partial_ws, grads_c, grads_f, acc0, depth0,
+                acc1, depth1, maps, 3, stream);
 }
 
 
@@ -295,7 +343,8 @@ static int rr_bwd_live(int math_mode, int64_t n, int N_samples, int N_importance
                        const float* params_c, const float* packed_fwd_c, const float* packed_bwd_c,
                        const float* params_f, const float* packed_fwd_f, const float* packed_bwd_f,
                        float* draw_ws, float* act_ws, float* dact_ws, float* partial_ws, int32_t* live_ws,
-                       float* grads_c, float* grads_f, int32_t* counts_out, int passes, fn_stream_t stream) {
+                       float* grads_c, float* grads_f, int32_t* counts_out, const float* acc0, const float* depth0,
+                       const float* acc1, const float* depth1, const fn_map_grads* mg, int passes, fn_stream_t stream) {
   if (math_mode < 0 || math_mode > 2 || n <= 0 || N_samples < 2 || N_importance < 0) {
     fn::set_error("fastnerf_render_rays_bwd_live: bad argument: math_mode in {0,1,2}, n>0, N_samples>=2, N_importance>=0");
     return -1;
@@ -310,9 +359,13 @@ static int rr_bwd_live(int math_mode, int64_t n, int N_samples, int N_importance
   int32_t* idx = live_ws + 4;
   int32_t* cws = idx + n * (int64_t)S1;
   int rc;
-  auto pass = [&](int S, const float* z, const float* raw, const float* noise, const float* g, const float* params,
+  auto pass = [&](int S, const float* z, const float* raw, const float* noise, const float* g, const PassMaps& m, const float* params,
                   const float* pf, const float* pb, float* grads, int32_t* cnt_out) -> int {
-    if ((rc = fastnerf_raw2outputs_bwd(n, S, raw, z, rays11, noise, white_bkgd, g, draw_ws, stream))) return rc;
+    if (m.g_disp && (!m.acc || !m.depth)) {
+      fn::set_error("fastnerf_render_rays_bwd_live: a disparity gradient needs the forward's acc and depth of its pass");
+      return -1;
+    }
+    if ((rc = comp_bwd(n, S, raw, z, rays11, noise, white_bkgd, g, m, draw_ws, stream))) return rc;
     if ((rc = fastnerf_compact_live(n * (int64_t)S, draw_ws, idx, cnt_out, cws, stream))) return rc;
     if ((rc = modes[math_mode].fwd_live(0, n, S, rays11, z, params, pf, act_ws, idx, cnt_out, stream))) return rc;
     return modes[math_mode].bwd_live(0, n, S, draw_ws, act_ws, params, pb, dact_ws, partial_ws, grads, idx, cnt_out, stream);
@@ -320,20 +373,25 @@ static int rr_bwd_live(int math_mode, int64_t n, int N_samples, int N_importance
   const float* g_coarse = g_rgb;
   int32_t* c_fine = counts_out ? counts_out : cnt;
   int32_t* c_coarse = counts_out ? counts_out + 2 : cnt + 2;
+  PassMaps m_coarse = pass_maps(mg, 1, acc0, depth0);      // (one pass: the *1 members, see rr_bwd)
   if (N_importance > 0) {
-    if (!g_rgb || !g_rgb0 || !z1 || !raw1 || !params_f || !packed_fwd_f || !packed_bwd_f || !grads_f) {
+    const PassMaps m_fine = pass_maps(mg, 1, acc1, depth1);
+    m_coarse = pass_maps(mg, 0, acc0, depth0);
+    if ((!g_rgb && !m_fine.any()) || (!g_rgb0 && !m_coarse.any()) || !z1 || !raw1 || !params_f || !packed_fwd_f || !packed_bwd_f ||
+        !grads_f) {
       fn::set_error("fastnerf_render_rays_bwd_live: null pointer (fine pass)");
       return -1;
     }
-    if ((passes & 1) && (rc = pass(S1, z1, raw1, noise1, g_rgb, params_f, packed_fwd_f, packed_bwd_f, grads_f, c_fine))) return rc;
+    if ((passes & 1) && (rc = pass(S1, z1, raw1, noise1, g_rgb, m_fine, params_f, packed_fwd_f, packed_bwd_f, grads_f, c_fine)))
+      return rc;
     g_coarse = g_rgb0;
   }
-  if (!g_coarse) {
+  if (!g_coarse && !m_coarse.any()) {
     fn::set_error("fastnerf_render_rays_bwd_live: null gradient");
     return -1;
   }
   if (!(passes & 2)) return 0;
-  return pass(N_samples, z0, raw0, noise0, g_coarse, params_c, packed_fwd_c, packed_bwd_c, grads_c, c_coarse);
+  return pass(N_samples, z0, raw0, noise0, g_coarse, m_coarse, params_c, packed_fwd_c, packed_bwd_c, grads_c, c_coarse);
 }
 
 extern "C" int fastnerf_render_rays_bwd_live(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11, int white_bkgd,
@@ -345,7 +403,21 @@ extern "C" int fastnerf_render_rays_bwd_live(int math_mode, int64_t n, int N_sam
                                              float* grads_c, float* grads_f, int32_t* counts_out, fn_stream_t stream) {
   return rr_bwd_live(math_mode, n, N_samples, N_importance, rays11, white_bkgd, g_rgb, g_rgb0, noise0, noise1, z0, raw0, z1, raw1,
                      params_c, packed_fwd_c, packed_bwd_c, params_f, packed_fwd_f, packed_bwd_f, draw_ws, act_ws, dact_ws,
-                     partial_ws, live_ws, grads_c, grads_f, counts_out, 3, stream);
+                     partial_ws, live_ws, grads_c, grads_f, counts_out, nullptr, nullptr, nullptr, nullptr, nullptr, 3, stream);
+}
+
+extern "C" int fastnerf_render_rays_bwd_live_maps(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11,
+                                                  int white_bkgd, const float* g_rgb, const float* g_rgb0, const float* noise0,
+                                                  const float* noise1, const float* z0, const float* raw0, const float* z1,
+                                                  const float* raw1, const float* params_c, const float* packed_fwd_c,
+                                                  const float* packed_bwd_c, const float* params_f, const float* packed_fwd_f,
+                                                  const float* packed_bwd_f, float* draw_ws, float* act_ws, float* dact_ws,
+                                                  float* partial_ws, int32_t* live_ws, float* grads_c, float* grads_f,
+                                                  int32_t* counts_out, const float* acc0, const float* depth0, const float* acc1,
+                                                  const float* depth1, const fn_map_grads* maps, fn_stream_t stream) {
+  return rr_bwd_live(math_mode, n, N_samples, N_importance, rays11, white_bkgd, g_rgb, g_rgb0, noise0, noise1, z0, raw0, z1, raw1,
+                     params_c, packed_fwd_c, packed_bwd_c, params_f, packed_fwd_f, packed_bwd_f, draw_ws, act_ws, dact_ws,
+                     partial_ws, live_ws, grads_c, grads_f, counts_out, acc0, depth0, acc1, depth1, maps, 3, stream);
 }
 
 
@@ -359,7 +431,11 @@ extern "C" int fastnerf_render_rays_bwd_live(int math_mode, int64_t n, int N_sam
 // ---------------------------------------------------------------------------------------------------------------------
 extern "C" int64_t fastnerf_step_args_size(void) { return (int64_t)sizeof(fn_step_args); }
 
-extern "C" int fastnerf_train_step(const fn_step_args* a, int phases, fn_stream_t stream) {
+extern "C" int64_t fastnerf_step_aux_size(void) { return (int64_t)sizeof(fn_step_aux); }
+
+// aux: NULL, or the depth / opacity terms (a term is on when its target is set)
+static int train_step(const fn_step_args* a, const fn_step_aux* aux, int phases, fn_stream_t stream) {
+  if (aux && !aux->depth_target && !aux->acc_target) aux = nullptr;
   if (!a || a->math_mode < 0 || a->math_mode > 2 || a->n <= 0 || a->N_samples < 2 || a->N_importance < 0) {
     fn::set_error("fastnerf_train_step: bad argument: args != NULL, math_mode in {0,1,2}, n>0, N_samples>=2, N_importance>=0");
     return -1;
@@ -420,20 +496,35 @@ extern "C" int fastnerf_train_step(const fn_step_args* a, int phases, fn_stream_
     if ((rc = fastnerf_mse_leafmax(a->n, two ? a->rgb1 : a->rgb0, two ? a->rgb0 : nullptr, a->target, a->grad_scale, a->g_rgb,
                                    two ? a->g_rgb0 : nullptr, a->loss2, a->leaf_tag, a->max_leaves, a->table, stream)))
       return rc;
+    if (aux && (rc = fastnerf_aux_loss(a->n, two ? a->depth1 : a->depth0, two ? a->acc1 : a->acc0, two ? a->depth0 : nullptr,
+                                       two ? a->acc0 : nullptr, aux->depth_target, aux->depth_weight, aux->acc_target,
+                                       aux->acc_weight, aux->lambda_depth, aux->lambda_acc, a->grad_scale, aux->g_depth1,
+                                       aux->g_acc1, two ? aux->g_depth0 : nullptr, two ? aux->g_acc0 : nullptr, aux->loss4, stream)))
+      return rc;
   }
   const int passes = ((phases & FN_STEP_BWD_FINE) ? 1 : 0) | ((phases & FN_STEP_BWD_COARSE) ? 2 : 0);
   if (passes) {
     const float* g_a = two ? g_fine : a->g_rgb;
     const float* g_b = two ? a->g_rgb0 : nullptr;
+    fn_map_grads mg = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (aux) {
+      if ((aux->depth_target && (!aux->g_depth1 || (two && !aux->g_depth0))) || (aux->acc_target && (!aux->g_acc1 || (two && !aux->g_acc0)))) {
+        fn::set_error("fastnerf_train_step_aux: null gradient buffer of a term whose target is set");
+        return -1;
+      }
+      if (aux->depth_target) { mg.g_depth1 = aux->g_depth1; mg.g_depth0 = two ? aux->g_depth0 : nullptr; }
+      if (aux->acc_target) { mg.g_acc1 = aux->g_acc1; mg.g_acc0 = two ? aux->g_acc0 : nullptr; }
+    }
+    const fn_map_grads* mgp = aux ? &mg : nullptr;
     if (a->live)
       rc = rr_bwd_live(a->math_mode, a->n, a->N_samples, a->N_importance, a->rays11, a->white_bkgd, g_a, g_b, a->noise0, a->noise1,
                        a->z0, a->raw0, a->z1, a->raw1, params_c, a->packed_fwd_c, a->packed_bwd_c, params_f, a->packed_fwd_f,
                        a->packed_bwd_f, a->draw_ws, a->act_ws, a->dact_ws, a->partial_ws, a->live_ws, grads_c, grads_f, a->counts,
-                       passes, stream);
+                       a->acc0, a->depth0, a->acc1, a->depth1, mgp, passes, stream);
     else
       rc = rr_bwd(a->math_mode, a->n, a->N_samples, a->N_importance, a->rays11, a->white_bkgd, g_a, g_b, a->noise0, a->noise1, a->z0,
                   a->raw0, a->act0, a->z1, a->raw1, a->act1, params_c, a->packed_bwd_c, params_f, a->packed_bwd_f, a->draw_ws,
-                  a->dact_ws, a->partial_ws, grads_c, grads_f, passes, stream);
+                  a->dact_ws, a->partial_ws, grads_c, grads_f, a->acc0, a->depth0, a->acc1, a->depth1, mgp, passes, stream);
     if (rc) return rc;
   }
   if (phases & FN_STEP_UPDATE) {
@@ -448,4 +539,10 @@ extern "C" int fastnerf_train_step(const fn_step_args* a, int phases, fn_stream_
     if (two && (rc = modes[a->math_mode].pack(0, params_f, a->packed_fwd_f, a->packed_bwd_f, stream))) return rc;
   }
   return 0;
+}
+
+extern "C" int fastnerf_train_step(const fn_step_args* a, int phases, fn_stream_t stream) { return train_step(a, nullptr, phases, stream); }
+
+extern "C" int fastnerf_train_step_aux(const fn_step_args* a, const fn_step_aux* aux, int phases, fn_stream_t stream) {
+  return train_step(a, aux, phases, stream);
 }

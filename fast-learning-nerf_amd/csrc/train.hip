@@ -66,6 +66,71 @@ __global__ void __launch_bounds__(MSE_THREADS) mse_leafmax_kernel(int64_t n, con
   }
 }
 
+// ---- auxiliary losses on the depth / opacity maps (fastnerf_aux_loss; the maps of render.py:149-192 under a loss the reference
+// would add in run_nerf.py:479-494) --------------------------------------------------------------------------------------------
+// ONE workgroup for every n (a batch is a few kB per map): a thread sums its rays i = tid, tid + 1024, ... in ascending order in
+// fp64, then the fixed butterfly of block_sum -- no atomics, two calls are bit-identical.  fp64 because the terms are cheap and
+// the sums then carry one fp32 rounding (the final store) instead of one per term; the gradient likewise: the difference and the
+// products are exact or 2^-53 in fp64, one rounding on the store.
+__device__ __forceinline__ double block_sum_d(double v, double* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (lane == 0) red[w] = v;
+  __syncthreads();
+  double t = (threadIdx.x < MSE_THREADS / 64) ? red[threadIdx.x] : 0.0;
+  if (w == 0) {
+#pragma unroll
+    for (int o = 1; o < MSE_THREADS / 64; o <<= 1) t += __shfl_xor(t, o, 64);
+  }
+  __syncthreads();
+  return t;  // valid in thread 0
+}
+
+// one ray of one term of one pass: stores its gradient, returns its w (x - t)^2.  SELECT, do not multiply: a weight of 0 gives
+// exactly 0 and +0 whatever x - t is (a NaN target marks "unknown" in sparse depth)
+__device__ __forceinline__ double aux_term(float w, float t, float x, double coef, float* __restrict__ g, int64_t i) {
+  if (w == 0.0f) {
+    if (g) g[i] = 0.0f;
+    return 0.0;
+  }
+  const double d = (double)x - (double)t;
+  const double wd = (double)w * d;
+  if (g) g[i] = (float)(coef * wd);
+  return wd * d;
+}
+
+__global__ void __launch_bounds__(MSE_THREADS) aux_loss_kernel(
+    int64_t n, const float* __restrict__ depth1, const float* __restrict__ acc1, const float* __restrict__ depth0,
+    const float* __restrict__ acc0, const float* __restrict__ dt, const float* __restrict__ dw, const float* __restrict__ at,
+    const float* __restrict__ aw, double coef_d, double coef_a, double inv_n, float* __restrict__ g_depth1,
+    float* __restrict__ g_acc1, float* __restrict__ g_depth0, float* __restrict__ g_acc0, float* __restrict__ loss4) {
+  __shared__ double red[MSE_THREADS / 64];
+  double sd1 = 0.0, sd0 = 0.0, sa1 = 0.0, sa0 = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += MSE_THREADS) {
+    if (dt) {
+      const float w = dw ? dw[i] : 1.0f, t = dt[i];
+      sd1 += aux_term(w, t, depth1[i], coef_d, g_depth1, i);
+      if (depth0) sd0 += aux_term(w, t, depth0[i], coef_d, g_depth0, i);
+    }
+    if (at) {
+      const float w = aw ? aw[i] : 1.0f, t = at[i];
+      sa1 += aux_term(w, t, acc1[i], coef_a, g_acc1, i);
+      if (acc0) sa0 += aux_term(w, t, acc0[i], coef_a, g_acc0, i);
+    }
+  }
+  sd1 = block_sum_d(sd1, red);
+  sd0 = block_sum_d(sd0, red);
+  sa1 = block_sum_d(sa1, red);
+  sa0 = block_sum_d(sa0, red);
+  if (threadIdx.x == 0 && loss4) {
+    loss4[0] = (float)(sd1 * inv_n);
+    loss4[1] = (float)(sd0 * inv_n);
+    loss4[2] = (float)(sa1 * inv_n);
+    loss4[3] = (float)(sa0 * inv_n);
+  }
+}
+
 __global__ void __launch_bounds__(256) adam_kernel(int64_t n4, int64_t n, float* __restrict__ p,
                                                     const float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, float b1, float b2, float omb1,
@@ -114,6 +179,22 @@ extern "C" int fastnerf_mse_leafmax(int64_t n, const float* rgb, const float* rg
   const float gscale = (float)(2.0 / (3.0 * (double)n) * (double)grad_scale);
   hipLaunchKernelGGL(mse_leafmax_kernel, dim3((int)g), dim3(MSE_THREADS), 0, fn::S(stream), n, rgb, rgb0, target, gscale,
                      inv_count, g_rgb, g_rgb0, loss2, leaf_tag, max_leaves, table);
+  FN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fastnerf_aux_loss(int64_t n, const float* depth1, const float* acc1, const float* depth0, const float* acc0,
+                                 const float* depth_target, const float* depth_weight, const float* acc_target,
+                                 const float* acc_weight, float lambda_depth, float lambda_acc, float grad_scale, float* g_depth1,
+                                 float* g_acc1, float* g_depth0, float* g_acc0, float* loss4, fn_stream_t stream) {
+  FN_CHECK_ARG(n > 0, "n>0");
+  FN_CHECK_ARG(!depth_target || depth1, "a depth target needs depth1");
+  FN_CHECK_ARG(!acc_target || acc1, "an opacity target needs acc1");
+  const double inv_n = 1.0 / (double)n;
+  const double coef_d = (double)grad_scale * (double)lambda_depth * 2.0 * inv_n;
+  const double coef_a = (double)grad_scale * (double)lambda_acc * 2.0 * inv_n;
+  hipLaunchKernelGGL(aux_loss_kernel, dim3(1), dim3(MSE_THREADS), 0, fn::S(stream), n, depth1, acc1, depth0, acc0, depth_target,
+                     depth_weight, acc_target, acc_weight, coef_d, coef_a, inv_n, g_depth1, g_acc1, g_depth0, g_acc0, loss4);
   FN_LAUNCH_CHECK();
   return 0;
 }

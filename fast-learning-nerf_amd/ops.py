@@ -2,6 +2,7 @@
 
 PyTorch is plumbing here: it owns device memory and the stream; every op calls
 straight into libfastnerf.so with raw pointers.  No op has a CPU fallback."""
+import ctypes
 import os
 import weakref
 
@@ -407,9 +408,31 @@ def render_rays_fwd(rays11, params_c, packed_c, params_f, packed_f, N_samples, N
     return o
 
 
+MAP_GRAD_KEYS = ('g_disp1', 'g_acc1', 'g_depth1', 'g_disp0', 'g_acc0', 'g_depth0')
+
+
+def _map_grads(map_grads, n):
+    """map_grads of render_rays_bwd / _bwd_live -> (None, []) when no map gradient is set (the plain entry point is called, as
+    ever), else ([acc0, depth0, acc1, depth1 pointers, byref(fn_map_grads)], tensors to keep alive over the call)."""
+    if not map_grads or all(map_grads.get(k) is None for k in MAP_GRAD_KEYS):
+        return None, []
+    unknown = set(map_grads) - set(MAP_GRAD_KEYS) - {'acc0', 'depth0', 'acc1', 'depth1'}
+    assert not unknown, unknown
+    keep = {k: (None if map_grads.get(k) is None else _f32(map_grads[k]))
+            for k in MAP_GRAD_KEYS + ('acc0', 'depth0', 'acc1', 'depth1')}
+    require_gpu(*keep.values())
+    for k, t in keep.items():
+        assert t is None or t.numel() == n, (k, tuple(t.shape))
+    mg = _lib.MapGrads(**{k: ptr(keep[k]) for k in MAP_GRAD_KEYS})
+    return [ptr(keep['acc0']), ptr(keep['depth0']), ptr(keep['acc1']), ptr(keep['depth1']), ctypes.byref(mg)], [keep, mg]
+
+
 def render_rays_bwd(rays11, white_bkgd, g_rgb, g_rgb0, noise0, noise1, z0, raw0, act0, z1, raw1, act1, params_c, packed_bwd_c,
-                    params_f, packed_bwd_f, draw_ws, dact_ws, partial, grads_c, grads_f, N_samples, N_importance):
-    """One C-ABI call for the backward of render_rays w.r.t. the parameters of the (distinct) coarse / fine nets."""
+                    params_f, packed_bwd_f, draw_ws, dact_ws, partial, grads_c, grads_f, N_samples, N_importance, map_grads=None):
+    """One C-ABI call for the backward of render_rays w.r.t. the parameters of the (distinct) coarse / fine nets.
+    map_grads: None, or a dict with d(loss)/d(disp, acc, depth) of the fine (1) and coarse (0) pass under MAP_GRAD_KEYS ([n] each,
+    absent / None = zero; one pass: the *1 keys) and the forward's 'acc0', 'depth0', 'acc1', 'depth1' (needed for a g_disp*):
+    fastnerf_render_rays_bwd_maps.  A pass with a map gradient may have g_rgb / g_rgb0 None."""
     require_gpu(rays11, g_rgb, g_rgb0, z0, raw0, act0, z1, raw1, act1, params_c, packed_bwd_c, params_f, packed_bwd_f, draw_ws,
                 dact_ws, partial, grads_c, grads_f)
     n = rays11.shape[0]
@@ -418,11 +441,14 @@ def render_rays_bwd(rays11, white_bkgd, g_rgb, g_rgb0, noise0, noise1, z0, raw0,
     assert packed_tag(packed_bwd_c) == tag and (packed_bwd_f is None or packed_tag(packed_bwd_f) == tag), \
         'packed weights were not produced by mlp_pack under the current math mode'
     assert draw_ws.numel() >= n * S1 * 4 and dact_ws.numel() >= dact_floats(n * S1)
-    check(lib().fastnerf_render_rays_bwd(
-        mode_id(), n, int(N_samples), int(N_importance), ptr(rays11), int(bool(white_bkgd)), ptr(g_rgb), ptr(g_rgb0),
-        ptr(noise0), ptr(noise1), ptr(z0), ptr(raw0), ptr(act0), ptr(z1), ptr(raw1), ptr(act1), ptr(params_c), ptr(packed_bwd_c),
-        ptr(params_f), ptr(packed_bwd_f), ptr(draw_ws), ptr(dact_ws), ptr(partial), ptr(grads_c), ptr(grads_f), stream()),
-        'fastnerf_render_rays_bwd')
+    args = [mode_id(), n, int(N_samples), int(N_importance), ptr(rays11), int(bool(white_bkgd)), ptr(g_rgb), ptr(g_rgb0),
+            ptr(noise0), ptr(noise1), ptr(z0), ptr(raw0), ptr(act0), ptr(z1), ptr(raw1), ptr(act1), ptr(params_c), ptr(packed_bwd_c),
+            ptr(params_f), ptr(packed_bwd_f), ptr(draw_ws), ptr(dact_ws), ptr(partial), ptr(grads_c), ptr(grads_f)]
+    maps, _keep = _map_grads(map_grads, n)
+    if maps is None:
+        check(lib().fastnerf_render_rays_bwd(*args, stream()), 'fastnerf_render_rays_bwd')
+    else:
+        check(lib().fastnerf_render_rays_bwd_maps(*args, *maps, stream()), 'fastnerf_render_rays_bwd_maps')
 
 
 def compact_live(draw):
@@ -466,10 +492,11 @@ def live_ws_ints(P):
 
 def render_rays_bwd_live(rays11, white_bkgd, g_rgb, g_rgb0, noise0, noise1, z0, raw0, z1, raw1, params_c, packed_c,
                          params_f, packed_f, draw_ws, act_ws, dact_ws, partial, live_ws, grads_c, grads_f, N_samples,
-                         N_importance, counts=None):
+                         N_importance, counts=None, map_grads=None):
     """One C-ABI call: backward of render_rays with exact zero-gradient point compaction, for a forward that saved
     nothing.  packed_c / packed_f: the (forward, backward) packed-weight pairs.  counts: optional int32[4] device
-    tensor receiving (live, total) of the fine and of the coarse pass."""
+    tensor receiving (live, total) of the fine and of the coarse pass.  map_grads: as render_rays_bwd
+    (fastnerf_render_rays_bwd_live_maps)."""
     require_gpu(rays11, g_rgb, g_rgb0, z0, raw0, z1, raw1, params_c, params_f, draw_ws, act_ws, dact_ws, partial, live_ws,
                 grads_c, grads_f, counts)
     n = rays11.shape[0]
@@ -479,12 +506,15 @@ def render_rays_bwd_live(rays11, white_bkgd, g_rgb, g_rgb0, noise0, noise1, z0, 
         assert pk is None or all(packed_tag(t) == tag for t in pk)
     assert draw_ws.numel() >= n * S1 * 4 and dact_ws.numel() >= dact_floats(n * S1) and act_ws.numel() >= act_floats(n * S1)
     assert live_ws.dtype == torch.int32 and live_ws.numel() >= live_ws_ints(n * S1)
-    check(lib().fastnerf_render_rays_bwd_live(
-        mode_id(), n, int(N_samples), int(N_importance), ptr(rays11), int(bool(white_bkgd)), ptr(g_rgb), ptr(g_rgb0), ptr(noise0), ptr(noise1),
-        ptr(z0), ptr(raw0), ptr(z1), ptr(raw1), ptr(params_c), ptr(packed_c[0]), ptr(packed_c[1]),
-        ptr(params_f), ptr(None if packed_f is None else packed_f[0]), ptr(None if packed_f is None else packed_f[1]),
-        ptr(draw_ws), ptr(act_ws), ptr(dact_ws), ptr(partial), ptr(live_ws), ptr(grads_c), ptr(grads_f), ptr(counts), stream()),
-        'fastnerf_render_rays_bwd_live')
+    args = [mode_id(), n, int(N_samples), int(N_importance), ptr(rays11), int(bool(white_bkgd)), ptr(g_rgb), ptr(g_rgb0), ptr(noise0),
+            ptr(noise1), ptr(z0), ptr(raw0), ptr(z1), ptr(raw1), ptr(params_c), ptr(packed_c[0]), ptr(packed_c[1]),
+            ptr(params_f), ptr(None if packed_f is None else packed_f[0]), ptr(None if packed_f is None else packed_f[1]),
+            ptr(draw_ws), ptr(act_ws), ptr(dact_ws), ptr(partial), ptr(live_ws), ptr(grads_c), ptr(grads_f), ptr(counts)]
+    maps, _keep = _map_grads(map_grads, n)
+    if maps is None:
+        check(lib().fastnerf_render_rays_bwd_live(*args, stream()), 'fastnerf_render_rays_bwd_live')
+    else:
+        check(lib().fastnerf_render_rays_bwd_live_maps(*args, *maps, stream()), 'fastnerf_render_rays_bwd_live_maps')
 
 
 def raw2outputs_bwd(raw, z, rays11, g_rgb, noise=None, white_bkgd=False, draw=None):
@@ -572,6 +602,34 @@ def mse_leafmax(rgb, rgb0, target, grad_scale=1.0, want_grads=True, leaf_tag=Non
                                      ptr(loss2), ptr(leaf_tag), int(max_leaves), ptr(table), stream()),
           'fastnerf_mse_leafmax')
     return loss2, g, g0
+
+
+def aux_loss(depth, acc, depth0=None, acc0=None, depth_target=None, depth_weight=None, acc_target=None, acc_weight=None,
+             lambda_depth=0., lambda_acc=0., grad_scale=1.0, want_grads=True):
+    """Depth / opacity losses of the maps of one render (fastnerf_aux_loss): depth / acc are the image pass's maps, depth0 / acc0
+    the coarse pass's of a two-pass render (None with one pass).  Returns (loss4, grads): loss4 = (Ld_fine, Ld_coarse, La_fine,
+    La_coarse) on the device, unscaled by the lambdas; grads = dict g_depth1, g_acc1, g_depth0, g_acc0 ([n] each; None for a term
+    whose target is None, for the coarse pass with one pass, and with want_grads=False) = grad_scale lambda 2 w (map - target) / n.
+    Weights None = ones; a ray with weight 0 contributes exactly 0 and gets +0 whatever its target holds."""
+    t = {k: (None if v is None else _f32(v).reshape(-1)) for k, v in dict(
+        depth1=depth, acc1=acc, depth0=depth0, acc0=acc0, dt=depth_target, dw=depth_weight, at=acc_target, aw=acc_weight).items()}
+    assert t['depth1'] is not None or t['acc1'] is not None, 'aux_loss needs the depth map or the opacity map'
+    require_gpu(*t.values())
+    ref = t['depth1'] if t['depth1'] is not None else t['acc1']
+    n, dev = ref.numel(), ref.device
+    for k, v in t.items():
+        assert v is None or v.numel() == n, (k, v.numel(), n)
+    assert t['dt'] is None or t['depth1'] is not None, 'a depth target needs the depth map'
+    assert t['at'] is None or t['acc1'] is not None, 'an opacity target needs the opacity map'
+    new = lambda on: torch.empty(n, device=dev, dtype=torch.float32) if (want_grads and on) else None      # noqa: E731
+    g = {'g_depth1': new(t['dt'] is not None), 'g_acc1': new(t['at'] is not None),
+         'g_depth0': new(t['dt'] is not None and t['depth0'] is not None), 'g_acc0': new(t['at'] is not None and t['acc0'] is not None)}
+    loss4 = torch.empty(4, device=dev, dtype=torch.float32)
+    check(lib().fastnerf_aux_loss(n, ptr(t['depth1']), ptr(t['acc1']), ptr(t['depth0']), ptr(t['acc0']), ptr(t['dt']), ptr(t['dw']),
+                                  ptr(t['at']), ptr(t['aw']), float(lambda_depth), float(lambda_acc), float(grad_scale),
+                                  ptr(g['g_depth1']), ptr(g['g_acc1']), ptr(g['g_depth0']), ptr(g['g_acc0']), ptr(loss4), stream()),
+          'fastnerf_aux_loss')
+    return loss4, g
 
 
 def sigma_noise(n, S0, S1, std, seed, device):

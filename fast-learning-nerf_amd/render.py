@@ -11,9 +11,15 @@ so the reference's `loss.backward(); optimizer.step()` loop works unchanged.  Ne
 NeRF modules take the closure route instead (`_render_rays_closure`): the caller's `network_query_fn` runs in torch
 between the same HIP sampling and compositing kernels, differentiable through torch.ops.fastnerf.raw2outputs_full.
 
-Ray and pose gradients: a `ray_batch` that requires grad gets `rgb_map` / `rgb0`'s gradient with respect to its columns o, d and
-viewdir on both routes (fused: ops.ray_grad after each pass's backward, `_RenderRaysRayGradFn`; near / far are constants and get
-zeros), and `render(..., c2w=pose)` with a pose that requires grad carries it on to the pose (`_PoseRaysFn`).
+Every map is differentiable, as under the reference's plain-torch render_rays: a loss on `disp_map`, `acc_map`, `disp0`, `acc0` (and on
+`depth_map` / `depth0`, handed out with retdepth=True) reaches both networks on the fused route too -- the autograd node hands
+d(loss)/d(maps) to the compositing backward (fastnerf_render_rays_bwd_maps -> raw2outputs_bwd_full); a loss on the colours alone
+makes exactly the calls it made before.  `raw` and `z_std` stay non-differentiable.
+
+Ray and pose gradients: a `ray_batch` that requires grad gets the gradient of every map with respect to its columns o, d and
+viewdir on both routes (fused: ops.ray_grad after each pass's backward, `_RenderRaysRayGradFn`; it consumes d(loss)/d(raw), so the
+depth / opacity terms arrive with no kernel of their own; near / far and z are constants and get zeros), and
+`render(..., c2w=pose)` with a pose that requires grad carries it on to the pose (`_PoseRaysFn`).
 """
 import os
 
@@ -102,7 +108,13 @@ def get_compact():
 
 class LivePolicy:
     """Decides per step whether the backward runs compacted; fed with the (live, total) counters of compacted steps
-    through pinned-memory copies that are only read once their event has completed (never stalls the stream)."""
+    through pinned-memory copies that are only read once their event has completed (never stalls the stream).
+
+    What is live depends on the loss.  Under the colour loss alone a sample behind an opaque surface is dead (T = 0 to fp32).
+    A depth or opacity term keeps the list exact -- a sample with sigma' <= 0 still has d(loss)/d(raw) == +-0 in all four
+    components -- but its d(acc)/d(alpha_i) = T_end / t_i reaches EVERY sample with sigma' > 0 of a ray whose transmittance
+    has not run out, so the measured fraction f (and with it the step time, 5.2 + 18.3 f ms at the bench shape) rises
+    until the surfaces close; the policy follows the counters as before and needs no change."""
     MAX_LAG = 6
     EVERY, PROBE = 4, 256   # (a measurement is a 16-byte asynchronous copy: cheap enough to follow fast changes early in training)
     # break-even live fractions from the measured kernel times (forward without saving + f x (saving forward + backward)
@@ -162,7 +174,7 @@ def _maps(o, N_importance):
     """The outputs of ops.render_rays_fwd / _fwd_occ under the names of render_rays' maps."""
     if N_importance > 0:
         return dict(rgb_map=o['rgb1'], disp_map=o['disp1'], acc_map=o['acc1'], raw=o['raw1'], rgb0=o['rgb0'], disp0=o['disp0'],
-                    acc0=o['acc0'], z_std=o['z_std'], weights=o['w1'], z_vals=o['z1'], depth_map=o['depth1'],
+                    acc0=o['acc0'], z_std=o['z_std'], weights=o['w1'], z_vals=o['z1'], depth_map=o['depth1'], depth0=o['depth0'],
                     z_samples=o['z_samples'], weights0=o['w0'], z0=o['z0'])
     return dict(rgb_map=o['rgb0'], disp_map=o['disp0'], acc_map=o['acc0'], raw=o['raw0'], weights=o['w0'], z_vals=o['z0'],
                 depth_map=o['depth0'])
@@ -190,10 +202,14 @@ def _forward_core(rays11, net_c, net_f, N_samples, N_importance, lindisp, pertur
                             seed0=_next_seed() if (perturb and t_rand is None) else 0,
                             seed1=_next_seed() if (N_importance > 0 and perturb and u is None) else 0, save=save,
                             skip_dead_rgb=bool(skip_dead_rgb and not save and net_c.use_viewdirs), act_bufs=act_bufs)
+    # acc / depth (the disparity clamp of the map backward is decided on them) are saved as detached aliases: the maps themselves
+    # are outputs of the autograd node that owns `saved`, and an output kept there would tie node -> saved -> output -> grad_fn -> node
+    # into a cycle that only the cyclic collector frees -- with the saved activations in it
     saved = {'rays11': rays11, 'z0': o['z0'], 'raw0': o['raw0'], 'act0': o['act0'], 'noise0': noise0, 'white': white_bkgd,
-             'net_c': net_c, 'net_f': None, 'pc': pc, 'live': not save}
+             'net_c': net_c, 'net_f': None, 'pc': pc, 'live': not save, 'acc0': o['acc0'].detach(), 'depth0': o['depth0'].detach()}
     if N_importance > 0:
-        saved.update(z1=o['z1'], raw1=o['raw1'], act1=o['act1'], noise1=noise1, net_f=fine, pf=pf)
+        saved.update(z1=o['z1'], raw1=o['raw1'], act1=o['act1'], noise1=noise1, net_f=fine, pf=pf, acc1=o['acc1'].detach(),
+                     depth1=o['depth1'].detach())
     return _maps(o, N_importance), saved
 
 
@@ -215,12 +231,25 @@ def _forward_occ(rays11, net_c, net_f, N_samples, N_importance, lindisp, perturb
     return dict(_maps(o, N_importance), z0=o['z0'], raw0=o['raw0'], counts=o['counts'])
 
 
-def _backward_core(saved, g_rgb, g_rgb0, out_c=None, out_f=None, counts=None):
+def _pass_maps(maps, k):
+    """(g_disp, g_acc, g_depth) of pass k ('1': the pass that produces the image, '0': the coarse pass of two) out of a dict over
+    ops.MAP_GRAD_KEYS, or None when none of the three is set."""
+    g = tuple((maps or {}).get(name + k) for name in ('g_disp', 'g_acc', 'g_depth'))
+    return None if all(t is None for t in g) else g
+
+
+def _backward_core(saved, g_rgb, g_rgb0, out_c=None, out_f=None, counts=None, maps=None):
     """Writes d(loss)/d(params) of the coarse (and fine) net, given d(loss)/d(rgb maps), into
     out_c / out_f (flat, parameter order; default: the nets' flat_grad buffers).  A forward that saved no activations
     (saved['live']) is followed by the compacted backward; `counts` (int32[4], device) then receives the live / total
-    point counts of the fine and the coarse pass."""
+    point counts of the fine and the coarse pass.  `maps`: None, or d(loss)/d(disp, acc, depth) of the two passes under
+    ops.MAP_GRAD_KEYS (one pass: the *1 keys); without any, the calls are those of the colour loss alone."""
     rays11 = saved['rays11']
+    has1, has0 = _pass_maps(maps, '1') is not None, _pass_maps(maps, '0') is not None
+    map_grads = None
+    if has1 or has0:
+        map_grads = dict({k: maps.get(k) for k in ops.MAP_GRAD_KEYS}, acc0=saved['acc0'], depth0=saved['depth0'],
+                         acc1=saved.get('acc1'), depth1=saved.get('depth1'))
     dev = rays11.device
     partial = _Workspace.partial(dev)
     net_c, net_f = saved['net_c'], saved['net_f']
@@ -232,8 +261,8 @@ def _backward_core(saved, g_rgb, g_rgb0, out_c=None, out_f=None, counts=None):
         assert net_f is None or net_f is not net_c, 'the compacted backward needs two distinct nets (or one pass)'
         Ni = 0 if net_f is None else saved['z1'].shape[1] - S0
         P = n * (S0 + Ni)
-        g_a = g_rgb if g_rgb is not None else torch.zeros(n, 3, device=dev)
-        g_b = (g_rgb0 if g_rgb0 is not None else torch.zeros(n, 3, device=dev)) if Ni > 0 else None
+        g_a = g_rgb if (g_rgb is not None or has1) else torch.zeros(n, 3, device=dev)
+        g_b = (g_rgb0 if (g_rgb0 is not None or has0) else torch.zeros(n, 3, device=dev)) if Ni > 0 else None
         ws = _Workspace.dact(dev, ops.dact_floats(P) + P * 4)
         draw_ws = ws[ops.dact_floats(P):]
         act_ws = _Workspace.get('act', dev, ops.act_floats(P))
@@ -241,48 +270,55 @@ def _backward_core(saved, g_rgb, g_rgb0, out_c=None, out_f=None, counts=None):
         ops.render_rays_bwd_live(rays11, saved['white'], g_a, g_b, saved['noise0'], saved.get('noise1'), saved['z0'], saved['raw0'],
                                  saved.get('z1'), saved.get('raw1'), net_c.flat, saved['pc'], None if Ni == 0 else net_f.flat,
                                  None if Ni == 0 else saved['pf'], draw_ws, act_ws, ws, partial, live_ws, out_c,
-                                 out_f if Ni > 0 else None, S0, Ni, counts=counts)
+                                 out_f if Ni > 0 else None, S0, Ni, counts=counts, map_grads=map_grads)
         return
     if net_f is None or net_f is not net_c:
         # one C-ABI call: compositing backward + MLP backward for the fine and the coarse pass
         Ni = 0 if net_f is None else saved['z1'].shape[1] - S0
-        g_a = g_rgb if g_rgb is not None else torch.zeros(n, 3, device=dev)
-        g_b = (g_rgb0 if g_rgb0 is not None else torch.zeros(n, 3, device=dev)) if Ni > 0 else None
+        g_a = g_rgb if (g_rgb is not None or has1) else torch.zeros(n, 3, device=dev)
+        g_b = (g_rgb0 if (g_rgb0 is not None or has0) else torch.zeros(n, 3, device=dev)) if Ni > 0 else None
         ws = _Workspace.dact(dev, ops.dact_floats(n * (S0 + Ni)) + n * (S0 + Ni) * 4)
         draw_ws = ws[ops.dact_floats(n * (S0 + Ni)):]
         ops.render_rays_bwd(rays11, saved['white'], g_a, g_b, saved['noise0'], saved.get('noise1'), saved['z0'], saved['raw0'],
                             saved['act0'], saved.get('z1'), saved.get('raw1'), saved.get('act1'), net_c.flat, saved['pc'][1],
                             None if Ni == 0 else net_f.flat, None if Ni == 0 else saved['pf'][1], draw_ws, ws, partial, out_c,
-                            out_f if Ni > 0 else None, S0, Ni)
+                            out_f if Ni > 0 else None, S0, Ni, map_grads=map_grads)
         return
     # one shared network for both passes (N_importance > 0 without network_fine): accumulate the two gradients
-    _backward_passes(saved, g_rgb, g_rgb0, out_c, None)
+    _backward_passes(saved, g_rgb, g_rgb0, out_c, None, maps=maps)
 
 
-def _backward_passes(saved, g_rgb, g_rgb0, out_c, out_f, d_rays=None):
+def _backward_passes(saved, g_rgb, g_rgb0, out_c, out_f, d_rays=None, maps=None):
     """The backward of a saving forward pass by pass -- raw2outputs_bwd -> mlp_bwd [-> ray_grad], the fine pass, then the coarse one --
     for what the one-call ops.render_rays_bwd cannot do: one shared network (the fine pass's gradient is added to the coarse
     pass's in out_c) and ray gradients (d_rays [n,11], overwritten: ops.ray_grad reads a pass's `dact` before the next pass
-    overwrites it).  Same kernels, inputs and order as the one call, so the parameter gradients are bit-identical to its."""
+    overwrites it).  Same kernels, inputs and order as the one call, so the parameter gradients are bit-identical to its.  `maps` as
+    in _backward_core: a pass with a map gradient goes through raw2outputs_bwd_full, and ops.ray_grad consumes its draw, so rays and
+    poses receive the depth / opacity terms (z is a constant of the backward, as in the reference)."""
     rays11 = saved['rays11']
     dev = rays11.device
     partial = _Workspace.partial(dev)
     net_c, net_f = saved['net_c'], saved['net_f']
     shared = net_f is net_c
-    passes = [('0', net_c, saved['pc'], g_rgb if net_f is None else g_rgb0, out_c)]
+    # (buffers k, colour gradient, map gradients: with one pass the coarse buffers carry the image pass, whose keys are the *1 ones)
+    passes = [('0', net_c, saved['pc'], g_rgb if net_f is None else g_rgb0, _pass_maps(maps, '1' if net_f is None else '0'), out_c)]
     if net_f is not None:
-        passes.insert(0, ('1', net_f, saved['pf'], g_rgb, torch.empty_like(out_c) if shared else out_f))
-    for i, (k, net, packed, g, out) in enumerate(passes):
+        passes.insert(0, ('1', net_f, saved['pf'], g_rgb, _pass_maps(maps, '1'), torch.empty_like(out_c) if shared else out_f))
+    for i, (k, net, packed, g, gm, out) in enumerate(passes):
         z, raw, noise, act = saved['z' + k], saved['raw' + k], saved['noise' + k], saved['act' + k]
-        if g is None:
-            g = torch.zeros(z.shape[0], 3, device=dev)
-        draw = ops.raw2outputs_bwd(raw, z, rays11, g, noise, saved['white'])
+        if gm is not None:
+            draw = ops.raw2outputs_bwd_full(raw, z, rays11, saved['acc' + k], saved['depth' + k], g_rgb=g, g_disp=gm[0], g_acc=gm[1],
+                                            g_depth=gm[2], noise=noise, white_bkgd=saved['white'])
+        else:
+            if g is None:
+                g = torch.zeros(z.shape[0], 3, device=dev)
+            draw = ops.raw2outputs_bwd(raw, z, rays11, g, noise, saved['white'])
         dact = _Workspace.dact(dev, ops.dact_floats(z.numel()))
         ops.mlp_bwd(draw, act, net.flat, packed[1], dact, partial, out)
         if d_rays is not None:
             ops.ray_grad(rays11, z, raw, noise, draw, act, dact, net.flat, d_rays=d_rays, accumulate=i > 0)
     if shared:
-        out_c.add_(passes[0][4])
+        out_c.add_(passes[0][5])
 
 
 _POLICY = LivePolicy()   # the autograd route's policy (the fused Trainer keeps its own)
@@ -290,6 +326,31 @@ _POLICY = LivePolicy()   # the autograd route's policy (the fused Trainer keeps 
 
 def _grad_views(flat):
     return list(flat_params.views(flat, param_slices()).values())
+
+
+def _fn_keys(two):
+    return ['rgb_map', 'disp_map', 'acc_map', 'raw', 'depth_map'] + (['rgb0', 'disp0', 'acc0', 'z_std', 'depth0'] if two else [])
+
+
+_MAP_OF_KEY = {'disp_map': 'g_disp1', 'acc_map': 'g_acc1', 'depth_map': 'g_depth1', 'disp0': 'g_disp0', 'acc0': 'g_acc0',
+               'depth0': 'g_depth0'}
+
+
+def _fn_outputs(ctx, out):
+    """The outputs of the two autograd nodes: every map differentiable, `raw` and `z_std` not.  Cotangents are not materialised:
+    a map no loss touches arrives as None in backward, so a loss on the colours alone reaches _backward_core with no map gradient."""
+    ctx.keys = _fn_keys('rgb0' in out)
+    outs = tuple(out[k] for k in ctx.keys)
+    ctx.mark_non_differentiable(*[o for k, o in zip(ctx.keys, outs) if k in ('raw', 'z_std')])
+    ctx.set_materialize_grads(False)
+    return outs
+
+
+def _fn_cotangents(ctx, gouts):
+    """-> ({'rgb_map': ., 'rgb0': .} as given, the map gradients under ops.MAP_GRAD_KEYS or None when there is none)."""
+    g = {k: (None if t is None else t.contiguous()) for k, t in zip(ctx.keys, gouts)}
+    maps = {_MAP_OF_KEY[k]: t for k, t in g.items() if k in _MAP_OF_KEY and t is not None}
+    return g, (maps or None)
 
 
 class _RenderRaysFn(torch.autograd.Function):
@@ -302,15 +363,11 @@ class _RenderRaysFn(torch.autograd.Function):
         out, saved = _forward_core(save=not live, **cfg)
         ctx.saved = saved
         ctx.n_params = len(params)
-        keys = ['rgb_map', 'disp_map', 'acc_map', 'raw'] + (['rgb0', 'disp0', 'acc0', 'z_std'] if 'rgb0' in out else [])
-        ctx.keys = keys
-        outs = tuple(out[k] for k in keys)
-        ctx.mark_non_differentiable(*[o for k, o in zip(keys, outs) if k not in ('rgb_map', 'rgb0')])
-        return outs
+        return _fn_outputs(ctx, out)
 
     @staticmethod
     def backward(ctx, *gouts):
-        g = dict(zip(ctx.keys, gouts))
+        g, maps = _fn_cotangents(ctx, gouts)
         saved = ctx.saved
         # fresh buffers: autograd accumulates the returned tensors into the parameters' .grad
         # (which may alias the nets' flat_grad), so the kernels must not write there directly
@@ -318,7 +375,7 @@ class _RenderRaysFn(torch.autograd.Function):
         out_c = torch.empty_like(saved['net_c'].flat)
         out_f = torch.empty_like(saved['net_f'].flat) if two else None
         counts = _Workspace.get('counts', out_c.device, 4, torch.int32) if saved.get('live') else None
-        _backward_core(saved, g.get('rgb_map'), g.get('rgb0'), out_c, out_f, counts=counts)
+        _backward_core(saved, g.get('rgb_map'), g.get('rgb0'), out_c, out_f, counts=counts, maps=maps)
         if counts is not None:
             _POLICY.after_live_step(counts)
         _POLICY.tick()
@@ -339,21 +396,17 @@ class _RenderRaysRayGradFn(torch.autograd.Function):
         ctx.saved = saved
         ctx.n_params = len(params)
         ctx.ray_like = (ray_batch.shape[-1], ray_batch.dtype)
-        keys = ['rgb_map', 'disp_map', 'acc_map', 'raw'] + (['rgb0', 'disp0', 'acc0', 'z_std'] if 'rgb0' in out else [])
-        ctx.keys = keys
-        outs = tuple(out[k] for k in keys)
-        ctx.mark_non_differentiable(*[o for k, o in zip(keys, outs) if k not in ('rgb_map', 'rgb0')])
-        return outs
+        return _fn_outputs(ctx, out)
 
     @staticmethod
     def backward(ctx, *gouts):
-        g = dict(zip(ctx.keys, gouts))
+        g, maps = _fn_cotangents(ctx, gouts)
         saved = ctx.saved
         two = saved['net_f'] is not None and saved['net_f'] is not saved['net_c']
         out_c = torch.empty_like(saved['net_c'].flat)      # (fresh buffers: see _RenderRaysFn.backward)
         out_f = torch.empty_like(saved['net_f'].flat) if two else None
         d_rays = torch.empty(saved['rays11'].shape[0], 11, device=out_c.device, dtype=torch.float32)
-        _backward_passes(saved, g.get('rgb_map'), g.get('rgb0'), out_c, out_f, d_rays=d_rays)
+        _backward_passes(saved, g.get('rgb_map'), g.get('rgb0'), out_c, out_f, d_rays=d_rays, maps=maps)
         grads = saved['net_c'].param_grads_from(out_c) + (saved['net_f'].param_grads_from(out_f) if two else [])
         assert len(grads) == ctx.n_params
         width, dtype = ctx.ray_like
@@ -419,7 +472,7 @@ def _query_occupied(network_query_fn, net, rays11, z, viewdirs, occupancy):
 
 
 def _render_rays_closure(ray_batch, rays11, network_fn, network_fine, network_query_fn, N_samples, N_importance, retraw, lindisp,
-                         perturb, white_bkgd, t_rand, u, noise0, noise1, occupancy=None):
+                         perturb, white_bkgd, t_rand, u, noise0, noise1, occupancy=None, retdepth=False):
     """render.py:195-305 for any torch network: sampling, inverse-CDF + merge and compositing run on the HIP kernels, the
     network runs as `network_query_fn(pts, viewdirs, net)` in torch, and autograd reaches its parameters through
     raw2outputs_full.  Random draws follow the fused route (same injected tensors, same host-RNG seed draws)."""
@@ -434,10 +487,12 @@ def _render_rays_closure(ray_batch, rays11, network_fn, network_fine, network_qu
     else:
         pts = rays_o[..., None, :] + rays_d[..., None, :] * z[..., :, None]      # render.py:268
         raw = network_query_fn(pts, viewdirs, network_fn)
-    rgb, disp, acc, weights, _ = _composite(raw, z, rays11, noise0, white_bkgd)
+    rgb, disp, acc, weights, depth = _composite(raw, z, rays11, noise0, white_bkgd)
     ret = {}
     if N_importance > 0:
         ret['rgb0'], ret['disp0'], ret['acc0'] = rgb, disp, acc
+        if retdepth:
+            ret['depth0'] = depth
         seed1 = _next_seed() if (perturb and u is None) else 0
         # sample_pdf(mid(z), weights[1:-1]) on the detached weights (render.py:279-283) + sort(cat)
         z1, _, z_std = ops.sample_pdf_merge(z, weights.detach().contiguous(), N_importance, det=(perturb == 0.), u=u, seed=seed1,
@@ -448,9 +503,11 @@ def _render_rays_closure(ray_batch, rays11, network_fn, network_fine, network_qu
         else:
             pts = rays_o[..., None, :] + rays_d[..., None, :] * z1[..., :, None]
             raw = network_query_fn(pts, viewdirs, network_fine if network_fine is not None else network_fn)
-        rgb, disp, acc, _, _ = _composite(raw, z1, rays11, noise1, white_bkgd)
+        rgb, disp, acc, _, depth = _composite(raw, z1, rays11, noise1, white_bkgd)
         ret['z_std'] = z_std
     out = {'rgb_map': rgb, 'disp_map': disp, 'acc_map': acc}
+    if retdepth:
+        out['depth_map'] = depth
     if retraw:
         out['raw'] = raw
     out.update(ret)
@@ -458,7 +515,8 @@ def _render_rays_closure(ray_batch, rays11, network_fn, network_fine, network_qu
 
 
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
-                N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False, occupancy=None):
+                N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False, occupancy=None,
+                retdepth=False):
     """render.py:195-305.  Two routes, chosen by the networks (after `.module` unwrapping):
 
     * fastnerf NeRF modules (8 x 256): positional encoding + MLP run fused inside the HIP kernels; `network_query_fn` is
@@ -475,10 +533,16 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     raw_noise_std > 0 (noise is added to sigma before the relu: a zero sigma is not a dead sample) and when gradients are
     wanted (the training step must not silently change its gradients).
 
-    A `ray_batch` that requires grad receives d(rgb_map, rgb0)/d(ray_batch) as the reference's plain-torch render_rays gives it:
-    columns o, d (through the sample points and through dists * |d|) and viewdir; near / far (columns 6:8) get zeros on the
-    fused route (they are constants there: `render` passes Python floats).  Fused route: math modes 'fp32' and 'bf16x6'
-    (NotImplementedError under 'bf16x3'), always through the saving backward; disp_map / acc_map stay non-differentiable."""
+    `retdepth=True` adds `depth_map` (and `depth0` with two passes), the expected sample distance sum_i w_i z_i of render.py:186,
+    to the returned dict on both routes; the default leaves the key set as it is.
+
+    Every returned map except `raw` and `z_std` is differentiable w.r.t. the networks' parameters on both routes (render.py:149-192
+    under the reference's autograd): rgb_map, disp_map, acc_map, depth_map and their coarse twins, in all three math modes.
+
+    A `ray_batch` that requires grad receives the gradient of those maps w.r.t. the ray batch as the reference's plain-torch
+    render_rays gives it: columns o, d (through the sample points and through dists * |d|) and viewdir; near / far (columns 6:8)
+    get zeros on the fused route (they are constants there: `render` passes Python floats), and z is a constant of the backward.
+    Fused route: math modes 'fp32' and 'bf16x6' (NotImplementedError under 'bf16x3'), always through the saving backward."""
     net_c = _unwrap(network_fn)
     net_f = _unwrap(network_fine)
     fused = isinstance(net_c, NeRF)
@@ -518,7 +582,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             noise0, noise1 = ops.sigma_noise(n, N_samples, N_samples + N_importance if N_importance > 0 else 0, raw_noise_std, _next_seed(), dev)
     if not fused:
         return _render_rays_closure(ray_batch, rays11, network_fn, network_fine, network_query_fn, N_samples, N_importance, retraw,
-                                    lindisp, perturb, white_bkgd, t_rand, u, noise0, noise1, occupancy=occupancy)
+                                    lindisp, perturb, white_bkgd, t_rand, u, noise0, noise1, occupancy=occupancy, retdepth=retdepth)
     cfg = dict(rays11=rays11, net_c=net_c, net_f=net_f, N_samples=N_samples, N_importance=N_importance,
                lindisp=lindisp, perturb=perturb, white_bkgd=white_bkgd, t_rand=t_rand, u=u, noise0=noise0,
                noise1=noise1,
@@ -534,19 +598,21 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
                                       "ops.set_math): 'bf16x3' has no ray-gradient kernel")
         cfg['rays11'] = rays11.detach()
         outs = _RenderRaysRayGradFn.apply(cfg, ray_batch, *params)
-        keys = ['rgb_map', 'disp_map', 'acc_map', 'raw'] + (['rgb0', 'disp0', 'acc0', 'z_std'] if N_importance > 0 else [])
-        out = dict(zip(keys, outs))
+        out = dict(zip(_fn_keys(N_importance > 0), outs))
     elif torch.is_grad_enabled() and any(p.requires_grad for p in params):
         outs = _RenderRaysFn.apply(cfg, *params)
-        keys = ['rgb_map', 'disp_map', 'acc_map', 'raw'] + (['rgb0', 'disp0', 'acc0', 'z_std'] if N_importance > 0 else [])
-        out = dict(zip(keys, outs))
+        out = dict(zip(_fn_keys(N_importance > 0), outs))
     else:
         out, _ = _forward_core(save=False, **cfg)
     ret = {'rgb_map': out['rgb_map'], 'disp_map': out['disp_map'], 'acc_map': out['acc_map']}
+    if retdepth:
+        ret['depth_map'] = out['depth_map']
     if retraw:
         ret['raw'] = out['raw']
     if N_importance > 0:
         ret['rgb0'], ret['disp0'], ret['acc0'], ret['z_std'] = out['rgb0'], out['disp0'], out['acc0'], out['z_std']
+        if retdepth:
+            ret['depth0'] = out['depth0']
     return ret
 
 
@@ -594,7 +660,7 @@ class _PoseRaysFn(torch.autograd.Function):
 def render(H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far=1., use_viewdirs=False,
            c2w_staticcam=None, **kwargs):
     """render.py:26-91 -> [rgb_map, disp_map, acc_map, extras].  A tensor `c2w` that requires grad receives the gradient of
-    rgb_map (and rgb0) through the rays (_PoseRaysFn); with ndc=True or c2w_staticcam that raises NotImplementedError."""
+    every differentiable map (render_rays) through the rays (_PoseRaysFn); with ndc=True or c2w_staticcam that raises NotImplementedError."""
     if torch.is_tensor(c2w) and c2w.requires_grad and torch.is_grad_enabled():
         if ndc or c2w_staticcam is not None:
             raise NotImplementedError('render: a pose that requires grad is differentiated through plain pinhole rays only '

@@ -229,10 +229,21 @@ class Trainer:
     (FASTNERF_COMPACT=0, one network shared by both passes and FASTNERF_FUSED_STEP=0 are ValueErrors), and
     raw_noise_std > 0 is a ValueError (noise is added before the relu: a zero sigma is not a dead sample).
     `occupancy_counts`: device int32 [4] = (occupied, total) samples of the coarse pass, then of the fine pass, of the last step
-    (None without a grid).  A step on an empty batch (a data-parallel tail) neither renders nor refreshes the grid."""
+    (None without a grid).  A step on an empty batch (a data-parallel tail) neither renders nor refreshes the grid.
+
+    Depth / opacity supervision (lambda_depth, lambda_acc; step(..., depth=, depth_weight=, acc=, acc_weight=), [n] each): the step
+    minimises mse(fine) + mse(coarse) + lambda_depth (Ld_fine + Ld_coarse) + lambda_acc (La_fine + La_coarse) with
+    L = mean_r w_r (map[r] - target[r])^2 on depth_map / acc_map of both passes (ops.aux_loss; weights default to ones, a ray
+    with weight 0 is ignored whatever its target holds -- sparse depth is "NaN where unknown, weight 0").  A term is on when its
+    target is given AND its lambda is not 0; with no term on, the step is the step without these keywords, launch for launch.
+    `aux_losses`: device tensor [4] = (Ld_fine, Ld_coarse, La_fine, La_coarse) of the last step, unscaled by the lambdas (zeros
+    for a term that is off, and after an empty batch); the return value of step() is unchanged.  Both routes, the plain and the
+    compacted backward, an occupancy grid and n_global scaling take the terms; they make every sample with positive density of a
+    ray that is not yet opaque live (render.LivePolicy), so early compacted steps run over more points than under the colour loss."""
 
     def __init__(self, render_kwargs_train, H, W, K, near, far, lrate=5e-4, lrate_decay=250, decay=True,
-                 beta1=0.9, beta2=0.999, eps=1e-8, occupancy=None, occupancy_every=16, occupancy_warmup=256, occupancy_cells=None):
+                 beta1=0.9, beta2=0.999, eps=1e-8, occupancy=None, occupancy_every=16, occupancy_warmup=256, occupancy_cells=None,
+                 lambda_depth=0., lambda_acc=0.):
         kw = render_kwargs_train
         self._kw = kw
         self.net_c = kw['network_fn']
@@ -271,6 +282,10 @@ class Trainer:
         self.occupancy_cells = occupancy_cells
         self.occupancy_counts = None if occupancy is None else torch.zeros(4, device=self.flat.device, dtype=torch.int32)
         self.occupancy_steps = 0     # steps taken with the grid set
+        self.lambda_depth, self.lambda_acc = float(lambda_depth), float(lambda_acc)
+        self._aux_zero = torch.zeros(4, device=self.flat.device, dtype=torch.float32)
+        self.aux_losses = self._aux_zero
+        self._aux = None         # fn_step_aux of the fused path's current step (None: no term on)
         self._check_occupancy()
         self.repack()
 
@@ -296,8 +311,23 @@ class Trainer:
         self.pc = self.net_c.packed(refresh=True)
         self.pf = self.net_f.packed(refresh=True) if self.net_f is not None else None
 
+    def _aux_terms(self, n, depth, depth_weight, acc, acc_weight):
+        """The terms that are on (target given, lambda != 0) as contiguous fp32 [n] tensors: {} or a dict with depth_target /
+        depth_weight / acc_target / acc_weight (+ the lambdas)."""
+        t = {}
+        for name, lam, tgt, w in (('depth', self.lambda_depth, depth, depth_weight), ('acc', self.lambda_acc, acc, acc_weight)):
+            if tgt is None or lam == 0.:
+                continue
+            ops.require_gpu(tgt, w)
+            t[name + '_target'] = ops._f32(tgt).reshape(-1)
+            t[name + '_weight'] = None if w is None else ops._f32(w).reshape(-1)
+            assert t[name + '_target'].numel() == n and (w is None or t[name + '_weight'].numel() == n), name
+        if t:
+            t['lambda_depth'], t['lambda_acc'] = self.lambda_depth, self.lambda_acc
+        return t
+
     def forward_backward(self, rays_o, rays_d, target, leaf_tag=None, table=None, max_leaves=0, t_rand=None, u=None,
-                         n_global=None):
+                         n_global=None, depth=None, depth_weight=None, acc=None, acc_weight=None):
         if self.occupancy is not None:
             raise ValueError('Trainer.forward_backward: the call-by-call route has no occupancy grid; use step()')
         n = rays_o.shape[0]
@@ -316,7 +346,13 @@ class Trainer:
         scale = 1.0 if n_global is None else float(n) / float(n_global)
         loss2, g, g0 = ops.mse_leafmax(out['rgb_map'], out.get('rgb0'), target, grad_scale=scale, leaf_tag=leaf_tag,
                                        max_leaves=max_leaves, table=table)
-        _backward_core(saved, g, g0, counts=self.live_counts if live else None)
+        maps = None
+        self.aux_losses = self._aux_zero
+        aux = self._aux_terms(n, depth, depth_weight, acc, acc_weight)
+        if aux:      # the same launch, behind the colour loss, as fastnerf_train_step_aux makes
+            self.aux_losses, gm = ops.aux_loss(out['depth_map'], out['acc_map'], out.get('depth0'), out.get('acc0'), grad_scale=scale, **aux)
+            maps = {k: t for k, t in gm.items() if t is not None}
+        _backward_core(saved, g, g0, counts=self.live_counts if live else None, maps=maps)
         self.net_c.collect_grads()          # (no-ops with view directions: the kernels write the parameters' gradients)
         if self.net_f is not None and self.net_f is not self.net_c:
             self.net_f.collect_grads()
@@ -327,8 +363,10 @@ class Trainer:
         return loss2, out
 
     # ---- fused route: one fastnerf_train_step call per phase group ------------------------------------------------
-    def _fused_prepare(self, rays_o, rays_d, target, leaf_tag, table, max_leaves, t_rand, u, n_global):
-        """Fill fn_step_args for this batch; returns (args, out mapping, loss2, live)."""
+    def _fused_prepare(self, rays_o, rays_d, target, leaf_tag, table, max_leaves, t_rand, u, n_global, depth=None,
+                       depth_weight=None, acc=None, acc_weight=None):
+        """Fill fn_step_args (and fn_step_aux, self._aux, when a depth / opacity term is on) for this batch; returns (args, out
+        mapping, loss2, live)."""
         n = rays_o.shape[0]
         dev = rays_o.device
         S0, Ni = self.N_samples, self.N_importance
@@ -385,7 +423,10 @@ class Trainer:
                 t2 = _Workspace.get('act1', dev, ops.act_floats(P1))
                 a.act1 = t2.data_ptr()
                 self._keep.append(t2)
-        block = torch.empty(self._block_floats, device=dev, dtype=torch.float32)
+        # a depth / opacity term appends its four gradient rows and loss4 to the block, regions like the others
+        aux = self._aux_terms(n, depth, depth_weight, acc, acc_weight)
+        row = (n + 63) // 64 * 64
+        block = torch.empty(self._block_floats + (4 * row + 64 if aux else 0), device=dev, dtype=torch.float32)
         base = block.data_ptr()
         for name, (off, _) in self._regions.items():
             setattr(a, name, base + 4 * off)
@@ -426,6 +467,17 @@ class Trainer:
         a.occ = None if occ is None else ctypes.addressof(occ._c)
         a.occ_counts = None if occ is None else self.occupancy_counts.data_ptr()
         hold.append(occ)
+        self._aux, self.aux_losses = None, self._aux_zero
+        if aux:
+            tail = self._block_floats
+            self.aux_losses = block[tail + 4 * row:tail + 4 * row + 4]
+            x = self._aux = _lib.StepAux()
+            for k in ('depth_target', 'depth_weight', 'acc_target', 'acc_weight'):
+                setattr(x, k, None if aux.get(k) is None else aux[k].data_ptr())
+            x.g_depth1, x.g_acc1, x.g_depth0, x.g_acc0 = [base + 4 * (tail + i * row) for i in range(4)]
+            x.loss4 = self.aux_losses.data_ptr()
+            x.lambda_depth, x.lambda_acc = aux['lambda_depth'], aux['lambda_acc']
+            hold += [aux, self.aux_losses]
         self._hold = hold       # inputs stay referenced until the next step is prepared (the launches are asynchronous)
         out = _StepOut(block, self._regions, _OUT_NAMES_2 if Ni > 0 else _OUT_NAMES_1)
         loss2 = block[self._regions['loss2'][0]:self._regions['loss2'][0] + 2]
@@ -443,6 +495,10 @@ class Trainer:
         self.occupancy_steps += 1
 
     def _fused_call(self, a, phases):
+        if self._aux is not None:      # (given in every phase call: the data-parallel step splits them)
+            _lib.check(_lib.lib().fastnerf_train_step_aux(ctypes.byref(a), ctypes.byref(self._aux), int(phases), _lib.stream()),
+                       'fastnerf_train_step_aux')
+            return
         _lib.check(_lib.lib().fastnerf_train_step(ctypes.byref(a), int(phases), _lib.stream()), 'fastnerf_train_step')
 
     def _after_backward(self, live):
@@ -452,7 +508,7 @@ class Trainer:
         self.last_step_live = live
 
     def step(self, rays_o, rays_d, target, leaf_tag=None, table=None, max_leaves=0, t_rand=None, u=None,
-             n_global=None, decay=None):
+             n_global=None, decay=None, depth=None, depth_weight=None, acc=None, acc_weight=None):
         n = rays_o.shape[0]
         Nn = ops.NET_PARAMS
         two = self.N_importance > 0 and self.net_f is not None and self.net_f is not self.net_c
@@ -462,7 +518,8 @@ class Trainer:
         if self.occupancy is not None and n > 0:
             self._occupancy_tick()
         if fused:
-            a, out, loss2, live = self._fused_prepare(rays_o, rays_d, target, leaf_tag, table, max_leaves, t_rand, u, n_global)
+            a, out, loss2, live = self._fused_prepare(rays_o, rays_d, target, leaf_tag, table, max_leaves, t_rand, u, n_global,
+                                                      depth, depth_weight, acc, acc_weight)
             a.lr, a.adam_t = float(self.lr), int(self.adam_t)
             if self.world == 1:
                 self._fused_call(a, _lib.STEP_FORWARD | _lib.STEP_BWD_FINE | _lib.STEP_BWD_COARSE | _lib.STEP_UPDATE)
@@ -488,8 +545,10 @@ class Trainer:
                 _burn_seeds((1 if self.raw_noise_std > 0. else 0) + (1 if (self.perturb and t_rand is None) else 0)
                             + (1 if (self.N_importance > 0 and self.perturb and u is None) else 0))
                 loss2, out = torch.zeros(2, device=self.grad.device), {}
+                self.aux_losses = self._aux_zero
             else:
-                loss2, out = self.forward_backward(rays_o, rays_d, target, leaf_tag, table, max_leaves, t_rand, u, n_global)
+                loss2, out = self.forward_backward(rays_o, rays_d, target, leaf_tag, table, max_leaves, t_rand, u, n_global,
+                                                   depth, depth_weight, acc, acc_weight)
             if self.world > 1:
                 if overlap:   # same two collectives as the fused route, so that every rank issues the same sequence
                     parallel.wait_all(parallel.all_reduce_sum_async(self.grad[Nn:]), parallel.all_reduce_sum_async(self.grad[:Nn]))

@@ -127,6 +127,19 @@ int fastnerf_sample_pdf(int64_t n, int M, int Ni, const float* bins, const float
 int fastnerf_mse_leafmax(int64_t n, const float* rgb, const float* rgb0, const float* target, float grad_scale,
                          float* g_rgb, float* g_rgb0, float* loss2, const int32_t* leaf_tag, int max_leaves,
                          uint32_t* table, fn_stream_t stream);
+/* Auxiliary losses on the depth and opacity maps of render_rays (render.py:149-192 hands out depth_map / acc_map, and the
+ * reference's loss of run_nerf.py:479-494 is plain torch, so any term on them trains both networks).  Per pass p (1 = the
+ * pass that produces the image, 0 = the coarse pass of a two-pass render; depth0 / acc0 / g_depth0 / g_acc0 NULL with one pass):
+ *   Ld_p = 1/n sum_r wd_r (depth_p[r] - D_r)^2     g_depth_p[r] = grad_scale lambda_depth 2 wd_r (depth_p[r] - D_r) / n
+ *   La_p = 1/n sum_r wa_r (acc_p[r]   - A_r)^2     g_acc_p[r]   = grad_scale lambda_acc   2 wa_r (acc_p[r]   - A_r) / n
+ * loss4 = (Ld_1, Ld_0, La_1, La_0), unscaled by the lambdas, WRITTEN (not accumulated) by the call.  A NULL weight means ones;
+ * a NULL target switches its term off (losses 0, its gradient buffers untouched).  A ray whose weight is 0 contributes exactly 0
+ * and gets a gradient of exactly +0 whatever its target holds (sparse depth: NaN where unknown, weight 0).  One workgroup sums
+ * in a fixed order in fp64 and no atomics are used: two calls on the same input are bit-identical, for every n. */
+int fastnerf_aux_loss(int64_t n, const float* depth1, const float* acc1, const float* depth0, const float* acc0,
+                      const float* depth_target, const float* depth_weight, const float* acc_target, const float* acc_weight,
+                      float lambda_depth, float lambda_acc, float grad_scale, float* g_depth1, float* g_acc1, float* g_depth0,
+                      float* g_acc0, float* loss4, fn_stream_t stream);
 /* torch.optim.Adam step (run_nerf.py:99,494) over a flat buffer. */
 int fastnerf_adam_step(int64_t n, float* params, const float* grads, float* m, float* v, double lr, double beta1,
                        double beta2, double eps, int step, fn_stream_t stream);
@@ -341,6 +354,36 @@ int fastnerf_render_rays_bwd_live(int math_mode, int64_t n, int N_samples, int N
                                   float* draw_ws, float* act_ws, float* dact_ws, float* partial_ws, int32_t* live_ws,
                                   float* grads_c, float* grads_f, int32_t* counts_out, fn_stream_t stream);
 
+/* ---- every rendered map differentiable on the fused route (render.py:149-192: disp_map, acc_map, depth_map and their coarse
+ * twins are plain torch in the reference, so a loss on them reaches both networks; run_nerf.py:479-494) ------------------------
+ * fn_map_grads: d(loss)/d(disp, acc, depth) of the fine pass (1) and of the coarse pass (0), [n] each, each NULL = zero.  With
+ * N_importance == 0 the *1 members belong to the only pass, as g_rgb does.  The _maps entry points are the plain ones plus the
+ * forward's acc0, depth0, acc1, depth1 (the disparity clamp and its NaN branch are decided on them; needed where a g_disp is set)
+ * and the struct (NULL = no map gradient).  A pass none of whose three members is set makes exactly the plain entry point's
+ * fastnerf_raw2outputs_bwd call (the plain entry points are that case); a pass with one set calls fastnerf_raw2outputs_bwd_full,
+ * and its g_rgb may then be NULL.  A sample with sigma' <= 0 still has draw == +-0 in all four components (w = alpha T = 0 and the
+ * density term is gated by sigma' > 0), so the live list of the compacted route stays exact -- but an opacity or depth term makes
+ * every sample with sigma' > 0 of a ray that has not saturated live, where the colour loss alone left the occluded ones dead. */
+typedef struct fn_map_grads {
+  const float *g_disp1, *g_acc1, *g_depth1, *g_disp0, *g_acc0, *g_depth0;
+} fn_map_grads;
+int fastnerf_render_rays_bwd_maps(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11, int white_bkgd,
+                                  const float* g_rgb, const float* g_rgb0, const float* noise0, const float* noise1,
+                                  const float* z0, const float* raw0, const float* act0, const float* z1, const float* raw1,
+                                  const float* act1, const float* params_c, const float* packed_bwd_c, const float* params_f,
+                                  const float* packed_bwd_f, float* draw_ws, float* dact_ws, float* partial_ws, float* grads_c,
+                                  float* grads_f, const float* acc0, const float* depth0, const float* acc1, const float* depth1,
+                                  const fn_map_grads* maps, fn_stream_t stream);
+int fastnerf_render_rays_bwd_live_maps(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11,
+                                       int white_bkgd, const float* g_rgb, const float* g_rgb0, const float* noise0,
+                                       const float* noise1, const float* z0, const float* raw0, const float* z1,
+                                       const float* raw1, const float* params_c, const float* packed_fwd_c,
+                                       const float* packed_bwd_c, const float* params_f, const float* packed_fwd_f,
+                                       const float* packed_bwd_f, float* draw_ws, float* act_ws, float* dact_ws,
+                                       float* partial_ws, int32_t* live_ws, float* grads_c, float* grads_f, int32_t* counts_out,
+                                       const float* acc0, const float* depth0, const float* acc1, const float* depth1,
+                                       const fn_map_grads* maps, fn_stream_t stream);
+
 /* ---- "bf16x6" math mode: fp32-WIDTH products on the bf16 matrix cores (csrc/mlp_*.hip, MM_X6) -------------------------------
  * Same network functions and call protocol as fastnerf_mlp_pack_ex / fwd_ex / fwd_flags_ex / bwd_ex / fwd_live_ex / bwd_live_ex
  * (run_nerf.py:50-64 run_network -> model.py:37-63, autograd backward of the same).  Every fp32 operand is decomposed EXACTLY
@@ -423,6 +466,20 @@ typedef struct fn_step_args {
 } fn_step_args;
 int64_t fastnerf_step_args_size(void);              /* sizeof(fn_step_args): binding sanity check */
 int fastnerf_train_step(const fn_step_args* args, int phases, fn_stream_t stream);
+/* The step with depth / opacity supervision (fastnerf_aux_loss): total loss = mse(fine) + mse(coarse) + lambda_depth (Ld_1 + Ld_0)
+ * + lambda_acc (La_1 + La_0), where the reference would add such terms to `loss` before loss.backward() (run_nerf.py:479-494).
+ * fn_step_args keeps its size; what the terms need travels in fn_step_aux, given in EVERY phase call (the data-parallel step
+ * splits the phases): FN_STEP_FORWARD runs fastnerf_aux_loss behind fastnerf_mse_leafmax with args->grad_scale, the backward
+ * phases hand the gradient buffers of the terms whose target is set to the compositing backward (fn_map_grads).  Targets and
+ * weights: [n] or NULL as in fastnerf_aux_loss; g_*: [n] each (the *0 ones unused with one pass); loss4: [4].
+ * aux == NULL (or both targets NULL) is fastnerf_train_step launch for launch. */
+typedef struct fn_step_aux {
+  const float *depth_target, *depth_weight, *acc_target, *acc_weight;
+  float *g_depth1, *g_acc1, *g_depth0, *g_acc0, *loss4;
+  float lambda_depth, lambda_acc;
+} fn_step_aux;
+int64_t fastnerf_step_aux_size(void);               /* sizeof(fn_step_aux): binding sanity check */
+int fastnerf_train_step_aux(const fn_step_args* args, const fn_step_aux* aux, int phases, fn_stream_t stream);
 
 /* ---- exchange steps of the data-parallel path ---------------------------------------------------
  * One process per GPU; every rank renders its shard of the ray batch end to end.  The reference's strategies for contrast:
