@@ -18,7 +18,7 @@ struct RedSeg {
   int64_t wg_stride;  // floats between consecutive workgroups' partials
   int64_t dst;        // offset into the flat gradient
   int nwg, rows, cols, ld, valid_cols;
-  int dyn;            // 1: the segment's chunk count is dw_trunk_chunks(point count) (the trunk launch); nwg is its capacity
+  int dyn;            // 1: the segment's chunk count is dw_trunk_chunks(point count) (the trunk launch), 2: head_rows(point count) (the head partials grouped from dX's tiles); nwg is its capacity
   int sc_cols;        // > 0: columns < sc_cols do not go to the gradient but to scratch[sc_dst + r * sc_cols + c] (G = dL/dM of the folded view layer)
   int64_t sc_dst;
 };

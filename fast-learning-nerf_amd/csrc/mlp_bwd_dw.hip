@@ -4,10 +4,11 @@
 #include "dw_pair.h"
 #include <atomic>
 #include <map>
+#include <mutex>
 #include <utility>
 
 int fn_launch_dx(int mm, int grid, hipStream_t st, int64_t P, const float* draw, const float* act, const float* params, const float* packed_bwd,
-                 float* dact, const NetLayout& L, const int* live_idx, const int* live_cnt);   // mlp_bwd_dx.hip
+                 float* dact, const NetLayout& L, const int* live_idx, const int* live_cnt, float* headws);   // mlp_bwd_dx.hip
 
 // =========================================================================================
 // backward: dW = dY^T X  (split over workgroups by point chunk, partials reduced afterwards)
@@ -551,6 +552,50 @@ __global__ void __launch_bounds__(128) head_grads_kernel(int64_t P, const float*
   if (k < 4) o[384 + k] = sb;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The same 388 values from the dX kernel (fp32 / bf16x6): phase A of mlp_bwd_dx_kernel holds hv and draw of its tile anyway and leaves one
+// row of 388 sums per 64-point TILE in a workspace the library owns (fn::head_workspace below), so head_grads_kernel's second pass over hv
+// and draw (0.55 GB per step at the bench shape) is not made.  head_group_kernel sums groups of G consecutive tiles, in ascending tile order,
+// into at most HEAD_ROWS rows of the head region, which reduce_all then walks like any other job's chunks.  G and the row count are functions
+// of the POINT COUNT ALONE (the tile scheduler of dX is dynamic: which workgroup ran a tile must not matter, and does not), so the live-list
+// backward -- tiles of the list, count on the device -- equals the plain backward of the same points bit for bit.
+// HEAD_ROWS = 256: reduce_all sums a column through nwg / 16 dependent rounds of loads, 16 for this segment as for a trunk job.
+// ---------------------------------------------------------------------------------------------------------------------
+#define HEAD_ROWS 256
+__host__ __device__ static inline int head_group(int64_t ntiles) {   // tiles per row
+  const int64_t g = (ntiles + HEAD_ROWS - 1) / HEAD_ROWS;
+  return g < 1 ? 1 : (int)g;
+}
+__host__ __device__ static inline int head_rows(int64_t P) {
+  const int64_t ntiles = (P + TM - 1) / TM;
+  const int g = head_group(ntiles);
+  return (int)((ntiles + g - 1) / g);
+}
+// grid (min(tiles of the capacity, HEAD_ROWS), 4) x 128: one output per thread, NF independent loads in flight, added in ascending tile order
+__global__ void __launch_bounds__(128) head_group_kernel(int64_t P, const float* __restrict__ ws, float* __restrict__ out,
+                                                          const int* __restrict__ live_cnt) {
+  if (live_cnt) P = (int64_t)*live_cnt;
+  const int64_t ntiles = (P + TM - 1) / TM;
+  const int g = head_group(ntiles);
+  const int col = (int)blockIdx.y * 128 + (int)threadIdx.x;
+  const int64_t t0 = (int64_t)blockIdx.x * g;
+  if (t0 >= ntiles || col >= 388) return;
+  const int n = (int)(ntiles - t0 < g ? ntiles - t0 : g);
+  const float* src = ws + t0 * 388 + col;
+  constexpr int NF = 16;
+  float s = 0.f;
+  int i = 0;
+  for (; i + NF <= n; i += NF) {
+    float v[NF];
+#pragma unroll
+    for (int j = 0; j < NF; ++j) v[j] = src[(int64_t)(i + j) * 388];
+#pragma unroll
+    for (int j = 0; j < NF; ++j) s += v[j];
+  }
+  for (; i < n; ++i) s += src[(int64_t)i * 388];
+  out[(int64_t)blockIdx.x * 388 + col] = s;
+}
+
 // ---- one launch reduces every job's per-workgroup partials into the flat gradient ------------
 // (struct RedSeg, MAX_SEGS, struct RedTable: dw_pair.h)
 
@@ -559,7 +604,7 @@ __global__ void __launch_bounds__(256) reduce_all_kernel(RedTable tab, const flo
   RedSeg sg = tab.s[blockIdx.y];
   if (sg.dyn) {
     if (live_cnt) P = (int64_t)*live_cnt;
-    const int n = dw_trunk_chunks(P, ncu);
+    const int n = sg.dyn == 2 ? head_rows(P) : dw_trunk_chunks(P, ncu);
     sg.nwg = n < sg.nwg ? n : sg.nwg;
   }
   const int64_t total = (int64_t)sg.rows * sg.cols;
@@ -743,6 +788,62 @@ static int bwd_reduce(const RedTable& T, const NetLayout& L, int64_t P, const fl
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The per-tile head partials [tiles][388] of the dX kernel: one buffer per (device, stream), grown on demand, reused every step, alive as long
+// as the process (the precedents: the fold buffer of mlp_pack.hip, fn::x6_pair_workspace below).  388 floats per 64 points: 19.1 MB for the
+// fine pass of the bench shape (12 288 tiles), which the coarse pass (4 096 tiles) of the same stream reuses behind it.  Never allocated inside
+// a stream capture; nullptr -- a capturing stream, a failed allocation (the refused size is remembered, one line goes to stderr), or
+// FASTNERF_HEAD_FROM_DX=0 in the environment (read at every call: the switch the tests compare the two routes with) -- sends the caller down
+// the head_grads_kernel route.  (FASTNERF_HEAD_FROM_DX=nan, also for the tests: the buffer is filled with NaNs before dX writes it.)
+// ---------------------------------------------------------------------------------------------------------------------
+namespace fn {
+struct HeadWs {
+  float* p = nullptr;
+  int64_t cap = 0, refused = 0;
+};
+static std::mutex g_head_mu;
+static std::map<std::pair<int, hipStream_t>, HeadWs> g_head;
+static float* head_workspace(int64_t ntiles, hipStream_t st) {
+  const char* e = getenv("FASTNERF_HEAD_FROM_DX");
+  if (e && e[0] == '0') return nullptr;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cs) != hipSuccess) {
+    (void)hipGetLastError();
+    return nullptr;
+  }
+  if (cs != hipStreamCaptureStatusNone) return nullptr;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+  const int64_t need = (ntiles > 0 ? ntiles : 1) * 388;
+  std::lock_guard<std::mutex> lk(g_head_mu);
+  HeadWs& w = g_head[{dev, st}];
+  const bool poison = e && e[0] == 'n';   // FASTNERF_HEAD_FROM_DX=nan: the buffer is filled with NaNs ahead of the dX launch (tests: every value read was written)
+  if (w.cap >= need) {
+    if (poison) (void)hipMemsetAsync(w.p, 0xFF, sizeof(float) * (size_t)w.cap, st);
+    return w.p;
+  }
+  if (w.refused > 0 && need >= w.refused) return nullptr;
+  hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;   // (another stream may be capturing in global mode: see pair_grow)
+  (void)hipThreadExchangeStreamCaptureMode(&mode);
+  if (w.p) (void)hipFree(w.p);   // (waits for the device: no launch that uses the old buffer is still running)
+  w.p = nullptr;
+  w.cap = 0;
+  const bool ok = hipMalloc(reinterpret_cast<void**>(&w.p), sizeof(float) * (size_t)need) == hipSuccess;
+  (void)hipThreadExchangeStreamCaptureMode(&mode);
+  if (!ok) {
+    (void)hipGetLastError();
+    w.p = nullptr;
+    w.refused = need;
+    fprintf(stderr, "fastnerf: no memory for the per-tile head partials of the backward (%.1f MB): this stream keeps the head_grads launch\n",
+            4e-6 * (double)need);
+    return nullptr;
+  }
+  w.cap = need;
+  if (poison) (void)hipMemsetAsync(w.p, 0xFF, sizeof(float) * (size_t)w.cap, st);
+  return w.p;
+}
+}  // namespace fn
+
 template <int MM>
 static int bwd_launch_t(int kind, int64_t n, int S, const float* draw, const float* act, const float* params,
                       const float* packed_bwd, float* dact, float* partial, float* grads, const int* live_idx,
@@ -756,7 +857,8 @@ static int bwd_launch_t(int kind, int64_t n, int S, const float* draw, const flo
   const int ncu = num_cus();
   int grid = ncu * WG_PER_CU;
   if (ntiles < grid) grid = (int)ntiles;
-  if (int rc_dx = fn_launch_dx(MM, grid, st, P, draw, act, params, packed_bwd, dact, L, live_idx, live_cnt)) return rc_dx;
+  float* const headws = fn::head_workspace(ntiles, st);   // nullptr: the rgb-head / alpha-bias gradients take their own pass below
+  if (int rc_dx = fn_launch_dx(MM, grid, st, P, draw, act, params, packed_bwd, dact, L, live_idx, live_cnt, headws)) return rc_dx;
 
   // ---- dW jobs: every job writes per-chunk partials into its own region ------------------
   // (grids and chunk counts are functions of the point count alone -- one workgroup per CU and a fixed head-gradient grid for the jobs with
@@ -850,8 +952,15 @@ static int bwd_launch_t(int kind, int64_t n, int S, const float* draw, const flo
     segs(11, L.VW + 256, 283, 27, 0, 0);
   }
   add_seg(T, dw_job_base(9, ncu, PEP), 256, nwg, 1, 256, L.AW, 256, 256);   // dWa: the rank-1 row
-  // rgb head + alpha bias
-  {
+  // rgb head + alpha bias: the per-tile sums that dX left in headws, grouped into rows of the head region; without a workspace, their own pass
+  if (headws != nullptr) {
+    const int64_t hb = dw_job_base(12, ncu, PEP);
+    const int rows = ntiles < HEAD_ROWS ? (int)ntiles : HEAD_ROWS;   // (live list: the rows of the capacity; head_rows(live count) of them are written and reduced)
+    hipLaunchKernelGGL(head_group_kernel, dim3(rows, 4), dim3(128), 0, st, P, headws, partial + hb, live_cnt);
+    FN_LAUNCH_CHECK();
+    add_seg(T, hb, 388, rows, 1, 388, L.RW, 388, 387, 2);   // dWr (384) + dbr (3), contiguous in every layout
+    add_seg(T, hb + 387, 388, rows, 1, 1, L.AB, 1, 1, 2);   // dba
+  } else {
     const int hg = HEAD_MAX_WG;
     const int64_t hb = dw_job_base(12, ncu, PEP);
     hipLaunchKernelGGL(head_grads_kernel, dim3(hg), dim3(128), 0, st, P, draw, act + act_hv(P, PEP), partial + hb, live_idx, live_cnt);
@@ -868,7 +977,7 @@ static int bwd_launch_t(int kind, int64_t n, int S, const float* draw, const flo
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The paired bf16x6 backward (render.cpp rr_bwd: one call runs both passes of a two-net step on the saving route).  Order on the stream:
-//   fine pass:   dX, pe job, view job, head gradients      (x6_pair_pass: the caller's dact / partial workspaces)
+//   fine pass:   dX (+ per-tile head sums), pe job, view job, head_group      (x6_pair_pass: the caller's dact / partial workspaces)
 //   coarse pass: the same                                   (x6_pair_pass: the SIDE dact / partial set below)
 //   ONE trunk launch over the 14 jobs of both passes        (x6_pair_finish)
 //   reduce_all + unfold of the fine net, then of the coarse net

@@ -99,12 +99,12 @@ __global__ void __launch_bounds__(NTHR, 2 * NTHR / 512 * WG_PER_CU)
 mlp_bwd_dx_kernel(int64_t P, const float* __restrict__ draw, const float* __restrict__ act,
                   const float* __restrict__ params, const float* __restrict__ packed_t, float* __restrict__ dact,
                   NetLayout lay, unsigned* __restrict__ sched, const int* __restrict__ live_idx,
-                  const int* __restrict__ live_cnt) {
+                  const int* __restrict__ live_cnt, float* __restrict__ headws) {
   const int64_t PL = P;   // (live-list mode: see the forward kernel)
   if (live_idx) P = (int64_t)__builtin_amdgcn_readfirstlane(*live_cnt);
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* Hs = smem;
-  float* Es = smem + LDS_H;  // Es[0..127] = dalpha of the tile's rows
+  float* Es = smem + LDS_H;  // Es[0..127] = dalpha of the tile's rows; headws: Es[128 + c * TM + m] = draw[m][c], c = 0..2 (the head-gradient block below)
   volatile int* sched_word = reinterpret_cast<volatile int*>(Es + 1024);   // tile scheduler word (sched.h): unused part of Es
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -125,7 +125,9 @@ mlp_bwd_dx_kernel(int64_t P, const float* __restrict__ draw, const float* __rest
       const int64_t pp = ok ? p0 + pm : P - 1;
       const float4 dr = *reinterpret_cast<const float4*>(draw + (live_idx ? (int64_t)live_idx[pp] : pp) * 4);
       if (pq == 0) Es[pm] = ok ? dr.w : 0.f;
+      if (pq < 3) Es[128 + pq * TM + pm] = ok ? (pq == 0 ? dr.x : pq == 1 ? dr.y : dr.z) : 0.f;   // (stored with or without headws, like hv below: no branch in this phase)
       const float* wr = params + lay.RW;
+      asm volatile("" : "+s"(wr));   // per tile: hoisted out of the tile loop, the 96 registers of Wr are spilled to scratch
       const float* hv = act + act_hv(PL, lay.pe_pad) + pp * 128;
       float* dyv = dact + dact_yv(PL) + pp * 128;
 #pragma unroll
@@ -143,9 +145,53 @@ mlp_bwd_dx_kernel(int64_t P, const float* __restrict__ draw, const float* __rest
         if (!ok) o = make_float4(0.f, 0.f, 0.f, 0.f);
         *reinterpret_cast<float4*>(Hs + pm * 256 + ((((k >> 2) ^ (pm & 15))) << 2)) = o;
         if (ok) store_nt(dyv + k, o);
+        // hv itself into the half of H that phase A leaves free (columns 128 + k, same swizzle): the head gradients below
+        *reinterpret_cast<float4*>(Hs + pm * 256 + ((32 + ((k >> 2) ^ (pm & 15))) << 2)) = ok ? h : make_float4(0.f, 0.f, 0.f, 0.f);
       }
     }
     __syncthreads();
+    // ---- rgb head + alpha bias gradients of this tile (what head_grads_kernel takes a second pass over hv and draw for) ----
+    // headws[tile][0..383] = dWr[c][k] = sum_m draw[m][c] hv[m][k], [384..386] = dbr[c], [387] = dba: one thread per output (threads
+    // 0..127: channels 0 and 2 of column tid, which share the hv reads; 128..255: channel 1 of column tid - 128; 128..131 also the four plain sums), each a
+    // sum over the tile's rows in ascending order -- the value depends on the tile's points alone.  Rows >= valid hold zeros.
+    if (headws != nullptr) {
+      float* const o = headws + tile * 388;
+      int ht = tid;
+      asm volatile("" : "+v"(ht));   // this block's addresses are formed per tile: as loop invariants they cost registers the products need
+      const int k = ht & 127;
+      const float* hc = Hs + ((32 + (k >> 2)) << 2) + (k & 3);   // column 128 + k of row 0, before the swizzle
+      const int sw = (k >> 2) & 15;
+      const float* da = Es + 128 + (wave >> 1) * TM;             // channel 0 (waves 0, 1) / channel 1 (waves 2, 3)
+      const float* dc = Es + 128 + 2 * TM;
+      float s0 = 0.f, s2 = 0.f;   // (waves 2, 3 form s2 as well and drop it: one loop for the workgroup)
+#pragma unroll 1
+      for (int m0 = 0; m0 < TM; m0 += 16) {   // 16 rows at a time: the swizzle is a compile-time offset, the registers stay few
+        float h[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) h[j] = hc[(m0 + j) * 256 + ((sw ^ j) - sw) * 4];
+#pragma unroll
+        for (int j = 0; j < 16; j += 4) {
+          const float4 a = *reinterpret_cast<const float4*>(da + m0 + j);
+          const float4 c = *reinterpret_cast<const float4*>(dc + m0 + j);
+          s0 = fmaf(a.x, h[j], s0);     s2 = fmaf(c.x, h[j], s2);
+          s0 = fmaf(a.y, h[j + 1], s0); s2 = fmaf(c.y, h[j + 1], s2);
+          s0 = fmaf(a.z, h[j + 2], s0); s2 = fmaf(c.z, h[j + 2], s2);
+          s0 = fmaf(a.w, h[j + 3], s0); s2 = fmaf(c.w, h[j + 3], s2);
+        }
+      }
+      o[(wave >> 1) * 128 + k] = s0;
+      if (wave < 2) o[256 + k] = s2;
+      if (ht >= 128 && ht < 132) {   // dbr[0..2], dba
+        const float* ds = ht == 131 ? Es : Es + 128 + (ht - 128) * TM;
+        float sb = 0.f;
+#pragma unroll 1
+        for (int m = 0; m < TM; m += 4) {
+          const float4 a = *reinterpret_cast<const float4*>(ds + m);
+          sb += a.x; sb += a.y; sb += a.z; sb += a.w;
+        }
+        o[256 + ht] = sb;
+      }
+    }
     constexpr bool L16 = MM != MM_F32;
     // every 256 x 256 product after the first finds its first weights loaded one layer ahead (gemm_seg16, "chained weights")
     constexpr bool CHAIN = L16;
@@ -189,7 +235,7 @@ mlp_bwd_dx_kernel(int64_t P, const float* __restrict__ draw, const float* __rest
 
 template <int MM>
 static int launch_dx_t(int grid, hipStream_t st, int64_t P, const float* draw, const float* act, const float* params, const float* packed_bwd,
-                       float* dact, const NetLayout& L, const int* live_idx, const int* live_cnt) {
+                       float* dact, const NetLayout& L, const int* live_idx, const int* live_cnt, float* headws) {
   static bool attr_done = false;
   if (!attr_done) {
     FN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_bwd_dx_kernel<MM>),
@@ -198,14 +244,15 @@ static int launch_dx_t(int grid, hipStream_t st, int64_t P, const float* draw, c
   }
   unsigned* sched = b_sched_pair();
   FN_CHECK_ARG(sched != nullptr, "scheduler counters (hipMalloc failed?)");
-  hipLaunchKernelGGL(mlp_bwd_dx_kernel<MM>, dim3(grid), dim3(NTHR), LDS_BYTES, st, P, draw, act, params, packed_bwd, dact, L, sched, live_idx, live_cnt);
+  hipLaunchKernelGGL(mlp_bwd_dx_kernel<MM>, dim3(grid), dim3(NTHR), LDS_BYTES, st, P, draw, act, params, packed_bwd, dact, L, sched, live_idx, live_cnt, headws);
   FN_LAUNCH_CHECK();
   return 0;
 }
+// headws: room for [ceil(P / TM)][388] per-tile rgb-head / alpha-bias partials (P the capacity in live-list mode), or nullptr: not formed
 int fn_launch_dx(int mm, int grid, hipStream_t st, int64_t P, const float* draw, const float* act, const float* params, const float* packed_bwd,
-                 float* dact, const NetLayout& L, const int* live_idx, const int* live_cnt) {
-  return mm == MM_X6 ? launch_dx_t<MM_X6>(grid, st, P, draw, act, params, packed_bwd, dact, L, live_idx, live_cnt)
-                     : launch_dx_t<MM_F32>(grid, st, P, draw, act, params, packed_bwd, dact, L, live_idx, live_cnt);
+                 float* dact, const NetLayout& L, const int* live_idx, const int* live_cnt, float* headws) {
+  return mm == MM_X6 ? launch_dx_t<MM_X6>(grid, st, P, draw, act, params, packed_bwd, dact, L, live_idx, live_cnt, headws)
+                     : launch_dx_t<MM_F32>(grid, st, P, draw, act, params, packed_bwd, dact, L, live_idx, live_cnt, headws);
 }
 // The chain alone, on the grid the backward entry points give it (mlp_bwd_dw.hip, bwd_launch_t): for a caller that wants the
 // pre-activation gradients and no dW (sigma_grad.hip).
@@ -214,5 +261,5 @@ int fn_launch_dx_alone(int mm, int kind, int64_t P, const float* draw, const flo
   const int64_t ntiles = (P + TM - 1) / TM;
   int grid = num_cus() * WG_PER_CU;
   if (ntiles < grid) grid = (int)ntiles;
-  return fn_launch_dx(mm, grid, st, P, draw, act, params, packed_bwd, dact, layout_of(kind), nullptr, nullptr);
+  return fn_launch_dx(mm, grid, st, P, draw, act, params, packed_bwd, dact, layout_of(kind), nullptr, nullptr, nullptr);
 }
