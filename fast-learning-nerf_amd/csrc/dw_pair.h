@@ -1,8 +1,39 @@
-// dw_pair.h -- plain structures shared by mlp_bwd_dw.hip (which fills and launches them) and render.cpp (which holds the two DwDeferred
-// of a paired backward on its stack): the job table of a trunk launch, the segment table of reduce_all, and what a pass of the paired
-// bf16x6 backward leaves undone.  No HIP types here.
+// dw_pair.h -- plain structures shared by mlp_bwd_dw.hip (which fills and launches them), mlp_bf16.hip (the dW job table) and render.cpp
+// (which holds the two DwDeferred of a paired backward on its stack): the dW jobs of a net and their partial regions, the job table of a
+// trunk launch, the segment table of reduce_all, and what a pass of the paired bf16x6 backward leaves undone.  No HIP types here.
 #pragma once
 #include <stdint.h>
+
+// dW jobs of one net (mlp_bwd_dw.hip and mlp_bf16.hip): NO, KI, bias?, rank1?   (KI of the two pe jobs = the layout's pe_pad)
+struct DwJobDesc { int NO, KI, bias, rank1; };
+inline DwJobDesc dw_job(int j, int pe_pad) {
+  switch (j) {
+    case 0: return {256, pe_pad, 1, 0};     // L0 (pe)
+    case 8: return {256, pe_pad, 0, 0};     // L5 (pe part)
+    case 9: return {256, 256, 1, 1};        // bf16x3: feature / remap layer (+ alpha / sigma row).  fp32 / bf16x6 (the layer is folded): its region holds the view job's rank-1 partials and G
+    case 10: return {128, 256, 1, 0};       // view layer (h7 part: G = dL/dM; bf16x3: feature part)
+    case 11: return {128, 32, 0, 0};        // view layer (vpe part)
+    default: return {256, 256, 1, 0};       // 1..7: L1..L7 (h part)
+  }
+}
+#define HEAD_MAX_WG 1024
+inline int64_t dw_job_floats(int j, int pe_pad) {
+  const DwJobDesc d = dw_job(j, pe_pad);
+  return (int64_t)d.NO * d.KI + (d.bias ? d.NO : 0) + (d.rank1 ? d.KI : 0);
+}
+// regions in the order 0, 8, 1..7, 9, 10, 11 (then the head partials, "job 12"): the pairs that the bf16x6 path runs as ONE job
+// (0 + 8: both multiply the positional encoding; 10 + 11: both multiply dYv) are neighbours
+inline int64_t dw_job_base(int j, int ncu, int pe_pad) {
+  static const int order[12] = {0, 8, 1, 2, 3, 4, 5, 6, 7, 9, 10, 11};
+  int64_t o = 0;
+  for (int i = 0; i < 12; ++i) {
+    if (order[i] == j) return o;
+    o += dw_job_floats(order[i], pe_pad) * ncu;
+  }
+  return o;   // j == 12: everything
+}
+// floats of a net's partial buffer on a part with `ncu` CUs, sized for the widest layout (both *_partial_floats exports)
+inline int64_t dw_partial_floats(int ncu) { return dw_job_base(12, ncu, 96) + (int64_t)HEAD_MAX_WG * 388; }
 
 #define DW_TRUNK_JOBS 7
 struct DwTrunk {

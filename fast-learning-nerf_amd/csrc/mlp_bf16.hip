@@ -25,6 +25,8 @@
 // (then every store instruction writes 512 contiguous bytes); the final reduction un-permutes.
 #include <stdlib.h>
 #include "common.h"
+#include "dw_pair.h"
+#include "host_state.h"
 #include "sched.h"
 #include "mlp_layout.h"
 
@@ -41,16 +43,6 @@ __device__ __forceinline__ void bdbg_drain() {
 #define BTM 64
 #define BNTHR 256
 #define BLDS_BYTES (2 * BTM * 256 * 2 + 2 * BTM * 64 * 2)   // 81920
-
-static int b_num_cus() {
-  static int n = 0;
-  if (n > 0) return n;
-  int dev = 0;
-  hipDeviceProp_t p;
-  if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount;
-  if (n <= 0) n = 256;
-  return n;
-}
 
 __device__ __forceinline__ unsigned bf16_rne(float v) {   // bits of bf16(v), round to nearest even
   unsigned u = __float_as_uint(v);
@@ -159,18 +151,14 @@ static BOff b_offsets_bwd() {
   o.total = p;
   return o;
 }
-static const NetLayout& b_layout(int kind) {
-  static const NetLayout L[3] = {make_layout(0), make_layout(1), make_layout(2)};
-  return L[kind < 0 || kind > 2 ? 0 : kind];
-}
 
 extern "C" int64_t fastnerf_mlp_bf16_floats(int kind, int what, int64_t n_points) {
   if (kind < 0 || kind > 2) return -1;
   const int64_t nt = (n_points + BTM - 1) / BTM;
   switch (what) {
-    case 1: return b_offsets(b_layout(kind)).total * 4;   // packed forward weights
+    case 1: return b_offsets(layout_of(kind)).total * 4;   // packed forward weights
     case 2: return b_offsets_bwd().total * 4;              // packed backward (transposed) weights
-    case 3: return ba_total(nt, b_layout(kind).pe_pad) * 4;                       // saved activations for n_points
+    case 3: return ba_total(nt, layout_of(kind).pe_pad) * 4;                       // saved activations for n_points
     case 4: return bd_total(nt) * 4;                       // pre-activation gradients for n_points
     default: return -1;
   }
@@ -179,7 +167,7 @@ extern "C" int64_t fastnerf_mlp_bf16_floats(int kind, int what, int64_t n_points
 extern "C" int fastnerf_mlp_bf16_pack(int kind, const float* params, float* packed_fwd, float* packed_bwd,
                                       fn_stream_t stream) {
   FN_CHECK_ARG(kind >= 0 && kind <= 2 && params && packed_fwd, "kind in 0..2, non-null pointers");
-  const NetLayout& L = b_layout(kind);
+  const NetLayout& L = layout_of(kind);
   const BOff O = b_offsets(L), OB = b_offsets_bwd();
   BPackTable T;
   for (int l = 0; l < 8; ++l) {
@@ -858,26 +846,17 @@ mlp_fwd_bf16_kernel(int64_t P, int S, const float* __restrict__ rays, const floa
 static int b_fwd_launch(int kind, int64_t n, int S, const float* rays11, const float* z, const float* params,
                         const float* packed_fwd, float* raw, float* act, const int* live_idx, const int* live_cnt,
                         fn_stream_t stream, int flags = 0) {
-  const NetLayout& lay = b_layout(kind);
+  const NetLayout& lay = layout_of(kind);
   const BOff O = b_offsets(lay);
   const int64_t P = n * S;
   const int64_t ntiles = (P + BTM - 1) / BTM;
-  int grid = b_num_cus() * 2;
+  int grid = fn::device_cus() * 2;
   if (ntiles < grid) grid = (int)ntiles;
-  static bool attr_done = false;
-  if (!attr_done) {
-    FN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fwd_bf16_kernel<false, false>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, BLDS_BYTES));
-    FN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fwd_bf16_kernel<true, false>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, BLDS_BYTES));
-    FN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fwd_bf16_kernel<false, true>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, BLDS_BYTES));
-    FN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fwd_bf16_kernel<true, true>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, BLDS_BYTES));
-    FN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fwd_bf16_kernel<false, false, true>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, BLDS_BYTES));
-    attr_done = true;
-  }
+  static fn::DevOnce once;   // one flag for the five forward kernels
+#define FN_K(...) reinterpret_cast<const void*>(&mlp_fwd_bf16_kernel<__VA_ARGS__>)
+  const void* const kerns[5] = {FN_K(false, false), FN_K(true, false), FN_K(false, true), FN_K(true, true), FN_K(false, false, true)};
+#undef FN_K
+  if (int rc = fn::set_dyn_lds(kerns, 5, once, BLDS_BYTES)) return rc;
   const uint4* pk = reinterpret_cast<const uint4*>(packed_fwd);
   uint4* a4 = reinterpret_cast<uint4*>(act);
   const dim3 g(grid), b(BNTHR);
@@ -1348,29 +1327,9 @@ __global__ void __launch_bounds__(256) breduce_kernel(BRedTable tab, const float
   }
 }
 
-struct BJob { int NO, KI, bias, rank1; };
-static BJob b_job(int j, int pe_pad) {
-  switch (j) {
-    case 0: return {256, pe_pad, 1, 0};     // L0 (pe)
-    case 8: return {256, pe_pad, 0, 0};     // L5 (pe part)
-    case 9: return {256, 256, 1, 1};    // feature / remap (+ alpha / sigma row)
-    case 10: return {128, 256, 1, 0};   // view layer (feature part)
-    case 11: return {128, 32, 0, 0};    // view layer (vpe part)
-    default: return {256, 256, 1, 0};   // 1..7: L1..L7 (h part)
-  }
-}
-#define BHEAD_MAX_WG 1024
-static int64_t b_job_floats(int j, int pe_pad) {
-  const BJob d = b_job(j, pe_pad);
-  return (int64_t)d.NO * d.KI + (d.bias ? d.NO : 0) + (d.rank1 ? d.KI : 0);
-}
-static int64_t b_job_base(int j, int ncu, int pe_pad) {
-  int64_t o = 0;
-  for (int i = 0; i < j; ++i) o += b_job_floats(i, pe_pad) * ncu;
-  return o;
-}
+// (the dW jobs and their partial regions: dw_pair.h, shared with the fp32 / bf16x6 backward)
 extern "C" int64_t fastnerf_mlp_bf16_partial_floats(void) {
-  return b_job_base(12, b_num_cus(), 96) + (int64_t)BHEAD_MAX_WG * 388;   // sized for the widest layout
+  return dw_partial_floats(fn::device_cus());
 }
 
 template <int WO, int WI, int TO, int TI, bool BIAS, bool RANK1>
@@ -1383,11 +1342,8 @@ static int b_launch_dw(int64_t P, int64_t ntiles, const uint4* dY, int CTo, cons
   FN_CHECK_ARG(CTo == WO * TO && CTi == WI * TI, "dW job shape");
   constexpr int lds = 3 * (WO * TO + WI * TI) * 128 * 16;
   auto kern = mlp_bwd_dw_lds_bf16_kernel<WO, WI, TO, TI, BIAS, RANK1>;
-  static bool attr = false;
-  if (!attr) {
-    FN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    attr = true;
-  }
+  static fn::DevOnce once;
+  if (int rc = fn::set_dyn_lds(reinterpret_cast<const void*>(kern), once, lds)) return rc;
   hipLaunchKernelGGL(kern, dim3(nwg), dim3(WO * WI * 64), lds, st, P, ntiles, dY, X, dalpha, pw, pb, pr, live_cnt);
   FN_LAUNCH_CHECK();
   return 0;
@@ -1404,17 +1360,13 @@ static void b_add_seg(BRedTable& T, int64_t src, int64_t wg_stride, int nwg, int
 // dW (sigma_grad.hip).
 int fn_launch_dx_bf16(int kind, int64_t P, const float* draw, const float* act_f, const float* params, const float* packed_bwd,
                       float* dact_f, const int* live_idx, const int* live_cnt, hipStream_t st) {
-  const NetLayout& L = b_layout(kind);
+  const NetLayout& L = layout_of(kind);
   const BOff OB = b_offsets_bwd();
   const int64_t nt = (P + BTM - 1) / BTM;
-  int grid = b_num_cus() * 2;
+  int grid = fn::device_cus() * 2;
   if (nt < grid) grid = (int)nt;
-  static bool attr_done = false;
-  if (!attr_done) {
-    FN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_bwd_dx_bf16_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, BLDS_BYTES));
-    attr_done = true;
-  }
+  static fn::DevOnce once;
+  if (int rc = fn::set_dyn_lds(reinterpret_cast<const void*>(&mlp_bwd_dx_bf16_kernel), once, BLDS_BYTES)) return rc;
   unsigned* sched = b_sched_pair();
   FN_CHECK_ARG(sched != nullptr, "scheduler counters (hipMalloc failed?)");
   hipLaunchKernelGGL(mlp_bwd_dx_bf16_kernel, dim3(grid), dim3(BNTHR), BLDS_BYTES, st, P, draw, reinterpret_cast<const uint4*>(act_f), params,
@@ -1433,11 +1385,11 @@ void fn_bf16_sigma_grad_offsets(int64_t P, int64_t* pe, int64_t* dy0, int64_t* d
 static int b_bwd_launch(int kind, int64_t n, int S, const float* draw, const float* act_f, const float* params,
                         const float* packed_bwd, float* dact_f, float* partial, float* grads, const int* live_idx,
                         const int* live_cnt, fn_stream_t stream) {
-  const NetLayout& L = b_layout(kind);
+  const NetLayout& L = layout_of(kind);
   hipStream_t st = fn::S(stream);
   const int64_t P = n * S;
   const int64_t nt = (P + BTM - 1) / BTM;
-  const int ncu = b_num_cus();
+  const int ncu = fn::device_cus();
   const uint4* act = reinterpret_cast<const uint4*>(act_f);
   uint4* dact = reinterpret_cast<uint4*>(dact_f);
   if (int rc_dx = fn_launch_dx_bf16(kind, P, draw, act_f, params, packed_bwd, dact_f, live_idx, live_cnt, st)) return rc_dx;
@@ -1450,11 +1402,11 @@ static int b_bwd_launch(int kind, int64_t n, int S, const float* draw, const flo
   T.n = 0;
   int rc;
   const int PEP = L.pe_pad;
-  auto region = [&](int j) { return partial + b_job_base(j, ncu, PEP); };
+  auto region = [&](int j) { return partial + dw_job_base(j, ncu, PEP); };
   // permW: bit0 rows permuted, bit1 cols permuted
   auto segs = [&](int j, int64_t dstW, int ld, int validc, int permW, int64_t dstB, int64_t dstR) {
-    const BJob d = b_job(j, PEP);
-    const int64_t b = b_job_base(j, ncu, PEP);
+    const DwJobDesc d = dw_job(j, PEP);
+    const int64_t b = dw_job_base(j, ncu, PEP);
     b_add_seg(T, b, (int64_t)d.NO * d.KI, nwg, d.NO, d.KI, dstW, ld, validc, permW, 1);
     int64_t o = b + (int64_t)nwg * d.NO * d.KI;
     if (d.bias) { b_add_seg(T, o, d.NO, nwg, 1, d.NO, dstB, d.NO, d.NO, (permW & 1) ? 2 : 0, 1); o += (int64_t)nwg * d.NO; }
@@ -1487,8 +1439,8 @@ static int b_bwd_launch(int kind, int64_t n, int S, const float* draw, const flo
   segs(11, L.VW + 256, 283, 27, 0, 0, 0);
   // rgb head + alpha bias
   {
-    const int hg = BHEAD_MAX_WG;   // fixed, for the same reason as nwg
-    const int64_t hb = b_job_base(12, ncu, PEP);
+    const int hg = HEAD_MAX_WG;   // fixed, for the same reason as nwg
+    const int64_t hb = dw_job_base(12, ncu, PEP);
     hipLaunchKernelGGL(head_grads_bf16_kernel, dim3(hg), dim3(128), 0, st, P, nt, draw, act + ba_hv(nt), partial + hb, live_idx, live_cnt);
     FN_LAUNCH_CHECK();
     b_add_seg(T, hb, 388, hg, 1, 388, L.RW, 388, 387, 0);   // dWr (384) + dbr (3), contiguous in every layout

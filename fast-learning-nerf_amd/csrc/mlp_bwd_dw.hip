@@ -3,9 +3,6 @@
 #include "mlp_common.h"
 #include "dw_pair.h"
 #include <atomic>
-#include <map>
-#include <mutex>
-#include <utility>
 
 int fn_launch_dx(int mm, int grid, hipStream_t st, int64_t P, const float* draw, const float* act, const float* params, const float* packed_bwd,
                  float* dact, const NetLayout& L, const int* live_idx, const int* live_cnt, float* headws);   // mlp_bwd_dx.hip
@@ -675,36 +672,9 @@ __global__ void __launch_bounds__(256) unfold_kernel(const float* __restrict__ G
   else grads[VW + (int64_t)(r0 + ty) * 283 + c0 + tx] = (float)fma((double)grads[VB + r0 + ty], (double)params[FB + c0 + tx], s);
 }
 
-// dW jobs of one net: NO, KI, bias?, rank1?   (KI of the two pe jobs = the layout's pe_pad)
-struct DwJobDesc { int NO, KI, bias, rank1; };
-static DwJobDesc dw_job(int j, int pe_pad) {
-  switch (j) {
-    case 0: return {256, pe_pad, 1, 0};     // L0 (pe)
-    case 8: return {256, pe_pad, 0, 0};     // L5 (pe part)
-    case 9: return {256, 256, 1, 1};        // (the feature / remap layer's job before the fold: its region now holds the view job's rank-1 partials and G)
-    case 10: return {128, 256, 1, 0};       // view layer (h7 part: G = dL/dM)
-    case 11: return {128, 32, 0, 0};        // view layer (vpe part)
-    default: return {256, 256, 1, 0};       // 1..7: L1..L7 (h part)
-  }
-}
-#define HEAD_MAX_WG 1024
-static int64_t dw_job_floats(int j, int pe_pad) {
-  const DwJobDesc d = dw_job(j, pe_pad);
-  return (int64_t)d.NO * d.KI + (d.bias ? d.NO : 0) + (d.rank1 ? d.KI : 0);
-}
-// regions in the order 0, 8, 1..7, 9, 10, 11 (then the head partials, "job 12"): the pairs that the bf16x6 path runs as ONE job
-// (0 + 8: both multiply the positional encoding; 10 + 11: both multiply dYv) are neighbours
-static int64_t dw_job_base(int j, int ncu, int pe_pad) {
-  static const int order[12] = {0, 8, 1, 2, 3, 4, 5, 6, 7, 9, 10, 11};
-  int64_t o = 0;
-  for (int i = 0; i < 12; ++i) {
-    if (order[i] == j) return o;
-    o += dw_job_floats(order[i], pe_pad) * ncu;
-  }
-  return o;   // j == 12: everything
-}
+// (the dW jobs of one net and their partial regions -- DwJobDesc, dw_job, dw_job_base: dw_pair.h)
 extern "C" int64_t fastnerf_mlp_bwd_partial_floats(void) {
-  return dw_job_base(12, num_cus(), 96) + (int64_t)HEAD_MAX_WG * 388;   // sized for the widest layout
+  return dw_partial_floats(fn::device_cus());
 }
 
 template <int WO, int WI, int TO, int TI, bool BIAS, bool RANK1, int MM = MM_F32, int CTI2 = 0, int CTO2 = 0>
@@ -722,11 +692,8 @@ static int launch_dw(int64_t P, const float* dY, int ldy, const float* X, int ld
     }
     constexpr int lds6 = 2 * (WO * TO + WI * TI) * 3 * 1024 + 128;
     auto kern6 = mlp_bwd_dw6_kernel<WO, WI, TO, TI, BIAS, RANK1, CTI2, CTO2>;
-    static bool attr6 = false;
-    if (!attr6) {
-      FN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern6), hipFuncAttributeMaxDynamicSharedMemorySize, lds6));
-      attr6 = true;
-    }
+    static fn::DevOnce once6;
+    if (int rc = fn::set_dyn_lds(reinterpret_cast<const void*>(kern6), once6, lds6)) return rc;
     hipLaunchKernelGGL(kern6, dim3(nwg), dim3(WO * WI * 64), lds6, st, P, dY, X, draw, pw, pb, pr, live_idx, live_cnt, X2, dY2);
     FN_LAUNCH_CHECK();
     return 0;
@@ -735,11 +702,8 @@ static int launch_dw(int64_t P, const float* dY, int ldy, const float* X, int ld
     constexpr int STAGE = DW_MT * (NO + KI) + DW_MT;
     const size_t lds = 2 * STAGE * sizeof(float);
     auto kern = mlp_bwd_dw_kernel<WO, WI, TO, TI, BIAS, RANK1>;
-    static bool attr = false;
-    if (!attr) {
-      FN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      attr = true;
-    }
+    static fn::DevOnce once;
+    if (int rc = fn::set_dyn_lds(reinterpret_cast<const void*>(kern), once, (int)lds)) return rc;
     hipLaunchKernelGGL(kern, dim3(nwg), dim3(WO * WI * 64), lds, st, P, dY, ldy, X, ldx, draw, pw, pb, pr, live_idx, live_cnt);
     FN_LAUNCH_CHECK();
     return 0;
@@ -753,19 +717,7 @@ static void add_seg(RedTable& T, int64_t src, int64_t wg_stride, int nwg, int ro
   s.valid_cols = valid_cols; s.dyn = dyn; s.sc_cols = sc_cols; s.sc_dst = sc_dst;
 }
 
-// the trunk entries need 96 KiB of dynamic LDS: the attribute is set once per device (a process may drive several).  The flags are plain bools
-// written without a lock: two threads that race set the same attribute twice, which is harmless
-#define FN_MAX_DEV 64
-template <class K>
-static int trunk_lds_attr(K kern, bool (&done)[FN_MAX_DEV], int lds) {
-  int dev = 0;
-  FN_HIP(hipGetDevice(&dev));
-  if (dev < 0 || dev >= FN_MAX_DEV || !done[dev]) {
-    FN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    if (dev >= 0 && dev < FN_MAX_DEV) done[dev] = true;
-  }
-  return 0;
-}
+// the trunk entries need 96 KiB of dynamic LDS (fn::set_dyn_lds)
 constexpr int DW_TRUNK_LDS = 2 * 16 * 3 * 1024 + 128;
 // a job's partial region holds nwg chunks: on a part with fewer than 8 CUs dw_trunk_chunks can ask for more
 static int trunk_chunks_fit(int64_t P, int ncu, int nwg) {
@@ -789,57 +741,20 @@ static int bwd_reduce(const RedTable& T, const NetLayout& L, int64_t P, const fl
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The per-tile head partials [tiles][388] of the dX kernel: one buffer per (device, stream), grown on demand, reused every step, alive as long
-// as the process (the precedents: the fold buffer of mlp_pack.hip, fn::x6_pair_workspace below).  388 floats per 64 points: 19.1 MB for the
-// fine pass of the bench shape (12 288 tiles), which the coarse pass (4 096 tiles) of the same stream reuses behind it.  Never allocated inside
-// a stream capture; nullptr -- a capturing stream, a failed allocation (the refused size is remembered, one line goes to stderr), or
-// FASTNERF_HEAD_FROM_DX=0 in the environment (read at every call: the switch the tests compare the two routes with) -- sends the caller down
-// the head_grads_kernel route.  (FASTNERF_HEAD_FROM_DX=nan, also for the tests: the buffer is filled with NaNs before dX writes it.)
+// The per-tile head partials [tiles][388] of the dX kernel: a workspace the library owns (fn::stream_ws, slot WS_HEAD_TILES).  388 floats per
+// 64 points: 19.1 MB for the fine pass of the bench shape (12 288 tiles), which the coarse pass (4 096 tiles) of the same stream reuses behind
+// it.  nullptr -- no workspace (a capturing stream, no memory), or FASTNERF_HEAD_FROM_DX=0 in the environment (read at every call: the switch
+// the tests compare the two routes with) -- sends the caller down the head_grads_kernel route.  (FASTNERF_HEAD_FROM_DX=nan, also for the tests:
+// the buffer is filled with NaNs before dX writes it: every value read was written.)
 // ---------------------------------------------------------------------------------------------------------------------
 namespace fn {
-struct HeadWs {
-  float* p = nullptr;
-  int64_t cap = 0, refused = 0;
-};
-static std::mutex g_head_mu;
-static std::map<std::pair<int, hipStream_t>, HeadWs> g_head;
 static float* head_workspace(int64_t ntiles, hipStream_t st) {
   const char* e = getenv("FASTNERF_HEAD_FROM_DX");
   if (e && e[0] == '0') return nullptr;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cs) != hipSuccess) {
-    (void)hipGetLastError();
-    return nullptr;
-  }
-  if (cs != hipStreamCaptureStatusNone) return nullptr;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-  const int64_t need = (ntiles > 0 ? ntiles : 1) * 388;
-  std::lock_guard<std::mutex> lk(g_head_mu);
-  HeadWs& w = g_head[{dev, st}];
-  const bool poison = e && e[0] == 'n';   // FASTNERF_HEAD_FROM_DX=nan: the buffer is filled with NaNs ahead of the dX launch (tests: every value read was written)
-  if (w.cap >= need) {
-    if (poison) (void)hipMemsetAsync(w.p, 0xFF, sizeof(float) * (size_t)w.cap, st);
-    return w.p;
-  }
-  if (w.refused > 0 && need >= w.refused) return nullptr;
-  hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;   // (another stream may be capturing in global mode: see pair_grow)
-  (void)hipThreadExchangeStreamCaptureMode(&mode);
-  if (w.p) (void)hipFree(w.p);   // (waits for the device: no launch that uses the old buffer is still running)
-  w.p = nullptr;
-  w.cap = 0;
-  const bool ok = hipMalloc(reinterpret_cast<void**>(&w.p), sizeof(float) * (size_t)need) == hipSuccess;
-  (void)hipThreadExchangeStreamCaptureMode(&mode);
-  if (!ok) {
-    (void)hipGetLastError();
-    w.p = nullptr;
-    w.refused = need;
-    fprintf(stderr, "fastnerf: no memory for the per-tile head partials of the backward (%.1f MB): this stream keeps the head_grads launch\n",
-            4e-6 * (double)need);
-    return nullptr;
-  }
-  w.cap = need;
-  if (poison) (void)hipMemsetAsync(w.p, 0xFF, sizeof(float) * (size_t)w.cap, st);
+  static const WsName what = {
+      "fastnerf: no memory for the per-tile head partials of the backward (%.1f MB): this stream keeps the head_grads launch\n", 1e-6};
+  const StreamWs w = stream_ws(WS_HEAD_TILES, st, (ntiles > 0 ? ntiles : 1) * 388, what);
+  if (w.p && e && e[0] == 'n') (void)hipMemsetAsync(w.p, 0xFF, sizeof(float) * (size_t)w.cap, st);
   return w.p;
 }
 }  // namespace fn
@@ -854,7 +769,7 @@ static int bwd_launch_t(int kind, int64_t n, int S, const float* draw, const flo
   hipStream_t st = fn::S(stream);
   const int64_t P = n * S;
   const int64_t ntiles = (P + TM - 1) / TM;
-  const int ncu = num_cus();
+  const int ncu = fn::device_cus();
   int grid = ncu * WG_PER_CU;
   if (ntiles < grid) grid = (int)ntiles;
   float* const headws = fn::head_workspace(ntiles, st);   // nullptr: the rgb-head / alpha-bias gradients take their own pass below
@@ -922,8 +837,8 @@ static int bwd_launch_t(int kind, int64_t n, int S, const float* draw, const flo
     if (defer) {
       defer->J = J;   // (the paired backward: one launch for both passes, fn::x6_pair_finish)
     } else {
-      static bool attr_t[FN_MAX_DEV] = {};
-      if ((rc = trunk_lds_attr(mlp_bwd_dw6_trunk_kernel, attr_t, DW_TRUNK_LDS))) return rc;
+      static fn::DevOnce once_t;
+      if ((rc = fn::set_dyn_lds(reinterpret_cast<const void*>(mlp_bwd_dw6_trunk_kernel), once_t, DW_TRUNK_LDS))) return rc;
       hipLaunchKernelGGL(mlp_bwd_dw6_trunk_kernel, dim3(dw_trunk_chunks(P, ncu), DW_TRUNK_JOBS), dim3(512), DW_TRUNK_LDS, st, P, J, live_idx, live_cnt, ncu);
       FN_LAUNCH_CHECK();
     }
@@ -981,64 +896,24 @@ static int bwd_launch_t(int kind, int64_t n, int S, const float* draw, const flo
 //   coarse pass: the same                                   (x6_pair_pass: the SIDE dact / partial set below)
 //   ONE trunk launch over the 14 jobs of both passes        (x6_pair_finish)
 //   reduce_all + unfold of the fine net, then of the coarse net
-// The fine pass's dact and partials must survive the coarse pass, so the coarse pass gets a second dact + partial set that the library owns:
-// one per (device, stream), grown on demand, reused every step, alive as long as the process (the precedent: the fold buffer of mlp_pack.hip).
-// Its size is dact of the coarse pass's points (9.7 KB per point) + one partial buffer: 2.55 GB + 0.63 GB at 4096 x 64 coarse points on a 256-CU part.
-// It is never allocated inside a stream capture, and a failed allocation is no error: x6_pair_workspace returns false (once per size: the refused size is remembered, one line goes to stderr) and the caller takes the
-// unpaired route -- the same kernels on the same data, bit-identical gradients.
+// The fine pass's dact and partials must survive the coarse pass, so the coarse pass gets a second dact + partial set that the library owns
+// (fn::stream_ws, slots WS_PAIR_DACT and WS_PAIR_PARTIAL): dact of the coarse pass's points (9.7 KB per point) + one partial buffer, 2.55 GB +
+// 0.63 GB at 4096 x 64 coarse points on a 256-CU part.  Without it (a capturing stream, no memory) x6_pair_workspace returns false, which is
+// no error: the caller takes the unpaired route -- the same kernels on the same data, bit-identical gradients.
 // ---------------------------------------------------------------------------------------------------------------------
 namespace fn {
-struct PairWs {
-  float *dact = nullptr, *partial = nullptr;
-  int64_t dact_cap = 0, partial_cap = 0;
-  int64_t refused = 0;   // > 0: an allocation of this many floats failed -- requests that large are not tried again (no hipMalloc per step)
-};
-static std::mutex g_pair_mu;   // held for the whole of x6_pair_workspace: the map and every buffer in it
-static std::map<std::pair<int, hipStream_t>, PairWs> g_pair;
 static std::atomic<int64_t> g_pair_launches{0};
-
-static bool pair_grow(PairWs& w, float*& p, int64_t& cap, int64_t need) {
-  if (cap >= need) return true;
-  if (w.refused > 0 && need >= w.refused) return false;
-  // (another stream of the process may be in a global-mode capture, which forbids allocation calls from other threads: relaxed mode for this
-  // thread while it allocates, as allocators that live beside captures do)
-  hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
-  (void)hipThreadExchangeStreamCaptureMode(&mode);
-  if (p) (void)hipFree(p);   // (waits for the device: no launch that uses the old buffer is still running)
-  p = nullptr;
-  cap = 0;
-  const bool ok = hipMalloc(reinterpret_cast<void**>(&p), sizeof(float) * (size_t)need) == hipSuccess;
-  (void)hipThreadExchangeStreamCaptureMode(&mode);
-  if (!ok) {
-    (void)hipGetLastError();
-    p = nullptr;
-    w.refused = need;
-    fprintf(stderr, "fastnerf: no memory for the side workspace of the paired bf16x6 backward (%.2f GB): this stream keeps the per-pass trunk launches\n",
-            4e-9 * (double)need);
-    return false;
-  }
-  cap = need;
-  return true;
-}
 
 // the side dact / partial set of this (device, stream) for a coarse pass of P_coarse points; false: take the unpaired route
 bool x6_pair_workspace(int64_t P_coarse, fn_stream_t stream, float** dact2, float** partial2) {
-  hipStream_t st = S(stream);
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cs) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  if (cs != hipStreamCaptureStatusNone) return false;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return false;
-  std::lock_guard<std::mutex> lk(g_pair_mu);
-  PairWs& w = g_pair[{dev, st}];
-  if (!pair_grow(w, w.dact, w.dact_cap, P_coarse * (int64_t)DACT_FLOATS) ||
-      !pair_grow(w, w.partial, w.partial_cap, fastnerf_mlp_bwd_partial_floats()))
-    return false;
-  *dact2 = w.dact;
-  *partial2 = w.partial;
+  static const WsName what = {
+      "fastnerf: no memory for the side workspace of the paired bf16x6 backward (%.2f GB): this stream keeps the per-pass trunk launches\n", 1e-9};
+  const StreamWs d = stream_ws(WS_PAIR_DACT, S(stream), P_coarse * (int64_t)DACT_FLOATS, what);
+  if (!d.p) return false;
+  const StreamWs p = stream_ws(WS_PAIR_PARTIAL, S(stream), fastnerf_mlp_bwd_partial_floats(), what);
+  if (!p.p) return false;
+  *dact2 = d.p;
+  *partial2 = p.p;
   return true;
 }
 
@@ -1053,7 +928,7 @@ int x6_pair_pass(DwDeferred* d, int64_t n, int S, const float* draw, const float
 // ONE trunk launch over both passes, then each net's reduction and unfold
 int x6_pair_finish(const DwDeferred* fine, const DwDeferred* coarse, fn_stream_t stream) {
   hipStream_t st = S(stream);
-  const int ncu = num_cus();
+  const int ncu = fn::device_cus();
   const DwDeferred* d[2] = {fine, coarse};
   DwTrunkPair A;
   int nwg = 0;
@@ -1062,8 +937,8 @@ int x6_pair_finish(const DwDeferred* fine, const DwDeferred* coarse, fn_stream_t
     A.P[k] = d[k]->P;
     nwg += DW_TRUNK_JOBS * dw_trunk_chunks(A.P[k], ncu);   // (each count fits its regions: bwd_launch_t has checked)
   }
-  static bool attr_p[FN_MAX_DEV] = {};
-  if (int rc = trunk_lds_attr(mlp_bwd_dw6_trunk_pair_kernel, attr_p, DW_TRUNK_LDS)) return rc;
+  static DevOnce once_p;
+  if (int rc = set_dyn_lds(reinterpret_cast<const void*>(mlp_bwd_dw6_trunk_pair_kernel), once_p, DW_TRUNK_LDS)) return rc;
   hipLaunchKernelGGL(mlp_bwd_dw6_trunk_pair_kernel, dim3(nwg), dim3(512), DW_TRUNK_LDS, st, A, ncu);
   FN_LAUNCH_CHECK();
   g_pair_launches.fetch_add(1, std::memory_order_relaxed);

@@ -236,12 +236,8 @@ mlp_bwd_dx_kernel(int64_t P, const float* __restrict__ draw, const float* __rest
 template <int MM>
 static int launch_dx_t(int grid, hipStream_t st, int64_t P, const float* draw, const float* act, const float* params, const float* packed_bwd,
                        float* dact, const NetLayout& L, const int* live_idx, const int* live_cnt, float* headws) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    FN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_bwd_dx_kernel<MM>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    attr_done = true;
-  }
+  static fn::DevOnce once;
+  if (int rc = fn::set_dyn_lds(reinterpret_cast<const void*>(&mlp_bwd_dx_kernel<MM>), once, LDS_BYTES)) return rc;
   unsigned* sched = b_sched_pair();
   FN_CHECK_ARG(sched != nullptr, "scheduler counters (hipMalloc failed?)");
   hipLaunchKernelGGL(mlp_bwd_dx_kernel<MM>, dim3(grid), dim3(NTHR), LDS_BYTES, st, P, draw, act, params, packed_bwd, dact, L, sched, live_idx, live_cnt, headws);
@@ -259,7 +255,7 @@ int fn_launch_dx(int mm, int grid, hipStream_t st, int64_t P, const float* draw,
 int fn_launch_dx_alone(int mm, int kind, int64_t P, const float* draw, const float* act, const float* params, const float* packed_bwd,
                        float* dact, hipStream_t st) {
   const int64_t ntiles = (P + TM - 1) / TM;
-  int grid = num_cus() * WG_PER_CU;
+  int grid = fn::device_cus() * WG_PER_CU;
   if (ntiles < grid) grid = (int)ntiles;
   return fn_launch_dx(mm, grid, st, P, draw, act, params, packed_bwd, dact, layout_of(kind), nullptr, nullptr, nullptr);
 }

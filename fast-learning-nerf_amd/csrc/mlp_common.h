@@ -27,6 +27,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "common.h"
+#include "host_state.h"
 #include "mlp_layout.h"
 #include "sched.h"
 
@@ -73,22 +74,6 @@ constexpr int ABL_WPIECES = (FASTNERF_ABLATION & 8) ? 1 : ((FASTNERF_ABLATION & 
 #define LDS_H (TM * 256)
 #define LDS_E (TM * 64)
 #define LDS_BYTES ((LDS_H + LDS_E) * 4)
-
-static int g_num_cus = 0;
-static inline int num_cus() {
-  if (g_num_cus > 0) return g_num_cus;
-  int dev = 0;
-  hipDeviceProp_t p;
-  if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) g_num_cus = p.multiProcessorCount;
-  if (g_num_cus <= 0) g_num_cus = 256;
-  return g_num_cus;
-}
-
-
-static inline const NetLayout& layout_of(int kind) {
-  static const NetLayout L[3] = {make_layout(0), make_layout(1), make_layout(2)};
-  return L[kind < 0 || kind > 2 ? 0 : kind];
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // operand splits (used by the weight packing and by the kernels)

@@ -300,11 +300,8 @@ static int fwd_launch_t(int grid, hipStream_t st, int64_t P, int S, const float*
                         const float* packed_fwd, float* raw, float* act, const NetLayout& lay, unsigned* sched, const int* live_idx,
                         const int* live_cnt, int flags) {
   auto kern = mlp_fwd_kernel<SAVE, BG, MM, LIST>;
-  static bool attr = false;
-  if (!attr) {
-    FN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    attr = true;
-  }
+  static fn::DevOnce once;
+  if (int rc = fn::set_dyn_lds(reinterpret_cast<const void*>(kern), once, LDS_BYTES)) return rc;
   const float* fold = fn_fold_buffer(packed_fwd, false);   // the folded view layer that the pack call left beside this buffer (mlp_pack.hip)
   FN_CHECK_ARG(fold != nullptr, "packed_fwd was not filled by a pack call of this process (the folded view layer is kept by its address)");
   hipLaunchKernelGGL(kern, dim3(grid), dim3(NTHR), LDS_BYTES, st, P, S, rays11, z, params, packed_fwd, fold, raw, act, lay, sched, live_idx,
@@ -319,7 +316,7 @@ static int fwd_launch(int kind, int64_t n, int S, const float* rays11, const flo
   const NetLayout& lay = layout_of(kind);
   const int64_t P = n * S;
   const int64_t ntiles = (P + TM - 1) / TM;
-  int grid = num_cus() * WG_PER_CU;
+  int grid = fn::device_cus() * WG_PER_CU;
   if (ntiles < grid) grid = (int)ntiles;
   hipStream_t st = fn::S(stream);
   unsigned* sched = b_sched_pair();

@@ -60,6 +60,11 @@ inline NetLayout make_layout(int kind) {
   L.pb_total = p;
   return L;
 }
+// the three layouts, made once (kind out of range: kind 0; the entry points check it first)
+inline const NetLayout& layout_of(int kind) {
+  static const NetLayout L[3] = {make_layout(0), make_layout(1), make_layout(2)};
+  return L[kind < 0 || kind > 2 ? 0 : kind];
+}
 
 // float offset of a plain-float region (PFB, PFR) in a packed buffer: the bf16x6 packing holds 3/2 floats per unit of the offsets above
 inline __host__ __device__ int64_t fold_plain(int64_t off, bool x6) { return x6 ? off * 3 / 2 : off; }

@@ -137,6 +137,32 @@ def test_side_workspace_regrowth(fn, golden_dir):
     assert torch.equal(first[0], third[0]) and torch.equal(first[1], third[1])
 
 
+def test_two_streams_own_their_workspaces(fn, golden_dir):
+    """The library-owned workspaces (head tiles, side dact, side partials: csrc/host_state.h fn::stream_ws) are kept per (device, stream):
+    a stream's first call allocates its own, a larger call on one stream regrows that stream's only, and every stream computes what the
+    default stream computes.  One call at a time, each followed by a synchronize: the keys are under test, not concurrency."""
+    small, large = (64, 16, 32), (256, 48, 16)
+    A, B = torch.cuda.Stream(), torch.cuda.Stream()
+
+    def one_call(stream, shape):
+        before = pair_launches(fn)
+        if stream is None:
+            res = both_routes(fn, golden_dir, 'bf16x6', *shape)[0]
+        else:
+            with torch.cuda.stream(stream):
+                res = both_routes(fn, golden_dir, 'bf16x6', *shape)[0]
+        torch.cuda.synchronize()
+        assert pair_launches(fn) - before == 1      # (both_routes has checked that it was the one call's)
+        return res
+
+    ref_small = one_call(None, small)
+    got = [(one_call(A, large), large), (one_call(B, small), small), (one_call(A, small), small)]
+    ref = {small: ref_small, large: one_call(None, large)}      # (the default stream's own regrowth comes last: the order above is the test)
+    for k, ((gc, gf), shape) in enumerate(got):
+        assert torch.isfinite(gc).all() and torch.isfinite(gf).all() and float(gf.abs().max()) > 0 and float(gc.abs().max()) > 0
+        assert torch.equal(gc, ref[shape][0]) and torch.equal(gf, ref[shape][1]), ('call', k + 2, shape)
+
+
 def _trainer(fn):
     torch.manual_seed(3)
     args = fn.run_nerf.make_args(N_importance=32, N_samples=16, perturb=1.0, white_bkgd=True, no_reload=True, lrate=5e-4, lrate_decay=500)
