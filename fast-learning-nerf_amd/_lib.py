@@ -175,6 +175,10 @@ SIGNATURES = {
     'fastnerf_mlp_x6_fwd_list': (I, [I, L, I, P, P, P, P, P, P, P, I, P]),
     'fastnerf_render_rays_fwd_occ': (I, [I, L, I, I, P, I, I, I, I, P, P, U64, U64, P, P, P, P, C.POINTER(OccGrid), P, P] + [P] * 16 + [I, P]),
     'fastnerf_render_rays_fwd_occ_cascade': (I, [I, L, I, I, P, I, I, I, I, P, P, U64, U64, P, P, P, P, C.POINTER(OccCascade), P, P] + [P] * 16 + [I, P]),
+    'fastnerf_ert_classify': (I, [C.POINTER(OccGrid), C.POINTER(OccCascade), L, I, I, I, P, P, P, F, P, P, P, P, P]),
+    'fastnerf_ert_advance': (I, [L, I, I, I, P, P, P, I, P, P, P, P]),
+    'fastnerf_render_rays_fwd_ert': (I, [I, L, I, I, P, I, I, I, I, P, P, U64, U64, P, P, P, P, C.POINTER(OccGrid), C.POINTER(OccCascade), F, I,
+                                         P, P, P] + [P] * 16 + [I, P]),
     'fastnerf_mlp_sigma_grad_ws_floats': (L, [I, L]),
     'fastnerf_mlp_sigma_grad': (I, [I, I, L, I, P, P, P, P, P, P, P, P, P]),
     'fastnerf_ray_grad_ws_floats': (L, [I, L, I]),

@@ -584,6 +584,53 @@ extern "C" int fastnerf_raw2outputs_bwd_full(int64_t n, int S, const float* raw,
   return 0;
 }
 
+// ---- early ray termination (include/fastnerf.h, occupancy.hip): the transmittance of every ray after the segment [s0, s1) of its S
+// samples, T[r] = (first ? 1 : T[r]) * prod_{s0 <= s < s1} (1 - alpha_s + 1e-10) with alpha, dist and |d| formed by eval_chunk under
+// nerf_cfg(), as raw2outputs_fwd_kernel forms them.  One wave per ray, lane l takes the samples s0 + l * C + j (C = ceil((s1 - s0) / 64),
+// consecutive lanes read consecutive float4 of raw and floats of z); eval_chunk sees the segment plus the sample behind it, or the
+// ray's end, so only the last sample of the ray gets the 1e10.  total (optional): the pass's running (evaluated, total) counters, + the segment's list length, one lane.
+__global__ void __launch_bounds__(256) ert_advance_kernel(int64_t n, int S, int s0, int s1, const float* __restrict__ raw,
+                                                           const float* __restrict__ z, const float* __restrict__ rays, int first,
+                                                           float* __restrict__ trans, const int* __restrict__ seg_count,
+                                                           int* __restrict__ total) {
+  const int lane = threadIdx.x & 63;
+  const int W = s1 - s0;
+  const int C = (W + WAVE - 1) / WAVE;
+  const int64_t wave0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  const CompCfg cfg = nerf_cfg();
+  for (int64_t r = wave0; r < n; r += nwaves) {
+    const float* rr = rays + r * 11;
+    const float dnorm = sqrtf(fadd(fadd(fmul(rr[3], rr[3]), fmul(rr[4], rr[4])), fmul(rr[5], rr[5])));
+    SampleVals v[MAXC];
+    int cnt;
+    // (length W + 1 while the ray goes on: sample s1 is there for s1 - 1's dist and is dropped below; lanes beyond it load nothing)
+    eval_chunk<false>(S - s0 < W + 1 ? S - s0 : W + 1, C, lane, raw + (r * S + s0) * 4, z + r * S + s0, nullptr, dnorm, v, cnt, cfg, 0.f);
+    float prod = 1.0f;
+#pragma unroll
+    for (int j = 0; j < MAXC; ++j)
+      if (j < cnt && lane * C + j < W) prod *= v[j].t;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) prod *= __shfl_xor(prod, o, WAVE);
+    if (lane == 0) trans[r] = first ? prod : trans[r] * prod;
+  }
+  if (total && blockIdx.x == 0 && threadIdx.x == 0) {
+    total[0] = (first ? 0 : total[0]) + seg_count[0];
+    total[1] = (int)(n * S);
+  }
+}
+
+extern "C" int fastnerf_ert_advance(int64_t n, int S, int s0, int s1, const float* raw, const float* z, const float* rays11, int first,
+                                    float* trans, const int32_t* seg_count, int32_t* total, fn_stream_t stream) {
+  FN_CHECK_ARG(n > 0 && S >= 1 && S <= WAVE * MAXC && n * (int64_t)S < ((int64_t)1 << 31), "n > 0, 1 <= S <= 512, n * S < 2^31");
+  FN_CHECK_ARG(s0 >= 0 && s0 < s1 && s1 <= S, "0 <= s0 < s1 <= S");
+  FN_CHECK_ARG(raw && z && rays11 && trans && (!total || seg_count), "non-null pointers (seg_count with total)");
+  hipLaunchKernelGGL(ert_advance_kernel, dim3(grid_waves(n)), dim3(256), 0, fn::S(stream), n, S, s0, s1, raw, z, rays11, first ? 1 : 0,
+                     trans, seg_count, total);
+  FN_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int fastnerf_sample_pdf_merge(int64_t n, int S, int Ni, const float* z, const float* weights, int det,
                                          const float* u, uint64_t seed, float* z_out, float* z_samples, float* z_std,
                                          fn_stream_t stream) {

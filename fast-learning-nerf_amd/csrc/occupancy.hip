@@ -28,6 +28,10 @@
 //   pointers) and are read through scalar loads: the level loop's bounds and counter are wave-uniform, each lane leaves it at its
 //   own level.  The six instantiations compile to the instructions of the kernels once written out per form (hipcc -S listings
 //   compared with tools/isa_funcs.py: 11 kernels identical, 0 differ); timings: profiles/occupancy_render.md.
+//   Early ray termination (fastnerf_ert_classify) is a further descriptor of the count / scatter kernels, ErtDev<G>: the entries of one
+//   segment of B consecutive samples per ray, evaluated when the ray's transmittance is still > eps AND G (one grid, a cascade, or
+//   OccAll = no grid) says occupied.  The instantiations above are untouched by it (isa_funcs.py: 11 identical, 0 differ).  The
+//   transmittance itself is advanced by ert_advance_kernel in composite.hip, next to the compositing arithmetic it repeats.
 // All of them are memory bound and small next to the MLP they spare: one lane per cell / point / four consecutive samples, a
 // ray's 44 bytes come through the cache for all its samples.
 #include "common.h"
@@ -36,6 +40,7 @@ namespace fn {
 void cp_scan_launch(int nb, int32_t* blk, int32_t* count_out, int n_points, hipStream_t st);   // train.hip
 }
 
+#define OCC_GRID_ARG "grid: non-null words, 1 <= n[i] <= 2^24, fewer than 2^31 cells, finite lo, finite inv > 0"
 #define OCC_BLOCK 256
 #define OCC_PTS 1024   // samples per block of the classify passes (256 threads x 4) = CP_PTS of train.hip, whose scan and
                        // fastnerf_compact_ws_ints this file reuses
@@ -61,6 +66,20 @@ struct OccCascadeDev {
   const uint32_t* words[FN_OCC_MAX_LEVELS];
   int levels;
   int outside;
+};
+
+// early ray termination (fastnerf_ert_classify): no grid at all -- every point counts as occupied, and nothing of it is loaded
+struct OccAll {};
+
+// One segment [s0, s0 + w) of a pass's S samples per ray, sorted by the ray's transmittance and then by G (OccDev, OccCascadeDev
+// or OccAll): entry q of the n * w samples of the segment is sample (q / w) * S + s0 + q % w of the pass, so ascending q is
+// ascending sample index.  trans == NULL: every ray passes (the first segment, whose T is 1).
+template <class G>
+struct ErtDev {
+  G g;
+  const float* trans;
+  float eps;
+  uint32_t s0, w;
 };
 
 struct OccDims {
@@ -92,6 +111,8 @@ __device__ __forceinline__ bool occ_point(const OccCascadeDev& c, float x, float
   }
   return c.outside != 0;
 }
+
+__device__ __forceinline__ bool occ_point(const OccAll&, float, float, float) { return true; }
 
 // the block's 256 predicate bits -> 8 words; every thread of the block calls it (c is the thread's cell, b false beyond the grid)
 __device__ __forceinline__ void occ_store_bits(bool b, int64_t c, uint32_t* __restrict__ words, int64_t nwords) {
@@ -216,19 +237,38 @@ __global__ void __launch_bounds__(OCC_BLOCK) occ_update_kernel(const float* __re
   if (words) occ_store_bits(b, c, words, d.nwords);   // (uniform: words == NULL updates the density only)
 }
 
-// bits 0..3: samples p0 .. p0+3 of the pass are occupied (x = o + d * z as the MLP kernels compute it)
+// entry q of a classify pass -> the sample index it stands for: itself, or the segment's sample (ErtDev)
+template <class G>
+__device__ __forceinline__ int64_t occ_sample(const G&, int64_t q, uint32_t) { return q; }
+template <class G>
+__device__ __forceinline__ int64_t occ_sample(const ErtDev<G>& e, int64_t q, uint32_t S) {
+  const uint32_t r = (uint32_t)q / e.w;   // n * w <= n * S < 2^31
+  return (int64_t)(r * S + e.s0 + ((uint32_t)q - r * e.w));
+}
+
+// sample p of the pass is evaluated: its point x = o + d * z (as the MLP kernels compute it) is occupied -- and, through an ErtDev,
+// its ray's transmittance is still > eps (a NaN is not)
+template <class G>
+__device__ __forceinline__ bool occ_live(const G& g, const float* __restrict__ rays, const float* __restrict__ zv, uint32_t S, int64_t p) {
+  const float* rr = rays + (int64_t)((uint32_t)p / S) * 11;   // n < 2^31
+  const float zz = zv[p];
+  return occ_point(g, fadd(rr[0], fmul(rr[3], zz)), fadd(rr[1], fmul(rr[4], zz)), fadd(rr[2], fmul(rr[5], zz)));
+}
+template <class G>
+__device__ __forceinline__ bool occ_live(const ErtDev<G>& e, const float* __restrict__ rays, const float* __restrict__ zv, uint32_t S,
+                                         int64_t p) {
+  if (e.trans && !(e.trans[(uint32_t)p / S] > e.eps)) return false;
+  return occ_live(e.g, rays, zv, S, p);
+}
+
+// bits 0..3: entries p0 .. p0+3 of the pass are evaluated
 template <class G>
 __device__ __forceinline__ unsigned occ_flags(const G& g, const float* __restrict__ rays, const float* __restrict__ zv, uint32_t S,
                                               int64_t p0, int64_t n) {
   unsigned f = 0;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const int64_t p = p0 + k;
-    if (p < n) {
-      const float* rr = rays + (int64_t)((uint32_t)p / S) * 11;   // n < 2^31
-      const float zz = zv[p];
-      if (occ_point(g, fadd(rr[0], fmul(rr[3], zz)), fadd(rr[1], fmul(rr[4], zz)), fadd(rr[2], fmul(rr[5], zz)))) f |= 1u << k;
-    }
+    if (p0 + k < n && occ_live(g, rays, zv, S, occ_sample(g, p0 + k, S))) f |= 1u << k;
   }
   return f;
 }
@@ -264,8 +304,8 @@ __global__ void __launch_bounds__(OCC_BLOCK) occ_scatter_kernel(G g, int64_t n, 
   for (int k = 0; k < w; ++k) pos += wsum[k];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    if (f & (1u << k)) live_idx[pos++] = (int)(p0 + k);
-    else if (raw && p0 + k < n) *reinterpret_cast<float4*>(raw + (p0 + k) * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (f & (1u << k)) live_idx[pos++] = (int)occ_sample(g, p0 + k, (uint32_t)S);
+    else if (raw && p0 + k < n) *reinterpret_cast<float4*>(raw + occ_sample(g, p0 + k, (uint32_t)S) * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
   }
 }
 
@@ -337,10 +377,10 @@ void occ_query_launch(const G& g, int64_t n, const float* pts, uint8_t* out, hip
   hipLaunchKernelGGL(occ_query_kernel<G>, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(OCC_BLOCK), 0, s, g, n, pts, out);
 }
 
+// P: the entries of the pass (n * S samples, or the n * w of a segment)
 template <class G>
-void occ_classify_launch(const G& g, int64_t n, int S, const float* rays11, const float* z, int32_t* live_idx, int32_t* count_out,
+void occ_classify_launch(const G& g, int64_t P, int S, const float* rays11, const float* z, int32_t* live_idx, int32_t* count_out,
                          float* raw, int32_t* ws, hipStream_t s) {
-  const int64_t P = n * (int64_t)S;
   const int nb = (int)((P + OCC_PTS - 1) / OCC_PTS);
   hipLaunchKernelGGL(occ_count_kernel<G>, dim3(nb), dim3(OCC_BLOCK), 0, s, g, P, S, rays11, z, ws);
   fn::cp_scan_launch(nb, ws, count_out, (int)P, s);
@@ -384,7 +424,7 @@ extern "C" int fastnerf_occ_from_mask(const uint8_t* mask, int64_t nx, int64_t n
 
 extern "C" int fastnerf_occ_query(const fn_occ_grid* grid, int64_t n, const float* pts, uint8_t* out, fn_stream_t stream) {
   OccDev g;
-  FN_CHECK_ARG(occ_dev(grid, &g), "grid: non-null words, 1 <= n[i] <= 2^24, fewer than 2^31 cells, finite lo, finite inv > 0");
+  FN_CHECK_ARG(occ_dev(grid, &g), OCC_GRID_ARG);
   FN_CHECK_ARG(n >= 0, "n >= 0");
   if (n == 0) return 0;
   FN_CHECK_ARG(pts && out, "non-null pointers");
@@ -427,21 +467,26 @@ extern "C" int fastnerf_occ_update(const float* raw_c, const float* raw_f, int64
 extern "C" int fastnerf_occ_classify(const fn_occ_grid* grid, int64_t n, int S, const float* rays11, const float* z, int32_t* live_idx,
                                      int32_t* count_out, float* raw, int32_t* ws, fn_stream_t stream) {
   OccDev g;
-  FN_CHECK_ARG(occ_dev(grid, &g), "grid: non-null words, 1 <= n[i] <= 2^24, fewer than 2^31 cells, finite lo, finite inv > 0");
+  FN_CHECK_ARG(occ_dev(grid, &g), OCC_GRID_ARG);
   FN_CHECK_ARG(n > 0 && S >= 1 && n * (int64_t)S < ((int64_t)1 << 31), "n > 0, S >= 1, n * S < 2^31");
   FN_CHECK_ARG(rays11 && z && live_idx && count_out && ws, "non-null pointers");
-  occ_classify_launch(g, n, S, rays11, z, live_idx, count_out, raw, ws, fn::S(stream));
+  occ_classify_launch(g, n * (int64_t)S, S, rays11, z, live_idx, count_out, raw, ws, fn::S(stream));
   FN_LAUNCH_CHECK();
   return 0;
 }
 
 #define OCC_CASCADE_ARG "cascade: 1 <= levels <= 8; every level: non-null words, 1 <= n[i] <= 2^24, fewer than 2^31 cells, finite lo, finite inv > 0"
 
-// render.cpp checks a cascade before it enqueues anything: NULL when every level is usable, else what is asked of one
+// render.cpp checks a cascade (a grid: fastnerf_render_rays_fwd_ert) before it enqueues anything: NULL when every level is usable, else
+// what is asked of one
 namespace fn {
 const char* occ_cascade_fault(const fn_occ_cascade* c) {
   OccCascadeDev d;
   return occ_cascade_dev(c, &d) ? nullptr : OCC_CASCADE_ARG;
+}
+const char* occ_grid_fault(const fn_occ_grid* g) {
+  OccDev d;
+  return occ_dev(g, &d) ? nullptr : OCC_GRID_ARG;
 }
 }  // namespace fn
 
@@ -462,7 +507,35 @@ extern "C" int fastnerf_occ_classify_cascade(const fn_occ_cascade* cascade, int6
   FN_CHECK_ARG(occ_cascade_dev(cascade, &g), OCC_CASCADE_ARG);
   FN_CHECK_ARG(n > 0 && S >= 1 && n * (int64_t)S < ((int64_t)1 << 31), "n > 0, S >= 1, n * S < 2^31");
   FN_CHECK_ARG(rays11 && z && live_idx && count_out && ws, "non-null pointers");
-  occ_classify_launch(g, n, S, rays11, z, live_idx, count_out, raw, ws, fn::S(stream));
+  occ_classify_launch(g, n * (int64_t)S, S, rays11, z, live_idx, count_out, raw, ws, fn::S(stream));
+  FN_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- early ray termination (include/fastnerf.h): one segment of the image pass sorted by T[ray] > eps AND the grid / cascade / nothing
+template <class G>
+static void ert_classify_launch(const G& g, int64_t n, int S, int s0, int s1, const float* rays11, const float* z, const float* trans,
+                                float eps, int32_t* live_idx, int32_t* count_out, float* raw, int32_t* ws, hipStream_t s) {
+  const ErtDev<G> e = {g, trans, eps, (uint32_t)s0, (uint32_t)(s1 - s0)};
+  occ_classify_launch(e, n * (int64_t)(s1 - s0), S, rays11, z, live_idx, count_out, raw, ws, s);
+}
+
+extern "C" int fastnerf_ert_classify(const fn_occ_grid* grid, const fn_occ_cascade* cascade, int64_t n, int S, int s0, int s1,
+                                     const float* rays11, const float* z, const float* trans, float eps, int32_t* live_idx,
+                                     int32_t* count_out, float* raw, int32_t* ws, fn_stream_t stream) {
+  OccDev g;
+  OccCascadeDev c;
+  FN_CHECK_ARG(!grid || !cascade, "at most one of grid / cascade");
+  FN_CHECK_ARG(!grid || occ_dev(grid, &g), OCC_GRID_ARG);
+  FN_CHECK_ARG(!cascade || occ_cascade_dev(cascade, &c), OCC_CASCADE_ARG);
+  FN_CHECK_ARG(n > 0 && S >= 1 && n * (int64_t)S < ((int64_t)1 << 31), "n > 0, S >= 1, n * S < 2^31");
+  FN_CHECK_ARG(s0 >= 0 && s0 < s1 && s1 <= S, "0 <= s0 < s1 <= S");
+  FN_CHECK_ARG(eps >= 0.f && eps < 1.f, "0 <= eps < 1");
+  FN_CHECK_ARG(rays11 && z && live_idx && count_out && ws, "non-null pointers");
+  hipStream_t s = fn::S(stream);
+  if (grid) ert_classify_launch(g, n, S, s0, s1, rays11, z, trans, eps, live_idx, count_out, raw, ws, s);
+  else if (cascade) ert_classify_launch(c, n, S, s0, s1, rays11, z, trans, eps, live_idx, count_out, raw, ws, s);
+  else ert_classify_launch(OccAll{}, n, S, s0, s1, rays11, z, trans, eps, live_idx, count_out, raw, ws, s);
   FN_LAUNCH_CHECK();
   return 0;
 }

@@ -9,6 +9,7 @@
 namespace fn {
 void set_error(const char* fmt, ...);
 const char* occ_cascade_fault(const fn_occ_cascade* c);   // occupancy.hip
+const char* occ_grid_fault(const fn_occ_grid* g);         // occupancy.hip
 // mlp_bwd_dw.hip, the paired bf16x6 backward: workspace -> the side dact / partial set of this (device, stream) for the coarse pass, or false (a stream
 // capture, no memory: take the unpaired route); pass -> everything of fastnerf_mlp_x6_bwd but the trunk launch, the reduction and the unfold, which
 // it records in *d; finish -> ONE trunk launch over both passes, then each net's reduction and unfold
@@ -196,6 +197,75 @@ extern "C" int fastnerf_render_rays_fwd_occ_cascade(int math_mode, int64_t n, in
                      white_bkgd, t_rand, u, nullptr, nullptr, seed0, seed1, params_c, packed_c, params_f, packed_f, z0, raw0, rgb0,
                      disp0, acc0, w0, depth0, z1, z_samples, z_std, raw1, rgb1, disp1, acc1, w1, depth1, flags, stream},
                     nullptr, cascade, live_ws, counts_out);
+}
+
+// The same chain with early ray termination in the pass that produces the image (include/fastnerf.h, "early ray termination"): the
+// coarse pass of two runs exactly as it does without it (plain, or through the grid / cascade); the image pass runs segment by
+// segment: fastnerf_ert_classify (T > eps AND the grid) -> the list forward -> fastnerf_ert_advance (T *= the segment's product, the
+// pass's counters += the list length).  live_ws: list | scan scratch | the segment's (count, entries).
+extern "C" int fastnerf_render_rays_fwd_ert(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11, int lindisp,
+                                            int perturb, int det, int white_bkgd, const float* t_rand, const float* u, uint64_t seed0,
+                                            uint64_t seed1, const float* params_c, const float* packed_c, const float* params_f,
+                                            const float* packed_f, const fn_occ_grid* grid, const fn_occ_cascade* cascade, float eps,
+                                            int block, float* trans_ws, int32_t* live_ws, int32_t* counts_out, float* z0, float* raw0,
+                                            float* rgb0, float* disp0, float* acc0, float* w0, float* depth0, float* z1,
+                                            float* z_samples, float* z_std, float* raw1, float* rgb1, float* disp1, float* acc1,
+                                            float* w1, float* depth1, int flags, fn_stream_t stream) {
+  const RrFwd a = {"fastnerf_render_rays_fwd_ert", math_mode, n, N_samples, N_importance, rays11, lindisp, perturb, det, white_bkgd,
+                   t_rand, u, nullptr, nullptr, seed0, seed1, params_c, packed_c, params_f, packed_f, z0, raw0, rgb0, disp0, acc0, w0,
+                   depth0, z1, z_samples, z_std, raw1, rgb1, disp1, acc1, w1, depth1, flags, stream};
+  if (!rr_fwd_scalars(a)) return -1;
+  if (!(eps >= 0.f && eps < 1.f) || block < 1) {
+    fn::set_error("%s: bad argument: 0 <= eps < 1, block >= 1", a.fname);
+    return -1;
+  }
+  if (grid && cascade) {
+    fn::set_error("%s: bad argument: at most one of grid / cascade", a.fname);
+    return -1;
+  }
+  if (n == 0) return 0;
+  const int S_img = N_samples + N_importance;
+  const int64_t P1 = n * (int64_t)S_img;
+  if (P1 >= ((int64_t)1 << 31) || S_img > 512) {
+    fn::set_error("%s: bad argument: n * (N_samples + N_importance) < 2^31 (lists index points with int32), at most 512 samples per ray", a.fname);
+    return -1;
+  }
+  if (!rr_fwd_coarse_ptrs(a) || !trans_ws || !live_ws || !counts_out) {
+    fn::set_error("%s: null pointer (coarse pass)", a.fname);
+    return -1;
+  }
+  if (N_importance > 0 && (!params_f || !packed_f || !z1 || !z_samples || !z_std || !raw1 || !rgb1 || !disp1 || !acc1 || !w1 || !depth1)) {
+    fn::set_error("%s: null pointer (fine pass)", a.fname);
+    return -1;
+  }
+  if (const char* fault = cascade ? fn::occ_cascade_fault(cascade) : (grid ? fn::occ_grid_fault(grid) : nullptr)) {   // before anything is enqueued
+    fn::set_error("%s: bad argument: %s", a.fname, fault);
+    return -1;
+  }
+  int32_t* idx = live_ws;
+  int32_t* cws = live_ws + P1;
+  int32_t* seg = cws + fastnerf_compact_ws_ints(P1);
+  const int img = N_importance > 0 ? 1 : 0;
+  return rr_fwd_chain(a, [&](int pass, int S, const float* z, const float* params, const float* packed, float* raw, const float*) {
+    int32_t* cnt = counts_out + 2 * pass;
+    int rc;
+    if (pass != img) {   // the coarse pass of two: as without ert
+      // (plain: every sample is evaluated, the host knows the pair (n * S, n * S) and nothing is written to it)
+      if (!grid && !cascade) return modes[math_mode].fwd(0, n, S, rays11, z, params, packed, raw, nullptr, flags, stream);
+      if ((rc = cascade ? fastnerf_occ_classify_cascade(cascade, n, S, rays11, z, idx, cnt, raw, cws, stream)
+                        : fastnerf_occ_classify(grid, n, S, rays11, z, idx, cnt, raw, cws, stream)))
+        return rc;
+      return modes[math_mode].fwd_list(0, n, S, rays11, z, params, packed, raw, idx, cnt, flags, stream);
+    }
+    for (int s0 = 0; s0 < S; s0 += block) {
+      const int s1 = (S - s0 > block) ? s0 + block : S;
+      if ((rc = fastnerf_ert_classify(grid, cascade, n, S, s0, s1, rays11, z, s0 ? trans_ws : nullptr, eps, idx, seg, raw, cws, stream)))
+        return rc;
+      if ((rc = modes[math_mode].fwd_list(0, n, S, rays11, z, params, packed, raw, idx, seg, flags, stream))) return rc;
+      if ((rc = fastnerf_ert_advance(n, S, s0, s1, raw, z, rays11, s0 == 0, trans_ws, seg, cnt, stream))) return rc;
+    }
+    return 0;
+  });
 }
 
 extern "C" int fastnerf_render_rays_fwd(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11,

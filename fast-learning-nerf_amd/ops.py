@@ -934,3 +934,86 @@ def render_rays_fwd_occ(rays11, params_c, packed_c, params_f, packed_f, N_sample
     fn, name = _occ_entry(cgrid, 'fastnerf_render_rays_fwd_occ')
     check(fn(*head, *nets, cgrid, ptr(live_ws), ptr(o['counts']), *outs, 1 if skip_dead_rgb else 0, stream()), name)
     return o
+
+
+# ---- early ray termination (csrc/occupancy.hip, csrc/composite.hip, render.cpp) ----------------------------------------------
+def _ert_grid_args(cgrid):
+    """(grid, cascade) arguments of the fastnerf_ert_* entry points for None, a _lib.OccGrid or a _lib.OccCascade."""
+    if cgrid is None:
+        return None, None
+    if isinstance(cgrid, _lib.OccCascade):
+        return None, cgrid
+    if isinstance(cgrid, _lib.OccGrid):
+        return cgrid, None
+    raise TypeError('expected None, a _lib.OccGrid or a _lib.OccCascade, got %s' % type(cgrid).__name__)
+
+
+def check_ert(ert, ert_block):
+    """(eps, block) as numbers, or ValueError: 0 <= eps < 1 (fp32, as the kernels compare it), block >= 1."""
+    eps, block = float(np.float32(ert)), int(ert_block)
+    if not (0. <= eps < 1.) or block < 1 or block != ert_block:
+        raise ValueError('early ray termination needs 0 <= ert < 1 and an integer ert_block >= 1, got ert=%r, ert_block=%r' % (ert, ert_block))
+    return eps, block
+
+
+def ert_classify(rays11, z, s0, s1, trans, eps, cgrid=None, raw=None):
+    """The segment [s0, s1) of the samples of a pass sorted by trans[ray] > eps (trans None: every ray) and by cgrid (None, a
+    _lib.OccGrid or a _lib.OccCascade): (live_idx int32 [n * (s1 - s0)], counts int32 [2] = (evaluated, n * (s1 - s0))), both on the
+    device; live_idx[:evaluated] ascends and holds indices ray * S + s.  raw ([n, S, 4], optional) is zeroed at the segment's other
+    samples and untouched elsewhere."""
+    require_gpu(rays11, z, trans, raw)
+    n, S = z.shape
+    s0, s1 = int(s0), int(s1)
+    assert rays11.shape == (n, 11) and rays11.is_contiguous() and z.is_contiguous() and z.dtype == torch.float32
+    assert rays11.dtype == torch.float32 and rays11.device == z.device
+    assert trans is None or (trans.shape == (n,) and trans.dtype == torch.float32 and trans.is_contiguous() and trans.device == z.device)
+    assert raw is None or raw.device == z.device
+    assert raw is None or (raw.numel() == n * S * 4 and raw.is_contiguous() and raw.dtype == torch.float32)
+    Q = max(1, n * max(0, s1 - s0))
+    idx = torch.empty(Q, device=z.device, dtype=torch.int32)
+    cnt = torch.empty(2, device=z.device, dtype=torch.int32)
+    ws = torch.empty(int(lib().fastnerf_compact_ws_ints(Q)), device=z.device, dtype=torch.int32)
+    grid, cascade = _ert_grid_args(cgrid)
+    check(lib().fastnerf_ert_classify(grid, cascade, n, S, s0, s1, ptr(rays11), ptr(z), ptr(trans), float(eps), ptr(idx), ptr(cnt),
+                                      ptr(raw), ptr(ws), stream()), 'fastnerf_ert_classify')
+    return idx, cnt
+
+
+def ert_advance(raw, z, rays11, s0, s1, trans, first=False, seg_count=None, total=None):
+    """trans[ray] (float32 [n], in place; taken as 1 when first) *= the product over the samples s0 <= s < s1 of 1 - alpha + 1e-10, as
+    raw2outputs forms alpha.  total (int32 [2], optional): total[0] (0 when first) += seg_count[0], total[1] = n * S."""
+    require_gpu(raw, z, rays11, trans, seg_count, total)
+    n, S = z.shape
+    assert raw.shape == (n, S, 4) and raw.is_contiguous() and raw.dtype == torch.float32 and z.is_contiguous() and z.dtype == torch.float32
+    assert rays11.shape == (n, 11) and rays11.is_contiguous() and rays11.dtype == torch.float32
+    assert trans.shape == (n,) and trans.dtype == torch.float32 and trans.is_contiguous()
+    assert total is None or (seg_count is not None and total.dtype == torch.int32 and seg_count.dtype == torch.int32 and
+                             total.is_contiguous() and seg_count.is_contiguous() and total.numel() >= 2 and seg_count.numel() >= 1)
+    assert all(t is None or t.device == z.device for t in (raw, rays11, trans, seg_count, total))
+    check(lib().fastnerf_ert_advance(n, S, int(s0), int(s1), ptr(raw), ptr(z), ptr(rays11), 1 if first else 0, ptr(trans), ptr(seg_count),
+                                     ptr(total), stream()), 'fastnerf_ert_advance')
+    return trans
+
+
+def render_rays_fwd_ert(rays11, params_c, packed_c, params_f, packed_f, N_samples, N_importance, eps, block, cgrid=None, lindisp=False,
+                        perturb=False, det=True, white_bkgd=False, t_rand=None, u=None, seed0=0, seed1=0, skip_dead_rgb=False):
+    """render_rays_fwd_occ with early ray termination in the pass that produces the image (fastnerf_render_rays_fwd_ert; cgrid may be
+    None): same dict, 'counts' = (evaluated, total) samples of the coarse pass, then of the fine pass, plus 'trans': float32 [n], the
+    image pass's transmittance per ray after its last segment."""
+    require_gpu(rays11, params_c, packed_c, params_f, packed_f, t_rand, u)
+    dev = rays11.device
+    eps, block = check_ert(eps, block)
+    o, t_rand, u = _rr_fwd_outputs(rays11, packed_c, packed_f, N_samples, N_importance, t_rand, u)
+    o['counts'] = torch.zeros(4, device=dev, dtype=torch.int32)
+    n = rays11.shape[0]
+    if cgrid is None and N_importance > 0:      # a plain coarse pass evaluates every sample: the library leaves that pair to the caller
+        o['counts'][:2] = n * N_samples
+    o['trans'] = torch.empty(n, device=dev, dtype=torch.float32)
+    P1 = n * (N_samples + N_importance)
+    live_ws = torch.empty(max(1, P1 + int(lib().fastnerf_compact_ws_ints(max(1, P1)))) + 2, device=dev, dtype=torch.int32)
+    head, nets, outs = _rr_fwd_ptrs(o, rays11, params_c, packed_c, params_f, packed_f, N_samples, N_importance, lindisp, perturb, det,
+                                    white_bkgd, t_rand, u, seed0, seed1, with_act=False)
+    grid, cascade = _ert_grid_args(cgrid)
+    check(lib().fastnerf_render_rays_fwd_ert(*head, *nets, grid, cascade, eps, block, ptr(o['trans']), ptr(live_ws), ptr(o['counts']),
+                                             *outs, 1 if skip_dead_rgb else 0, stream()), 'fastnerf_render_rays_fwd_ert')
+    return o

@@ -231,6 +231,26 @@ def _forward_occ(rays11, net_c, net_f, N_samples, N_importance, lindisp, perturb
     return dict(_maps(o, N_importance), z0=o['z0'], raw0=o['raw0'], counts=o['counts'])
 
 
+def _forward_ert(rays11, net_c, net_f, N_samples, N_importance, lindisp, perturb, white_bkgd, t_rand, u, ert, ert_block=32,
+                 occupancy=None, skip_dead_rgb=False):
+    """The fused inference forward with early ray termination in the pass that produces the image (fastnerf_render_rays_fwd_ert),
+    optionally through an occupancy grid or cascade as well: _forward_occ with the image pass run segment by segment.  Returns
+    the outputs dict, plus 'counts' (device int32 [4] = (evaluated, total) of the coarse pass, then of the fine pass; one pass: the
+    first pair) and 'trans' (the image pass's final transmittance per ray)."""
+    pc = net_c.packed()
+    fine = pf = None
+    if N_importance > 0:
+        fine = net_f if net_f is not None else net_c
+        pf = fine.packed() if fine is not net_c else pc
+    o = ops.render_rays_fwd_ert(rays11, net_c.flat, pc[0], None if fine is None else fine.flat, None if pf is None else pf[0],
+                                N_samples, N_importance, ert, ert_block, None if occupancy is None else occupancy._c, lindisp=lindisp,
+                                perturb=perturb, det=(perturb == 0.), white_bkgd=white_bkgd, t_rand=t_rand, u=u,
+                                seed0=_next_seed() if (perturb and t_rand is None) else 0,
+                                seed1=_next_seed() if (N_importance > 0 and perturb and u is None) else 0,
+                                skip_dead_rgb=bool(skip_dead_rgb and net_c.use_viewdirs))
+    return dict(_maps(o, N_importance), z0=o['z0'], raw0=o['raw0'], counts=o['counts'], trans=o['trans'])
+
+
 def _pass_maps(maps, k):
     """(g_disp, g_acc, g_depth) of pass k ('1': the pass that produces the image, '0': the coarse pass of two) out of a dict over
     ops.MAP_GRAD_KEYS, or None when none of the three is set."""
@@ -516,7 +536,7 @@ def _render_rays_closure(ray_batch, rays11, network_fn, network_fine, network_qu
 
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
                 N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False, occupancy=None,
-                retdepth=False):
+                retdepth=False, ert=None, ert_block=32):
     """render.py:195-305.  Two routes, chosen by the networks (after `.module` unwrapping):
 
     * fastnerf NeRF modules (8 x 256): positional encoding + MLP run fused inside the HIP kernels; `network_query_fn` is
@@ -535,6 +555,18 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
 
     `retdepth=True` adds `depth_map` (and `depth0` with two passes), the expected sample distance sum_i w_i z_i of render.py:186,
     to the returned dict on both routes; the default leaves the key set as it is.
+
+    `ert=eps` (0 <= eps < 1; inference only, fused route only) with `ert_block=B`: early ray termination in the pass that produces the
+    image -- the fine pass when N_importance > 0, else the only pass.  Its sorted samples are cut into segments of B; a ray's
+    transmittance T (fp32, 1 at the start) is multiplied by a segment's product of 1 - alpha + 1e-10 once the segment has its logits, and
+    a sample is evaluated only when its ray's T at the start of its segment is > eps (and its occupancy bit is set, with `occupancy=`);
+    every other sample gets raw = 0 without the network.  The coarse pass of two is not touched, so rgb0, disp0, acc0, z_std and the fine
+    depths are bit-identical to the call without `ert`.  The skipped samples of a ray weigh at most eps in the plain render:
+    |d rgb_map| <= eps per channel (white_bkgd or not), 0 <= acc_plain - acc_ert <= eps, |d depth_map| <= eps * z_max.  `disp_map`, a
+    quotient of two maps, has NO such bound.  eps = 0 skips only once T is exactly 0: every map is bit-identical to the call without
+    `ert`; ert_block >= the number of samples is one segment: nothing is skipped.  ValueError with raw_noise_std > 0, when gradients
+    are wanted, and for eps outside [0, 1) or ert_block < 1; NotImplementedError on the closure route.  `ert=None` (the default) makes
+    exactly the calls it made before.
 
     Every returned map except `raw` and `z_std` is differentiable w.r.t. the networks' parameters on both routes (render.py:149-192
     under the reference's autograd): rgb_map, disp_map, acc_map, depth_map and their coarse twins, in all three math modes.
@@ -564,6 +596,18 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
         if torch.is_grad_enabled() and (ray_batch.requires_grad or any(p.requires_grad for m in nets for p in m.parameters())):
             raise ValueError('render_rays: an occupancy grid is an inference feature; call it under torch.no_grad() (or with '
                              'parameters and rays that do not require grad)')
+    if ert is not None:
+        ops.check_ert(ert, ert_block)
+        if not fused:
+            raise NotImplementedError('render_rays: early ray termination (ert=) runs on the fused route only (fastnerf NeRF networks); '
+                                      'the closure route has none')
+        if raw_noise_std > 0.:
+            raise ValueError('render_rays: early ray termination cannot be combined with raw_noise_std > 0 (sigma noise is added before '
+                             'the relu, so a sample with zero sigma is not dead)')
+        nets = [m for m in (net_c, net_f) if isinstance(m, torch.nn.Module)]
+        if torch.is_grad_enabled() and (ray_batch.requires_grad or any(p.requires_grad for m in nets for p in m.parameters())):
+            raise ValueError('render_rays: early ray termination is an inference feature; call it under torch.no_grad() (or with '
+                             'parameters and rays that do not require grad)')
     rays11 = ray_batch.contiguous().float()
     if rays11.shape[-1] == 8:      # no view directions: the kernels' direction slots stay zero (their weights are zero too)
         rays11 = torch.cat([rays11, torch.zeros(rays11.shape[0], 3, device=rays11.device)], -1)
@@ -589,7 +633,10 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
                # nobody sees the colour logits of this call: tiles without a live sample may skip them (FN_FWD_SKIP_DEAD_RGB)
                skip_dead_rgb=not retraw)
     params = list(net_c.parameters()) + (list(net_f.parameters()) if (net_f is not None and net_f is not net_c) else [])
-    if occupancy is not None:
+    if ert is not None:
+        out = _forward_ert(rays11, net_c, net_f, N_samples, N_importance, lindisp, perturb, white_bkgd, t_rand, u, ert, ert_block,
+                           occupancy=occupancy, skip_dead_rgb=not retraw)
+    elif occupancy is not None:
         out = _forward_occ(rays11, net_c, net_f, N_samples, N_importance, lindisp, perturb, white_bkgd, t_rand, u, occupancy,
                            skip_dead_rgb=not retraw)
     elif torch.is_grad_enabled() and ray_batch.requires_grad:

@@ -644,6 +644,55 @@ int fastnerf_render_rays_fwd_occ_cascade(int math_mode, int64_t n, int N_samples
                                          float* z1, float* z_samples, float* z_std, float* raw1, float* rgb1, float* disp1,
                                          float* acc1, float* w1, float* depth1, int flags, fn_stream_t stream);
 
+/* ---- early ray termination (inference): stop evaluating the network on a ray once it is opaque ---------------------------------------
+ * `ert = eps`, 0 <= eps < 1, with `ert_block = B` >= 1.  The image pass is the fine pass when N_importance > 0 and the only pass
+ * otherwise.  Its S sorted samples of every ray are cut into segments of B consecutive sample indices [kB, min((k+1)B, S)).  Per
+ * ray a transmittance T is kept in fp32, starting at 1; after segment k has its logits, T is multiplied by the segment's product of
+ * (1 - alpha_i + 1e-10), alpha_i = 1 - exp(-relu(sigma_i) dist_i), dist_i = z_{i+1} - z_i (1e10 for the ray's last sample) times
+ * |d|, each formed with the rounded operations of fastnerf_raw2outputs_fwd.  A sample of segment k is evaluated when its ray's T at
+ * the START of the segment is > eps and, if a grid or a cascade is given, its occupancy bit is set; every other sample of the segment
+ * gets raw = (0, 0, 0, 0) without the network.  An evaluated sample gets exactly the logits of the plain forward (rows of the matrix
+ * products do not see each other).  Compositing is the unchanged fastnerf_raw2outputs_fwd over the whole raw.
+ * The coarse pass of a two-pass render is not touched: it runs plain, or through the grid / cascade, as without `ert`, so z0, raw0,
+ * the coarse maps, z1, z_samples and z_std are bit-identical to the same call without `ert`.
+ * Consequences: the skipped samples of a ray carry a total weight <= T_start (1 + S 1e-10) <= eps in the plain render, hence
+ * |d rgb_map| <= eps per channel (with or without white_bkgd), 0 <= acc_plain - acc_ert <= eps, |d depth_map| <= eps z_max; disp_map
+ * (a quotient) has no such bound.  With eps = 0 a segment is skipped only once T has underflowed to exactly 0 and every map equals
+ * the plain call's bit for bit; with B >= S there is one segment, nothing is skipped, and every output, raw included, equals that of
+ * fastnerf_render_rays_fwd_occ / _occ_cascade (a grid / cascade) or of the plain non-saving forward (neither).
+ *   fastnerf_ert_classify  one segment [s0, s1) of a pass of n * S samples: live_idx[0 .. count) = ascending indices ray * S + s,
+ *                          s0 <= s < s1, of the samples whose ray has trans[ray] > eps (trans == NULL: every ray; a NaN is not >
+ *                          eps) and whose bit is set in `grid` / `cascade` (at most one non-NULL; neither: every sample);
+ *                          count_out[0] = count, count_out[1] = n * (s1 - s0); raw[p*4 .. p*4+3] = 0 for the segment's other
+ *                          samples (raw may be NULL), nothing outside the segment is written.  ws: fastnerf_compact_ws_ints(n *
+ *                          (s1 - s0)) int32.  The three launches of fastnerf_occ_classify with another descriptor: no atomics.
+ *   fastnerf_ert_advance   trans[ray] = (first ? 1 : trans[ray]) * prod over s0 <= s < s1 of (1 - alpha_s + 1e-10) from raw, z and
+ *                          rays11 as above (S <= 512); total (may be NULL): total[0] = (first ? 0 : total[0]) + seg_count[0],
+ *                          total[1] = n * S.  One launch, one wave per ray, plain stores.
+ *   fastnerf_render_rays_fwd_ert  the arguments of fastnerf_render_rays_fwd_occ with `grid` AND `cascade` (at most one non-NULL, both
+ *                          may be NULL), eps, block = B and trans_ws (n floats: on return the image pass's final T per ray).  The
+ *                          coarse pass of two: as fastnerf_render_rays_fwd_occ / _occ_cascade, or the plain forward with neither.
+ *                          The image pass: per segment fastnerf_ert_classify + the list forward + fastnerf_ert_advance (4 launches
+ *                          beside the list forward).  live_ws: the int32 of fastnerf_render_rays_fwd_occ + 2.  counts_out: 4 int32 =
+ *                          (evaluated, total) of the coarse pass, then of the fine pass (one pass: the first pair only).  A
+ *                          coarse pass that runs plain (neither grid nor cascade) evaluates every sample and writes NOTHING
+ *                          to its pair: (n * N_samples, n * N_samples) is known to the caller.
+ *                          -1 before anything is enqueued unless 0 <= eps < 1, block >= 1, n * (N_samples + N_importance) < 2^31,
+ *                          the pointers are set and the cascade passes its checks. */
+int fastnerf_ert_classify(const fn_occ_grid* grid, const fn_occ_cascade* cascade, int64_t n, int S, int s0, int s1, const float* rays11,
+                          const float* z, const float* trans, float eps, int32_t* live_idx, int32_t* count_out, float* raw,
+                          int32_t* ws, fn_stream_t stream);
+int fastnerf_ert_advance(int64_t n, int S, int s0, int s1, const float* raw, const float* z, const float* rays11, int first,
+                         float* trans, const int32_t* seg_count, int32_t* total, fn_stream_t stream);
+int fastnerf_render_rays_fwd_ert(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11, int lindisp,
+                                 int perturb, int det, int white_bkgd, const float* t_rand, const float* u, uint64_t seed0,
+                                 uint64_t seed1, const float* params_c, const float* packed_c, const float* params_f,
+                                 const float* packed_f, const fn_occ_grid* grid, const fn_occ_cascade* cascade, float eps, int block,
+                                 float* trans_ws, int32_t* live_ws, int32_t* counts_out, float* z0, float* raw0, float* rgb0,
+                                 float* disp0, float* acc0, float* w0, float* depth0, float* z1, float* z_samples, float* z_std,
+                                 float* raw1, float* rgb1, float* disp1, float* acc1, float* w1, float* depth1, int flags,
+                                 fn_stream_t stream);
+
 /* ---- density gradient: d(sigma)/d(x) through the fused MLP (csrc/sigma_grad.hip) -------------------------------------------------
  * sigma[n,S] (may be NULL) = raw[..., 3] of the forward of `math_mode` (0 exact fp32, 1 split-bf16 "bf16x3", 2 "bf16x6") at the
  * points o + d*z of fastnerf_mlp_fwd, and grad[n,S,3] = its gradient with respect to the point.  Both are taken BEFORE the ReLU
