@@ -137,7 +137,6 @@ SIGNATURES = {
     'fastnerf_render_rays_bwd_live_maps': (I, [I, L, I, I, P, I] + [P] * 22 + [P] * 4 + [C.POINTER(MapGrads), P]),
     'fastnerf_mlp_x6_packed_floats': (L, [I, I]),
     'fastnerf_mlp_x6_pack': (I, [I, P, P, P, P]),
-    'fastnerf_mlp_fold_buffer': (P, [P]),
     'fastnerf_mlp_fold_offset': (L, [I, I]),
     'fastnerf_mlp_x6_fwd': (I, [I, L, I, P, P, P, P, P, P, I, P]),
     'fastnerf_mlp_x6_bwd': (I, [I, L, I, P, P, P, P, P, P, P, P]),

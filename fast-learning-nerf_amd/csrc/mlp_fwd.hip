@@ -2,8 +2,6 @@
 // 8 layers (skip at 5) -> alpha head -> view branch (feature layer folded in) -> rgb, one persistent kernel, three math modes (mlp_common.h).
 #include "mlp_common.h"
 
-float* fn_fold_buffer(const float* packed_fwd, bool create);   // mlp_pack.hip
-
 // =========================================================================================
 // forward
 // =========================================================================================
@@ -50,6 +48,7 @@ __device__ __forceinline__ int x2idx(int m, int k) { return m * 32 + ((((k >> 2)
 #define FN_COS(a) (ABL_NOPE ? (a) : cosf(a))
 // LIST (inference over a point list, SAVE == false, BG == false): as the live-list mode below, but nothing is saved and row j's
 // logits go to raw[live_idx[j]] -- the occupancy-grid render (occupancy.hip); a separate instantiation: the others come out instruction-identical.
+// `fold` == `packed` (the folded view layer is part of packed_fwd, NetLayout PFM / PFB): a parameter of its own keeps the code generation as it was.
 template <bool SAVE, bool BG, int MM = MM_F32, bool LIST = false>
 __global__ void __launch_bounds__(NTHR, 2 * NTHR / 512 * WG_PER_CU)
 mlp_fwd_kernel(int64_t P, int S, const float* __restrict__ rays, const float* __restrict__ zv,
@@ -302,9 +301,7 @@ static int fwd_launch_t(int grid, hipStream_t st, int64_t P, int S, const float*
   auto kern = mlp_fwd_kernel<SAVE, BG, MM, LIST>;
   static fn::DevOnce once;
   if (int rc = fn::set_dyn_lds(reinterpret_cast<const void*>(kern), once, LDS_BYTES)) return rc;
-  const float* fold = fn_fold_buffer(packed_fwd, false);   // the folded view layer that the pack call left beside this buffer (mlp_pack.hip)
-  FN_CHECK_ARG(fold != nullptr, "packed_fwd was not filled by a pack call of this process (the folded view layer is kept by its address)");
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(NTHR), LDS_BYTES, st, P, S, rays11, z, params, packed_fwd, fold, raw, act, lay, sched, live_idx,
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(NTHR), LDS_BYTES, st, P, S, rays11, z, params, packed_fwd, /*fold=*/packed_fwd, raw, act, lay, sched, live_idx,
                      live_cnt, flags);
   FN_LAUNCH_CHECK();
   return 0;

@@ -13,12 +13,13 @@ namespace fnl {
 struct NetLayout {
   int64_t LW[8], LB[8];                    // trunk weights / biases (flat offsets, [out][in] row-major)
   int64_t VW, VB, FW, FB, AW, AB, RW, RB;  // view layer, feature/remap, alpha/sigma, rgb
-  int64_t PF[10], PB[9];                   // packed (fragment order) offsets: fwd L0..L7,F,V ; bwd Vt,Ft,L7t..L1t
+  int64_t PF[10], PB[9];                   // packed (fragment order) offsets: fwd L0..L7,F,V ; bwd Vt,Ft,L7t..L1t (F, V, Vt, Ft: unfused, no kernel reads them)
   // the folded view layer (feature / remap layer multiplied into the view layer's first 256 columns: M = Wv[:, :256] Wf, b' = bv + Wv[:, :256] bf).
-  // PBM = M^T in the order of PB[0], appended to the backward buffer.  The forward's part lives in a buffer of its own beside packed_fwd
-  // (mlp_pack.hip fn_fold_buffer: the forward buffer's size is pinned), offsets into it: PFM = [M | Wv[:, 256:]] in the view layer's forward
-  // order, PFB = b' (128 plain floats), PFR = M as plain row-major fp32 [128][256] (what the two packings are made from).  PFB / PFR hold
-  // plain floats in every math mode: `fold_plain` gives their float offset in a buffer of that mode.
+  // Both packed buffers carry their part as appended regions, so a packed buffer is plain data (a copy of it is as good as the original):
+  // PBM = M^T in the order of PB[0], behind PB[8] in the backward buffer; behind PF[9] in the forward buffer PFM = [M | Wv[:, 256:]] in the
+  // view layer's forward order, PFB = b' (128 plain floats), PFR = M as plain row-major fp32 [128][256] (what the two packings are made from).
+  // PFB / PFR hold plain floats in every math mode: `fold_plain` gives their float offset in a buffer of that mode.  fold_total = the size of
+  // PFM | PFB | PFR, the tail of pf_total (host only; it keeps its place: the kernels load the members behind it by their offset).
   int64_t PFM, PFB, PFR, PBM, fold_total;
   int64_t n_params, pf_total, pb_total;
   int in_pe, pe_pad;                       // 63 -> 64, 84 -> 96
@@ -48,12 +49,11 @@ inline NetLayout make_layout(int kind) {
     const int kp = (l == 0) ? L.pe_pad : (l == 5 ? L.pe_pad + 256 : (l == 9 ? 288 : 256));
     p += (int64_t)kp * (l == 9 ? 128 : 256);
   }
-  L.pf_total = p;
-  p = 0;
   L.PFM = p; p += (int64_t)288 * 128;
   L.PFB = p; p += 128;
   L.PFR = p; p += (int64_t)128 * 256;
-  L.fold_total = p;
+  L.fold_total = p - L.PFM;
+  L.pf_total = p;
   p = 0;
   for (int j = 0; j < 9; ++j) { L.PB[j] = p; p += (int64_t)(j == 0 ? 128 : 256) * 256; }
   L.PBM = p; p += (int64_t)128 * 256;

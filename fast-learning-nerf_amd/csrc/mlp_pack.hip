@@ -1,8 +1,5 @@
 // mlp_pack.hip -- weight packing for the fp32-width MLP kernels (fragment order of the MFMA that consumes them) and the net-size queries.
 #include "mlp_common.h"
-#include <map>
-#include <mutex>
-#include <utility>
 
 // =========================================================================================
 // weight packing
@@ -21,17 +18,19 @@ struct PackDesc {
 #define N_PACK 21
 struct PackTable {
   PackDesc d[N_PACK];
-  int64_t m_off;     // plain-float offset of M in the fold buffer (fold_kernel writes it before the pack kernel runs)
+  int64_t m_off;     // plain-float offset of M in packed_fwd (fold_kernel writes it before the pack kernel runs)
 };
 
 // =========================================================================================
 // the fold: feature / remap layer (256 -> 256, no activation) into the view layer's first 256 columns
 //   M = Wv[:, :256] Wf  [128][256],   b' = bv + Wv[:, :256] bf  [128]
 // fp64 products and sums in ascending k, rounded once to fp32.  One thread per entry: the Wf row is a coalesced read, the Wv entry a broadcast;
-// 8.4 M fp64 FMAs per net, once per weight update.
+// 8.4 M fp64 FMAs per net, once per weight update.  M and b' go into packed_fwd itself (NetLayout PFR / PFB) as plain floats.  A bf16x6 buffer
+// holds 3/2 floats per unit of the layout, so the plain floats fill two thirds of their regions: `slack` zeroes the last third (every word
+// of a packed buffer is defined data).
 // =========================================================================================
 __global__ void __launch_bounds__(256) fold_kernel(const float* __restrict__ params, int64_t VW, int64_t VB, int64_t FW, int64_t FB,
-                                                    float* __restrict__ m_out, float* __restrict__ b_out) {
+                                                    float* __restrict__ m_out, float* __restrict__ b_out, bool slack) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e < 128 * 256) {
     const int o = e >> 8, j = e & 255;
@@ -41,46 +40,30 @@ __global__ void __launch_bounds__(256) fold_kernel(const float* __restrict__ par
 #pragma unroll 8
     for (int i = 0; i < 256; ++i) s = fma((double)wv[i], (double)wf[(int64_t)i * 256], s);
     m_out[e] = (float)s;
+    if (slack && e < 128 * 256 / 2) m_out[128 * 256 + e] = 0.f;
   } else if (e < 128 * 256 + 128) {
     const int o = e - 128 * 256;
     const float* wv = params + VW + (int64_t)o * 283;
     double s = (double)params[VB + o];
     for (int i = 0; i < 256; ++i) s = fma((double)wv[i], (double)params[FB + i], s);
     b_out[o] = (float)s;
+    if (slack && o < 128 / 2) b_out[128 + o] = 0.f;
   }
 }
-static void launch_fold(const NetLayout& L, const float* params, float* fold, bool x6, hipStream_t st) {
-  hipLaunchKernelGGL(fold_kernel, dim3(129), dim3(256), 0, st, params, L.VW, L.VB, L.FW, L.FB, fold + fold_plain(L.PFR, x6),
-                     fold + fold_plain(L.PFB, x6));
-}
-// The forward's folded view layer (NetLayout PFM | PFB | PFR) lives in a device buffer of the library's own, one per packed forward buffer
-// and found by that buffer's address: the packed forward buffer itself keeps its size and content (callers and tests decode it region by
-// region).  A pack call creates (first time: hipMalloc, sized for the wider packing) and fills it on the caller's stream, in order with the
-// packing itself; a forward whose packed_fwd no pack call of this process has filled is an error.  Entries live as long as the process.
-static std::mutex g_fold_mu;
-static std::map<std::pair<int, const void*>, float*> g_fold;
-float* fn_fold_buffer(const float* packed_fwd, bool create) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-  std::lock_guard<std::mutex> lk(g_fold_mu);
-  auto it = g_fold.find({dev, packed_fwd});
-  if (it != g_fold.end()) return it->second;
-  if (!create) return nullptr;
-  float* p = nullptr;
-  if (hipMalloc(reinterpret_cast<void**>(&p), sizeof(float) * (size_t)(layout_of(0).fold_total * 3 / 2)) != hipSuccess) return nullptr;
-  g_fold[{dev, packed_fwd}] = p;
-  return p;
+static void launch_fold(const NetLayout& L, const float* params, float* packed_fwd, bool x6, hipStream_t st) {
+  hipLaunchKernelGGL(fold_kernel, dim3(129), dim3(256), 0, st, params, L.VW, L.VB, L.FW, L.FB, packed_fwd + fold_plain(L.PFR, x6),
+                     packed_fwd + fold_plain(L.PFB, x6), x6);
 }
 
 // fwd  : dst[((nt*KS+ks)*64 + l)*4 + t] = W'[nt*32 + (l&31)][ks*8 + (l>>5)*4 + t]
 // bwd  : dst[((jt*KS+ks)*64 + l)*4 + t] = W [ks*8 + (l>>5)*4 + t][col0 + jt*32 + (l&31)]
 __global__ void __launch_bounds__(256) pack_kernel(PackTable tab, const float* __restrict__ params,
-                                                    float* __restrict__ pf, float* __restrict__ pb, float* fold) {
+                                                    float* pf, float* __restrict__ pb) {
   const PackDesc d = tab.d[blockIdx.y];
   const int64_t total = (int64_t)d.n_rows * d.n_cols;
-  float* dst = (d.transposed ? pb : (d.fold ? fold : pf)) + d.dst_off;
+  float* dst = (d.transposed ? pb : pf) + d.dst_off;
   const float* src = params + d.src_off;
-  const float* mraw = fold + tab.m_off;
+  const float* mraw = pf + tab.m_off;   // read-only here, and no descriptor's destination
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
     const int t = (int)(e & 3);
     const int l = (int)((e >> 2) & 63);
@@ -111,15 +94,15 @@ __global__ void __launch_bounds__(256) pack_kernel(PackTable tab, const float* _
 }
 
 __global__ void __launch_bounds__(256) pack6_kernel(PackTable tab, const float* __restrict__ params,
-                                                     uint4* __restrict__ pf, uint4* __restrict__ pb, uint4* fold) {
+                                                     uint4* pf, uint4* __restrict__ pb) {
   const PackDesc d = tab.d[blockIdx.y];
   constexpr int TW = 16, KW = 32;
   const int KS = (d.transposed ? d.n_rows : d.n_cols) / KW;
   const int NTL = (d.transposed ? d.n_cols : d.n_rows) / TW;
   const int64_t total = (int64_t)NTL * KS * 64;          // one thread = the three planes of one (tile, k-step, lane)
-  uint4* dst = (d.transposed ? pb : (d.fold ? fold : pf)) + d.dst_off * 3 / 8;   // dst_off: floats of the fp32 packing = 8/3 of these uint4
+  uint4* dst = (d.transposed ? pb : pf) + d.dst_off * 3 / 8;   // dst_off: floats of the fp32 packing = 8/3 of these uint4
   const float* src = params + d.src_off;
-  const float* mraw = reinterpret_cast<const float*>(fold) + tab.m_off;
+  const float* mraw = reinterpret_cast<const float*>(pf) + tab.m_off;   // read-only here, and no descriptor's destination
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
     const int l = (int)(e & 63);
     const int64_t blk = e >> 6;
@@ -204,11 +187,9 @@ extern "C" int fastnerf_mlp_pack_ex(int kind, const float* params, float* packed
   FN_CHECK_ARG(kind >= 0 && kind <= 2 && params && packed_fwd && packed_bwd, "kind in 0..2, non-null pointers");
   static const PackTable T[3] = {make_pack_table(layout_of(0), false), make_pack_table(layout_of(1), false),
                                  make_pack_table(layout_of(2), false)};
-  float* fold = fn_fold_buffer(packed_fwd, true);
-  FN_CHECK_ARG(fold != nullptr, "buffer of the folded view layer (hipMalloc failed?)");
-  launch_fold(layout_of(kind), params, fold, false, fn::S(stream));
+  launch_fold(layout_of(kind), params, packed_fwd, false, fn::S(stream));
   FN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(pack_kernel, dim3(64, N_PACK), dim3(256), 0, fn::S(stream), T[kind], params, packed_fwd, packed_bwd, fold);
+  hipLaunchKernelGGL(pack_kernel, dim3(64, N_PACK), dim3(256), 0, fn::S(stream), T[kind], params, packed_fwd, packed_bwd);
   FN_LAUNCH_CHECK();
   return 0;
 }
@@ -222,12 +203,10 @@ extern "C" int fastnerf_mlp_x6_pack(int kind, const float* params, float* packed
   FN_CHECK_ARG(kind >= 0 && kind <= 2 && params && packed_fwd && packed_bwd, "kind in 0..2, non-null pointers");
   static const PackTable T[3] = {make_pack_table(layout_of(0), true), make_pack_table(layout_of(1), true),
                                  make_pack_table(layout_of(2), true)};
-  float* fold = fn_fold_buffer(packed_fwd, true);
-  FN_CHECK_ARG(fold != nullptr, "buffer of the folded view layer (hipMalloc failed?)");
-  launch_fold(layout_of(kind), params, fold, true, fn::S(stream));
+  launch_fold(layout_of(kind), params, packed_fwd, true, fn::S(stream));
   FN_LAUNCH_CHECK();
   hipLaunchKernelGGL(pack6_kernel, dim3(32, N_PACK), dim3(256), 0, fn::S(stream), T[kind], params,
-                     reinterpret_cast<uint4*>(packed_fwd), reinterpret_cast<uint4*>(packed_bwd), reinterpret_cast<uint4*>(fold));
+                     reinterpret_cast<uint4*>(packed_fwd), reinterpret_cast<uint4*>(packed_bwd));
   FN_LAUNCH_CHECK();
   return 0;
 }
@@ -236,12 +215,10 @@ extern "C" int fastnerf_mlp_pack(const float* params, float* packed_fwd, float* 
 }
 
 
-// The folded view layer that belongs to a packed forward buffer (device pointer, NetLayout PFM | PFB | PFR in the packing of the mode that
-// filled it; NULL when no pack call has filled this packed_fwd) and its offsets: what = 0 PFM, 1 PFB, 2 PFR (units of the fp32 packing), 3 PBM
-// (offset into the packed backward buffer), 4 size of the fold buffer.
-extern "C" const float* fastnerf_mlp_fold_buffer(const float* packed_fwd) { return fn_fold_buffer(packed_fwd, false); }
+// Offsets of the folded view layer, in units of the fp32 packing: what = 0 PFM, 1 PFB, 2 PFR (into the packed forward buffer), 3 PBM (into
+// the packed backward buffer).
 extern "C" int64_t fastnerf_mlp_fold_offset(int kind, int what) {
   if (kind < 0 || kind > 2) return -1;
   const NetLayout& L = layout_of(kind);
-  return what == 0 ? L.PFM : what == 1 ? L.PFB : what == 2 ? L.PFR : what == 3 ? L.PBM : what == 4 ? L.fold_total : -1;
+  return what == 0 ? L.PFM : what == 1 ? L.PFB : what == 2 ? L.PFR : what == 3 ? L.PBM : -1;
 }

@@ -13,10 +13,6 @@ from . import _lib
 from ._lib import check, lib, ptr, require_gpu, stream  # noqa: F401 (re-exported: tree.py uses ops.ptr / ops.stream)
 
 NET_PARAMS = 595844
-PACKED_FWD = 593920
-PACKED_BWD = 557056
-ACT_FLOATS = 2592
-ACT_SLACK = 8192
 DACT_FLOATS = 2432
 
 

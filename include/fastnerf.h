@@ -60,8 +60,8 @@ int fastnerf_posenc(int64_t n, int L, const float* x, float* out, fn_stream_t st
 
 /* ---- MLP (model.py:8-63, D=8 W=256 skip@4 use_viewdirs) ---------------- */
 #define FASTNERF_NET_PARAMS 595844      /* floats per net, model.parameters() order */
-#define FASTNERF_PACKED_FWD 593920      /* floats: fragment-ordered forward weights  */
-#define FASTNERF_PACKED_BWD 557056      /* floats: fragment-ordered transposed weights */
+#define FASTNERF_PACKED_FWD 663680      /* floats: fragment-ordered forward weights (kind 0; in general fastnerf_net_floats(kind, 1)) */
+#define FASTNERF_PACKED_BWD 589824      /* floats: fragment-ordered transposed weights (fastnerf_net_floats(kind, 2)) */
 /* saved activations: n*S*FASTNERF_ACT_FLOATS + FASTNERF_ACT_SLACK floats
  * (per point pe64 + 8*h256 + feat256 + vpe32 + hv128 + 64 floats of ReLU sign words) */
 #define FASTNERF_ACT_FLOATS 2592
@@ -396,13 +396,12 @@ int fastnerf_render_rays_bwd_live_maps(int math_mode, int64_t n, int N_samples, 
 int64_t fastnerf_mlp_x6_packed_floats(int kind, int which);
 int fastnerf_mlp_x6_pack(int kind, const float* params, float* packed_fwd, float* packed_bwd, fn_stream_t stream);
 /* The fp32 / bf16x6 kernels run the feature (remap) layer and the view layer as ONE linear map of h7: M = Wv[:, :256] Wf, b' = bv + Wv[:, :256] bf,
- * folded in fp64 at every pack call.  M^T is appended to packed_bwd; the forward's part lives in a device buffer the library keeps beside
- * packed_fwd, found by that buffer's ADDRESS: the forward entry points need the very packed_fwd a pack call of this process filled (a copy
- * of it is an error, not garbage).  The backward writes the gradients of both layers as before (an fp64 unfold behind the reduction).
- * fastnerf_mlp_fold_buffer: that device buffer (NULL: never packed); fastnerf_mlp_fold_offset(kind, what): what = 0 [M | Wv[:, 256:]] in the
- * view layer's forward order, 1 b' (128 plain floats), 2 M row-major fp32 [128][256] -- offsets in floats of the fp32 packing (x 3/2 under
- * bf16x6) --, 3 the offset of M^T in packed_bwd (same units), 4 the fold buffer's size. */
-const float* fastnerf_mlp_fold_buffer(const float* packed_fwd);
+ * folded in fp64 at every pack call.  The folded layer is appended to the packed buffers themselves, M^T to packed_bwd and the forward's part
+ * to packed_fwd: a packed buffer is plain data, a pack call allocates nothing, and a copy of a packed buffer is as good as the original.  The
+ * backward writes the gradients of both layers as before (an fp64 unfold behind the reduction).
+ * fastnerf_mlp_fold_offset(kind, what): what = 0 [M | Wv[:, 256:]] in the view layer's forward order, 1 b' (128 plain floats), 2 M row-major
+ * fp32 [128][256] -- offsets into packed_fwd, in floats of the fp32 packing (x 3/2 under bf16x6) --, 3 the offset of M^T in packed_bwd (same
+ * units); anything else: -1. */
 int64_t fastnerf_mlp_fold_offset(int kind, int what);
 int fastnerf_mlp_x6_fwd(int kind, int64_t n, int S, const float* rays11, const float* z, const float* params,
                         const float* packed_fwd, float* raw, float* act, int flags, fn_stream_t stream);

@@ -9,6 +9,13 @@ Cases: kind 0 at P = 17, 64, 65, 1000 (below one 64-point tile, one tile, tile +
   * after an Adam step and a repack, M^T in the packed backward buffer is the fp64 product Wv[:, :256] Wf of the NEW weights rounded to
     fp32 (bf16x6: its three planes sum back to it bit for bit);
   * the feat / dfeat regions of act / dact are holes: a NaN pattern written before the calls is still there, and every gradient is finite.
+
+The forward's part of the fold lives in the packed forward buffer itself (csrc/mlp_layout.h PFM | PFB | PFR), kinds 0 and 2 at P = 65 (one
+64-point tile plus one point; kind 2 shifts every offset), both modes:
+  * a clone of a packed forward buffer gives the same logits bit for bit, saving and non-saving, through the C entry points;
+  * a pack call writes every word of the packed forward buffer, and what was there before does not reach the logits;
+  * the plain floats at PFR / PFB and the decoded PFM block are the fp64 M = Wv[:, :256] Wf and b' = bv + Wv[:, :256] bf rounded once to fp32
+    ([M | Wv[:, 256:] | 0]; bf16x6: the three planes sum back bit for bit).
 """
 import os
 
@@ -156,3 +163,104 @@ def test_repack_after_adam_refolds(fn, golden_dir, mode):
         assert float(d.max()) <= 2e-5, float(d.max())
     finally:
         fn.ops.set_math(old)
+
+
+# ---- the forward's part of the fold is part of the packed forward buffer ----------------------------------------------------------
+IN_BUFFER_CASES = [(0, 65), (2, 65)]
+
+
+def c_fwd(fn, rays, z, flat, pf, kind, save):
+    """Logits from the current mode's forward entry point of the C ABI, called on `pf` as it is (ops.mlp_fwd refuses a packed buffer
+    that ops.mlp_pack did not hand out)."""
+    P = z.numel()
+    raw = torch.full((P, 1, 4), float('nan'), device='cuda')
+    act = nan_filled(fn.ops.act_floats(P, kind)) if save else None
+    f, name = fn.ops._mlp('fwd', kind)
+    flags = (0,) if name == 'fastnerf_mlp_x6_fwd' else ()
+    fn.ops.check(f(kind, P, 1, fn.ops.ptr(rays), fn.ops.ptr(z), fn.ops.ptr(flat), fn.ops.ptr(pf), fn.ops.ptr(raw), fn.ops.ptr(act),
+                   *flags, fn.ops.stream()), name)
+    torch.cuda.synchronize()
+    return raw
+
+
+def fold_offsets(fn, kind, mode):
+    """(PFM in units of the fp32 packing, float offsets of the plain b' and M) in a packed forward buffer of this mode."""
+    pfm, pfb, pfr = (int(fn._lib.lib().fastnerf_mlp_fold_offset(kind, w)) for w in range(3))
+    x = 3 if mode == 'bf16x6' else 2
+    return pfm, pfb * x // 2, pfr * x // 2
+
+
+def packed_pfm(pf, pfm, mode):
+    """[128][288] (float64) decoded from the PFM block of the packed forward buffer, and the bf16x6 planes (None under fp32)."""
+    if mode == 'fp32':      # [(nt*KS + ks)*64 + l][t] = W'[nt*32 + (l&31)][ks*8 + (l>>5)*4 + t], KS = 36
+        blk = pf[pfm:pfm + 128 * 288].cpu().numpy().reshape(4, 36, 2, 32, 4)             # [nt][ks][half][n][t]
+        return blk.transpose(0, 3, 1, 2, 4).reshape(128, 288).astype(np.float64), None
+    u16 = pf.cpu().numpy().view(np.uint16)
+    u0 = pfm * 3 // 8       # uint4 units: [tile][ks][plane][lane][8] = W'[tile*16 + (l&15)][ks*32 + (l>>4)*8 + e]
+    blk = u16[u0 * 8:(u0 + 8 * 9 * 3 * 64) * 8].reshape(8, 9, 3, 4, 16, 8)               # [tile][ks][plane][kc][n][e]
+    planes = (blk.astype(np.uint32) << 16).view(np.float32).astype(np.float64)
+    tot = planes[:, :, 0] + planes[:, :, 1] + planes[:, :, 2]                            # [tile][ks][kc][n][e]
+    return tot.transpose(0, 3, 1, 2, 4).reshape(128, 288), planes
+
+
+@pytest.mark.parametrize('kind,P', IN_BUFFER_CASES)
+@pytest.mark.parametrize('mode', MODES)
+def test_copy_of_packed_fwd_is_the_buffer(fn, golden_dir, mode, kind, P):
+    flat, rays, z, _ = net_and_batch(fn, golden_dir, kind, P)
+    old = fn.ops.get_math()
+    try:
+        fn.ops.set_math(mode)
+        pf, _ = fn.ops.mlp_pack(flat, kind=kind)
+        pf2 = pf.clone()
+        for save in (False, True):
+            want, got = c_fwd(fn, rays, z, flat, pf, kind, save), c_fwd(fn, rays, z, flat, pf2, kind, save)
+            assert torch.isfinite(want).all(), (mode, kind, save)
+            assert torch.equal(got, want), (mode, kind, save, 'logits from a clone of packed_fwd differ')
+    finally:
+        fn.ops.set_math(old)
+
+
+@pytest.mark.parametrize('kind,P', IN_BUFFER_CASES)
+@pytest.mark.parametrize('mode', MODES)
+def test_pack_writes_all_of_packed_fwd_and_reads_nothing_else(fn, golden_dir, mode, kind, P):
+    flat, rays, z, _ = net_and_batch(fn, golden_dir, kind, P)
+    old = fn.ops.get_math()
+    try:
+        fn.ops.set_math(mode)
+        n = fn.ops.packed_floats(kind, 1)
+        pf_nan, _ = fn.ops.mlp_pack(flat, nan_filled(n), kind=kind)
+        pf_zero, _ = fn.ops.mlp_pack(flat, torch.zeros(n, device='cuda'), kind=kind)
+        torch.cuda.synchronize()
+        left = int((pf_nan.view(torch.int32) == PATTERN).sum())
+        assert left == 0, (mode, kind, '%d of %d words of packed_fwd were not written by the pack call' % (left, n))
+        assert torch.equal(pf_nan.view(torch.int32), pf_zero.view(torch.int32))
+        raw = fn.ops.mlp_fwd(rays, z, flat, pf_nan, kind=kind)
+        assert torch.isfinite(raw).all(), (mode, kind)
+        assert torch.equal(raw, fn.ops.mlp_fwd(rays, z, flat, pf_zero, kind=kind)), (mode, kind)
+    finally:
+        fn.ops.set_math(old)
+
+
+@pytest.mark.parametrize('kind,P', IN_BUFFER_CASES)
+@pytest.mark.parametrize('mode', MODES)
+def test_fold_regions_of_packed_fwd_hold_the_fp64_fold(fn, golden_dir, mode, kind, P):
+    flat, _, _, _ = net_and_batch(fn, golden_dir, kind, P)
+    W = F.split_flat(flat.double(), kind)
+    Wv = W['V.W']
+    m_want = (Wv[:, :256] @ W['F.W']).float().cpu().numpy()                       # fp64, rounded once
+    b_want = (W['V.b'] + Wv[:, :256] @ W['F.b']).float().cpu().numpy()
+    block_want = np.concatenate([m_want, Wv[:, 256:].float().cpu().numpy(), np.zeros((128, 5), np.float32)], 1)
+    old = fn.ops.get_math()
+    try:
+        fn.ops.set_math(mode)
+        pf, _ = fn.ops.mlp_pack(flat, kind=kind)
+        torch.cuda.synchronize()
+    finally:
+        fn.ops.set_math(old)
+    pfm, b_off, m_off = fold_offsets(fn, kind, mode)
+    assert np.array_equal(pf[m_off:m_off + 128 * 256].cpu().numpy().reshape(128, 256), m_want), (mode, kind, 'plain M')
+    assert np.array_equal(pf[b_off:b_off + 128].cpu().numpy(), b_want), (mode, kind, "plain b'")
+    got, planes = packed_pfm(pf, pfm, mode)
+    assert np.array_equal(got.astype(np.float32), block_want), (mode, kind, 'the PFM block is not [M | Wv[:, 256:] | 0]')
+    if planes is not None:
+        assert np.array_equal(got, block_want.astype(np.float64)), (mode, kind, 'the three bf16 planes do not sum back bit for bit')

@@ -446,7 +446,19 @@ def test_bf16x6_decomposition_is_exact_and_products_have_fp32_width(fn, weights)
                 ref = w
             assert np.array_equal(got.astype(np.float32), ref) and np.array_equal(got, ref.astype(np.float64)), name
             off += n_u4
-        assert off * 4 == pf.numel()
+        # behind the ten blocks: the folded view layer [M | Wv[:, 256:] | 0] (M = Wv[:, :256] Wf in fp64, rounded once to fp32) in the view
+        # layer's order, then b' and M as plain floats (128 and 32768 units of the fp32 packing, 3/2 floats each here)
+        lib = fn._lib.lib()
+        assert off * 8 == lib.fastnerf_mlp_fold_offset(0, 0) * 3
+        wv, wf = weights['views_linears.0.weight'].double(), weights['feature_linear.weight'].double()
+        ref = np.concatenate([(wv[:, :256] @ wf).float().numpy(), wv[:, 256:].float().numpy(), np.zeros((128, 5), np.float32)], 1)
+        n_u4 = 8 * 9 * 3 * 64
+        blk = u16[off * 8:(off + n_u4) * 8].reshape(8, 9, 3, 64, 8)
+        tot = bf(blk[:, :, 0]) + bf(blk[:, :, 1]) + bf(blk[:, :, 2])
+        got = tot.reshape(8, 9, 4, 16, 8).transpose(0, 3, 1, 2, 4).reshape(128, 288)
+        assert np.array_equal(got.astype(np.float32), ref) and np.array_equal(got, ref.astype(np.float64)), 'folded view layer'
+        off += n_u4
+        assert off * 4 + (128 + 32768) * 3 // 2 == pf.numel()
         # (b) logits against fp64
         gen = torch.Generator().manual_seed(4)
         P = 4096
