@@ -3,7 +3,7 @@
 //
 // Mapping: ONE 64-lane wavefront per ray.  Each lane owns a contiguous chunk of C =
 // ceil(S/64) samples (S=64 -> 1, S=192 -> 3); the transmittance product and the backward
-// suffix sums are wave-level scans done with DPP/`__shfl_up` (no LDS round trip, no barrier).
+// suffix sums are wave-level scans done with DPP/`__shfl_up` / `__shfl_down` (no LDS round trip, no barrier).
 // The sampler keeps the ray's cdf/bins/new samples in a per-wave LDS slice so that the
 // per-sample binary searches and the bitonic sort are bank-parallel.
 //
@@ -29,26 +29,33 @@ __device__ __forceinline__ float wave_scan_mul(float v, int lane) {
   }
   return v;
 }
-__device__ __forceinline__ float wave_scan_add(float v, int lane) {
+// Exclusive suffix sums over lanes (the sum of the lanes ABOVE this one), added from the far end.  A ray that saturates early
+// has a total of order 1 and suffixes of order T_i: `total - inclusive prefix` returns those as rounding noise of the total
+// (2^-24 of it, against a true value that may be smaller still), which the backward then multiplies by the sample's interval.
+// Summed from the far end every partial sum is of the size of the suffix itself.
+__device__ __forceinline__ float wave_suffix_add(float v, int lane) {
 #pragma unroll
   for (int o = 1; o < WAVE; o <<= 1) {
-    float t = __shfl_up(v, o, WAVE);
-    if (lane >= o) v += t;
+    const float t = __shfl_down(v, o, WAVE);
+    if (lane + o < WAVE) v += t;
   }
-  return v;
+  const float above = __shfl_down(v, 1, WAVE);
+  return lane == WAVE - 1 ? 0.0f : above;
 }
 
-// three independent inclusive add-scans, interleaved so that their cross-lane latencies overlap
-__device__ __forceinline__ void wave_scan_add3(float& a, float& b, float& c, int lane) {
+// two independent ones, interleaved so that their cross-lane latencies overlap (a: the same additions as wave_suffix_add)
+__device__ __forceinline__ void wave_suffix_add2(float& a, float& b, int lane) {
 #pragma unroll
   for (int o = 1; o < WAVE; o <<= 1) {
-    const float ta = __shfl_up(a, o, WAVE), tb = __shfl_up(b, o, WAVE), tc = __shfl_up(c, o, WAVE);
-    if (lane >= o) {
+    const float ta = __shfl_down(a, o, WAVE), tb = __shfl_down(b, o, WAVE);
+    if (lane + o < WAVE) {
       a += ta;
       b += tb;
-      c += tc;
     }
   }
+  const float aa = __shfl_down(a, 1, WAVE), ab = __shfl_down(b, 1, WAVE);
+  a = lane == WAVE - 1 ? 0.0f : aa;
+  b = lane == WAVE - 1 ? 0.0f : ab;
 }
 
 __device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
@@ -219,9 +226,7 @@ __global__ void __launch_bounds__(256) raw2outputs_bwd_kernel(int64_t n, int S, 
         T *= v[j].t;
       }
     }
-    const float incl_gw = wave_scan_add(gw_chunk, lane);
-    const float total = __shfl(incl_gw, WAVE - 1, WAVE);
-    float suffix = total - incl_gw;  // sum over lanes > this lane
+    float suffix = wave_suffix_add(gw_chunk, lane);  // sum over lanes > this lane
     // walk the chunk backwards: suffix = sum_{j' > j} G w
     float4 out[MAXC];
 #pragma unroll
@@ -334,20 +339,16 @@ __global__ void __launch_bounds__(256) raw2outputs_bwd_full_kernel(
         T *= v[j].t;
       }
     }
-    float incl_gw = gw_chunk, incl_h = h_chunk, incl_d = dlast;
+    float suffix = gw_chunk, suffix_h = h_chunk, end_term = 0.f;
     if (ray_terms)
-      wave_scan_add3(incl_gw, incl_h, incl_d, lane);
+      wave_suffix_add2(suffix, suffix_h, lane);
     else
-      incl_gw = wave_scan_add(gw_chunk, lane);
-    const float total = __shfl(incl_gw, WAVE - 1, WAVE);
-    float suffix = total - incl_gw;
-    float suffix_h = 0.f, end_term = 0.f;
+      suffix = wave_suffix_add(gw_chunk, lane);
     if (ray_terms) {
-      suffix_h = __shfl(incl_h, WAVE - 1, WAVE) - incl_h;
       // (a + b z_last) T_end.  Its disparity part k (1 - disp z_last) cancels when the last sample holds the depth; written
       // as -(g_disp / depth^2) (acc z_last - depth) with acc z_last - depth = sum_j w_j (z_last - z_j) >= 0, it does not
       float coef = ga + gd * zlast;
-      if (kd != 0.0f) coef = (ga0 + gd0 * zlast) - kd * __shfl(incl_d, WAVE - 1, WAVE);
+      if (kd != 0.0f) coef = (ga0 + gd0 * zlast) - kd * wave_sum(dlast);
       end_term = coef * __shfl(incl, WAVE - 1, WAVE);
     }
     float4 out[MAXC];
