@@ -61,6 +61,7 @@ class OccCascade(C.Structure):
 
 
 STEP_FORWARD, STEP_BWD_FINE, STEP_BWD_COARSE, STEP_UPDATE = 1, 2, 4, 8
+STEP_TIGHTEN = 2      # FN_STEP_TIGHTEN: a bit of StepArgs.fwd_flags
 
 # name -> (restype, argtypes); mirrors include/fastnerf.h one to one
 SIGNATURES = {
@@ -178,6 +179,7 @@ SIGNATURES = {
     'fastnerf_ert_advance': (I, [L, I, I, I, P, P, P, I, P, P, P, P]),
     'fastnerf_render_rays_fwd_ert': (I, [I, L, I, I, P, I, I, I, I, P, P, U64, U64, P, P, P, P, C.POINTER(OccGrid), C.POINTER(OccCascade), F, I,
                                          P, P, P] + [P] * 16 + [I, P]),
+    'fastnerf_occ_ray_bounds': (I, [C.POINTER(OccGrid), C.POINTER(OccCascade), L, P, I, P, P, P]),
     'fastnerf_mlp_sigma_grad_ws_floats': (L, [I, L]),
     'fastnerf_mlp_sigma_grad': (I, [I, I, L, I, P, P, P, P, P, P, P, P, P]),
     'fastnerf_ray_grad_ws_floats': (L, [I, L, I]),

@@ -531,7 +531,11 @@ static int train_step(const fn_step_args* a, const fn_step_aux* aux, int phases,
       fn::set_error("fastnerf_train_step: an occupancy grid needs live_ws");
       return -1;
     }
+  } else if (a->fwd_flags & FN_STEP_TIGHTEN) {
+    fn::set_error("fastnerf_train_step: FN_STEP_TIGHTEN needs an occupancy grid (occ != NULL)");
+    return -1;
   }
+  const int fwd_flags = a->fwd_flags & ~FN_STEP_TIGHTEN;   // the step's own bit does not travel on to the forward
   const float* params_c = a->params;
   const float* params_f = two ? a->params + a->net_floats : nullptr;
   float* grads_c = a->grads;
@@ -545,6 +549,9 @@ static int train_step(const fn_step_args* a, const fn_step_aux* aux, int phases,
     }
     if ((rc = fastnerf_pack_rays(a->n, a->rays_o, a->rays_d, a->near_plane, a->far_plane, a->ndc, a->H, a->W, a->focal, a->rays11,
                                  stream))) return rc;
+    // near / far of every ray clamped to what the grid's bits, as they are now, leave occupied; rays11 persists to the backward
+    if ((a->fwd_flags & FN_STEP_TIGHTEN) && (rc = fastnerf_occ_ray_bounds(a->occ, nullptr, a->n, a->rays11, 1, nullptr, nullptr, stream)))
+      return rc;
     const bool save = !a->live;
     if (a->occ) {
       // live_ws: [4] counters of the backward | list | scan scratch -- the forward's list and scratch are dead before the backward
@@ -554,14 +561,14 @@ static int train_step(const fn_step_args* a, const fn_step_aux* aux, int phases,
                                              a->seed0, a->seed1, params_c, a->packed_fwd_c, params_f, a->packed_fwd_f, a->occ,
                                              a->live_ws + 4, a->occ_counts ? a->occ_counts : a->live_ws, a->z0, a->raw0, a->rgb0,
                                              a->disp0, a->acc0, a->w0, a->depth0, a->z1, a->z_samples, a->z_std, a->raw1, a->rgb1,
-                                             a->disp1, a->acc1, a->w1, a->depth1, a->fwd_flags, stream)))
+                                             a->disp1, a->acc1, a->w1, a->depth1, fwd_flags, stream)))
         return rc;
     } else if ((rc = fastnerf_render_rays_fwd_ex(a->math_mode, a->n, a->N_samples, a->N_importance, a->rays11, a->lindisp,
                                           (a->perturb || a->t_rand) ? 1 : 0, a->perturb ? 0 : 1, a->white_bkgd, a->t_rand, a->u,
                                           a->noise0, a->noise1, a->seed0, a->seed1, params_c, a->packed_fwd_c, params_f,
                                           a->packed_fwd_f, a->z0, a->raw0, save ? a->act0 : nullptr, a->rgb0, a->disp0, a->acc0,
                                           a->w0, a->depth0, a->z1, a->z_samples, a->z_std, a->raw1, save ? a->act1 : nullptr,
-                                          a->rgb1, a->disp1, a->acc1, a->w1, a->depth1, save ? 0 : a->fwd_flags, stream)))
+                                          a->rgb1, a->disp1, a->acc1, a->w1, a->depth1, save ? 0 : fwd_flags, stream)))
       return rc;
     if ((rc = fastnerf_mse_leafmax(a->n, two ? a->rgb1 : a->rgb0, two ? a->rgb0 : nullptr, a->target, a->grad_scale, a->g_rgb,
                                    two ? a->g_rgb0 : nullptr, a->loss2, a->leaf_tag, a->max_leaves, a->table, stream)))

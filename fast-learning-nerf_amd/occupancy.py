@@ -20,7 +20,13 @@ over the object and coarser grids over larger boxes around it.  A sample takes t
 skipped because it was looked at and found empty, not because it was assumed empty.
 
     cascade = fastnerf.occupancy.OccupancyCascade.from_network(render_kwargs_test, levels=3)
-    render_kwargs_test['occupancy'] = cascade"""
+    render_kwargs_test['occupancy'] = cascade
+
+Per-ray bounds (opt-in): `grid.ray_bounds(ray_batch)` / `grid.tighten(ray_batch)` (grids and cascades; csrc/ray_bounds.hip) clamp near
+and far of every ray to the part of [near, far] outside which the lookup above calls no sample occupied, so that the coarse depths are
+placed on the object; render_rays(..., occupancy=grid, tighten=True) and run_nerf.Trainer(..., occupancy=grid, tighten=True) do it
+on the way.  Conservative without exceptions; stretches outside every box count as occupied when `outside_occupied` is set, so the
+default grids tighten little: outside_occupied=False is the configuration this is for."""
 import ctypes as C
 
 import numpy as np
@@ -50,7 +56,38 @@ def _network_volume(render_kwargs, N, bound, which='both', chunk=1024 * 64):
     return vol
 
 
-class OccupancyGrid:
+class _RayBounds:
+    """ray_bounds / tighten of OccupancyGrid and OccupancyCascade (fastnerf_occ_ray_bounds through `self._c`)."""
+
+    def _bounds(self, ray_batch):
+        if not torch.is_tensor(ray_batch):
+            raise RuntimeError('fastnerf ops run on the GPU only (no CPU fallback): got a host array')
+        ops.require_gpu(ray_batch)
+        if ray_batch.dim() != 2 or ray_batch.shape[-1] not in (8, 11):
+            raise ValueError('ray batches are [N,8] (o, d, near, far) or [N,11] (+ view directions)')
+        r = ray_batch.detach().float()
+        if r.shape[-1] == 8:      # the kernel reads rows of 11 floats; the view directions are not looked at
+            r = torch.cat([r, torch.zeros(r.shape[0], 3, device=r.device)], -1)
+        return ops.occ_ray_bounds(self._c, r.contiguous())
+
+    def ray_bounds(self, ray_batch):
+        """ray_batch [n,8] or [n,11] (cuda; o, d, near, far in the space the grid lives in -- NDC space for NDC batches) ->
+        (near' [n], far' [n], hit bool [n]): near <= near' < far' <= far, and every depth of [near, far] at which the grid calls the
+        sample o + d * z occupied lies in [near', far'] -- no exceptions, fp32 rounding at cell faces included.  hit False: the ray
+        meets nothing occupied (bounds unchanged).  Stretches outside every box count as occupied when `outside_occupied` is set,
+        so such a grid tightens little: outside_occupied=False is the configuration this is for.  A ray the kernel does not walk
+        (non-finite, near >= far, terms too large for fp32) keeps its bounds with hit True.  Constants: no gradient flows."""
+        bounds, hit = self._bounds(ray_batch)
+        return bounds[:, 0], bounds[:, 1], hit.bool()
+
+    def tighten(self, ray_batch):
+        """(a new batch of the same shape and dtype with columns 6:8 replaced by `ray_bounds`, hit bool [n]).  The input is not
+        modified; the result is an ordinary ray batch for render_rays on any route (near / far are constants there, as always)."""
+        bounds, hit = self._bounds(ray_batch)
+        return torch.cat([ray_batch[:, :6], bounds.to(ray_batch.dtype), ray_batch[:, 8:]], -1), hit.bool()
+
+
+class OccupancyGrid(_RayBounds):
     """Bits of an nx x ny x nz grid over [lo, hi) on the GPU.  Build one with from_mask / from_density / from_network / load,
     or for_training (a grid with a density that `update` maintains)."""
     CHUNK = 1 << 19      # cells per network launch of update()
@@ -242,7 +279,7 @@ class OccupancyGrid:
         return ops.occ_classify(self._c, rays11, z, raw)
 
 
-class OccupancyCascade:
+class OccupancyCascade(_RayBounds):
     """An ordered list of 1 to 8 OccupancyGrids, innermost first (the cascade keeps references to them).  A point is looked up
     level by level with each grid's own index arithmetic; the first grid whose box contains it decides, and the sample takes that
     cell's bit.  A point that no box contains -- every non-finite point -- takes `outside_occupied` (None = the last grid's); the

@@ -875,6 +875,24 @@ def occ_classify(cgrid, rays11, z, raw=None):
     return idx, cnt
 
 
+def occ_ray_bounds(cgrid, rays11, write_back=False):
+    """Per ray of rays11 [n, 11] the part [near', far'] of [near, far] (columns 6:8) outside which the grid (cgrid a _lib.OccGrid) or the
+    cascade (a _lib.OccCascade) calls no sample o + d * z occupied: (bounds float32 [n, 2], hit uint8 [n]); a ray with hit = 0 meets
+    nothing occupied and keeps its bounds.  Conservative without exceptions, `outside_occupied` honoured (fastnerf_occ_ray_bounds).
+    write_back=True also stores near' / far' into columns 6:8 of rays11, in place; no other column is written."""
+    require_gpu(rays11)
+    assert rays11.dim() == 2 and rays11.shape[1] == 11 and rays11.is_contiguous() and rays11.dtype == torch.float32
+    n = rays11.shape[0]
+    bounds = torch.empty(n, 2, device=rays11.device, dtype=torch.float32)
+    hit = torch.empty(n, device=rays11.device, dtype=torch.uint8)
+    grid, cascade = _ert_grid_args(cgrid)
+    if grid is None and cascade is None:
+        raise TypeError('expected a _lib.OccGrid or a _lib.OccCascade, got None')
+    check(lib().fastnerf_occ_ray_bounds(grid, cascade, n, ptr(rays11), 1 if write_back else 0, ptr(bounds), ptr(hit), stream()),
+          'fastnerf_occ_ray_bounds')
+    return bounds, hit
+
+
 def occ_cell_points(cgrid, c0, rays11, seed=0):
     """One point inside each of the cells c0 .. c0 + len(rays11) - 1 of the grid as rays11 rows (o = point, rest 0): the cell's
     centre (seed 0) or a Philox-jittered point keyed by (seed, cell)."""

@@ -536,7 +536,7 @@ def _render_rays_closure(ray_batch, rays11, network_fn, network_fine, network_qu
 
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
                 N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False, occupancy=None,
-                retdepth=False, ert=None, ert_block=32):
+                tighten=False, retdepth=False, ert=None, ert_block=32):
     """render.py:195-305.  Two routes, chosen by the networks (after `.module` unwrapping):
 
     * fastnerf NeRF modules (8 x 256): positional encoding + MLP run fused inside the HIP kernels; `network_query_fn` is
@@ -552,6 +552,14 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     other sample gets the logits it gets without the grid.  ValueError with
     raw_noise_std > 0 (noise is added to sigma before the relu: a zero sigma is not a dead sample) and when gradients are
     wanted (the training step must not silently change its gradients).
+
+    `tighten=True` (with `occupancy=`; ValueError without): before the coarse depths are placed, near and far of every ray are clamped
+    to the part of [near, far] outside which the grid calls no sample occupied (`occupancy.tighten`: fastnerf_occ_ray_bounds, one launch),
+    so the N_samples coarse depths spread over the object instead of the scene-wide range.  Exactly render_rays(occupancy.tighten(
+    ray_batch)[0], ...): both routes, and with `ert=`.  A ray that meets nothing occupied keeps its bounds and its result.  Stretches
+    outside every box count as occupied when the grid's `outside_occupied` is set, so the default grids tighten little:
+    outside_occupied=False is the configuration this is for.  The depths change, so the maps differ from the untightened render
+    by what the two sets of samples resolve; `tighten=False` (the default) makes exactly the calls it made before.
 
     `retdepth=True` adds `depth_map` (and `depth0` with two passes), the expected sample distance sum_i w_i z_i of render.py:186,
     to the returned dict on both routes; the default leaves the key set as it is.
@@ -587,6 +595,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
         raise ValueError('a ray batch with view directions needs networks built with use_viewdirs=True')
     if fused and ray_batch.shape[-1] == 8 and net_c.use_viewdirs:
         raise ValueError('networks built with use_viewdirs=True need ray batches with view directions [N,11]')
+    if tighten and occupancy is None:
+        raise ValueError('render_rays: tighten=True clamps near / far to an occupancy grid: it needs occupancy=')
     ops.require_gpu(ray_batch)
     if occupancy is not None:
         if raw_noise_std > 0.:
@@ -608,6 +618,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
         if torch.is_grad_enabled() and (ray_batch.requires_grad or any(p.requires_grad for m in nets for p in m.parameters())):
             raise ValueError('render_rays: early ray termination is an inference feature; call it under torch.no_grad() (or with '
                              'parameters and rays that do not require grad)')
+    if tighten:
+        ray_batch = occupancy.tighten(ray_batch)[0]
     rays11 = ray_batch.contiguous().float()
     if rays11.shape[-1] == 8:      # no view directions: the kernels' direction slots stay zero (their weights are zero too)
         rays11 = torch.cat([rays11, torch.zeros(rays11.shape[0], 3, device=rays11.device)], -1)

@@ -230,6 +230,13 @@ class Trainer:
     raw_noise_std > 0 is a ValueError (noise is added before the relu: a zero sigma is not a dead sample).
     `occupancy_counts`: device int32 [4] = (occupied, total) samples of the coarse pass, then of the fine pass, of the last step
     (None without a grid).  A step on an empty batch (a data-parallel tail) neither renders nor refreshes the grid.
+    `tighten=True` (with a grid; ValueError without, or off the fused step): between packing the rays and the forward, near and far
+    of every ray are clamped to the part of [near, far] outside which the grid -- its bits as they are at that step, nothing is
+    cached across `grid.update` -- calls no sample occupied (fastnerf_occ_ray_bounds, FN_STEP_TIGHTEN), so the coarse depths spread
+    over the object.  A ray that meets nothing occupied keeps its bounds.  Stretches outside the box count as occupied when the grid's
+    `outside_occupied` is set, so the default grid tightens little: OccupancyGrid.for_training(outside_occupied=False) is the
+    configuration this is for.  It raises the occupied fraction of a step's samples (`occupancy_counts`): a step may get slower
+    while each sample does more.
 
     Depth / opacity supervision (lambda_depth, lambda_acc; step(..., depth=, depth_weight=, acc=, acc_weight=), [n] each): the step
     minimises mse(fine) + mse(coarse) + lambda_depth (Ld_fine + Ld_coarse) + lambda_acc (La_fine + La_coarse) with
@@ -243,7 +250,7 @@ class Trainer:
 
     def __init__(self, render_kwargs_train, H, W, K, near, far, lrate=5e-4, lrate_decay=250, decay=True,
                  beta1=0.9, beta2=0.999, eps=1e-8, occupancy=None, occupancy_every=16, occupancy_warmup=256, occupancy_cells=None,
-                 lambda_depth=0., lambda_acc=0.):
+                 lambda_depth=0., lambda_acc=0., tighten=False):
         kw = render_kwargs_train
         self._kw = kw
         self.net_c = kw['network_fn']
@@ -282,6 +289,7 @@ class Trainer:
         self.occupancy_cells = occupancy_cells
         self.occupancy_counts = None if occupancy is None else torch.zeros(4, device=self.flat.device, dtype=torch.int32)
         self.occupancy_steps = 0     # steps taken with the grid set
+        self.tighten = bool(tighten)
         self.lambda_depth, self.lambda_acc = float(lambda_depth), float(lambda_acc)
         self._aux_zero = torch.zeros(4, device=self.flat.device, dtype=torch.float32)
         self.aux_losses = self._aux_zero
@@ -291,6 +299,8 @@ class Trainer:
 
     def _check_occupancy(self):
         if self.occupancy is None:
+            if self.tighten:
+                raise ValueError('Trainer: tighten=True clamps near / far to an occupancy grid: it needs occupancy=')
             return
         from .occupancy import OccupancyCascade
         if isinstance(self.occupancy, OccupancyCascade):
@@ -328,7 +338,7 @@ class Trainer:
 
     def forward_backward(self, rays_o, rays_d, target, leaf_tag=None, table=None, max_leaves=0, t_rand=None, u=None,
                          n_global=None, depth=None, depth_weight=None, acc=None, acc_weight=None):
-        if self.occupancy is not None:
+        if self.occupancy is not None or self.tighten:
             raise ValueError('Trainer.forward_backward: the call-by-call route has no occupancy grid; use step()')
         n = rays_o.shape[0]
         dev = rays_o.device
@@ -378,7 +388,7 @@ class Trainer:
             self.repack()           # the math mode changed under this trainer
             self._sa_key = None
         live = self.live.use_live(self.net_c, self.net_f, Ni)
-        if self.occupancy is not None:
+        if self.occupancy is not None or self.tighten:
             self._check_occupancy()
             live = True             # the grid's first forward feeds the compacted backward only
         key = (n, str(dev), torch.cuda.current_stream(dev).cuda_stream, tag)
@@ -460,7 +470,7 @@ class Trainer:
         a.max_leaves = int(max_leaves)
         a.grad_scale = 1.0 if n_global is None else float(n) / float(n_global)
         a.live = int(live)
-        a.fwd_flags = 1 if (live and self.skip_dead_rgb and noise0 is None) else 0
+        a.fwd_flags = (1 if (live and self.skip_dead_rgb and noise0 is None) else 0) | (_lib.STEP_TIGHTEN if self.tighten else 0)
         occ = self.occupancy
         if occ is not None and self.occupancy_counts is None:      # a grid set after construction
             self.occupancy_counts = torch.zeros(4, device=self.flat.device, dtype=torch.int32)
@@ -673,7 +683,8 @@ def train(images, poses, H, W, focal, args, near=2., far=6., device='cuda', log=
     if getattr(args, 'occupancy_train', False):     # opt-in (no such flag in the reference's parser): train through an occupancy grid
         from .occupancy import OccupancyGrid
         occ_kw = dict(occupancy=OccupancyGrid.for_training(N=getattr(args, 'occupancy_N', 128), bound=getattr(args, 'occupancy_bound', 1.2),
-                                                           device=dev),
+                                                           outside_occupied=getattr(args, 'occupancy_outside_occupied', True), device=dev),
+                      tighten=getattr(args, 'occupancy_tighten', False),     # (matters with occupancy_outside_occupied=False)
                       occupancy_every=getattr(args, 'occupancy_every', 16), occupancy_warmup=getattr(args, 'occupancy_warmup', 256))
     trainer = Trainer(kw_train, H, W, K, near, far, lrate=args.lrate, lrate_decay=args.lrate_decay, **occ_kw)
     trainer.global_iter = global_iter

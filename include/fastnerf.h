@@ -431,6 +431,11 @@ int fastnerf_mlp_x6_bwd_live(int kind, int64_t n, int S, const float* draw, cons
 #define FN_STEP_BWD_FINE 2    /* backward of the fine pass -> grads + net_floats (no-op when N_importance == 0) */
 #define FN_STEP_BWD_COARSE 4  /* backward of the coarse pass -> grads */
 #define FN_STEP_UPDATE 8      /* Adam over both nets + re-pack of their weights */
+/* A bit of fn_step_args.fwd_flags, not an FN_FWD_* option: between fastnerf_pack_rays and the forward of FN_STEP_FORWARD, near and
+ * far of every row of rays11 are clamped by fastnerf_occ_ray_bounds(occ, ..., write_back = 1) -- the bits as they are at this step,
+ * nothing cached -- so the coarse depths spread over the occupied part of the ray.  Needs occ != NULL (-1 otherwise).  The step
+ * masks the bit off before the flags go on to the forward; the backward phases read the clamped rays11 that the forward left. */
+#define FN_STEP_TIGHTEN 2
 struct fn_occ_grid; /* the occupancy grid, declared below */
 typedef struct fn_step_args {
   /* the batch */
@@ -455,7 +460,7 @@ typedef struct fn_step_args {
   int32_t math_mode;                                /* 0 exact fp32 MFMA, 1 split-bf16 (x3), 2 bf16x6 (fp32 width) */
   int32_t N_samples, N_importance, lindisp, perturb, white_bkgd, ndc, H, W;
   int32_t live;                                     /* != 0: forward without saving + compacted backward */
-  int32_t fwd_flags;                                /* FN_FWD_* of the first forward of a compacted step */
+  int32_t fwd_flags;                                /* FN_FWD_* of the first forward of a compacted step | FN_STEP_TIGHTEN */
   int32_t max_leaves, adam_t;
   /* training through an occupancy grid (declared below; live != 0 and no sigma noise): the first forward of each pass runs over
    * the occupied samples only, as fastnerf_render_rays_fwd_occ does; occ_counts: NULL or 4 int32 = (occupied, total) of the
@@ -691,6 +696,27 @@ int fastnerf_render_rays_fwd_ert(int math_mode, int64_t n, int N_samples, int N_
                                  float* disp0, float* acc0, float* w0, float* depth0, float* z1, float* z_samples, float* z_std,
                                  float* raw1, float* rgb1, float* disp1, float* acc1, float* w1, float* depth1, int flags,
                                  fn_stream_t stream);
+
+/* ---- per-ray bounds from the occupancy grid: do not PLACE samples in empty space (csrc/ray_bounds.hip) ---------------------------------
+ * Row r of rays11 [n,11] gives o, d, near (column 6) and far (column 7) in the space the grid lives in (NDC space for NDC batches:
+ * where the samples are looked up).  Per ray (near', far', hit) through `grid` or `cascade` (exactly one non-NULL):
+ *   conservative  for every depth near <= z <= far whose sample x = o + d * z (one rounded multiply, one rounded add, as
+ *                 fastnerf_occ_classify forms it) the lookup calls occupied: hit = 1 and near' <= z <= far'.  No exceptions:
+ *                 `outside_occupied` is honoured, so stretches of [near, far] outside every box count as occupied when it is set --
+ *                 such a grid tightens little; outside_occupied = 0 is the configuration this is for.
+ *   tight         near <= near' < far' <= far, and near' / far' lie less than a cell (the width of the fp32 uncertainty of a face
+ *                 crossing, see ray_bounds.hip) before the first / after the last cell of the ray that is occupied.
+ *   unchanged     near' = near, far' = far when the ray meets no occupied stretch in [near, far] (hit = 0), and, with hit = 1, when
+ *                 the clamped interval would be empty or a point, when o, d, near or far is not finite, when near >= far, when the
+ *                 ray's terms are too large for the rounding bound (|o|, |d| far or the cell counts beyond some 2^18 cells), or when
+ *                 the iteration cap -- 2 (nx + ny + nz) + 16 per level, + 16, computed by this call -- is reached.  Unchanged
+ *                 bounds with hit = 1 are always a valid answer.
+ * bounds [n,2] (near', far') and hit [n] bytes may each be NULL; write_back != 0 also stores near' / far' into columns 6 / 7 of
+ * the row -- no other column is written, and a ray whose bounds are unchanged is not written at all.  One launch, one thread per
+ * ray, no atomics, no scratch: the result is bit-identical from run to run, and a cascade of one level gives the grid's bits.
+ * Not differentiable: near' and far' are constants of a backward, as near and far are. */
+int fastnerf_occ_ray_bounds(const fn_occ_grid* grid, const fn_occ_cascade* cascade, int64_t n, float* rays11, int write_back,
+                            float* bounds, uint8_t* hit, fn_stream_t stream);
 
 /* ---- density gradient: d(sigma)/d(x) through the fused MLP (csrc/sigma_grad.hip) -------------------------------------------------
  * sigma[n,S] (may be NULL) = raw[..., 3] of the forward of `math_mode` (0 exact fp32, 1 split-bf16 "bf16x3", 2 "bf16x6") at the
