@@ -180,6 +180,9 @@ SIGNATURES = {
     'fastnerf_render_rays_fwd_ert': (I, [I, L, I, I, P, I, I, I, I, P, P, U64, U64, P, P, P, P, C.POINTER(OccGrid), C.POINTER(OccCascade), F, I,
                                          P, P, P] + [P] * 16 + [I, P]),
     'fastnerf_occ_ray_bounds': (I, [C.POINTER(OccGrid), C.POINTER(OccCascade), L, P, I, P, P, P]),
+    'fastnerf_occ_march': (I, [C.POINTER(OccGrid), C.POINTER(OccCascade), L, I, I, P, I, I, I, I, P, F, P, P, P, P, P]),
+    'fastnerf_march_list': (I, [L, I, I, I, P, P, P, P, P, P, C.c_int32, P]),
+    'fastnerf_render_rays_fwd_march': (I, [I, L, I, I, P, I, I, P, P, C.POINTER(OccGrid), C.POINTER(OccCascade), F, I] + [P] * 10 + [I, P]),
     'fastnerf_mlp_sigma_grad_ws_floats': (L, [I, L]),
     'fastnerf_mlp_sigma_grad': (I, [I, I, L, I, P, P, P, P, P, P, P, P, P]),
     'fastnerf_ray_grad_ws_floats': (L, [I, L, I]),

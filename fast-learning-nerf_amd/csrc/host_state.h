@@ -19,7 +19,7 @@ inline int set_dyn_lds(const void* kern, DevOnce& once, int bytes) { return set_
 // The library-owned workspaces of a stream (policy: ws_cache.h), one per (current device, stream, slot).  -> the buffer and its capacity in
 // floats (>= need_floats), or null: the stream is capturing (nothing is allocated inside a capture), or there is no memory -- `what` is
 // the line that says so, once per refused size.  Null is no error: the caller takes the route that needs no workspace.
-enum { WS_HEAD_TILES = 0, WS_PAIR_DACT = 1, WS_PAIR_PARTIAL = 2 };
+enum { WS_HEAD_TILES = 0, WS_PAIR_DACT = 1, WS_PAIR_PARTIAL = 2, WS_MARCH = 3 };
 struct StreamWs { float* p; int64_t cap; };
 StreamWs stream_ws(int slot, hipStream_t stream, int64_t need_floats, const WsName& what);
 }  // namespace fn

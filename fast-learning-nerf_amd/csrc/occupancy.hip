@@ -32,41 +32,23 @@
 //   segment of B consecutive samples per ray, evaluated when the ray's transmittance is still > eps AND G (one grid, a cascade, or
 //   OccAll = no grid) says occupied.  The instantiations above are untouched by it (isa_funcs.py: 11 identical, 0 differ).  The
 //   transmittance itself is advanced by ert_advance_kernel in composite.hip, next to the compositing arithmetic it repeats.
+//   The marched render (fastnerf_march_list) is one more, MarchDev: the entries of one segment of the packed rows of march.hip, evaluated
+//   when the slot's lattice index is >= 0.  The lookup itself (descriptors, occ_point, the host checks) lives in occ_lookup.h, which
+//   march.hip shares.
 // All of them are memory bound and small next to the MLP they spare: one lane per cell / point / four consecutive samples, a
 // ray's 44 bytes come through the cache for all its samples.
 #include "common.h"
+#include "occ_lookup.h"   // OccDev, OccCascadeDev, occ_point, occ_dev / occ_cascade_dev: shared with march.hip
 
 namespace fn {
 void cp_scan_launch(int nb, int32_t* blk, int32_t* count_out, int n_points, hipStream_t st);   // train.hip
 }
 
-#define OCC_GRID_ARG "grid: non-null words, 1 <= n[i] <= 2^24, fewer than 2^31 cells, finite lo, finite inv > 0"
 #define OCC_BLOCK 256
 #define OCC_PTS 1024   // samples per block of the classify passes (256 threads x 4) = CP_PTS of train.hip, whose scan and
                        // fastnerf_compact_ws_ints this file reuses
 
 namespace {
-
-struct OccDev {
-  const uint32_t* words;
-  float lo[3], inv[3];
-  int n[3];
-  int outside;
-};
-
-// a cascade (fn_occ_cascade): per level the geometry of OccDev (40 bytes) and, apart from it, the pointer to its bits
-struct OccLevel {
-  float lo[3], inv[3];
-  int n[3];
-  int pad;
-};
-
-struct OccCascadeDev {
-  OccLevel g[FN_OCC_MAX_LEVELS];
-  const uint32_t* words[FN_OCC_MAX_LEVELS];
-  int levels;
-  int outside;
-};
 
 // early ray termination (fastnerf_ert_classify): no grid at all -- every point counts as occupied, and nothing of it is loaded
 struct OccAll {};
@@ -82,35 +64,12 @@ struct ErtDev {
   uint32_t s0, w;
 };
 
-struct OccDims {
-  int nx, ny, nz;
-  int64_t ncells, nwords;
+// The marched render (fastnerf_march_list, march.hip): one segment [s0, s0 + w) of the C slots of every packed row, sorted by the slot's
+// lattice index alone -- kidx >= 0 is a live sample, -1 a closing entry or padding.  Entries as for ErtDev; no ray, no depth, no grid is read.
+struct MarchDev {
+  const int32_t* kidx;
+  uint32_t s0, w;
 };
-
-__device__ __forceinline__ bool occ_bit(const uint32_t* __restrict__ words, uint32_t c) { return (words[c >> 5] >> (c & 31u)) & 1u; }
-
-__device__ __forceinline__ bool occ_point(const OccDev& g, float x, float y, float z) {
-  const float fi = floorf(fmul(fsub(x, g.lo[0]), g.inv[0]));
-  const float fj = floorf(fmul(fsub(y, g.lo[1]), g.inv[1]));
-  const float fk = floorf(fmul(fsub(z, g.lo[2]), g.inv[2]));
-  const bool inside = fi >= 0.f && fi < (float)g.n[0] && fj >= 0.f && fj < (float)g.n[1] && fk >= 0.f && fk < (float)g.n[2];
-  if (!inside) return g.outside != 0;
-  return occ_bit(g.words, ((uint32_t)fi * (uint32_t)g.n[1] + (uint32_t)fj) * (uint32_t)g.n[2] + (uint32_t)fk);
-}
-
-// first level whose box contains the point decides; l and c.levels are uniform, so g[l] and words[l] are scalar loads
-__device__ __forceinline__ bool occ_point(const OccCascadeDev& c, float x, float y, float z) {
-  for (int l = 0; l < c.levels; ++l) {
-    const OccLevel& g = c.g[l];
-    const float fi = floorf(fmul(fsub(x, g.lo[0]), g.inv[0]));
-    const float fj = floorf(fmul(fsub(y, g.lo[1]), g.inv[1]));
-    const float fk = floorf(fmul(fsub(z, g.lo[2]), g.inv[2]));
-    // (& not &&: one straight-line test per level, its 40 bytes of geometry fetched by one batch of scalar loads)
-    if ((fi >= 0.f) & (fi < (float)g.n[0]) & (fj >= 0.f) & (fj < (float)g.n[1]) & (fk >= 0.f) & (fk < (float)g.n[2]))
-      return occ_bit(c.words[l], ((uint32_t)fi * (uint32_t)g.n[1] + (uint32_t)fj) * (uint32_t)g.n[2] + (uint32_t)fk);
-  }
-  return c.outside != 0;
-}
 
 __device__ __forceinline__ bool occ_point(const OccAll&, float, float, float) { return true; }
 
@@ -245,6 +204,10 @@ __device__ __forceinline__ int64_t occ_sample(const ErtDev<G>& e, int64_t q, uin
   const uint32_t r = (uint32_t)q / e.w;   // n * w <= n * S < 2^31
   return (int64_t)(r * S + e.s0 + ((uint32_t)q - r * e.w));
 }
+__device__ __forceinline__ int64_t occ_sample(const MarchDev& e, int64_t q, uint32_t S) {   // S = C, the slots of a row
+  const uint32_t r = (uint32_t)q / e.w;
+  return (int64_t)(r * S + e.s0 + ((uint32_t)q - r * e.w));
+}
 
 // sample p of the pass is evaluated: its point x = o + d * z (as the MLP kernels compute it) is occupied -- and, through an ErtDev,
 // its ray's transmittance is still > eps (a NaN is not)
@@ -259,6 +222,9 @@ __device__ __forceinline__ bool occ_live(const ErtDev<G>& e, const float* __rest
                                          int64_t p) {
   if (e.trans && !(e.trans[(uint32_t)p / S] > e.eps)) return false;
   return occ_live(e.g, rays, zv, S, p);
+}
+__device__ __forceinline__ bool occ_live(const MarchDev& e, const float* __restrict__, const float* __restrict__, uint32_t, int64_t p) {
+  return e.kidx[p] >= 0;
 }
 
 // bits 0..3: entries p0 .. p0+3 of the pass are evaluated
@@ -309,54 +275,7 @@ __global__ void __launch_bounds__(OCC_BLOCK) occ_scatter_kernel(G g, int64_t n, 
   }
 }
 
-// ---- host side ---------------------------------------------------------------------------------------------------
-bool occ_dims(int64_t nx, int64_t ny, int64_t nz, OccDims* d) {
-  if (nx < 1 || ny < 1 || nz < 1 || nx > (1 << 24) || ny > (1 << 24) || nz > (1 << 24)) return false;
-  if (nx > (((int64_t)1 << 31) - 1) / ny / nz) return false;
-  d->nx = (int)nx;
-  d->ny = (int)ny;
-  d->nz = (int)nz;
-  d->ncells = nx * ny * nz;
-  d->nwords = (d->ncells + 31) / 32;
-  return true;
-}
-
-// the grid's geometry without its bits (o->words = g->words, which may be NULL)
-bool occ_geom(const fn_occ_grid* g, OccDev* o) {
-  OccDims d;
-  if (!g || !occ_dims(g->n[0], g->n[1], g->n[2], &d)) return false;
-  o->words = g->words;
-  for (int c = 0; c < 3; ++c) {
-    if (!(g->inv[c] > 0.f) || !(g->inv[c] <= 3.0e38f) || !(g->lo[c] == g->lo[c])) return false;
-    o->lo[c] = g->lo[c];
-    o->inv[c] = g->inv[c];
-    o->n[c] = g->n[c];
-  }
-  o->outside = g->outside_occupied ? 1 : 0;
-  return true;
-}
-
-bool occ_dev(const fn_occ_grid* g, OccDev* o) { return g && g->words && occ_geom(g, o); }
-
-// every level passes occ_dev's checks; the cascade's `outside` is the LAST level's outside_occupied
-bool occ_cascade_dev(const fn_occ_cascade* c, OccCascadeDev* o) {
-  if (!c || c->levels < 1 || c->levels > FN_OCC_MAX_LEVELS) return false;
-  *o = OccCascadeDev{};
-  for (int l = 0; l < c->levels; ++l) {
-    OccDev d;
-    if (!occ_dev(&c->level[l], &d)) return false;
-    for (int a = 0; a < 3; ++a) {
-      o->g[l].lo[a] = d.lo[a];
-      o->g[l].inv[a] = d.inv[a];
-      o->g[l].n[a] = d.n[a];
-    }
-    o->words[l] = d.words;
-    o->outside = d.outside;
-  }
-  o->levels = c->levels;
-  return true;
-}
-
+// ---- host side (occ_dims, occ_geom, occ_dev, occ_cascade_dev: occ_lookup.h) ----------------------------------------
 inline unsigned occ_blocks(int64_t ncells) { return (unsigned)((ncells + OCC_BLOCK - 1) / OCC_BLOCK); }
 
 // the three dilation passes (k, j, i) of a grid whose undilated bits are in ws[0 .. nwords): -> words.  ws: 2 * nwords.
@@ -475,8 +394,6 @@ extern "C" int fastnerf_occ_classify(const fn_occ_grid* grid, int64_t n, int S, 
   return 0;
 }
 
-#define OCC_CASCADE_ARG "cascade: 1 <= levels <= 8; every level: non-null words, 1 <= n[i] <= 2^24, fewer than 2^31 cells, finite lo, finite inv > 0"
-
 // render.cpp checks a cascade (a grid: fastnerf_render_rays_fwd_ert) before it enqueues anything: NULL when every level is usable, else
 // what is asked of one
 namespace fn {
@@ -536,6 +453,25 @@ extern "C" int fastnerf_ert_classify(const fn_occ_grid* grid, const fn_occ_casca
   if (grid) ert_classify_launch(g, n, S, s0, s1, rays11, z, trans, eps, live_idx, count_out, raw, ws, s);
   else if (cascade) ert_classify_launch(c, n, S, s0, s1, rays11, z, trans, eps, live_idx, count_out, raw, ws, s);
   else ert_classify_launch(OccAll{}, n, S, s0, s1, rays11, z, trans, eps, live_idx, count_out, raw, ws, s);
+  FN_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- the marched render (include/fastnerf.h, "marched render"): the live list of one segment of the packed rows that fastnerf_occ_march wrote
+// the render's counters: (evaluated so far, lattice points); one thread, behind the scan that wrote seg_count on the same stream
+__global__ void march_total_kernel(const int32_t* __restrict__ seg_count, int first, int32_t lattice, int32_t* __restrict__ total) {
+  total[0] = (first ? 0 : total[0]) + seg_count[0];
+  total[1] = lattice;
+}
+
+extern "C" int fastnerf_march_list(int64_t n, int C, int s0, int s1, const int32_t* kidx, int32_t* live_idx, int32_t* count_out, float* raw,
+                                   int32_t* ws, int32_t* total, int32_t lattice, fn_stream_t stream) {
+  FN_CHECK_ARG(n > 0 && C >= 1 && n * (int64_t)C < ((int64_t)1 << 31), "n > 0, C >= 1, n * C < 2^31");
+  FN_CHECK_ARG(s0 >= 0 && s0 < s1 && s1 <= C, "0 <= s0 < s1 <= C");
+  FN_CHECK_ARG(kidx && live_idx && count_out && ws, "non-null pointers");
+  const MarchDev m = {kidx, (uint32_t)s0, (uint32_t)(s1 - s0)};
+  occ_classify_launch(m, n * (int64_t)(s1 - s0), C, (const float*)nullptr, (const float*)nullptr, live_idx, count_out, raw, ws, fn::S(stream));
+  if (total) hipLaunchKernelGGL(march_total_kernel, dim3(1), dim3(1), 0, fn::S(stream), (const int32_t*)count_out, s0 == 0 ? 1 : 0, lattice, total);
   FN_LAUNCH_CHECK();
   return 0;
 }

@@ -8,6 +8,7 @@
 // -ffp-contract=off).
 #include <stdarg.h>
 #include "common.h"
+#include "depths.h"
 
 namespace fn {
 static thread_local std::string g_err;
@@ -131,20 +132,7 @@ __global__ void pack_rays_kernel(int64_t n, const float* __restrict__ ro, const 
   }
 }
 
-// torch.linspace(0,1,S) fp32: symmetric evaluation (start+step*i below the midpoint,
-// end-step*(S-1-i) above it).
-__device__ __forceinline__ float lin01(int i, int S) {
-  const float step = 1.0f / (float)(S - 1);
-  return (i < S / 2) ? fmul(step, (float)i) : fsub(1.0f, fmul(step, (float)(S - 1 - i)));
-}
-
-__device__ __forceinline__ float coarse_depth(float near, float far, int i, int S, int lindisp) {
-  if (S == 1) return near;
-  const float t = lin01(i, S);
-  if (!lindisp) return fadd(fmul(near, fsub(1.0f, t)), fmul(far, t));
-  return 1.0f / fadd(fmul(1.0f / near, fsub(1.0f, t)), fmul(1.0f / far, t));
-}
-
+// (lin01 / coarse_depth: depths.h)
 __global__ void sample_coarse_kernel(int64_t n, int S, const float* __restrict__ rays, int lindisp, int perturb,
                                      const float* __restrict__ t_rand, uint64_t seed, float* __restrict__ z) {
   const int64_t total = n * S;

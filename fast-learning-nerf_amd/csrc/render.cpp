@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include "../../include/fastnerf.h"
 #include "dw_pair.h"
+#include "host_state.h"   // fn::stream_ws: the marched render's scratch
 
 namespace fn {
 void set_error(const char* fmt, ...);
@@ -266,6 +267,68 @@ extern "C" int fastnerf_render_rays_fwd_ert(int math_mode, int64_t n, int N_samp
     }
     return 0;
   });
+}
+
+// The marched render (include/fastnerf.h, "marched render"): no sampler and no coarse pass.  Per round fastnerf_occ_march places the
+// segment's slots of every packed row, fastnerf_march_list lists its live slots (and zeroes the logits of the others), the list forward
+// evaluates them on the packed z with S = C, and -- with ert -- fastnerf_ert_advance carries the transmittance that cuts the next round.
+// One fastnerf_raw2outputs_fwd over [n, C] follows.  The scratch (list, scan, segment count, per-ray state, transmittance) is the
+// stream's library-owned workspace, slot WS_MARCH.
+extern "C" int fastnerf_render_rays_fwd_march(int math_mode, int64_t n, int K, int C, const float* rays11, int lindisp, int white_bkgd,
+                                              const float* params, const float* packed, const fn_occ_grid* grid,
+                                              const fn_occ_cascade* cascade, float eps, int block, int32_t* counts_out, float* z,
+                                              int32_t* kidx, uint8_t* overflow, float* raw, float* rgb, float* disp, float* acc, float* w,
+                                              float* depth, int flags, fn_stream_t stream) {
+  const char* fname = "fastnerf_render_rays_fwd_march";
+  if (math_mode < 0 || math_mode > 2 || n < 0 || K < 2 || K >= (1 << 24) || C < 2 || C > 512) {
+    fn::set_error("%s: bad argument: math_mode in {0,1,2}, n >= 0, 2 <= K < 2^24, 2 <= C <= 512", fname);
+    return -1;
+  }
+  if (block != 0 && (!(eps >= 0.f && eps < 1.f) || block < 1)) {   // block == 0: no early ray termination, one round
+    fn::set_error("%s: bad argument: 0 <= eps < 1, block >= 1 (block == 0: no early ray termination)", fname);
+    return -1;
+  }
+  if ((grid != nullptr) == (cascade != nullptr)) {
+    fn::set_error("%s: bad argument: exactly one of grid / cascade", fname);
+    return -1;
+  }
+  if (n == 0) return 0;
+  if (n * (int64_t)C >= ((int64_t)1 << 31) || n * (int64_t)K >= ((int64_t)1 << 31)) {
+    fn::set_error("%s: bad argument: n * C < 2^31 (lists index slots with int32), n * K < 2^31 (the counters are int32)", fname);
+    return -1;
+  }
+  if (!rays11 || !params || !packed || !counts_out || !z || !kidx || !overflow || !raw || !rgb || !disp || !acc || !w || !depth) {
+    fn::set_error("%s: null pointer", fname);
+    return -1;
+  }
+  if (const char* fault = cascade ? fn::occ_cascade_fault(cascade) : fn::occ_grid_fault(grid)) {   // before anything is enqueued
+    fn::set_error("%s: bad argument: %s", fname, fault);
+    return -1;
+  }
+  const int B = (block == 0 || block > C) ? C : block;
+  const int64_t Q = n * (int64_t)B, cws_ints = fastnerf_compact_ws_ints(Q);
+  static const fn::WsName what = {"fastnerf: no memory for the %.1f MB scratch of the marched render\n", 1e-6};
+  const fn::StreamWs sw = fn::stream_ws(fn::WS_MARCH, fn::S(stream), Q + cws_ints + 2 + 3 * n, what);
+  if (!sw.p) {
+    fn::set_error("%s: no workspace (the stream is capturing, or there is no memory for %lld int32)", fname, (long long)(Q + cws_ints + 2 + 3 * n));
+    return -1;
+  }
+  int32_t* idx = reinterpret_cast<int32_t*>(sw.p);
+  int32_t* cws = idx + Q;
+  int32_t* seg = cws + cws_ints;
+  int32_t* state = seg + 2;
+  float* trans = sw.p + (Q + cws_ints + 2 + 2 * n);
+  int rc;
+  for (int s0 = 0; s0 < C; s0 += B) {
+    const int s1 = (C - s0 > B) ? s0 + B : C;
+    if ((rc = fastnerf_occ_march(grid, cascade, n, K, lindisp, rays11, C, s0, s1, s0 == 0, (block && s0) ? trans : nullptr, eps, state, z, kidx,
+                                 overflow, stream)))
+      return rc;
+    if ((rc = fastnerf_march_list(n, C, s0, s1, kidx, idx, seg, raw, cws, counts_out, (int32_t)(n * (int64_t)K), stream))) return rc;
+    if ((rc = modes[math_mode].fwd_list(0, n, C, rays11, z, params, packed, raw, idx, seg, flags, stream))) return rc;
+    if (block && s1 < C && (rc = fastnerf_ert_advance(n, C, s0, s1, raw, z, rays11, s0 == 0, trans, nullptr, nullptr, stream))) return rc;
+  }
+  return fastnerf_raw2outputs_fwd(n, C, raw, z, rays11, nullptr, white_bkgd, rgb, disp, acc, w, depth, stream);
 }
 
 extern "C" int fastnerf_render_rays_fwd(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11,

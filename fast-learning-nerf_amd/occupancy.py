@@ -86,6 +86,23 @@ class _RayBounds:
         bounds, hit = self._bounds(ray_batch)
         return torch.cat([ray_batch[:, :6], bounds.to(ray_batch.dtype), ray_batch[:, 8:]], -1), hit.bool()
 
+    def march(self, ray_batch, K, cap=128, lindisp=False):
+        """ray_batch [n,8] or [n,11] (cuda) -> (z float32 [n, cap], kidx int32 [n, cap], overflow bool [n]): the packed rows of the
+        marched render (fastnerf_occ_march, one round; include/fastnerf.h, "marched render").  Of the K lattice depths of every ray --
+        the coarse depths for N_samples = K, perturb = 0 -- the ones this grid calls occupied are kept, run by run, each run followed
+        by one closing entry (kidx -1); padding repeats the last depth with kidx -1.  overflow: the ray has more entries than `cap`
+        slots, and the row holds the first cap of them."""
+        if not torch.is_tensor(ray_batch):
+            raise RuntimeError('fastnerf ops run on the GPU only (no CPU fallback): got a host array')
+        ops.require_gpu(ray_batch)
+        if ray_batch.dim() != 2 or ray_batch.shape[-1] not in (8, 11):
+            raise ValueError('ray batches are [N,8] (o, d, near, far) or [N,11] (+ view directions)')
+        r = ray_batch.detach().float()
+        if r.shape[-1] == 8:
+            r = torch.cat([r, torch.zeros(r.shape[0], 3, device=r.device)], -1)
+        z, kidx, overflow, _ = ops.occ_march(self._c, r.contiguous(), K, cap, lindisp=lindisp)
+        return z, kidx, overflow.bool()
+
 
 class OccupancyGrid(_RayBounds):
     """Bits of an nx x ny x nz grid over [lo, hi) on the GPU.  Build one with from_mask / from_density / from_network / load,

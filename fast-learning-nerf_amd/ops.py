@@ -1009,6 +1009,97 @@ def ert_advance(raw, z, rays11, s0, s1, trans, first=False, seg_count=None, tota
     return trans
 
 
+# ---- marched render (csrc/march.hip, csrc/occupancy.hip, render.cpp) ------------------------------------------------------------
+MARCH_K_MAX = (1 << 24) - 1      # lattice depths per ray: 2 <= K < 2^24
+MARCH_CAP_MAX = 512              # slots of a packed row: 2 <= C <= 512 (the compositing kernels' limit)
+
+
+def check_march(march, march_cap):
+    """(K, C) as numbers, or ValueError: integers with 2 <= K < 2^24 and 2 <= C <= 512."""
+    ok = all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in (march, march_cap))
+    if not ok or not (2 <= march <= MARCH_K_MAX) or not (2 <= march_cap <= MARCH_CAP_MAX):
+        raise ValueError('the marched render needs integers 2 <= march < 2^24 and 2 <= march_cap <= 512, got march=%r, march_cap=%r'
+                         % (march, march_cap))
+    return int(march), int(march_cap)
+
+
+def occ_march(cgrid, rays11, K, C, s0=0, s1=None, trans=None, eps=0., lindisp=False, state=None, z=None, kidx=None, overflow=None):
+    """One round [s0, s1) of fastnerf_occ_march over the rays of rays11 [n, 11], through cgrid (a _lib.OccGrid or a _lib.OccCascade):
+    -> (z float32 [n, C], kidx int32 [n, C], overflow uint8 [n], state int32 [n, 2]).  The first round (s0 == 0) allocates what is not
+    given; a later round takes the four tensors of the round before it and writes in place.  trans (float32 [n], optional): a ray
+    with trans <= eps (or NaN) is cut."""
+    require_gpu(rays11, trans, state, z, kidx, overflow)
+    K, C = check_march(K, C)
+    s0 = int(s0)
+    s1 = C if s1 is None else int(s1)
+    assert rays11.dim() == 2 and rays11.shape[1] == 11 and rays11.is_contiguous() and rays11.dtype == torch.float32
+    n, dev = rays11.shape[0], rays11.device
+    if s0 > 0 and any(t is None for t in (state, z, kidx, overflow)):
+        raise ValueError('a round with s0 > 0 continues the state, z, kidx and overflow of the round before it')
+    z = torch.empty(n, C, device=dev, dtype=torch.float32) if z is None else z
+    kidx = torch.empty(n, C, device=dev, dtype=torch.int32) if kidx is None else kidx
+    overflow = torch.empty(n, device=dev, dtype=torch.uint8) if overflow is None else overflow
+    state = torch.empty(n, 2, device=dev, dtype=torch.int32) if state is None else state
+    assert z.shape == (n, C) and z.dtype == torch.float32 and z.is_contiguous() and z.device == dev
+    assert kidx.shape == (n, C) and kidx.dtype == torch.int32 and kidx.is_contiguous() and kidx.device == dev
+    assert overflow.shape == (n,) and overflow.dtype == torch.uint8 and overflow.is_contiguous() and overflow.device == dev
+    assert state.shape == (n, 2) and state.dtype == torch.int32 and state.is_contiguous() and state.device == dev
+    assert trans is None or (trans.shape == (n,) and trans.dtype == torch.float32 and trans.is_contiguous() and trans.device == dev)
+    grid, cascade = _ert_grid_args(cgrid)
+    if grid is None and cascade is None:
+        raise TypeError('expected a _lib.OccGrid or a _lib.OccCascade, got None')
+    check(lib().fastnerf_occ_march(grid, cascade, n, K, 1 if lindisp else 0, ptr(rays11), C, s0, s1, 1 if s0 == 0 else 0, ptr(trans),
+                                   float(eps), ptr(state), ptr(z), ptr(kidx), ptr(overflow), stream()), 'fastnerf_occ_march')
+    return z, kidx, overflow, state
+
+
+def march_list(kidx, s0, s1, raw=None, total=None, lattice=0):
+    """The live list of the segment [s0, s1) of packed rows kidx [n, C]: (live_idx int32 [n * (s1 - s0)], counts int32 [2] = (live,
+    n * (s1 - s0))), on the device; live_idx[:live] ascends and holds ray * C + slot.  raw ([n, C, 4], optional) is zeroed at the
+    segment's other slots."""
+    require_gpu(kidx, raw, total)
+    n, C = kidx.shape
+    s0, s1 = int(s0), int(s1)
+    assert kidx.dtype == torch.int32 and kidx.is_contiguous()
+    assert raw is None or (raw.numel() == n * C * 4 and raw.is_contiguous() and raw.dtype == torch.float32 and raw.device == kidx.device)
+    assert total is None or (total.dtype == torch.int32 and total.is_contiguous() and total.numel() >= 2 and total.device == kidx.device)
+    Q = max(1, n * max(0, s1 - s0))
+    idx = torch.empty(Q, device=kidx.device, dtype=torch.int32)
+    cnt = torch.empty(2, device=kidx.device, dtype=torch.int32)
+    ws = torch.empty(int(lib().fastnerf_compact_ws_ints(Q)), device=kidx.device, dtype=torch.int32)
+    check(lib().fastnerf_march_list(n, C, s0, s1, ptr(kidx), ptr(idx), ptr(cnt), ptr(raw), ptr(ws), ptr(total), int(lattice), stream()),
+          'fastnerf_march_list')
+    return idx, cnt
+
+
+def render_rays_fwd_march(rays11, params, packed, K, C, cgrid, eps=None, block=32, lindisp=False, white_bkgd=False, skip_dead_rgb=False):
+    """The marched render (fastnerf_render_rays_fwd_march): one C-ABI call.  -> dict of rgb, disp, acc, depth, w [n, C] (the maps and
+    the weights of the packed row), raw [n, C, 4], z [n, C], kidx int32 [n, C], overflow uint8 [n], counts int32 [2] = (evaluated
+    samples, n * K).  eps None: no early ray termination."""
+    require_gpu(rays11, params, packed)
+    K, C = check_march(K, C)
+    if eps is None:
+        eps, block = 0., 0
+    else:
+        eps, block = check_ert(eps, block)
+    assert rays11.dim() == 2 and rays11.shape[1] == 11 and rays11.is_contiguous() and rays11.dtype == torch.float32
+    assert packed.numel() == packed_floats(0, 1) and packed_tag(packed) == _MATH, \
+        'packed weights were not produced by mlp_pack under the current math mode'
+    n, dev = rays11.shape[0], rays11.device
+    f = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)      # noqa: E731
+    o = dict(rgb=f(n, 3), disp=f(n), acc=f(n), depth=f(n), w=f(n, C), raw=f(n, C, 4), z=f(n, C),
+             kidx=torch.empty(n, C, device=dev, dtype=torch.int32), overflow=torch.empty(n, device=dev, dtype=torch.uint8),
+             counts=torch.zeros(2, device=dev, dtype=torch.int32))
+    grid, cascade = _ert_grid_args(cgrid)
+    if grid is None and cascade is None:
+        raise TypeError('expected a _lib.OccGrid or a _lib.OccCascade, got None')
+    check(lib().fastnerf_render_rays_fwd_march(mode_id(), n, K, C, ptr(rays11), 1 if lindisp else 0, 1 if white_bkgd else 0, ptr(params),
+                                               ptr(packed), grid, cascade, eps, block, ptr(o['counts']), ptr(o['z']), ptr(o['kidx']),
+                                               ptr(o['overflow']), ptr(o['raw']), ptr(o['rgb']), ptr(o['disp']), ptr(o['acc']), ptr(o['w']),
+                                               ptr(o['depth']), 1 if skip_dead_rgb else 0, stream()), 'fastnerf_render_rays_fwd_march')
+    return o
+
+
 def render_rays_fwd_ert(rays11, params_c, packed_c, params_f, packed_f, N_samples, N_importance, eps, block, cgrid=None, lindisp=False,
                         perturb=False, det=True, white_bkgd=False, t_rand=None, u=None, seed0=0, seed1=0, skip_dead_rgb=False):
     """render_rays_fwd_occ with early ray termination in the pass that produces the image (fastnerf_render_rays_fwd_ert; cgrid may be

@@ -251,6 +251,16 @@ def _forward_ert(rays11, net_c, net_f, N_samples, N_importance, lindisp, perturb
     return dict(_maps(o, N_importance), z0=o['z0'], raw0=o['raw0'], counts=o['counts'], trans=o['trans'])
 
 
+def _forward_march(rays11, net, K, cap, lindisp, white_bkgd, occupancy, ert=None, ert_block=32, skip_dead_rgb=False):
+    """The marched render (fastnerf_render_rays_fwd_march): the K lattice depths of every ray that `occupancy` calls occupied, packed
+    into rows of `cap` slots, one network, one compositing launch.  Returns the maps under render_rays' names plus the packed row
+    (raw, march_z, march_k, weights), 'march_overflow' (bool [n]) and 'counts' (device int32 [2] = (evaluated, n * K))."""
+    o = ops.render_rays_fwd_march(rays11, net.flat, net.packed()[0], K, cap, occupancy._c, eps=ert, block=ert_block, lindisp=lindisp,
+                                  white_bkgd=white_bkgd, skip_dead_rgb=bool(skip_dead_rgb and net.use_viewdirs))
+    return dict(rgb_map=o['rgb'], disp_map=o['disp'], acc_map=o['acc'], depth_map=o['depth'], weights=o['w'], raw=o['raw'],
+                march_z=o['z'], march_k=o['kidx'], march_overflow=o['overflow'].bool(), counts=o['counts'])
+
+
 def _pass_maps(maps, k):
     """(g_disp, g_acc, g_depth) of pass k ('1': the pass that produces the image, '0': the coarse pass of two) out of a dict over
     ops.MAP_GRAD_KEYS, or None when none of the three is set."""
@@ -536,7 +546,7 @@ def _render_rays_closure(ray_batch, rays11, network_fn, network_fine, network_qu
 
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
                 N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False, occupancy=None,
-                tighten=False, retdepth=False, ert=None, ert_block=32):
+                tighten=False, march=None, march_cap=128, retdepth=False, ert=None, ert_block=32):
     """render.py:195-305.  Two routes, chosen by the networks (after `.module` unwrapping):
 
     * fastnerf NeRF modules (8 x 256): positional encoding + MLP run fused inside the HIP kernels; `network_query_fn` is
@@ -576,6 +586,20 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     are wanted, and for eps outside [0, 1) or ert_block < 1; NotImplementedError on the closure route.  `ert=None` (the default) makes
     exactly the calls it made before.
 
+    `march=K` (2 <= K < 2^24; with `occupancy=`; inference only, fused route only) with `march_cap=C` (2 <= C <= 512): the marched render
+    (include/fastnerf.h, "marched render").  No coarse pass and no inverse-CDF: every ray walks the K unperturbed coarse depths of
+    [near, far], keeps the ones the grid calls occupied, and ONE network -- `network_fine` when there is one, else `network_fn` --
+    is evaluated on them, packed into rows of C slots (runs of occupied depths, each closed by one entry without logits that gives
+    the run's last sample its dense width).  `N_samples` and `N_importance` are not read.  Returns rgb_map, disp_map, acc_map,
+    depth_map with `retdepth`, `march_overflow` (bool [n]: the ray has more entries than C slots and was cut there), and with
+    `retraw` the packed `raw` [n, C, 4], `march_z` [n, C] and `march_k` (int32 [n, C]: the lattice index, -1 for closing entries and
+    padding); no coarse-pass keys.  A ray without overflow whose last lattice depth is empty gets the dense one-pass render through
+    the grid at N_samples = K, up to the grouping of fp32 sums.  With `ert=` / `ert_block=` the rows are filled in segments of
+    ert_block slots and a ray stops being walked once its transmittance is <= eps (the bounds above, against the marched render
+    without `ert`); with `tighten=True` the lattice spans the tightened interval.  ValueError without `occupancy=`, with
+    perturb > 0, raw_noise_std > 0, when gradients are wanted, and for K or C out of range; NotImplementedError on the closure route.
+    `march=None` (the default) makes exactly the calls it made before.
+
     Every returned map except `raw` and `z_std` is differentiable w.r.t. the networks' parameters on both routes (render.py:149-192
     under the reference's autograd): rgb_map, disp_map, acc_map, depth_map and their coarse twins, in all three math modes.
 
@@ -598,6 +622,15 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     if tighten and occupancy is None:
         raise ValueError('render_rays: tighten=True clamps near / far to an occupancy grid: it needs occupancy=')
     ops.require_gpu(ray_batch)
+    if march is not None:
+        K_march, cap_march = ops.check_march(march, march_cap)
+        if occupancy is None:
+            raise ValueError('render_rays: march= walks an occupancy grid: it needs occupancy=')
+        if not fused:
+            raise NotImplementedError('render_rays: the marched render (march=) runs on the fused route only (fastnerf NeRF networks); '
+                                      'the closure route has none')
+        if perturb > 0.:
+            raise ValueError('render_rays: the marched render walks a fixed lattice of depths: perturb > 0 has no meaning there')
     if occupancy is not None:
         if raw_noise_std > 0.:
             raise ValueError('render_rays: an occupancy grid cannot be combined with raw_noise_std > 0 (sigma noise is added before '
@@ -623,6 +656,15 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     rays11 = ray_batch.contiguous().float()
     if rays11.shape[-1] == 8:      # no view directions: the kernels' direction slots stay zero (their weights are zero too)
         rays11 = torch.cat([rays11, torch.zeros(rays11.shape[0], 3, device=rays11.device)], -1)
+    if march is not None:
+        net = net_f if net_f is not None else net_c
+        out = _forward_march(rays11, net, K_march, cap_march, lindisp, white_bkgd, occupancy, ert, ert_block, skip_dead_rgb=not retraw)
+        ret = {'rgb_map': out['rgb_map'], 'disp_map': out['disp_map'], 'acc_map': out['acc_map'], 'march_overflow': out['march_overflow']}
+        if retdepth:
+            ret['depth_map'] = out['depth_map']
+        if retraw:
+            ret['raw'], ret['march_z'], ret['march_k'] = out['raw'], out['march_z'], out['march_k']
+        return ret
     n = rays11.shape[0]
     dev = rays11.device
     t_rand = u = noise0 = noise1 = None

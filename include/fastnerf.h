@@ -718,6 +718,63 @@ int fastnerf_render_rays_fwd_ert(int math_mode, int64_t n, int N_samples, int N_
 int fastnerf_occ_ray_bounds(const fn_occ_grid* grid, const fn_occ_cascade* cascade, int64_t n, float* rays11, int write_back,
                             float* bounds, uint8_t* hit, fn_stream_t stream);
 
+/* ---- marched render (inference): walk a dense lattice of depths through the grid, evaluate ONE network on the occupied ones ------------
+ * (csrc/march.hip; no sampler, no coarse pass, no inverse-CDF.)
+ * Lattice.  A ray has K lattice depths, 2 <= K < 2^24: z_k = the depth fastnerf_sample_coarse gives sample k for S = K, perturb = 0 (the
+ * same device function, hence the same bits), k = 0 .. K-1, and z_K := z_{K-1} + (z_{K-1} - z_{K-2}), each operation rounded to fp32:
+ * the closing depth of the last lattice point.
+ * Live.  live(k) is the lookup of fastnerf_occ_classify / _classify_cascade at x = o + d * z_k (one rounded multiply, one rounded add),
+ * through `grid` or `cascade` (exactly one non-NULL) with their `outside_occupied`.  Nothing conservative: the live set is exactly the
+ * live list that a dense classify of the K lattice depths produces.
+ * Packed sequence.  For every maximal run a .. b of consecutive live lattice points the ray has the entries (z_a, a), ..., (z_b, b) and
+ * one closing entry (z_{b+1}, -1); the runs follow each other in depth order.  The closing entry carries zero logits and is never
+ * evaluated: it gives sample b the width z_{b+1} - z_b that it has in the dense pass instead of the gap to the next run.
+ * Packed row.  C slots, 2 <= C <= 512: z [n,C] float32, kidx [n,C] int32, raw [n,C,4].  The first min(L, C) entries of the sequence (of
+ * length L) are stored.  When L > C the last kept entry's kidx is -1 (its z stays) and overflow[ray] = 1, else 0: slot C-1 never holds a
+ * live sample (fastnerf_raw2outputs_fwd gives a row's last slot the width 1e10).  The remaining slots are padding, (z of the slot
+ * before, -1); a ray without a live lattice point holds (z_0, -1) throughout.  z is non-decreasing along a row wherever the lattice is.
+ * Rounds.  The row is produced in rounds over consecutive segments [s0, s1) of its slots -- one round [0, C) without early ray termination,
+ * segments of B slots with `ert = eps`, `ert_block = B`.  A ray whose transmittance (fastnerf_ert_advance over the packed row) at the
+ * start of segment j is not > eps is cut at slot jB: if slot jB-1 holds live sample k, slot jB still receives its closing entry
+ * (z_{k+1}, -1); everything after is padding, the ray's lattice position does not advance, and its overflow flag is what the earlier
+ * rounds left.  Every round with s1 < C also stores z[s1]: z_{k+1} when slot s1-1 holds live sample k (that IS the depth of the next
+ * entry, whatever it turns out to be), else the padding depth; fastnerf_ert_advance of the segment reads it for the width of slot s1-1,
+ * and the next round overwrites it only with the depth of a new run after a gap, behind a slot whose logits are zero.  With B >= C the
+ * arrays, maps and raw equal those without ert bit for bit; with eps = 0 every map does; otherwise the bounds of the early-ray-
+ * termination block hold against the marched render without ert, by the same argument (|d rgb_map| <= eps, 0 <= d acc <= eps,
+ * |d depth_map| <= eps z_max).
+ * Consequence.  For a ray without overflow whose lattice point K-1 is not live, the packed row is the dense one-pass render through the
+ * grid at N_samples = K (fastnerf_render_rays_fwd_occ, N_importance = 0, perturb = 0) with its empty samples dropped: the evaluated
+ * logits are bit-identical, every live sample has the same width bits, and the maps differ only by the grouping of the fp32 scan and
+ * sums.  A live K-1 is closed at z_K here and gets 1e10 there.
+ *   fastnerf_occ_march   one round [s0, s1) for all rays, `first` exactly when s0 == 0.  state: 2 int32 per ray of caller scratch, written
+ *                        by the first round and carried between rounds -- the next lattice index, and (bit 0) whether slot s1-1 is live,
+ *                        (bits 1..5) the lookups made and not yet consumed: over all rounds a ray makes at most K lookups.  trans (may be
+ *                        NULL: no ray is cut), eps as fastnerf_ert_classify.  Outputs z, kidx, overflow (n bytes).  One launch, one thread
+ *                        per ray, no atomics: bit-identical from run to run.  At most s1 - s0 + 1 slots are written per ray, every index
+ *                        < C, and the walk ends after at most K steps whatever the rays hold (non-finite, near >= far: such rays get the
+ *                        rows that the lookup's answers imply).
+ *   fastnerf_march_list  the live list of segment [s0, s1): live_idx[0 .. count) = ascending ray * C + slot with kidx >= 0, count_out[0]
+ *                        = count, count_out[1] = n * (s1 - s0); raw[p*4 .. +3] = 0 for the segment's other slots (raw may be NULL).  ws:
+ *                        fastnerf_compact_ws_ints(n * (s1 - s0)) int32.  The launches of fastnerf_occ_classify with another descriptor.
+ *                        total (may be NULL): total[0] = (s0 == 0 ? 0 : total[0]) + count, total[1] = lattice.
+ *   fastnerf_render_rays_fwd_march  per round march + list + fastnerf_mlp_*_fwd_list on the packed z with S = C (+ fastnerf_ert_advance
+ *                        while a further round follows), then one fastnerf_raw2outputs_fwd over [n, C].  block = 0: no early ray
+ *                        termination; else eps, block as fastnerf_render_rays_fwd_ert.  params / packed: the one network.  counts_out:
+ *                        2 int32 = (evaluated samples, n * K).  The scratch is the stream's library-owned workspace.  -1 before
+ *                        anything is enqueued unless math_mode in {0,1,2}, 2 <= K < 2^24, 2 <= C <= 512, n * C and n * K < 2^31, the
+ *                        ert arguments are in range, exactly one of grid / cascade is set and passes its checks, the pointers are set,
+ *                        and the workspace is there (not inside a stream capture). */
+int fastnerf_occ_march(const fn_occ_grid* grid, const fn_occ_cascade* cascade, int64_t n, int K, int lindisp, const float* rays11, int C,
+                       int s0, int s1, int first, const float* trans, float eps, int32_t* state, float* z, int32_t* kidx,
+                       uint8_t* overflow, fn_stream_t stream);
+int fastnerf_march_list(int64_t n, int C, int s0, int s1, const int32_t* kidx, int32_t* live_idx, int32_t* count_out, float* raw,
+                        int32_t* ws, int32_t* total, int32_t lattice, fn_stream_t stream);
+int fastnerf_render_rays_fwd_march(int math_mode, int64_t n, int K, int C, const float* rays11, int lindisp, int white_bkgd,
+                                   const float* params, const float* packed, const fn_occ_grid* grid, const fn_occ_cascade* cascade,
+                                   float eps, int block, int32_t* counts_out, float* z, int32_t* kidx, uint8_t* overflow, float* raw,
+                                   float* rgb, float* disp, float* acc, float* w, float* depth, int flags, fn_stream_t stream);
+
 /* ---- density gradient: d(sigma)/d(x) through the fused MLP (csrc/sigma_grad.hip) -------------------------------------------------
  * sigma[n,S] (may be NULL) = raw[..., 3] of the forward of `math_mode` (0 exact fp32, 1 split-bf16 "bf16x3", 2 "bf16x6") at the
  * points o + d*z of fastnerf_mlp_fwd, and grad[n,S,3] = its gradient with respect to the point.  Both are taken BEFORE the ReLU
