@@ -47,6 +47,12 @@ class StepAux(C.Structure):
                 + [('lambda_depth', F), ('lambda_acc', F)])
 
 
+class StepMarch(C.Structure):
+    """fn_step_march of include/fastnerf.h, field for field."""
+    _fields_ = [('K', C.c_int32), ('C', C.c_int32), ('which', C.c_int32), ('u', P), ('seed', U64), ('kidx', P), ('overflow', P),
+                ('list_ws', P), ('counts', P)]
+
+
 class OccGrid(C.Structure):
     """fn_occ_grid of include/fastnerf.h, field for field."""
     _fields_ = [('words', P), ('lo', F * 3), ('inv', F * 3), ('n', C.c_int32 * 3), ('outside_occupied', C.c_int32)]
@@ -183,6 +189,11 @@ SIGNATURES = {
     'fastnerf_occ_march': (I, [C.POINTER(OccGrid), C.POINTER(OccCascade), L, I, I, P, I, I, I, I, P, F, P, P, P, P, P]),
     'fastnerf_march_list': (I, [L, I, I, I, P, P, P, P, P, P, C.c_int32, P]),
     'fastnerf_render_rays_fwd_march': (I, [I, L, I, I, P, I, I, P, P, C.POINTER(OccGrid), C.POINTER(OccCascade), F, I] + [P] * 10 + [I, P]),
+    'fastnerf_occ_march_jitter': (I, [C.POINTER(OccGrid), C.POINTER(OccCascade), L, I, I, P, I, I, I, I, P, F, P, U64, P, P, P, P, P]),
+    'fastnerf_march_mask': (I, [L, P, P, P]),
+    'fastnerf_step_march_size': (L, []),
+    'fastnerf_step_march_ws_ints': (L, [L, I]),
+    'fastnerf_train_step_march': (I, [C.POINTER(StepArgs), C.POINTER(StepMarch), I, P]),
     'fastnerf_mlp_sigma_grad_ws_floats': (L, [I, L]),
     'fastnerf_mlp_sigma_grad': (I, [I, I, L, I, P, P, P, P, P, P, P, P, P]),
     'fastnerf_ray_grad_ws_floats': (L, [I, L, I]),
@@ -209,6 +220,8 @@ def lib():
             raise RuntimeError('fn_step_args: the ctypes mirror does not match the library (stale libfastnerf.so?)')
         if l.fastnerf_step_aux_size() != C.sizeof(StepAux):
             raise RuntimeError('fn_step_aux: the ctypes mirror does not match the library (stale libfastnerf.so?)')
+        if l.fastnerf_step_march_size() != C.sizeof(StepMarch):
+            raise RuntimeError('fn_step_march: the ctypes mirror does not match the library (stale libfastnerf.so?)')
         _lib = l
     return _lib
 

@@ -686,3 +686,104 @@ extern "C" int fastnerf_train_step(const fn_step_args* a, int phases, fn_stream_
 extern "C" int fastnerf_train_step_aux(const fn_step_args* a, const fn_step_aux* aux, int phases, fn_stream_t stream) {
   return train_step(a, aux, phases, stream);
 }
+
+// The marched step (include/fastnerf.h, "marched training"): one network on the packed rows of a jittered lattice.  The row is [n, C] in
+// the *0 buffers of fn_step_args; the backward is rr_bwd_live over it as a single pass of C samples -- closing and padding slots hold
+// zero logits, whose d(loss)/d(raw) is exactly zero, so they never enter its list.  Every check comes before the first launch.
+extern "C" int64_t fastnerf_step_march_size(void) { return (int64_t)sizeof(fn_step_march); }
+
+extern "C" int64_t fastnerf_step_march_ws_ints(int64_t n, int C) {
+  if (n <= 0 || C < 2 || C > 512 || n * (int64_t)C >= ((int64_t)1 << 31)) return -1;
+  return n * (int64_t)C + fastnerf_compact_ws_ints(n * (int64_t)C) + 2 + 2 * n;
+}
+
+extern "C" int fastnerf_train_step_march(const fn_step_args* a, const fn_step_march* mx, int phases, fn_stream_t stream) {
+  const char* fname = "fastnerf_train_step_march";
+  if (!a || !mx || a->math_mode < 0 || a->math_mode > 2 || a->n <= 0 || mx->which < 0 || mx->which > 1) {
+    fn::set_error("%s: bad argument: args and march != NULL, math_mode in {0,1,2}, n > 0, which in {0,1}", fname);
+    return -1;
+  }
+  const int K = mx->K, C = mx->C;
+  const int64_t n = a->n;
+  if (K < 2 || K >= (1 << 24) || C < 2 || C > 512 || n * (int64_t)C >= ((int64_t)1 << 31) || n * (int64_t)K >= ((int64_t)1 << 31)) {
+    fn::set_error("%s: bad argument: 2 <= K < 2^24, 2 <= C <= 512, n * C < 2^31, n * K < 2^31", fname);
+    return -1;
+  }
+  if (!a->occ) {
+    fn::set_error("%s: the march walks an occupancy grid (occ != NULL)", fname);
+    return -1;
+  }
+  if (!a->live) {
+    fn::set_error("%s: the marched step is a compacted step (live != 0): the plain backward has no list", fname);
+    return -1;
+  }
+  if (a->noise0 || a->noise1) {
+    fn::set_error("%s: the march cannot be combined with sigma noise (it is added before the relu)", fname);
+    return -1;
+  }
+  if (const char* fault = fn::occ_grid_fault(a->occ)) {
+    fn::set_error("%s: bad argument: %s", fname, fault);
+    return -1;
+  }
+  float* pf = mx->which ? a->packed_fwd_f : a->packed_fwd_c;
+  float* pb = mx->which ? a->packed_bwd_f : a->packed_bwd_c;
+  if (!a->params || !a->grads || !pf || !pb || a->net_floats <= 0 || !a->rays11 || !a->z0 || !a->raw0 || !a->g_rgb || !mx->kidx ||
+      !mx->overflow || !mx->list_ws || !mx->counts) {
+    fn::set_error("%s: null network, row or march buffer", fname);
+    return -1;
+  }
+  const int64_t off = mx->which ? a->net_floats : 0;
+  const float* params = a->params + off;
+  float* grads = a->grads + off;
+  const bool bwd = (phases & FN_STEP_BWD_COARSE) != 0;
+  if ((phases & FN_STEP_FORWARD) && (!a->rays_o || !a->rays_d || !a->target || !a->loss2 || !a->rgb0 || !a->disp0 || !a->acc0 || !a->w0 ||
+                                     !a->depth0)) {
+    fn::set_error("%s: null batch / output buffer", fname);
+    return -1;
+  }
+  if (bwd && (!a->draw_ws || !a->act_ws || !a->dact_ws || !a->partial_ws || !a->live_ws)) {
+    fn::set_error("%s: null scratch of the compacted backward", fname);
+    return -1;
+  }
+  if ((phases & FN_STEP_UPDATE) && (!a->adam_m || !a->adam_v || a->adam_t < 1)) {
+    fn::set_error("%s: update phase needs adam_m, adam_v and adam_t >= 1", fname);
+    return -1;
+  }
+  int rc;
+  if (phases & FN_STEP_FORWARD) {
+    const int64_t Q = n * (int64_t)C;
+    int32_t* idx = mx->list_ws;   // list | scan scratch | segment count | per-ray state (fastnerf_step_march_ws_ints)
+    int32_t* cws = idx + Q;
+    int32_t* seg = cws + fastnerf_compact_ws_ints(Q);
+    int32_t* state = seg + 2;
+    if ((rc = fastnerf_pack_rays(n, a->rays_o, a->rays_d, a->near_plane, a->far_plane, a->ndc, a->H, a->W, a->focal, a->rays11, stream)))
+      return rc;
+    if ((a->fwd_flags & FN_STEP_TIGHTEN) && (rc = fastnerf_occ_ray_bounds(a->occ, nullptr, n, a->rays11, 1, nullptr, nullptr, stream)))
+      return rc;
+    if ((rc = fastnerf_occ_march_jitter(a->occ, nullptr, n, K, a->lindisp, a->rays11, C, 0, C, 1, nullptr, 0.f, mx->u, mx->seed, state, a->z0,
+                                        mx->kidx, mx->overflow, stream)))
+      return rc;
+    if ((rc = fastnerf_march_list(n, C, 0, C, mx->kidx, idx, seg, a->raw0, cws, mx->counts, (int32_t)(n * (int64_t)K), stream))) return rc;
+    if ((rc = modes[a->math_mode].fwd_list(0, n, C, a->rays11, a->z0, params, pf, a->raw0, idx, seg, a->fwd_flags & ~FN_STEP_TIGHTEN, stream)))
+      return rc;
+    if ((rc = fastnerf_raw2outputs_fwd(n, C, a->raw0, a->z0, a->rays11, nullptr, a->white_bkgd, a->rgb0, a->disp0, a->acc0, a->w0, a->depth0,
+                                       stream)))
+      return rc;
+    if ((rc = fastnerf_mse_leafmax(n, a->rgb0, nullptr, a->target, a->grad_scale, a->g_rgb, nullptr, a->loss2, a->leaf_tag, a->max_leaves,
+                                   a->table, stream)))
+      return rc;
+    // a truncated row has lost what lies behind the cut: its colour error does not train the field (loss2 stays the mean over all rays)
+    if ((rc = fastnerf_march_mask(n, mx->overflow, a->g_rgb, stream))) return rc;
+  }
+  if (bwd && (rc = rr_bwd_live(a->math_mode, n, C, 0, a->rays11, a->white_bkgd, a->g_rgb, nullptr, nullptr, nullptr, a->z0, a->raw0, nullptr,
+                               nullptr, params, pf, pb, nullptr, nullptr, nullptr, a->draw_ws, a->act_ws, a->dact_ws, a->partial_ws,
+                               a->live_ws, grads, nullptr, a->counts, nullptr, nullptr, nullptr, nullptr, nullptr, 2, stream)))
+    return rc;
+  if (phases & FN_STEP_UPDATE) {
+    if ((rc = fastnerf_adam_step(a->net_floats, a->params + off, grads, a->adam_m + off, a->adam_v + off, a->lr, a->beta1, a->beta2, a->eps,
+                                 a->adam_t, stream)))
+      return rc;
+    if ((rc = modes[a->math_mode].pack(0, params, pf, pb, stream))) return rc;
+  }
+  return 0;
+}

@@ -86,12 +86,15 @@ class _RayBounds:
         bounds, hit = self._bounds(ray_batch)
         return torch.cat([ray_batch[:, :6], bounds.to(ray_batch.dtype), ray_batch[:, 8:]], -1), hit.bool()
 
-    def march(self, ray_batch, K, cap=128, lindisp=False):
+    def march(self, ray_batch, K, cap=128, lindisp=False, u=None, seed=0):
         """ray_batch [n,8] or [n,11] (cuda) -> (z float32 [n, cap], kidx int32 [n, cap], overflow bool [n]): the packed rows of the
         marched render (fastnerf_occ_march, one round; include/fastnerf.h, "marched render").  Of the K lattice depths of every ray --
         the coarse depths for N_samples = K, perturb = 0 -- the ones this grid calls occupied are kept, run by run, each run followed
         by one closing entry (kidx -1); padding repeats the last depth with kidx -1.  overflow: the ray has more entries than `cap`
-        slots, and the row holds the first cap of them."""
+        slots, and the row holds the first cap of them.
+        u (float32 [n] in [0, 1)) or seed != 0: the rows of the marched TRAINING step (fastnerf_occ_march_jitter; include/fastnerf.h,
+        "marched training") -- the lattice of ray r shifted by u[r] of its spacing, u drawn from the 'mrch' stream of `seed` when not
+        given.  The defaults make exactly the call made before."""
         if not torch.is_tensor(ray_batch):
             raise RuntimeError('fastnerf ops run on the GPU only (no CPU fallback): got a host array')
         ops.require_gpu(ray_batch)
@@ -100,7 +103,16 @@ class _RayBounds:
         r = ray_batch.detach().float()
         if r.shape[-1] == 8:
             r = torch.cat([r, torch.zeros(r.shape[0], 3, device=r.device)], -1)
-        z, kidx, overflow, _ = ops.occ_march(self._c, r.contiguous(), K, cap, lindisp=lindisp)
+        if u is None and not seed:
+            z, kidx, overflow, _ = ops.occ_march(self._c, r.contiguous(), K, cap, lindisp=lindisp)
+        else:
+            if u is not None:
+                if not torch.is_tensor(u):
+                    raise RuntimeError('fastnerf ops run on the GPU only (no CPU fallback): got a host array')
+                u = u.detach().float().reshape(-1).contiguous()
+                if u.shape[0] != r.shape[0]:
+                    raise ValueError('u holds one shift per ray')
+            z, kidx, overflow, _ = ops.occ_march_jitter(self._c, r.contiguous(), K, cap, u=u, seed=int(seed), lindisp=lindisp)
         return z, kidx, overflow.bool()
 
 
@@ -223,7 +235,7 @@ class OccupancyGrid(_RayBounds):
             np.savez(fh, **self._fields())
 
     # ---- training ---------------------------------------------------------------------------------------------------
-    def update(self, render_kwargs, seed=None, cells_per_call=None, _packed=None):
+    def update(self, render_kwargs, seed=None, cells_per_call=None, _packed=None, which='both'):
         """Refresh the density and the bits from the networks of `render_kwargs` (fastnerf NeRF modules): a point inside each
         cell (fastnerf_occ_cell_points: Philox jitter keyed by (seed, cell); seed 0 = cell centres; default = 1 + the number
         of updates so far, so that every rank of a data-parallel run draws the same points), the non-saving forward of the
@@ -232,15 +244,23 @@ class OccupancyGrid(_RayBounds):
 
         cells_per_call: refresh only that many cells, a slice that rotates through the grid from call to call, so that the cost
         per call is bounded; a cell decays once per refresh of its own.  The first call always takes every cell: a cell that
-        was never sampled has no density to stand on."""
+        was never sampled has no density to stand on.
+
+        which: 'both' (default), or 'coarse' / 'fine' as in from_network: the density then follows that network alone (the coarse
+        one when there is no fine one) -- what a trainer that marches one network refreshes its grid from."""
         from .model import NeRF
         if self.dens is None:
             raise ValueError('update() needs a grid with a density: OccupancyGrid.for_training(...)')
+        if which not in ('both', 'fine', 'coarse'):
+            raise ValueError("which is 'both', 'fine' or 'coarse'")
         nets = [getattr(render_kwargs['network_fn'], 'module', render_kwargs['network_fn'])]
         fine = render_kwargs.get('network_fine')
         fine = getattr(fine, 'module', fine)
         if fine is not None and fine is not nets[0]:
-            nets.append(fine)
+            if which == 'both':
+                nets.append(fine)
+            elif which == 'fine':
+                nets = [fine]
         if not all(isinstance(m, NeRF) for m in nets):
             raise TypeError('OccupancyGrid.update runs the fused HIP forward: it needs fastnerf NeRF networks')
         packed = _packed if _packed is not None else [m.packed()[0] for m in nets]

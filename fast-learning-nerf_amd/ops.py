@@ -1023,11 +1023,12 @@ def check_march(march, march_cap):
     return int(march), int(march_cap)
 
 
-def occ_march(cgrid, rays11, K, C, s0=0, s1=None, trans=None, eps=0., lindisp=False, state=None, z=None, kidx=None, overflow=None):
+def occ_march(cgrid, rays11, K, C, s0=0, s1=None, trans=None, eps=0., lindisp=False, state=None, z=None, kidx=None, overflow=None,
+              jitter=None):
     """One round [s0, s1) of fastnerf_occ_march over the rays of rays11 [n, 11], through cgrid (a _lib.OccGrid or a _lib.OccCascade):
     -> (z float32 [n, C], kidx int32 [n, C], overflow uint8 [n], state int32 [n, 2]).  The first round (s0 == 0) allocates what is not
     given; a later round takes the four tensors of the round before it and writes in place.  trans (float32 [n], optional): a ray
-    with trans <= eps (or NaN) is cut."""
+    with trans <= eps (or NaN) is cut.  jitter = (u, seed): the call goes to fastnerf_occ_march_jitter (occ_march_jitter below)."""
     require_gpu(rays11, trans, state, z, kidx, overflow)
     K, C = check_march(K, C)
     s0 = int(s0)
@@ -1048,9 +1049,39 @@ def occ_march(cgrid, rays11, K, C, s0=0, s1=None, trans=None, eps=0., lindisp=Fa
     grid, cascade = _ert_grid_args(cgrid)
     if grid is None and cascade is None:
         raise TypeError('expected a _lib.OccGrid or a _lib.OccCascade, got None')
+    if jitter is not None:
+        u, seed = jitter
+        require_gpu(u)
+        assert u is None or (u.shape == (n,) and u.dtype == torch.float32 and u.is_contiguous() and u.device == dev)
+        check(lib().fastnerf_occ_march_jitter(grid, cascade, n, K, 1 if lindisp else 0, ptr(rays11), C, s0, s1, 1 if s0 == 0 else 0,
+                                              ptr(trans), float(eps), ptr(u), int(seed), ptr(state), ptr(z), ptr(kidx), ptr(overflow),
+                                              stream()), 'fastnerf_occ_march_jitter')
+        return z, kidx, overflow, state
     check(lib().fastnerf_occ_march(grid, cascade, n, K, 1 if lindisp else 0, ptr(rays11), C, s0, s1, 1 if s0 == 0 else 0, ptr(trans),
                                    float(eps), ptr(state), ptr(z), ptr(kidx), ptr(overflow), stream()), 'fastnerf_occ_march')
     return z, kidx, overflow, state
+
+
+def occ_march_jitter(cgrid, rays11, K, C, u=None, seed=0, **kw):
+    """occ_march through fastnerf_occ_march_jitter (include/fastnerf.h, "marched training"): the lattice of ray r shifted by u[r] in
+    [0, 1) of its spacing.  u: float32 [n] or None; with None, seed != 0 draws the shifts from the 'mrch' stream and seed == 0 is the
+    unshifted lattice.  The other keywords and the result are occ_march's."""
+    return occ_march(cgrid, rays11, K, C, jitter=(u, seed), **kw)
+
+
+def march_mask(overflow, g_rgb):
+    """fastnerf_march_mask, in place: the rows of g_rgb [n, 3] of the rays with overflow[r] != 0 are zeroed.  -> g_rgb."""
+    require_gpu(overflow, g_rgb)
+    n = overflow.shape[0]
+    assert overflow.dtype == torch.uint8 and overflow.is_contiguous() and overflow.shape == (n,)
+    assert g_rgb.dtype == torch.float32 and g_rgb.is_contiguous() and g_rgb.shape == (n, 3) and g_rgb.device == overflow.device
+    check(lib().fastnerf_march_mask(n, ptr(overflow), ptr(g_rgb), stream()), 'fastnerf_march_mask')
+    return g_rgb
+
+
+def step_march_ws_ints(n, C):
+    """int32 count of fn_step_march.list_ws for n rays and rows of C slots."""
+    return int(check(lib().fastnerf_step_march_ws_ints(int(n), int(C)), 'fastnerf_step_march_ws_ints'))
 
 
 def march_list(kidx, s0, s1, raw=None, total=None, lattice=0):

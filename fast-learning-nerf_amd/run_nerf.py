@@ -246,11 +246,25 @@ class Trainer:
     `aux_losses`: device tensor [4] = (Ld_fine, Ld_coarse, La_fine, La_coarse) of the last step, unscaled by the lambdas (zeros
     for a term that is off, and after an empty batch); the return value of step() is unchanged.  Both routes, the plain and the
     compacted backward, an occupancy grid and n_global scaling take the terms; they make every sample with positive density of a
-    ray that is not yet opaque live (render.LivePolicy), so early compacted steps run over more points than under the colour loss."""
+    ray that is not yet opaque live (render.LivePolicy), so early compacted steps run over more points than under the colour loss.
+
+    Marched training (`march=K` with `march_cap=C`, `march_after=M`; with a grid whose `outside_occupied` is False; include/fastnerf.h,
+    "marched training"): the steps with `occupancy_steps < M` are the step through the grid above, launch for launch -- that is how the
+    grid gets warm before the lattice relies on it.  Every later step trains ONE network, `network_fine` when there is one, else
+    `network_fn` (the network render_rays(..., march=K) renders with), on the packed rows of a lattice of K depths per ray that is
+    shifted per ray by u in [0, 1) of its spacing: no coarse pass, no inverse-CDF, one fastnerf_train_step_march call.  `perturb`
+    switches the shift (seeded from `_next_seed()`); step(..., march_u=) injects [n] shifts.  A ray whose row overflows C slots does
+    not train the field (its colour gradient is zeroed; the loss stays the mean over all rays).  The other network, its moments and
+    its packed weights are left untouched, and the grid is refreshed from the marched network alone.  `march_counts`: device int32
+    [2] = (evaluated samples, n * K) of the last marched step.  The step's `out` holds rgb_map, disp_map, acc_map, depth_map and
+    march_overflow (bool [n]) (+ raw, weights, z_vals, march_k of the packed row).  `tighten=True` combines: the lattice spans the
+    clamped interval.  ValueError: march without a grid, a grid with outside_occupied=True (every lattice point outside the box would be
+    live and the rows would overflow), a depth / opacity term that is on, raw_noise_std > 0, forward_backward, a trainer off the fused
+    step.  No early ray termination while training."""
 
     def __init__(self, render_kwargs_train, H, W, K, near, far, lrate=5e-4, lrate_decay=250, decay=True,
                  beta1=0.9, beta2=0.999, eps=1e-8, occupancy=None, occupancy_every=16, occupancy_warmup=256, occupancy_cells=None,
-                 lambda_depth=0., lambda_acc=0., tighten=False):
+                 lambda_depth=0., lambda_acc=0., tighten=False, march=None, march_cap=128, march_after=0):
         kw = render_kwargs_train
         self._kw = kw
         self.net_c = kw['network_fn']
@@ -294,7 +308,12 @@ class Trainer:
         self._aux_zero = torch.zeros(4, device=self.flat.device, dtype=torch.float32)
         self.aux_losses = self._aux_zero
         self._aux = None         # fn_step_aux of the fused path's current step (None: no term on)
+        self.march, self.march_cap, self.march_after = march, march_cap, march_after
+        self.march_counts = None if march is None else torch.zeros(2, device=self.flat.device, dtype=torch.int32)
+        self._ma = None          # fn_step_args / fn_step_march of the marched step
+        self._ma_key = None
         self._check_occupancy()
+        self._check_march()
         self.repack()
 
     def _check_occupancy(self):
@@ -317,6 +336,24 @@ class Trainer:
             raise ValueError('Trainer: an occupancy grid needs the compacted step (FASTNERF_COMPACT=0 or one network shared by '
                              'both passes rules it out): the plain backward has no list')
 
+    def _check_march(self):
+        """(K, C) of the marched step, or None when march is off; ValueError for a configuration that cannot march."""
+        if self.march is None:
+            return None
+        if self.occupancy is None:
+            raise ValueError('Trainer: march= walks an occupancy grid: it needs occupancy=')
+        K, C = ops.check_march(self.march, self.march_cap)
+        if self.occupancy.outside_occupied:
+            raise ValueError('Trainer: march= needs a grid with outside_occupied=False: with True every lattice point outside the box '
+                             'is live and the packed rows overflow')
+        return K, C
+
+    def _marched(self):
+        """(which, network, its packed pair): the network the marched step trains -- network_fine when there is one."""
+        if self.net_f is not None and self.net_f is not self.net_c:
+            return 1, self.net_f, self.pf
+        return 0, self.net_c, self.pc
+
     def repack(self):
         self.pc = self.net_c.packed(refresh=True)
         self.pf = self.net_f.packed(refresh=True) if self.net_f is not None else None
@@ -338,6 +375,8 @@ class Trainer:
 
     def forward_backward(self, rays_o, rays_d, target, leaf_tag=None, table=None, max_leaves=0, t_rand=None, u=None,
                          n_global=None, depth=None, depth_weight=None, acc=None, acc_weight=None):
+        if self.march is not None:
+            raise ValueError('Trainer.forward_backward: the call-by-call route has no marched step; use step()')
         if self.occupancy is not None or self.tighten:
             raise ValueError('Trainer.forward_backward: the call-by-call route has no occupancy grid; use step()')
         n = rays_o.shape[0]
@@ -493,16 +532,104 @@ class Trainer:
         loss2 = block[self._regions['loss2'][0]:self._regions['loss2'][0] + 2]
         return a, out, loss2, live
 
-    def _occupancy_tick(self):
-        """Before a step with the grid set: refresh it when its turn has come (a grid without a density is never touched)."""
+    def _occupancy_tick(self, marching=False):
+        """Before a step with the grid set: refresh it when its turn has come (a grid without a density is never touched).  A marched
+        step refreshes it from the marched network alone."""
         k = self.occupancy_steps - self.occupancy_warmup
         if self.occupancy.dens is not None and k >= 0 and k % self.occupancy_every == 0:
             if ops.packed_tag(self.pc[0]) != ops.get_math():
                 self.repack()
-                self._sa_key = None
-            self.occupancy.update(self._kw, cells_per_call=self.occupancy_cells,
-                                  _packed=[self.pc[0]] + ([self.pf[0]] if (self.pf is not None and self.net_f is not self.net_c) else []))
+                self._sa_key = self._ma_key = None
+            if marching:
+                which, _, pk = self._marched()
+                self.occupancy.update(self._kw, cells_per_call=self.occupancy_cells, _packed=[pk[0]], which='fine' if which else 'coarse')
+            else:
+                self.occupancy.update(self._kw, cells_per_call=self.occupancy_cells,
+                                      _packed=[self.pc[0]] + ([self.pf[0]] if (self.pf is not None and self.net_f is not self.net_c) else []))
         self.occupancy_steps += 1
+
+    # ---- marched route: one fastnerf_train_step_march call per phase group ------------------------------------------
+    def _march_prepare(self, K, C, rays_o, rays_d, target, leaf_tag, table, max_leaves, march_u, n_global):
+        """Fill fn_step_args and fn_step_march for this batch; returns (args, march, out dict, loss2).  out['march_overflow'] is the
+        step's uint8 buffer here: step() hands it out as bool once the forward is enqueued."""
+        n = rays_o.shape[0]
+        dev = rays_o.device
+        P = n * C
+        ops.require_gpu(rays_o, rays_d, target, leaf_tag, table, march_u)
+        self._check_occupancy()
+        tag = ops.get_math()
+        if ops.packed_tag(self.pc[0]) != tag:
+            self.repack()
+            self._sa_key = self._ma_key = None
+        which, _, pk = self._marched()
+        key = (n, K, C, str(dev), torch.cuda.current_stream(dev).cuda_stream, tag)
+        if self._ma is None or self._ma_key != key:
+            a, x = _lib.StepArgs(), _lib.StepMarch()
+            self._ma, self._ma_key = (a, x), key
+            self._march_regions, self._march_floats = _step_regions(n, C, 0)
+            a.n, a.net_floats, a.math_mode = n, ops.NET_PARAMS, ops.mode_id()
+            a.params, a.grads, a.adam_m, a.adam_v = self.flat.data_ptr(), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr()
+            a.packed_fwd_c, a.packed_bwd_c = self.pc[0].data_ptr(), self.pc[1].data_ptr()
+            if self.pf is not None:
+                a.packed_fwd_f, a.packed_bwd_f = self.pf[0].data_ptr(), self.pf[1].data_ptr()
+            ws = _Workspace.dact(dev, ops.dact_floats(P) + P * 4)
+            a.dact_ws = ws.data_ptr()
+            a.draw_ws = ws.data_ptr() + 4 * ops.dact_floats(P)
+            a.partial_ws = _Workspace.partial(dev).data_ptr()
+            t1 = _Workspace.get('act', dev, ops.act_floats(P))
+            t2 = _Workspace.get('live', dev, ops.live_ws_ints(P), torch.int32)
+            t3 = _Workspace.get('march_list', dev, ops.step_march_ws_ints(n, C), torch.int32)
+            a.act_ws, a.live_ws = t1.data_ptr(), t2.data_ptr()
+            a.counts = self.live_counts.data_ptr()
+            a.live = 1
+            x.list_ws = t3.data_ptr()
+            x.counts = self.march_counts.data_ptr()
+            self._march_keep = [ws, t1, t2, t3]
+        a, x = self._ma
+        a.lindisp, a.white_bkgd = int(bool(self.lindisp)), int(bool(self.white_bkgd))
+        a.ndc, a.H, a.W = int(bool(self.ndc)), int(self.H), int(self.W)
+        a.focal, a.near_plane, a.far_plane = float(self.K[0][0]), float(self.near), float(self.far)
+        a.beta1, a.beta2, a.eps = self.beta1, self.beta2, self.eps
+        block = torch.empty(self._march_floats, device=dev, dtype=torch.float32)
+        base = block.data_ptr()
+        for name, (off, _) in self._march_regions.items():
+            setattr(a, name, base + 4 * off)
+        ro, rd, tg = ops._f32(rays_o).reshape(-1, 3), ops._f32(rays_d).reshape(-1, 3), ops._f32(target)
+        a.rays_o, a.rays_d, a.target = ro.data_ptr(), rd.data_ptr(), tg.data_ptr()
+        kidx = torch.empty(n, C, device=dev, dtype=torch.int32)
+        overflow = torch.empty(n, device=dev, dtype=torch.uint8)
+        hold = [ro, rd, tg, kidx, overflow, self.occupancy]
+        if march_u is not None:
+            march_u = ops._f32(march_u).reshape(-1)
+            assert march_u.shape == (n,)
+            hold.append(march_u)
+        x.K, x.C, x.which = K, C, which
+        x.u = None if march_u is None else march_u.data_ptr()
+        x.seed = _next_seed() if (self.perturb and march_u is None) else 0
+        x.kidx, x.overflow = kidx.data_ptr(), overflow.data_ptr()
+        if leaf_tag is not None:
+            leaf_tag = leaf_tag.contiguous()
+            hold.append(leaf_tag)
+        a.leaf_tag = None if leaf_tag is None else leaf_tag.data_ptr()
+        a.table = None if table is None else table.data_ptr()
+        a.max_leaves = int(max_leaves)
+        a.grad_scale = 1.0 if n_global is None else float(n) / float(n_global)
+        a.fwd_flags = (1 if self.skip_dead_rgb else 0) | (_lib.STEP_TIGHTEN if self.tighten else 0)
+        a.occ = ctypes.addressof(self.occupancy._c)
+        self._hold = hold
+        self._march_block = block      # (with _march_regions: the step's tensors, g_rgb included, for inspection)
+
+        def view(name):
+            off, shape = self._march_regions[name]
+            return block[off:off + math.prod(shape)].view(shape)
+
+        out = {'rgb_map': view('rgb0'), 'disp_map': view('disp0'), 'acc_map': view('acc0'), 'depth_map': view('depth0'),
+               'raw': view('raw0'), 'weights': view('w0'), 'z_vals': view('z0'), 'march_k': kidx, 'march_overflow': overflow}
+        return a, x, out, view('loss2')
+
+    def _march_call(self, a, x, phases):
+        _lib.check(_lib.lib().fastnerf_train_step_march(ctypes.byref(a), ctypes.byref(x), int(phases), _lib.stream()),
+                   'fastnerf_train_step_march')
 
     def _fused_call(self, a, phases):
         if self._aux is not None:      # (given in every phase call: the data-parallel step splits them)
@@ -518,16 +645,46 @@ class Trainer:
         self.last_step_live = live
 
     def step(self, rays_o, rays_d, target, leaf_tag=None, table=None, max_leaves=0, t_rand=None, u=None,
-             n_global=None, decay=None, depth=None, depth_weight=None, acc=None, acc_weight=None):
+             n_global=None, decay=None, march_u=None, depth=None, depth_weight=None, acc=None, acc_weight=None):
         n = rays_o.shape[0]
         Nn = ops.NET_PARAMS
         two = self.N_importance > 0 and self.net_f is not None and self.net_f is not self.net_c
         overlap = self.world > 1 and two and self.overlap_allreduce and self.grad.numel() == 2 * Nn
         fused = self.fused and n > 0
+        KC = self._check_march()            # (read on every step, like perturb and white_bkgd)
+        if KC is not None and self._aux_terms(n, depth, depth_weight, acc, acc_weight):
+            raise ValueError('Trainer: the marched step has no depth / opacity terms (lambda_depth / lambda_acc with a target)')
+        marching = KC is not None and self.occupancy_steps >= int(self.march_after)
         self.adam_t += 1
         if self.occupancy is not None and n > 0:
-            self._occupancy_tick()
-        if fused:
+            self._occupancy_tick(marching)
+        if marching and n > 0:
+            a, x, out, loss2 = self._march_prepare(KC[0], KC[1], rays_o, rays_d, target, leaf_tag, table, max_leaves, march_u, n_global)
+            a.lr, a.adam_t = float(self.lr), int(self.adam_t)
+            self.aux_losses = self._aux_zero
+            if self.world == 1:
+                self._march_call(a, x, _lib.STEP_FORWARD | _lib.STEP_BWD_COARSE | _lib.STEP_UPDATE)
+            else:      # data parallel, not overlapped: one network, one collective over its half of the gradient
+                self._march_call(a, x, _lib.STEP_FORWARD | _lib.STEP_BWD_COARSE)
+                parallel.all_reduce_sum(self.grad[x.which * Nn:(x.which + 1) * Nn])
+                self._march_call(a, x, _lib.STEP_UPDATE)
+            out['march_overflow'] = out['march_overflow'].bool()
+            self.live.tick()
+            self.last_step_live = True
+        elif marching:
+            # a rank whose shard of a (tail) batch is empty joins the collective with a zero gradient and takes the update
+            which, net, _ = self._marched()
+            g = self.grad[which * Nn:(which + 1) * Nn]
+            g.zero_()
+            _burn_seeds(1 if (self.perturb and march_u is None) else 0)
+            loss2, out = torch.zeros(2, device=self.grad.device), {}
+            self.aux_losses = self._aux_zero
+            if self.world > 1:
+                parallel.all_reduce_sum(g)
+            sl = slice(which * Nn, (which + 1) * Nn)
+            ops.adam_step(self.flat[sl], g, self.m[sl], self.v[sl], self.lr, self.adam_t, self.beta1, self.beta2, self.eps)
+            self.repack()
+        elif fused:
             a, out, loss2, live = self._fused_prepare(rays_o, rays_d, target, leaf_tag, table, max_leaves, t_rand, u, n_global,
                                                       depth, depth_weight, acc, acc_weight)
             a.lr, a.adam_t = float(self.lr), int(self.adam_t)
@@ -685,6 +842,8 @@ def train(images, poses, H, W, focal, args, near=2., far=6., device='cuda', log=
         occ_kw = dict(occupancy=OccupancyGrid.for_training(N=getattr(args, 'occupancy_N', 128), bound=getattr(args, 'occupancy_bound', 1.2),
                                                            outside_occupied=getattr(args, 'occupancy_outside_occupied', True), device=dev),
                       tighten=getattr(args, 'occupancy_tighten', False),     # (matters with occupancy_outside_occupied=False)
+                      # marched training (needs occupancy_outside_occupied=False): steps from march_after on train the fine network alone
+                      march=getattr(args, 'march', None), march_cap=getattr(args, 'march_cap', 128), march_after=getattr(args, 'march_after', 0),
                       occupancy_every=getattr(args, 'occupancy_every', 16), occupancy_warmup=getattr(args, 'occupancy_warmup', 256))
     trainer = Trainer(kw_train, H, W, K, near, far, lrate=args.lrate, lrate_decay=args.lrate_decay, **occ_kw)
     trainer.global_iter = global_iter

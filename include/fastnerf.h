@@ -775,6 +775,57 @@ int fastnerf_render_rays_fwd_march(int math_mode, int64_t n, int K, int C, const
                                    float eps, int block, int32_t* counts_out, float* z, int32_t* kidx, uint8_t* overflow, float* raw,
                                    float* rgb, float* disp, float* acc, float* w, float* depth, int flags, fn_stream_t stream);
 
+/* ---- marched training: the lattice jittered per ray, ONE network trained on the packed rows ----------------------------------------
+ * (csrc/march.hip, render.cpp.)  A lattice sampled at the same depths every step fits those depths only, so training shifts the whole
+ * lattice of ray r by u_r in [0, 1) of its own spacing:
+ *   z_k(u) = fadd(z_k, fmul(u_r, fsub(z_{k+1}, z_k)))     k = 0 .. K-1   (z_k, z_K: the lattice and closing depth of the marched render)
+ *   z_K(u) = fadd(z_{K-1}(u), fsub(z_K, z_{K-1}))
+ * for the linear and the lindisp lattice alike, each operation rounded to fp32.  The lookup is made at o + d * z_k(u), the stored depths
+ * are the z_k(u), a closing entry after sample b stores z_{b+1}(u); runs, closing entries, padding, overflow, rounds and state are
+ * exactly those of fastnerf_occ_march.  z_k <= z_k(u) <= z_{k+1} on the linear lattice, and z stays non-decreasing along a row.
+ *   fastnerf_occ_march_jitter  the arguments of fastnerf_occ_march plus u ([n] or NULL) and seed.  u given: used as it is.  u == NULL,
+ *                        seed != 0: u_r = u01(word 0) of Philox block r of the stream 'mrch' (0x6d726368) keyed by seed.  u == NULL, seed
+ *                        == 0: no shift -- the launch of fastnerf_occ_march itself.  With u_r = 0 every z_k(u) has the bits of z_k (finite
+ *                        rays with 0 < near < far: u_r * w = 0, and a + ((a + w) - a) = a + w since a <= a + w <= 2a makes the difference
+ *                        exact), so z, kidx, overflow and state equal fastnerf_occ_march's bit for bit.  One thread per ray, no atomics:
+ *                        bit-identical from run to run; the bounds of fastnerf_occ_march hold (the same walk).
+ *   fastnerf_march_mask  g_rgb [n,3]: row r is zeroed where overflow[r] != 0, every other row keeps its bits.  A truncated row has lost
+ *                        everything behind the cut: its colour error is an artefact of the row, not of the field.
+ *   fastnerf_train_step_march  one optimisation step of the marched network per call, phases as fastnerf_train_step:
+ *     FN_STEP_FORWARD     fastnerf_pack_rays, (FN_STEP_TIGHTEN: fastnerf_occ_ray_bounds, write_back = 1,) one round [0, C) of
+ *                         fastnerf_occ_march_jitter, fastnerf_march_list, fastnerf_mlp_*_fwd_list of the mode with S = C,
+ *                         fastnerf_raw2outputs_fwd over [n, C], fastnerf_mse_leafmax(rgb, NULL, target, ...), fastnerf_march_mask.
+ *                         loss2[0] stays the mean over all n rays and grad_scale is unchanged.
+ *     FN_STEP_BWD_COARSE  the compacted backward (fastnerf_render_rays_bwd_live) over the row as N_samples = C, N_importance = 0, into
+ *                         the marched half of grads: a closing or padding slot has raw = (0,0,0,0), d(loss)/d(raw) is exactly zero
+ *                         there, so its list is a subset of the row's live slots.  FN_STEP_BWD_FINE is a no-op.
+ *     FN_STEP_UPDATE      fastnerf_adam_step over the marched half of params / grads / adam_m / adam_v and the pack of that network.
+ *                         The other network, its moments and its packed buffers are not touched.
+ *   Exactly the launches those entry points make, in that order, on the caller's stream: bit-identical to calling them one by one.
+ *   No early ray termination (one round) and no depth / opacity terms.  fn_step_args keeps its size and meaning; of it the step reads
+ *   the batch, the networks and optimiser state, rays11, the row buffers z0 raw0 rgb0 disp0 acc0 w0 depth0 sized for [n, C], g_rgb,
+ *   loss2, the scratch of the compacted backward sized for n * C points, counts, the scalars and occ; N_samples, N_importance, t_rand,
+ *   u, seed0 and seed1 are NOT read.  What the march needs travels in fn_step_march, given in every phase call.
+ *   -1 before anything is enqueued: occ == NULL or a grid that fails its checks, live == 0, sigma noise, K / C outside the bounds of
+ *   fastnerf_render_rays_fwd_march, which outside {0, 1}, a missing buffer of a requested phase. */
+typedef struct fn_step_march {
+  int32_t K, C;                 /* lattice depths per ray, slots per packed row */
+  int32_t which;                /* 0 / 1: the half of params, grads, adam_m, adam_v and the packed pair (_c / _f) that is marched */
+  const float* u;               /* [n] injected shifts or NULL */
+  uint64_t seed;                /* u == NULL: the key of the 'mrch' stream, 0 = no shift */
+  int32_t* kidx;                /* [n, C] out */
+  uint8_t* overflow;            /* [n] out */
+  int32_t* list_ws;             /* fastnerf_step_march_ws_ints(n, C) int32: list | scan scratch | count | per-ray state */
+  int32_t* counts;              /* int32[2] out = (evaluated samples, n * K) */
+} fn_step_march;
+int64_t fastnerf_step_march_size(void);             /* sizeof(fn_step_march): binding sanity check */
+int64_t fastnerf_step_march_ws_ints(int64_t n, int C);   /* -1 outside n > 0, 2 <= C <= 512, n * C < 2^31 */
+int fastnerf_occ_march_jitter(const fn_occ_grid* grid, const fn_occ_cascade* cascade, int64_t n, int K, int lindisp, const float* rays11,
+                              int C, int s0, int s1, int first, const float* trans, float eps, const float* u, uint64_t seed,
+                              int32_t* state, float* z, int32_t* kidx, uint8_t* overflow, fn_stream_t stream);
+int fastnerf_march_mask(int64_t n, const uint8_t* overflow, float* g_rgb, fn_stream_t stream);
+int fastnerf_train_step_march(const fn_step_args* args, const fn_step_march* march, int phases, fn_stream_t stream);
+
 /* ---- density gradient: d(sigma)/d(x) through the fused MLP (csrc/sigma_grad.hip) -------------------------------------------------
  * sigma[n,S] (may be NULL) = raw[..., 3] of the forward of `math_mode` (0 exact fp32, 1 split-bf16 "bf16x3", 2 "bf16x6") at the
  * points o + d*z of fastnerf_mlp_fwd, and grad[n,S,3] = its gradient with respect to the point.  Both are taken BEFORE the ReLU
