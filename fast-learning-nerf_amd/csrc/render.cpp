@@ -1,7 +1,10 @@
 // render.cpp -- host-side sequencing of the fused forward of render_rays (render.py:238-299): one C-ABI call
 // enqueues  coarse sampler -> coarse MLP -> compositing -> [inverse-CDF + merge -> fine MLP -> compositing]
 // on the caller's stream.  No kernels here; every stage is one of the library's own entry points.  The chain is written once
-// (rr_fwd_chain) and every MLP call goes through one table of entry points indexed by the math mode (modes[]).
+// (rr_fwd_chain) and every MLP call goes through one table of entry points indexed by the math mode (modes[]).  Likewise the marched
+// round (march_round: the marched render's rounds and the marched step's forward), the backward -- a pass is a value (BwdPass), resolved
+// from the flat argument lists in one place (bwd_passes) and run by rr_bwd / rr_bwd_live -- and the stages the two optimisation steps
+// share (step_pack_rays, step_list_ok, step_update).
 #include <stdint.h>
 #include "../../include/fastnerf.h"
 #include "dw_pair.h"
@@ -269,18 +272,58 @@ extern "C" int fastnerf_render_rays_fwd_ert(int math_mode, int64_t n, int N_samp
   });
 }
 
-// The marched render (include/fastnerf.h, "marched render"): no sampler and no coarse pass.  Per round fastnerf_occ_march places the
-// segment's slots of every packed row, fastnerf_march_list lists its live slots (and zeroes the logits of the others), the list forward
-// evaluates them on the packed z with S = C, and -- with ert -- fastnerf_ert_advance carries the transmittance that cuts the next round.
-// One fastnerf_raw2outputs_fwd over [n, C] follows.  The scratch (list, scan, segment count, per-ray state, transmittance) is the
-// stream's library-owned workspace, slot WS_MARCH.
+// ---- the marched round: what the marched render and the marched step share ----------------------------------------------------
+// The limits of a packed row: lists index slots with int32 and the counters are int32.  (fastnerf_step_march_ws_ints knows no K: K = 2
+// asks no more of n than C >= 2 does.)
+static bool march_kc_ok(int K, int C) { return K >= 2 && K < (1 << 24) && C >= 2 && C <= 512; }
+static bool march_n_ok(int64_t n, int K, int C) { return n * (int64_t)C < ((int64_t)1 << 31) && n * (int64_t)K < ((int64_t)1 << 31); }
+
+// A round's scratch, cut from one run of int32: list [n * B] | scan scratch | the segment's (count, entries) | per-ray state [2 n]
+// [| transmittance [n], where the run was sized with it].  B: the most slots a round places per ray.
+struct MarchWs {
+  int32_t *idx, *cws, *seg, *state;
+  float* trans;
+};
+static int64_t march_ws_ints(int64_t n, int B, bool trans) { return n * (int64_t)B + fastnerf_compact_ws_ints(n * (int64_t)B) + 2 + (trans ? 3 : 2) * n; }
+static MarchWs march_ws(int32_t* p, int64_t n, int B) {
+  int32_t* cws = p + n * (int64_t)B;
+  int32_t* seg = cws + fastnerf_compact_ws_ints(n * (int64_t)B);
+  return {p, cws, seg, seg + 2, reinterpret_cast<float*>(seg + 2 + 2 * n)};
+}
+
+// the packed rows [n, C] of one network and where the round's counters go
+struct MarchRow {
+  int math_mode, K, C, flags;
+  int64_t n;
+  const float *rays11, *params, *packed;
+  float *z, *raw;
+  int32_t *kidx, *counts;
+  fn_stream_t stream;
+};
+
+// The round, once: place() fills the slots [s0, s1) of every row (fastnerf_occ_march or fastnerf_occ_march_jitter: the caller's
+// launch), fastnerf_march_list lists the live ones (and zeroes the logits of the others), the list forward evaluates them on the packed
+// z with S = C, and -- with ert, before a further round -- fastnerf_ert_advance carries the transmittance that cuts that round.
+template <class Place>
+static int march_round(const MarchRow& r, const MarchWs& w, int s0, int s1, bool ert, Place&& place) {
+  int rc;
+  if ((rc = place())) return rc;
+  if ((rc = fastnerf_march_list(r.n, r.C, s0, s1, r.kidx, w.idx, w.seg, r.raw, w.cws, r.counts, (int32_t)(r.n * (int64_t)r.K), r.stream)))
+    return rc;
+  if ((rc = modes[r.math_mode].fwd_list(0, r.n, r.C, r.rays11, r.z, r.params, r.packed, r.raw, w.idx, w.seg, r.flags, r.stream))) return rc;
+  if (ert && s1 < r.C) return fastnerf_ert_advance(r.n, r.C, s0, s1, r.raw, r.z, r.rays11, s0 == 0, w.trans, nullptr, nullptr, r.stream);
+  return 0;
+}
+
+// The marched render (include/fastnerf.h, "marched render"): no sampler and no coarse pass.  Rounds of march_round, placed by
+// fastnerf_occ_march, then one fastnerf_raw2outputs_fwd over [n, C].  The scratch is the stream's library-owned workspace, slot WS_MARCH.
 extern "C" int fastnerf_render_rays_fwd_march(int math_mode, int64_t n, int K, int C, const float* rays11, int lindisp, int white_bkgd,
                                               const float* params, const float* packed, const fn_occ_grid* grid,
                                               const fn_occ_cascade* cascade, float eps, int block, int32_t* counts_out, float* z,
                                               int32_t* kidx, uint8_t* overflow, float* raw, float* rgb, float* disp, float* acc, float* w,
                                               float* depth, int flags, fn_stream_t stream) {
   const char* fname = "fastnerf_render_rays_fwd_march";
-  if (math_mode < 0 || math_mode > 2 || n < 0 || K < 2 || K >= (1 << 24) || C < 2 || C > 512) {
+  if (math_mode < 0 || math_mode > 2 || n < 0 || !march_kc_ok(K, C)) {
     fn::set_error("%s: bad argument: math_mode in {0,1,2}, n >= 0, 2 <= K < 2^24, 2 <= C <= 512", fname);
     return -1;
   }
@@ -293,7 +336,7 @@ extern "C" int fastnerf_render_rays_fwd_march(int math_mode, int64_t n, int K, i
     return -1;
   }
   if (n == 0) return 0;
-  if (n * (int64_t)C >= ((int64_t)1 << 31) || n * (int64_t)K >= ((int64_t)1 << 31)) {
+  if (!march_n_ok(n, K, C)) {
     fn::set_error("%s: bad argument: n * C < 2^31 (lists index slots with int32), n * K < 2^31 (the counters are int32)", fname);
     return -1;
   }
@@ -306,27 +349,22 @@ extern "C" int fastnerf_render_rays_fwd_march(int math_mode, int64_t n, int K, i
     return -1;
   }
   const int B = (block == 0 || block > C) ? C : block;
-  const int64_t Q = n * (int64_t)B, cws_ints = fastnerf_compact_ws_ints(Q);
+  const int64_t ints = march_ws_ints(n, B, true);
   static const fn::WsName what = {"fastnerf: no memory for the %.1f MB scratch of the marched render\n", 1e-6};
-  const fn::StreamWs sw = fn::stream_ws(fn::WS_MARCH, fn::S(stream), Q + cws_ints + 2 + 3 * n, what);
+  const fn::StreamWs sw = fn::stream_ws(fn::WS_MARCH, fn::S(stream), ints, what);
   if (!sw.p) {
-    fn::set_error("%s: no workspace (the stream is capturing, or there is no memory for %lld int32)", fname, (long long)(Q + cws_ints + 2 + 3 * n));
+    fn::set_error("%s: no workspace (the stream is capturing, or there is no memory for %lld int32)", fname, (long long)ints);
     return -1;
   }
-  int32_t* idx = reinterpret_cast<int32_t*>(sw.p);
-  int32_t* cws = idx + Q;
-  int32_t* seg = cws + cws_ints;
-  int32_t* state = seg + 2;
-  float* trans = sw.p + (Q + cws_ints + 2 + 2 * n);
-  int rc;
+  const MarchWs ws = march_ws(reinterpret_cast<int32_t*>(sw.p), n, B);
+  const MarchRow row = {math_mode, K, C, flags, n, rays11, params, packed, z, raw, kidx, counts_out, stream};
   for (int s0 = 0; s0 < C; s0 += B) {
     const int s1 = (C - s0 > B) ? s0 + B : C;
-    if ((rc = fastnerf_occ_march(grid, cascade, n, K, lindisp, rays11, C, s0, s1, s0 == 0, (block && s0) ? trans : nullptr, eps, state, z, kidx,
-                                 overflow, stream)))
+    if (int rc = march_round(row, ws, s0, s1, block != 0, [&] {
+          return fastnerf_occ_march(grid, cascade, n, K, lindisp, rays11, C, s0, s1, s0 == 0, (block && s0) ? ws.trans : nullptr, eps, ws.state, z,
+                                    kidx, overflow, stream);
+        }))
       return rc;
-    if ((rc = fastnerf_march_list(n, C, s0, s1, kidx, idx, seg, raw, cws, counts_out, (int32_t)(n * (int64_t)K), stream))) return rc;
-    if ((rc = modes[math_mode].fwd_list(0, n, C, rays11, z, params, packed, raw, idx, seg, flags, stream))) return rc;
-    if (block && s1 < C && (rc = fastnerf_ert_advance(n, C, s0, s1, raw, z, rays11, s0 == 0, trans, nullptr, nullptr, stream))) return rc;
   }
   return fastnerf_raw2outputs_fwd(n, C, raw, z, rays11, nullptr, white_bkgd, rgb, disp, acc, w, depth, stream);
 }
@@ -364,90 +402,107 @@ static PassMaps pass_maps(const fn_map_grads* m, int pass, const float* acc, con
   if (!m) return {acc, depth, nullptr, nullptr, nullptr};
   return pass ? PassMaps{acc, depth, m->g_disp1, m->g_acc1, m->g_depth1} : PassMaps{acc, depth, m->g_disp0, m->g_acc0, m->g_depth0};
 }
-static int comp_bwd(int64_t n, int S, const float* raw, const float* z, const float* rays11, const float* noise, int white_bkgd,
-                    const float* g_rgb, const PassMaps& m, float* draw, fn_stream_t stream) {
-  if (!m.any()) return fastnerf_raw2outputs_bwd(n, S, raw, z, rays11, noise, white_bkgd, g_rgb, draw, stream);
-  return fastnerf_raw2outputs_bwd_full(n, S, raw, z, rays11, noise, white_bkgd, m.acc, m.depth, g_rgb, m.g_disp, m.g_acc, nullptr,
-                                       m.g_depth, draw, stream);
+
+// One pass of a backward, in the style of RrFwd: its S samples, the forward's tensors over them, the gradients that come in, the network, and
+// where its gradient goes.  act: the activations the forward saved (plain backward only); packed_fwd and counts -- where the pass's
+// (live, total) goes -- the compacted backward only.
+struct BwdPass {
+  int S;
+  const float *z, *raw, *noise, *g_rgb;
+  PassMaps maps;
+  const float *params, *packed_fwd, *packed_bwd, *act;
+  float* grads;
+  int32_t* counts;
+  bool has_gradient() const { return g_rgb || maps.any(); }
+  bool disp_needs_maps() const { return maps.g_disp && (!maps.acc || !maps.depth); }
+};
+// two == false: `coarse` is the only pass (and the one that produces the image); `fine` is then unused
+struct BwdPasses { bool two; BwdPass fine, coarse; };
+// what the passes of one backward share.  passes: bit 0 = the fine pass, bit 1 = the coarse pass; act_ws / live_ws: the compacted backward only
+struct RrBwd {
+  int math_mode, white_bkgd, passes;
+  int64_t n;
+  const float* rays11;
+  float *draw_ws, *dact_ws, *partial_ws, *act_ws;
+  int32_t* live_ws;
+  fn_stream_t stream;
+};
+static int comp_bwd(const RrBwd& c, const BwdPass& q) {
+  const PassMaps& m = q.maps;
+  if (!m.any()) return fastnerf_raw2outputs_bwd(c.n, q.S, q.raw, q.z, c.rays11, q.noise, c.white_bkgd, q.g_rgb, c.draw_ws, c.stream);
+  return fastnerf_raw2outputs_bwd_full(c.n, q.S, q.raw, q.z, c.rays11, q.noise, c.white_bkgd, m.acc, m.depth, q.g_rgb, m.g_disp, m.g_acc, nullptr,
+                                       m.g_depth, c.draw_ws, c.stream);
 }
 
-static int rr_bwd(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11,
-                  int white_bkgd, const float* g_rgb, const float* g_rgb0, const float* noise0,
-                  const float* noise1, const float* z0, const float* raw0, const float* act0,
-                  const float* z1, const float* raw1, const float* act1, const float* params_c,
-                  const float* packed_bwd_c, const float* params_f, const float* packed_bwd_f,
-                  float* draw_ws, float* dact_ws, float* partial_ws, float* grads_c, float* grads_f,
-                  const float* acc0, const float* depth0, const float* acc1, const float* depth1, const fn_map_grads* mg,
-                  int passes, fn_stream_t stream) {
-  if (math_mode < 0 || math_mode > 2 || n <= 0 || N_samples < 2 || N_importance < 0) {
-    fn::set_error("fastnerf_render_rays_bwd: bad argument: math_mode in {0,1,2}, n>0, N_samples>=2, N_importance>=0");
-    return -1;
+// The ONE place that decides which buffers carry which pass, from the flat list of the entry points / the fields of fn_step_args.  With one
+// pass only (N_importance == 0) the coarse buffers carry the image pass: its colour gradient is g_rgb and its map gradients are the *1
+// members.  counts: 4 int32 = (live, total) of the fine pass, then of the coarse pass (the only pass writes the second pair), or NULL.
+// (fine.S < coarse.S says N_importance < 0 to the checks.)
+static BwdPasses bwd_passes(int N_samples, int N_importance, const float* g_rgb, const float* g_rgb0, const float* noise0, const float* noise1,
+                            const float* z0, const float* raw0, const float* act0, const float* z1, const float* raw1, const float* act1,
+                            const float* params_c, const float* packed_fwd_c, const float* packed_bwd_c, const float* params_f,
+                            const float* packed_fwd_f, const float* packed_bwd_f, float* grads_c, float* grads_f, const float* acc0,
+                            const float* depth0, const float* acc1, const float* depth1, const fn_map_grads* mg, int32_t* counts) {
+  const bool two = N_importance > 0;
+  return {two,
+          {N_samples + N_importance, z1, raw1, noise1, g_rgb, pass_maps(mg, 1, acc1, depth1), params_f, packed_fwd_f, packed_bwd_f, act1,
+           grads_f, counts},
+          {N_samples, z0, raw0, noise0, two ? g_rgb0 : g_rgb, pass_maps(mg, two ? 0 : 1, acc0, depth0), params_c, packed_fwd_c, packed_bwd_c,
+           act0, grads_c, counts ? counts + 2 : nullptr}};
+}
+
+// the checks of both backwards up to the gradients' presence; live: the compacted backward
+static bool rr_bwd_checks(const RrBwd& c, const BwdPasses& p, bool live, const char* fname) {
+  const BwdPass &f = p.fine, &k = p.coarse;
+  if (c.math_mode < 0 || c.math_mode > 2 || c.n <= 0 || k.S < 2 || f.S < k.S) {
+    fn::set_error("%s: bad argument: math_mode in {0,1,2}, n>0, N_samples>=2, N_importance>=0", fname);
+    return false;
   }
-  if (!rays11 || !z0 || !raw0 || !act0 || !params_c || !packed_bwd_c || !draw_ws || !dact_ws || !partial_ws || !grads_c) {
-    fn::set_error("fastnerf_render_rays_bwd: null pointer (coarse pass)");
+  auto net = [&](const BwdPass& q) { return q.z && q.raw && q.params && q.packed_bwd && q.grads && (live ? q.packed_fwd : q.act); };
+  if (!c.rays11 || !net(k) || !c.draw_ws || !c.dact_ws || !c.partial_ws || (live && (!c.act_ws || !c.live_ws))) {
+    fn::set_error("%s: null pointer (coarse pass)", fname);
+    return false;
+  }
+  if (p.two && (!f.has_gradient() || !k.has_gradient() || !net(f))) {
+    fn::set_error("%s: null pointer (fine pass)", fname);
+    return false;
+  }
+  if (!k.has_gradient()) {      // (one pass: with two, the check above has covered it)
+    fn::set_error("%s: null gradient", fname);
+    return false;
+  }
+  return true;
+}
+
+static int rr_bwd(const RrBwd& c, const BwdPasses& p) {
+  const char* fname = "fastnerf_render_rays_bwd";
+  const BwdPass &f = p.fine, &k = p.coarse;
+  if (!rr_bwd_checks(c, p, false, fname)) return -1;
+  if ((p.two && f.disp_needs_maps()) || k.disp_needs_maps()) {
+    fn::set_error("%s: a disparity gradient needs the forward's acc and depth of its pass", fname);
     return -1;
   }
   int rc;
-  auto mlp = [&](int S, const float* act, const float* params, const float* packed, float* grads) {
-    return modes[math_mode].bwd(0, n, S, draw_ws, act, params, packed, dact_ws, partial_ws, grads, stream);
+  auto run = [&](const BwdPass& q) {
+    if ((rc = comp_bwd(c, q))) return rc;
+    return modes[c.math_mode].bwd(0, c.n, q.S, c.draw_ws, q.act, q.params, q.packed_bwd, c.dact_ws, c.partial_ws, q.grads, c.stream);
   };
-  const float* g_coarse = g_rgb;
-  // the coarse buffers carry the image pass when there is one pass only: its map gradients are the *1 members then
-  PassMaps m_coarse = pass_maps(mg, 1, acc0, depth0);
-  if (N_importance > 0) {
-    const PassMaps m_fine = pass_maps(mg, 1, acc1, depth1);
-    m_coarse = pass_maps(mg, 0, acc0, depth0);
-    if ((!g_rgb && !m_fine.any()) || (!g_rgb0 && !m_coarse.any()) || !z1 || !raw1 || !act1 || !params_f || !packed_bwd_f || !grads_f) {
-      fn::set_error("fastnerf_render_rays_bwd: null pointer (fine pass)");
-      return -1;
-    }
-    if ((m_fine.g_disp && (!acc1 || !depth1)) || (m_coarse.g_disp && (!acc0 || !depth0))) {
-      fn::set_error("fastnerf_render_rays_bwd: a disparity gradient needs the forward's acc and depth of its pass");
-      return -1;
-    }
-    const int S1 = N_samples + N_importance;
-    // Both passes in this call, bf16x6: the paired backward.  The trunk dW jobs of the two passes (7 jobs of 256 x 256 each) go into ONE
-    // launch behind both passes' other kernels, so the coarse pass runs on a second dact / partial set of the library's (the fine pass's must
-    // survive it); draw_ws is shared as before: the trunk jobs do not read it.  Same kernels on the same data as the two passes below, in another
-    // order: bit-identical gradients.  Phase-split calls, the other math modes and N_importance == 0 never come here.
-    float *dact2 = nullptr, *partial2 = nullptr;
-    if (passes == 3 && math_mode == 2 && fn::x6_pair_workspace(n * (int64_t)N_samples, stream, &dact2, &partial2)) {
-      DwDeferred d_fine, d_coarse;   // (this call's own: nothing of a call outlives it but the workspace)
-      if ((rc = comp_bwd(n, S1, raw1, z1, rays11, noise1, white_bkgd, g_rgb, m_fine, draw_ws, stream))) return rc;
-      if ((rc = fn::x6_pair_pass(&d_fine, n, S1, draw_ws, act1, params_f, packed_bwd_f, dact_ws, partial_ws, grads_f, stream))) return rc;
-      if ((rc = comp_bwd(n, N_samples, raw0, z0, rays11, noise0, white_bkgd, g_rgb0, m_coarse, draw_ws, stream))) return rc;
-      if ((rc = fn::x6_pair_pass(&d_coarse, n, N_samples, draw_ws, act0, params_c, packed_bwd_c, dact2, partial2, grads_c, stream))) return rc;
-      return fn::x6_pair_finish(&d_fine, &d_coarse, stream);
-    }
-    if (passes & 1) {
-      if ((rc = comp_bwd(n, S1, raw1, z1, rays11, noise1, white_bkgd, g_rgb, m_fine, draw_ws, stream))) return rc;
-      if ((rc = mlp(S1, act1, params_f, packed_bwd_f, grads_f))) return rc;
-    }
-    g_coarse = g_rgb0;
+  // Both passes in this call, bf16x6: the paired backward.  The trunk dW jobs of the two passes (7 jobs of 256 x 256 each) go into ONE
+  // launch behind both passes' other kernels, so the coarse pass runs on a second dact / partial set of the library's (the fine pass's must
+  // survive it); draw_ws is shared as before: the trunk jobs do not read it.  Same kernels on the same data as the two passes below, in another
+  // order: bit-identical gradients.  Phase-split calls, the other math modes and N_importance == 0 never come here.
+  float *dact2 = nullptr, *partial2 = nullptr;
+  if (p.two && c.passes == 3 && c.math_mode == 2 && fn::x6_pair_workspace(c.n * (int64_t)k.S, c.stream, &dact2, &partial2)) {
+    DwDeferred d_fine, d_coarse;   // (this call's own: nothing of a call outlives it but the workspace)
+    if ((rc = comp_bwd(c, f))) return rc;
+    if ((rc = fn::x6_pair_pass(&d_fine, c.n, f.S, c.draw_ws, f.act, f.params, f.packed_bwd, c.dact_ws, c.partial_ws, f.grads, c.stream)))
+      return rc;
+    if ((rc = comp_bwd(c, k))) return rc;
+    if ((rc = fn::x6_pair_pass(&d_coarse, c.n, k.S, c.draw_ws, k.act, k.params, k.packed_bwd, dact2, partial2, k.grads, c.stream))) return rc;
+    return fn::x6_pair_finish(&d_fine, &d_coarse, c.stream);
   }
-  if (!g_coarse && !m_coarse.any()) {
-    fn::set_error("fastnerf_render_rays_bwd: null gradient");
-    return -1;
-  }
-  if (m_coarse.g_disp && (!acc0 || !depth0)) {
-    fn::set_error("fastnerf_render_rays_bwd: a disparity gradient needs the forward's acc and depth of its pass");
-    return -1;
-  }
-  if (!(passes & 2)) return 0;
-  if ((rc = comp_bwd(n, N_samples, raw0, z0, rays11, noise0, white_bkgd, g_coarse, m_coarse, draw_ws, stream))) return rc;
-  return mlp(N_samples, act0, params_c, packed_bwd_c, grads_c);
-}
-
-extern "C" int fastnerf_render_rays_bwd(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11,
-                                        int white_bkgd, const float* g_rgb, const float* g_rgb0, const float* noise0,
-                                        const float* noise1, const float* z0, const float* raw0, const float* act0,
-                                        const float* z1, const float* raw1, const float* act1, const float* params_c,
-                                        const float* packed_bwd_c, const float* params_f, const float* packed_bwd_f,
-                                        float* draw_ws, float* dact_ws, float* partial_ws, float* grads_c, float* grads_f,
-                                        fn_stream_t stream) {
-  return rr_bwd(math_mode, n, N_samples, N_importance, rays11, white_bkgd, g_rgb, g_rgb0, noise0, noise1, z0, raw0, act0, z1, raw1,
-                act1, params_c, packed_bwd_c, params_f, packed_bwd_f, draw_ws, dact_ws, partial_ws, grads_c, grads_f, nullptr, nullptr,
-                nullptr, nullptr, nullptr, 3, stream);
+  if (p.two && (c.passes & 1) && (rc = run(f))) return rc;
+  return (c.passes & 2) ? run(k) : 0;
 }
 
 extern "C" int fastnerf_render_rays_bwd_maps(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11,
@@ -458,85 +513,50 @@ extern "C" int fastnerf_render_rays_bwd_maps(int math_mode, int64_t n, int N_sam
                                              float* draw_ws, float* dact_ws, float* partial_ws, float* grads_c, float* grads_f,
                                              const float* acc0, const float* depth0, const float* acc1, const float* depth1,
                                              const fn_map_grads* maps, fn_stream_t stream) {
-  return rr_bwd(math_mode, n, N_samples, N_importance, rays11, white_bkgd, g_rgb, g_rgb0, noise0, noise1, z0, raw0, act0, z1, raw1,
-                act1, params_c, packed_bwd_c, params_f, packed_bwd_f, draw_ws, dact_ws, partial_ws, grads_c, grads_f, acc0, depth0,
-                acc1, depth1, maps, 3, stream);
+  return rr_bwd({math_mode, white_bkgd, 3, n, rays11, draw_ws, dact_ws, partial_ws, nullptr, nullptr, stream},
+                bwd_passes(N_samples, N_importance, g_rgb, g_rgb0, noise0, noise1, z0, raw0, act0, z1, raw1, act1, params_c, nullptr,
+                           packed_bwd_c, params_f, nullptr, packed_bwd_f, grads_c, grads_f, acc0, depth0, acc1, depth1, maps, nullptr));
 }
 
+extern "C" int fastnerf_render_rays_bwd(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11,
+                                        int white_bkgd, const float* g_rgb, const float* g_rgb0, const float* noise0,
+                                        const float* noise1, const float* z0, const float* raw0, const float* act0,
+                                        const float* z1, const float* raw1, const float* act1, const float* params_c,
+                                        const float* packed_bwd_c, const float* params_f, const float* packed_bwd_f,
+                                        float* draw_ws, float* dact_ws, float* partial_ws, float* grads_c, float* grads_f,
+                                        fn_stream_t stream) {
+  return fastnerf_render_rays_bwd_maps(math_mode, n, N_samples, N_importance, rays11, white_bkgd, g_rgb, g_rgb0, noise0, noise1, z0, raw0,
+                                       act0, z1, raw1, act1, params_c, packed_bwd_c, params_f, packed_bwd_f, draw_ws, dact_ws, partial_ws,
+                                       grads_c, grads_f, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+}
 
 // Training backward with exact zero-gradient point compaction (math_mode 1: split-bf16 kernels, 0: exact-fp32 kernels).  The forward ran WITHOUT saving
 // activations (the inference kernels); per pass:  compositing backward -> list of the points with a non-zero
 // d(loss)/d(raw) (fastnerf_compact_live) -> forward over that list, saving activations -> dX / dW over that list.
 // The gradients equal fastnerf_render_rays_bwd's up to fp32 summation order (the dead points' terms are exact zeros).
 // No host round trip: the list length stays on the device.  live_ws: 4 + n*S1 + fastnerf_compact_ws_ints(n*S1) int32;
-// act_ws: fastnerf_mlp_bf16_floats(0, 3, n*S1) / fastnerf_mlp_act_floats(0, n*S1) floats; counts_out (optional): 4 int32 = live/total fine, live/total coarse.
-static int rr_bwd_live(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11, int white_bkgd,
-                       const float* g_rgb, const float* g_rgb0, const float* noise0, const float* noise1,
-                       const float* z0, const float* raw0, const float* z1, const float* raw1,
-                       const float* params_c, const float* packed_fwd_c, const float* packed_bwd_c,
-                       const float* params_f, const float* packed_fwd_f, const float* packed_bwd_f,
-                       float* draw_ws, float* act_ws, float* dact_ws, float* partial_ws, int32_t* live_ws,
-                       float* grads_c, float* grads_f, int32_t* counts_out, const float* acc0, const float* depth0,
-                       const float* acc1, const float* depth1, const fn_map_grads* mg, int passes, fn_stream_t stream) {
-  if (math_mode < 0 || math_mode > 2 || n <= 0 || N_samples < 2 || N_importance < 0) {
-    fn::set_error("fastnerf_render_rays_bwd_live: bad argument: math_mode in {0,1,2}, n>0, N_samples>=2, N_importance>=0");
-    return -1;
-  }
-  if (!rays11 || !z0 || !raw0 || !params_c || !packed_fwd_c || !packed_bwd_c || !draw_ws || !act_ws || !dact_ws ||
-      !partial_ws || !live_ws || !grads_c) {
-    fn::set_error("fastnerf_render_rays_bwd_live: null pointer (coarse pass)");
-    return -1;
-  }
-  const int S1 = N_samples + N_importance;
-  int32_t* cnt = live_ws;            // [4]: (live, total) of the fine pass, of the coarse pass
-  int32_t* idx = live_ws + 4;
-  int32_t* cws = idx + n * (int64_t)S1;
+// act_ws: fastnerf_mlp_bf16_floats(0, 3, n*S1) / fastnerf_mlp_act_floats(0, n*S1) floats; counts_out (optional): 4 int32 = live/total fine, live/total coarse
+// (without it the counters stay in the first 4 int32 of live_ws).
+static int rr_bwd_live(const RrBwd& c, const BwdPasses& p) {
+  const char* fname = "fastnerf_render_rays_bwd_live";
+  const BwdPass &f = p.fine, &k = p.coarse;
+  if (!rr_bwd_checks(c, p, true, fname)) return -1;
+  int32_t* idx = c.live_ws + 4;   // behind the [4] counters: list | scan scratch, sized for the longer pass
+  int32_t* cws = idx + c.n * (int64_t)(p.two ? f.S : k.S);
   int rc;
-  auto pass = [&](int S, const float* z, const float* raw, const float* noise, const float* g, const PassMaps& m, const float* params,
-                  const float* pf, const float* pb, float* grads, int32_t* cnt_out) -> int {
-    if (m.g_disp && (!m.acc || !m.depth)) {
-      fn::set_error("fastnerf_render_rays_bwd_live: a disparity gradient needs the forward's acc and depth of its pass");
+  auto run = [&](const BwdPass& q) -> int {
+    if (q.disp_needs_maps()) {
+      fn::set_error("%s: a disparity gradient needs the forward's acc and depth of its pass", fname);
       return -1;
     }
-    if ((rc = comp_bwd(n, S, raw, z, rays11, noise, white_bkgd, g, m, draw_ws, stream))) return rc;
-    if ((rc = fastnerf_compact_live(n * (int64_t)S, draw_ws, idx, cnt_out, cws, stream))) return rc;
-    if ((rc = modes[math_mode].fwd_live(0, n, S, rays11, z, params, pf, act_ws, idx, cnt_out, stream))) return rc;
-    return modes[math_mode].bwd_live(0, n, S, draw_ws, act_ws, params, pb, dact_ws, partial_ws, grads, idx, cnt_out, stream);
+    if ((rc = comp_bwd(c, q))) return rc;
+    if ((rc = fastnerf_compact_live(c.n * (int64_t)q.S, c.draw_ws, idx, q.counts, cws, c.stream))) return rc;
+    if ((rc = modes[c.math_mode].fwd_live(0, c.n, q.S, c.rays11, q.z, q.params, q.packed_fwd, c.act_ws, idx, q.counts, c.stream))) return rc;
+    return modes[c.math_mode].bwd_live(0, c.n, q.S, c.draw_ws, c.act_ws, q.params, q.packed_bwd, c.dact_ws, c.partial_ws, q.grads, idx, q.counts,
+                                       c.stream);
   };
-  const float* g_coarse = g_rgb;
-  int32_t* c_fine = counts_out ? counts_out : cnt;
-  int32_t* c_coarse = counts_out ? counts_out + 2 : cnt + 2;
-  PassMaps m_coarse = pass_maps(mg, 1, acc0, depth0);      // (one pass: the *1 members, see rr_bwd)
-  if (N_importance > 0) {
-    const PassMaps m_fine = pass_maps(mg, 1, acc1, depth1);
-    m_coarse = pass_maps(mg, 0, acc0, depth0);
-    if ((!g_rgb && !m_fine.any()) || (!g_rgb0 && !m_coarse.any()) || !z1 || !raw1 || !params_f || !packed_fwd_f || !packed_bwd_f ||
-        !grads_f) {
-      fn::set_error("fastnerf_render_rays_bwd_live: null pointer (fine pass)");
-      return -1;
-    }
-    if ((passes & 1) && (rc = pass(S1, z1, raw1, noise1, g_rgb, m_fine, params_f, packed_fwd_f, packed_bwd_f, grads_f, c_fine)))
-      return rc;
-    g_coarse = g_rgb0;
-  }
-  if (!g_coarse && !m_coarse.any()) {
-    fn::set_error("fastnerf_render_rays_bwd_live: null gradient");
-    return -1;
-  }
-  if (!(passes & 2)) return 0;
-  return pass(N_samples, z0, raw0, noise0, g_coarse, m_coarse, params_c, packed_fwd_c, packed_bwd_c, grads_c, c_coarse);
-}
-
-extern "C" int fastnerf_render_rays_bwd_live(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11, int white_bkgd,
-                                             const float* g_rgb, const float* g_rgb0, const float* noise0, const float* noise1,
-                                             const float* z0, const float* raw0, const float* z1, const float* raw1,
-                                             const float* params_c, const float* packed_fwd_c, const float* packed_bwd_c,
-                                             const float* params_f, const float* packed_fwd_f, const float* packed_bwd_f,
-                                             float* draw_ws, float* act_ws, float* dact_ws, float* partial_ws, int32_t* live_ws,
-                                             float* grads_c, float* grads_f, int32_t* counts_out, fn_stream_t stream) {
-  return rr_bwd_live(math_mode, n, N_samples, N_importance, rays11, white_bkgd, g_rgb, g_rgb0, noise0, noise1, z0, raw0, z1, raw1,
-                     params_c, packed_fwd_c, packed_bwd_c, params_f, packed_fwd_f, packed_bwd_f, draw_ws, act_ws, dact_ws,
-                     partial_ws, live_ws, grads_c, grads_f, counts_out, nullptr, nullptr, nullptr, nullptr, nullptr, 3, stream);
+  if (p.two && (c.passes & 1) && (rc = run(f))) return rc;
+  return (c.passes & 2) ? run(k) : 0;
 }
 
 extern "C" int fastnerf_render_rays_bwd_live_maps(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11,
@@ -548,9 +568,23 @@ extern "C" int fastnerf_render_rays_bwd_live_maps(int math_mode, int64_t n, int 
                                                   float* partial_ws, int32_t* live_ws, float* grads_c, float* grads_f,
                                                   int32_t* counts_out, const float* acc0, const float* depth0, const float* acc1,
                                                   const float* depth1, const fn_map_grads* maps, fn_stream_t stream) {
-  return rr_bwd_live(math_mode, n, N_samples, N_importance, rays11, white_bkgd, g_rgb, g_rgb0, noise0, noise1, z0, raw0, z1, raw1,
-                     params_c, packed_fwd_c, packed_bwd_c, params_f, packed_fwd_f, packed_bwd_f, draw_ws, act_ws, dact_ws,
-                     partial_ws, live_ws, grads_c, grads_f, counts_out, acc0, depth0, acc1, depth1, maps, 3, stream);
+  return rr_bwd_live({math_mode, white_bkgd, 3, n, rays11, draw_ws, dact_ws, partial_ws, act_ws, live_ws, stream},
+                     bwd_passes(N_samples, N_importance, g_rgb, g_rgb0, noise0, noise1, z0, raw0, nullptr, z1, raw1, nullptr, params_c,
+                                packed_fwd_c, packed_bwd_c, params_f, packed_fwd_f, packed_bwd_f, grads_c, grads_f, acc0, depth0, acc1, depth1,
+                                maps, counts_out ? counts_out : live_ws));
+}
+
+extern "C" int fastnerf_render_rays_bwd_live(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11, int white_bkgd,
+                                             const float* g_rgb, const float* g_rgb0, const float* noise0, const float* noise1,
+                                             const float* z0, const float* raw0, const float* z1, const float* raw1,
+                                             const float* params_c, const float* packed_fwd_c, const float* packed_bwd_c,
+                                             const float* params_f, const float* packed_fwd_f, const float* packed_bwd_f,
+                                             float* draw_ws, float* act_ws, float* dact_ws, float* partial_ws, int32_t* live_ws,
+                                             float* grads_c, float* grads_f, int32_t* counts_out, fn_stream_t stream) {
+  return fastnerf_render_rays_bwd_live_maps(math_mode, n, N_samples, N_importance, rays11, white_bkgd, g_rgb, g_rgb0, noise0, noise1, z0, raw0,
+                                            z1, raw1, params_c, packed_fwd_c, packed_bwd_c, params_f, packed_fwd_f, packed_bwd_f, draw_ws,
+                                            act_ws, dact_ws, partial_ws, live_ws, grads_c, grads_f, counts_out, nullptr, nullptr, nullptr,
+                                            nullptr, nullptr, stream);
 }
 
 
@@ -561,60 +595,88 @@ extern "C" int fastnerf_render_rays_bwd_live_maps(int math_mode, int64_t n, int 
 // FN_STEP_BWD_FINE and travels while FN_STEP_BWD_COARSE runs).  Exactly the launches the entry points above make, in the same
 // order, on the caller's stream: results are bit-identical to calling them one by one.  (One exception to "the same order", not to the
 // results: a call with both backward phases in bf16x6 runs the paired backward of rr_bwd -- one trunk dW launch for both passes.)
+// The two steps, fastnerf_train_step and fastnerf_train_step_march, share the stages below.
 // ---------------------------------------------------------------------------------------------------------------------
 extern "C" int64_t fastnerf_step_args_size(void) { return (int64_t)sizeof(fn_step_args); }
 
 extern "C" int64_t fastnerf_step_aux_size(void) { return (int64_t)sizeof(fn_step_aux); }
 
+// the refusals of a step whose first forward runs over a list: it is a compacted step, without sigma noise; `what` / `who`: the caller's words
+static bool step_list_ok(const fn_step_args* a, const char* fname, const char* what, const char* who) {
+  if (!a->live) {
+    fn::set_error("%s: %s (live != 0): the plain backward has no list", fname, what);
+    return false;
+  }
+  if (a->noise0 || a->noise1) {
+    fn::set_error("%s: %s cannot be combined with sigma noise (it is added before the relu)", fname, who);
+    return false;
+  }
+  return true;
+}
+
+// the rays of the batch -> rays11; with FN_STEP_TIGHTEN near / far of every ray are then clamped to what the grid's bits, as they are
+// now, leave occupied.  rays11 persists to the backward.
+static int step_pack_rays(const fn_step_args* a, fn_stream_t stream) {
+  if (int rc = fastnerf_pack_rays(a->n, a->rays_o, a->rays_d, a->near_plane, a->far_plane, a->ndc, a->H, a->W, a->focal, a->rays11, stream))
+    return rc;
+  return (a->fwd_flags & FN_STEP_TIGHTEN) ? fastnerf_occ_ray_bounds(a->occ, nullptr, a->n, a->rays11, 1, nullptr, nullptr, stream) : 0;
+}
+
+static bool step_update_ok(const fn_step_args* a, const char* fname) {
+  if (a->adam_m && a->adam_v && a->adam_t >= 1) return true;
+  fn::set_error("%s: update phase needs adam_m, adam_v and adam_t >= 1", fname);
+  return false;
+}
+
+// the update phase over the networks [first, first + count) of the flat buffer: ONE Adam launch over their parameters, then each one's re-pack
+static int step_update(const fn_step_args* a, int first, int count, fn_stream_t stream) {
+  const int64_t off = first * a->net_floats;
+  if (int rc = fastnerf_adam_step(count * a->net_floats, a->params + off, a->grads + off, a->adam_m + off, a->adam_v + off, a->lr, a->beta1,
+                                  a->beta2, a->eps, a->adam_t, stream))
+    return rc;
+  for (int k = first; k < first + count; k++)
+    if (int rc = modes[a->math_mode].pack(0, a->params + k * a->net_floats, k ? a->packed_fwd_f : a->packed_fwd_c,
+                                          k ? a->packed_bwd_f : a->packed_bwd_c, stream))
+      return rc;
+  return 0;
+}
+
 // aux: NULL, or the depth / opacity terms (a term is on when its target is set)
 static int train_step(const fn_step_args* a, const fn_step_aux* aux, int phases, fn_stream_t stream) {
+  const char* fname = "fastnerf_train_step";
   if (aux && !aux->depth_target && !aux->acc_target) aux = nullptr;
   if (!a || a->math_mode < 0 || a->math_mode > 2 || a->n <= 0 || a->N_samples < 2 || a->N_importance < 0) {
-    fn::set_error("fastnerf_train_step: bad argument: args != NULL, math_mode in {0,1,2}, n>0, N_samples>=2, N_importance>=0");
+    fn::set_error("%s: bad argument: args != NULL, math_mode in {0,1,2}, n>0, N_samples>=2, N_importance>=0", fname);
     return -1;
   }
   const bool two = a->N_importance > 0;
   if (!a->params || !a->grads || !a->packed_fwd_c || !a->packed_bwd_c || (two && (!a->packed_fwd_f || !a->packed_bwd_f)) ||
       a->net_floats <= 0) {
-    fn::set_error("fastnerf_train_step: null network buffer");
+    fn::set_error("%s: null network buffer", fname);
     return -1;
   }
   if (a->occ) {
     // the grid removes samples from the FIRST forward of a compacted step; the plain backward has no list to run over, and sigma
     // noise is added before the relu: a sample with zero sigma is not dead then
-    if (!a->live) {
-      fn::set_error("fastnerf_train_step: an occupancy grid needs the compacted step (live != 0): the plain backward has no list");
-      return -1;
-    }
-    if (a->noise0 || a->noise1) {
-      fn::set_error("fastnerf_train_step: an occupancy grid cannot be combined with sigma noise (it is added before the relu)");
-      return -1;
-    }
+    if (!step_list_ok(a, fname, "an occupancy grid needs the compacted step", "an occupancy grid")) return -1;
     if (!a->live_ws) {
-      fn::set_error("fastnerf_train_step: an occupancy grid needs live_ws");
+      fn::set_error("%s: an occupancy grid needs live_ws", fname);
       return -1;
     }
   } else if (a->fwd_flags & FN_STEP_TIGHTEN) {
-    fn::set_error("fastnerf_train_step: FN_STEP_TIGHTEN needs an occupancy grid (occ != NULL)");
+    fn::set_error("%s: FN_STEP_TIGHTEN needs an occupancy grid (occ != NULL)", fname);
     return -1;
   }
   const int fwd_flags = a->fwd_flags & ~FN_STEP_TIGHTEN;   // the step's own bit does not travel on to the forward
   const float* params_c = a->params;
   const float* params_f = two ? a->params + a->net_floats : nullptr;
-  float* grads_c = a->grads;
-  float* grads_f = two ? a->grads + a->net_floats : nullptr;
-  const float* g_fine = two ? a->g_rgb : nullptr;       // d(loss)/d(rgb_map) of the pass that produces the image
   int rc;
   if (phases & FN_STEP_FORWARD) {
     if (!a->rays_o || !a->rays_d || !a->target || !a->rays11 || !a->g_rgb || (two && !a->g_rgb0) || !a->loss2) {
-      fn::set_error("fastnerf_train_step: null batch / output buffer");
+      fn::set_error("%s: null batch / output buffer", fname);
       return -1;
     }
-    if ((rc = fastnerf_pack_rays(a->n, a->rays_o, a->rays_d, a->near_plane, a->far_plane, a->ndc, a->H, a->W, a->focal, a->rays11,
-                                 stream))) return rc;
-    // near / far of every ray clamped to what the grid's bits, as they are now, leave occupied; rays11 persists to the backward
-    if ((a->fwd_flags & FN_STEP_TIGHTEN) && (rc = fastnerf_occ_ray_bounds(a->occ, nullptr, a->n, a->rays11, 1, nullptr, nullptr, stream)))
-      return rc;
+    if ((rc = step_pack_rays(a, stream))) return rc;
     const bool save = !a->live;
     if (a->occ) {
       // live_ws: [4] counters of the backward | list | scan scratch -- the forward's list and scratch are dead before the backward
@@ -644,40 +706,24 @@ static int train_step(const fn_step_args* a, const fn_step_aux* aux, int phases,
   }
   const int passes = ((phases & FN_STEP_BWD_FINE) ? 1 : 0) | ((phases & FN_STEP_BWD_COARSE) ? 2 : 0);
   if (passes) {
-    const float* g_a = two ? g_fine : a->g_rgb;
-    const float* g_b = two ? a->g_rgb0 : nullptr;
     fn_map_grads mg = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (aux) {
       if ((aux->depth_target && (!aux->g_depth1 || (two && !aux->g_depth0))) || (aux->acc_target && (!aux->g_acc1 || (two && !aux->g_acc0)))) {
         fn::set_error("fastnerf_train_step_aux: null gradient buffer of a term whose target is set");
         return -1;
       }
-      if (aux->depth_target) { mg.g_depth1 = aux->g_depth1; mg.g_depth0 = two ? aux->g_depth0 : nullptr; }
-      if (aux->acc_target) { mg.g_acc1 = aux->g_acc1; mg.g_acc0 = two ? aux->g_acc0 : nullptr; }
+      // (the *0 members are read with two passes only: bwd_passes)
+      if (aux->depth_target) { mg.g_depth1 = aux->g_depth1; mg.g_depth0 = aux->g_depth0; }
+      if (aux->acc_target) { mg.g_acc1 = aux->g_acc1; mg.g_acc0 = aux->g_acc0; }
     }
-    const fn_map_grads* mgp = aux ? &mg : nullptr;
-    if (a->live)
-      rc = rr_bwd_live(a->math_mode, a->n, a->N_samples, a->N_importance, a->rays11, a->white_bkgd, g_a, g_b, a->noise0, a->noise1,
-                       a->z0, a->raw0, a->z1, a->raw1, params_c, a->packed_fwd_c, a->packed_bwd_c, params_f, a->packed_fwd_f,
-                       a->packed_bwd_f, a->draw_ws, a->act_ws, a->dact_ws, a->partial_ws, a->live_ws, grads_c, grads_f, a->counts,
-                       a->acc0, a->depth0, a->acc1, a->depth1, mgp, passes, stream);
-    else
-      rc = rr_bwd(a->math_mode, a->n, a->N_samples, a->N_importance, a->rays11, a->white_bkgd, g_a, g_b, a->noise0, a->noise1, a->z0,
-                  a->raw0, a->act0, a->z1, a->raw1, a->act1, params_c, a->packed_bwd_c, params_f, a->packed_bwd_f, a->draw_ws,
-                  a->dact_ws, a->partial_ws, grads_c, grads_f, a->acc0, a->depth0, a->acc1, a->depth1, mgp, passes, stream);
-    if (rc) return rc;
+    const RrBwd c = {a->math_mode, a->white_bkgd, passes, a->n, a->rays11, a->draw_ws, a->dact_ws, a->partial_ws, a->act_ws, a->live_ws, stream};
+    const BwdPasses p = bwd_passes(a->N_samples, a->N_importance, a->g_rgb, a->g_rgb0, a->noise0, a->noise1, a->z0, a->raw0, a->act0, a->z1,
+                                   a->raw1, a->act1, params_c, a->packed_fwd_c, a->packed_bwd_c, params_f, a->packed_fwd_f, a->packed_bwd_f,
+                                   a->grads, two ? a->grads + a->net_floats : nullptr, a->acc0, a->depth0, a->acc1, a->depth1,
+                                   aux ? &mg : nullptr, a->counts ? a->counts : a->live_ws);
+    if ((rc = a->live ? rr_bwd_live(c, p) : rr_bwd(c, p))) return rc;
   }
-  if (phases & FN_STEP_UPDATE) {
-    if (!a->adam_m || !a->adam_v || a->adam_t < 1) {
-      fn::set_error("fastnerf_train_step: update phase needs adam_m, adam_v and adam_t >= 1");
-      return -1;
-    }
-    const int64_t total = a->net_floats * (two ? 2 : 1);
-    if ((rc = fastnerf_adam_step(total, a->params, a->grads, a->adam_m, a->adam_v, a->lr, a->beta1, a->beta2, a->eps, a->adam_t,
-                                 stream))) return rc;
-    if ((rc = modes[a->math_mode].pack(0, params_c, a->packed_fwd_c, a->packed_bwd_c, stream))) return rc;
-    if (two && (rc = modes[a->math_mode].pack(0, params_f, a->packed_fwd_f, a->packed_bwd_f, stream))) return rc;
-  }
+  if (phases & FN_STEP_UPDATE) return step_update_ok(a, fname) ? step_update(a, 0, two ? 2 : 1, stream) : -1;
   return 0;
 }
 
@@ -688,13 +734,14 @@ extern "C" int fastnerf_train_step_aux(const fn_step_args* a, const fn_step_aux*
 }
 
 // The marched step (include/fastnerf.h, "marched training"): one network on the packed rows of a jittered lattice.  The row is [n, C] in
-// the *0 buffers of fn_step_args; the backward is rr_bwd_live over it as a single pass of C samples -- closing and padding slots hold
-// zero logits, whose d(loss)/d(raw) is exactly zero, so they never enter its list.  Every check comes before the first launch.
+// the *0 buffers of fn_step_args; the forward is ONE march_round placed by fastnerf_occ_march_jitter, on the caller's list_ws; the backward
+// is rr_bwd_live over the row as a single pass of C samples -- closing and padding slots hold zero logits, whose d(loss)/d(raw) is exactly
+// zero, so they never enter its list.  Every check comes before the first launch.
 extern "C" int64_t fastnerf_step_march_size(void) { return (int64_t)sizeof(fn_step_march); }
 
 extern "C" int64_t fastnerf_step_march_ws_ints(int64_t n, int C) {
-  if (n <= 0 || C < 2 || C > 512 || n * (int64_t)C >= ((int64_t)1 << 31)) return -1;
-  return n * (int64_t)C + fastnerf_compact_ws_ints(n * (int64_t)C) + 2 + 2 * n;
+  if (n <= 0 || !march_kc_ok(2, C) || !march_n_ok(n, 2, C)) return -1;
+  return march_ws_ints(n, C, false);
 }
 
 extern "C" int fastnerf_train_step_march(const fn_step_args* a, const fn_step_march* mx, int phases, fn_stream_t stream) {
@@ -705,7 +752,7 @@ extern "C" int fastnerf_train_step_march(const fn_step_args* a, const fn_step_ma
   }
   const int K = mx->K, C = mx->C;
   const int64_t n = a->n;
-  if (K < 2 || K >= (1 << 24) || C < 2 || C > 512 || n * (int64_t)C >= ((int64_t)1 << 31) || n * (int64_t)K >= ((int64_t)1 << 31)) {
+  if (!march_kc_ok(K, C) || !march_n_ok(n, K, C)) {
     fn::set_error("%s: bad argument: 2 <= K < 2^24, 2 <= C <= 512, n * C < 2^31, n * K < 2^31", fname);
     return -1;
   }
@@ -713,14 +760,7 @@ extern "C" int fastnerf_train_step_march(const fn_step_args* a, const fn_step_ma
     fn::set_error("%s: the march walks an occupancy grid (occ != NULL)", fname);
     return -1;
   }
-  if (!a->live) {
-    fn::set_error("%s: the marched step is a compacted step (live != 0): the plain backward has no list", fname);
-    return -1;
-  }
-  if (a->noise0 || a->noise1) {
-    fn::set_error("%s: the march cannot be combined with sigma noise (it is added before the relu)", fname);
-    return -1;
-  }
+  if (!step_list_ok(a, fname, "the marched step is a compacted step", "the march")) return -1;
   if (const char* fault = fn::occ_grid_fault(a->occ)) {
     fn::set_error("%s: bad argument: %s", fname, fault);
     return -1;
@@ -734,7 +774,6 @@ extern "C" int fastnerf_train_step_march(const fn_step_args* a, const fn_step_ma
   }
   const int64_t off = mx->which ? a->net_floats : 0;
   const float* params = a->params + off;
-  float* grads = a->grads + off;
   const bool bwd = (phases & FN_STEP_BWD_COARSE) != 0;
   if ((phases & FN_STEP_FORWARD) && (!a->rays_o || !a->rays_d || !a->target || !a->loss2 || !a->rgb0 || !a->disp0 || !a->acc0 || !a->w0 ||
                                      !a->depth0)) {
@@ -745,26 +784,16 @@ extern "C" int fastnerf_train_step_march(const fn_step_args* a, const fn_step_ma
     fn::set_error("%s: null scratch of the compacted backward", fname);
     return -1;
   }
-  if ((phases & FN_STEP_UPDATE) && (!a->adam_m || !a->adam_v || a->adam_t < 1)) {
-    fn::set_error("%s: update phase needs adam_m, adam_v and adam_t >= 1", fname);
-    return -1;
-  }
+  if ((phases & FN_STEP_UPDATE) && !step_update_ok(a, fname)) return -1;
   int rc;
   if (phases & FN_STEP_FORWARD) {
-    const int64_t Q = n * (int64_t)C;
-    int32_t* idx = mx->list_ws;   // list | scan scratch | segment count | per-ray state (fastnerf_step_march_ws_ints)
-    int32_t* cws = idx + Q;
-    int32_t* seg = cws + fastnerf_compact_ws_ints(Q);
-    int32_t* state = seg + 2;
-    if ((rc = fastnerf_pack_rays(n, a->rays_o, a->rays_d, a->near_plane, a->far_plane, a->ndc, a->H, a->W, a->focal, a->rays11, stream)))
-      return rc;
-    if ((a->fwd_flags & FN_STEP_TIGHTEN) && (rc = fastnerf_occ_ray_bounds(a->occ, nullptr, n, a->rays11, 1, nullptr, nullptr, stream)))
-      return rc;
-    if ((rc = fastnerf_occ_march_jitter(a->occ, nullptr, n, K, a->lindisp, a->rays11, C, 0, C, 1, nullptr, 0.f, mx->u, mx->seed, state, a->z0,
-                                        mx->kidx, mx->overflow, stream)))
-      return rc;
-    if ((rc = fastnerf_march_list(n, C, 0, C, mx->kidx, idx, seg, a->raw0, cws, mx->counts, (int32_t)(n * (int64_t)K), stream))) return rc;
-    if ((rc = modes[a->math_mode].fwd_list(0, n, C, a->rays11, a->z0, params, pf, a->raw0, idx, seg, a->fwd_flags & ~FN_STEP_TIGHTEN, stream)))
+    const MarchWs ws = march_ws(mx->list_ws, n, C);      // (fastnerf_step_march_ws_ints: no transmittance)
+    const MarchRow row = {a->math_mode, K, C, a->fwd_flags & ~FN_STEP_TIGHTEN, n, a->rays11, params, pf, a->z0, a->raw0, mx->kidx, mx->counts, stream};
+    if ((rc = step_pack_rays(a, stream))) return rc;
+    if ((rc = march_round(row, ws, 0, C, false, [&] {
+           return fastnerf_occ_march_jitter(a->occ, nullptr, n, K, a->lindisp, a->rays11, C, 0, C, 1, nullptr, 0.f, mx->u, mx->seed, ws.state,
+                                            a->z0, mx->kidx, mx->overflow, stream);
+         })))
       return rc;
     if ((rc = fastnerf_raw2outputs_fwd(n, C, a->raw0, a->z0, a->rays11, nullptr, a->white_bkgd, a->rgb0, a->disp0, a->acc0, a->w0, a->depth0,
                                        stream)))
@@ -775,15 +804,15 @@ extern "C" int fastnerf_train_step_march(const fn_step_args* a, const fn_step_ma
     // a truncated row has lost what lies behind the cut: its colour error does not train the field (loss2 stays the mean over all rays)
     if ((rc = fastnerf_march_mask(n, mx->overflow, a->g_rgb, stream))) return rc;
   }
-  if (bwd && (rc = rr_bwd_live(a->math_mode, n, C, 0, a->rays11, a->white_bkgd, a->g_rgb, nullptr, nullptr, nullptr, a->z0, a->raw0, nullptr,
-                               nullptr, params, pf, pb, nullptr, nullptr, nullptr, a->draw_ws, a->act_ws, a->dact_ws, a->partial_ws,
-                               a->live_ws, grads, nullptr, a->counts, nullptr, nullptr, nullptr, nullptr, nullptr, 2, stream)))
-    return rc;
-  if (phases & FN_STEP_UPDATE) {
-    if ((rc = fastnerf_adam_step(a->net_floats, a->params + off, grads, a->adam_m + off, a->adam_v + off, a->lr, a->beta1, a->beta2, a->eps,
-                                 a->adam_t, stream)))
+  if (bwd) {
+    // the single pass, built directly (one pass: both members of BwdPasses name it); its counters are the coarse pair, as after a one-pass
+    // fastnerf_train_step
+    const BwdPass pass = {C, a->z0, a->raw0, nullptr, a->g_rgb, PassMaps{}, params, pf, pb, nullptr,
+                          a->grads + off, (a->counts ? a->counts : a->live_ws) + 2};
+    if ((rc = rr_bwd_live({a->math_mode, a->white_bkgd, 2, n, a->rays11, a->draw_ws, a->dact_ws, a->partial_ws, a->act_ws, a->live_ws, stream},
+                          {false, pass, pass})))
       return rc;
-    if ((rc = modes[a->math_mode].pack(0, params, pf, pb, stream))) return rc;
   }
+  if (phases & FN_STEP_UPDATE) return step_update(a, mx->which, 1, stream);
   return 0;
 }

@@ -951,9 +951,12 @@ def render_rays_fwd_occ(rays11, params_c, packed_c, params_f, packed_f, N_sample
 
 
 # ---- early ray termination (csrc/occupancy.hip, csrc/composite.hip, render.cpp) ----------------------------------------------
-def _ert_grid_args(cgrid):
-    """(grid, cascade) arguments of the fastnerf_ert_* entry points for None, a _lib.OccGrid or a _lib.OccCascade."""
+def _ert_grid_args(cgrid, required=False):
+    """(grid, cascade) arguments of the fastnerf_ert_* / march entry points for None (unless `required`), a _lib.OccGrid or a
+    _lib.OccCascade."""
     if cgrid is None:
+        if required:
+            raise TypeError('expected a _lib.OccGrid or a _lib.OccCascade, got None')
         return None, None
     if isinstance(cgrid, _lib.OccCascade):
         return None, cgrid
@@ -1046,19 +1049,15 @@ def occ_march(cgrid, rays11, K, C, s0=0, s1=None, trans=None, eps=0., lindisp=Fa
     assert overflow.shape == (n,) and overflow.dtype == torch.uint8 and overflow.is_contiguous() and overflow.device == dev
     assert state.shape == (n, 2) and state.dtype == torch.int32 and state.is_contiguous() and state.device == dev
     assert trans is None or (trans.shape == (n,) and trans.dtype == torch.float32 and trans.is_contiguous() and trans.device == dev)
-    grid, cascade = _ert_grid_args(cgrid)
-    if grid is None and cascade is None:
-        raise TypeError('expected a _lib.OccGrid or a _lib.OccCascade, got None')
-    if jitter is not None:
+    grid, cascade = _ert_grid_args(cgrid, required=True)
+    name, shift = 'fastnerf_occ_march', ()
+    if jitter is not None:      # the same list with (u, seed) behind eps
         u, seed = jitter
         require_gpu(u)
         assert u is None or (u.shape == (n,) and u.dtype == torch.float32 and u.is_contiguous() and u.device == dev)
-        check(lib().fastnerf_occ_march_jitter(grid, cascade, n, K, 1 if lindisp else 0, ptr(rays11), C, s0, s1, 1 if s0 == 0 else 0,
-                                              ptr(trans), float(eps), ptr(u), int(seed), ptr(state), ptr(z), ptr(kidx), ptr(overflow),
-                                              stream()), 'fastnerf_occ_march_jitter')
-        return z, kidx, overflow, state
-    check(lib().fastnerf_occ_march(grid, cascade, n, K, 1 if lindisp else 0, ptr(rays11), C, s0, s1, 1 if s0 == 0 else 0, ptr(trans),
-                                   float(eps), ptr(state), ptr(z), ptr(kidx), ptr(overflow), stream()), 'fastnerf_occ_march')
+        name, shift = 'fastnerf_occ_march_jitter', (ptr(u), int(seed))
+    check(getattr(lib(), name)(grid, cascade, n, K, 1 if lindisp else 0, ptr(rays11), C, s0, s1, 1 if s0 == 0 else 0, ptr(trans),
+                               float(eps), *shift, ptr(state), ptr(z), ptr(kidx), ptr(overflow), stream()), name)
     return z, kidx, overflow, state
 
 
@@ -1121,9 +1120,7 @@ def render_rays_fwd_march(rays11, params, packed, K, C, cgrid, eps=None, block=3
     o = dict(rgb=f(n, 3), disp=f(n), acc=f(n), depth=f(n), w=f(n, C), raw=f(n, C, 4), z=f(n, C),
              kidx=torch.empty(n, C, device=dev, dtype=torch.int32), overflow=torch.empty(n, device=dev, dtype=torch.uint8),
              counts=torch.zeros(2, device=dev, dtype=torch.int32))
-    grid, cascade = _ert_grid_args(cgrid)
-    if grid is None and cascade is None:
-        raise TypeError('expected a _lib.OccGrid or a _lib.OccCascade, got None')
+    grid, cascade = _ert_grid_args(cgrid, required=True)
     check(lib().fastnerf_render_rays_fwd_march(mode_id(), n, K, C, ptr(rays11), 1 if lindisp else 0, 1 if white_bkgd else 0, ptr(params),
                                                ptr(packed), grid, cascade, eps, block, ptr(o['counts']), ptr(o['z']), ptr(o['kidx']),
                                                ptr(o['overflow']), ptr(o['raw']), ptr(o['rgb']), ptr(o['disp']), ptr(o['acc']), ptr(o['w']),

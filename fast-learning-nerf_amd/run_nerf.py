@@ -152,6 +152,12 @@ def create_nerf(args, device='cuda'):
     return render_kwargs_train, render_kwargs_test, start_epoch, start_iter, grad_vars, optimizer
 
 
+def _region(block, regions, name):
+    """The tensor of region `name` (_step_regions) as a view into a step's block."""
+    off, shape = regions[name]
+    return block[off:off + math.prod(shape)].view(shape)
+
+
 class _StepOut:
     """The tensors of one fused step as a read-only mapping with the keys of render_rays' output dict (plus the extras the
     fused Trainer has always returned); views into the step's output block are built on first access."""
@@ -162,11 +168,7 @@ class _StepOut:
     def __getitem__(self, key):
         t = self._cache.get(key)
         if t is None:
-            off, shape = self._regions[self._names[key]]
-            n = 1
-            for d in shape:
-                n *= d
-            t = self._cache[key] = self._block[off:off + n].view(shape)
+            t = self._cache[key] = _region(self._block, self._regions, self._names[key])
         return t
 
     def __contains__(self, key):
@@ -196,11 +198,8 @@ def _step_regions(n, S0, Ni):
                    ('disp1', (n,)), ('acc1', (n,)), ('w1', (n, S1)), ('depth1', (n,)), ('g_rgb0', (n, 3))]
     regions, off = {}, 0
     for name, shape in shapes:
-        cnt = 1
-        for d in shape:
-            cnt *= d
         regions[name] = (off, shape)
-        off += (cnt + 63) // 64 * 64
+        off += (math.prod(shape) + 63) // 64 * 64
     return regions, off
 
 
@@ -411,6 +410,70 @@ class Trainer:
         self.last_step_live = live
         return loss2, out
 
+    # ---- what preparing a step shares between the fused and the marched route ------------------------------------------
+    def _follow_math(self):
+        """The math mode's tag; when it changed under this trainer: repack, and drop the cached step arguments."""
+        tag = ops.get_math()
+        if ops.packed_tag(self.pc[0]) != tag:
+            self.repack()
+            self._sa_key = self._ma_key = None
+        return tag
+
+    def _new_step_args(self, n, S0, Ni, dev):
+        """A fn_step_args for n rays of the sample shape (S0, Ni), filled with what lasts while its route's key does: the network,
+        moment and packed pointers, the dact | draw and partial scratch of this (device, stream) -- shared with the call-by-call
+        route (render._Workspace) -- and counts.  -> (args, regions, floats of a step's block, keep-alive list)"""
+        P = n * (S0 + Ni)
+        a = _lib.StepArgs()
+        a.n, a.net_floats, a.math_mode = n, ops.NET_PARAMS, ops.mode_id()
+        a.N_samples, a.N_importance = S0, Ni
+        a.params, a.grads, a.adam_m, a.adam_v = self.flat.data_ptr(), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr()
+        a.packed_fwd_c, a.packed_bwd_c = self.pc[0].data_ptr(), self.pc[1].data_ptr()
+        if self.pf is not None:
+            a.packed_fwd_f, a.packed_bwd_f = self.pf[0].data_ptr(), self.pf[1].data_ptr()
+        ws = _Workspace.dact(dev, ops.dact_floats(P) + P * 4)
+        a.dact_ws = ws.data_ptr()
+        a.draw_ws = ws.data_ptr() + 4 * ops.dact_floats(P)
+        a.partial_ws = _Workspace.partial(dev).data_ptr()
+        a.counts = self.live_counts.data_ptr()
+        return (a,) + _step_regions(n, S0, Ni) + ([ws],)
+
+    @staticmethod
+    def _compacted_scratch(a, keep, dev):
+        """act_ws / live_ws of the compacted backward, allocated on first use."""
+        if not a.act_ws:
+            P = a.n * (a.N_samples + a.N_importance)
+            t1 = _Workspace.get('act', dev, ops.act_floats(P))
+            t2 = _Workspace.get('live', dev, ops.live_ws_ints(P), torch.int32)
+            a.act_ws, a.live_ws = t1.data_ptr(), t2.data_ptr()
+            keep += [t1, t2]
+
+    def _fill_step(self, a, regions, floats, rays_o, rays_d, target, leaf_tag, table, max_leaves, n_global):
+        """What every step writes into its fn_step_args: the scalar settings, one fresh block of `floats` with the region pointers,
+        the batch, the leaf table and grad_scale.  -> (block, the tensors to keep referenced while the launches run)"""
+        n, dev = rays_o.shape[0], rays_o.device
+        # scalar settings are read from the trainer on EVERY step, like the call-by-call route does (a caller may change
+        # trainer.perturb / white_bkgd / near / far between steps): a handful of ctypes stores
+        a.lindisp, a.perturb = int(bool(self.lindisp)), int(bool(self.perturb))
+        a.white_bkgd, a.ndc, a.H, a.W = int(bool(self.white_bkgd)), int(bool(self.ndc)), int(self.H), int(self.W)
+        a.focal, a.near_plane, a.far_plane = float(self.K[0][0]), float(self.near), float(self.far)
+        a.beta1, a.beta2, a.eps = self.beta1, self.beta2, self.eps
+        block = torch.empty(floats, device=dev, dtype=torch.float32)
+        base = block.data_ptr()
+        for name, (off, _) in regions.items():
+            setattr(a, name, base + 4 * off)
+        ro, rd, tg = ops._f32(rays_o).reshape(-1, 3), ops._f32(rays_d).reshape(-1, 3), ops._f32(target)
+        a.rays_o, a.rays_d, a.target = ro.data_ptr(), rd.data_ptr(), tg.data_ptr()
+        hold = [ro, rd, tg]
+        if leaf_tag is not None:
+            leaf_tag = leaf_tag.contiguous()
+            hold.append(leaf_tag)
+        a.leaf_tag = None if leaf_tag is None else leaf_tag.data_ptr()
+        a.table = None if table is None else table.data_ptr()
+        a.max_leaves = int(max_leaves)
+        a.grad_scale = 1.0 if n_global is None else float(n) / float(n_global)
+        return block, hold
+
     # ---- fused route: one fastnerf_train_step call per phase group ------------------------------------------------
     def _fused_prepare(self, rays_o, rays_d, target, leaf_tag, table, max_leaves, t_rand, u, n_global, depth=None,
                        depth_weight=None, acc=None, acc_weight=None):
@@ -420,68 +483,35 @@ class Trainer:
         dev = rays_o.device
         S0, Ni = self.N_samples, self.N_importance
         S1 = S0 + Ni
-        P0, P1 = n * S0, n * S1
         ops.require_gpu(rays_o, rays_d, target, leaf_tag, table, t_rand, u)
-        tag = ops.get_math()
-        if ops.packed_tag(self.pc[0]) != tag:
-            self.repack()           # the math mode changed under this trainer
-            self._sa_key = None
+        tag = self._follow_math()
         live = self.live.use_live(self.net_c, self.net_f, Ni)
         if self.occupancy is not None or self.tighten:
             self._check_occupancy()
             live = True             # the grid's first forward feeds the compacted backward only
         key = (n, str(dev), torch.cuda.current_stream(dev).cuda_stream, tag)
-        a = self._sa
-        if a is None or self._sa_key != key:
-            a = self._sa = _lib.StepArgs()
+        if self._sa is None or self._sa_key != key:
+            self._sa, self._regions, self._block_floats, self._keep = self._new_step_args(n, S0, Ni, dev)
             self._sa_key = key
-            self._regions, self._block_floats = _step_regions(n, S0, Ni)
-            a.n, a.net_floats = n, ops.NET_PARAMS
-            a.math_mode = ops.mode_id()
-            a.N_samples, a.N_importance = S0, Ni
-            a.params, a.grads, a.adam_m, a.adam_v = self.flat.data_ptr(), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr()
-            a.packed_fwd_c, a.packed_bwd_c = self.pc[0].data_ptr(), self.pc[1].data_ptr()
-            if Ni > 0:
-                a.packed_fwd_f, a.packed_bwd_f = self.pf[0].data_ptr(), self.pf[1].data_ptr()
-            # scratch of this (device, stream), shared with the call-by-call route (render._Workspace)
-            ws = _Workspace.dact(dev, ops.dact_floats(P1) + P1 * 4)
-            a.dact_ws = ws.data_ptr()
-            a.draw_ws = ws.data_ptr() + 4 * ops.dact_floats(P1)
-            a.partial_ws = _Workspace.partial(dev).data_ptr()
-            a.counts = self.live_counts.data_ptr()
-            self._keep = [ws]
-        # scalar settings are read from the trainer on EVERY step, like the call-by-call route does (a caller may change
-        # trainer.perturb / white_bkgd / near / far between steps): a handful of ctypes stores
-        a.lindisp, a.perturb = int(bool(self.lindisp)), int(bool(self.perturb))
-        a.white_bkgd, a.ndc, a.H, a.W = int(bool(self.white_bkgd)), int(bool(self.ndc)), int(self.H), int(self.W)
-        a.focal, a.near_plane, a.far_plane = float(self.K[0][0]), float(self.near), float(self.far)
-        a.beta1, a.beta2, a.eps = self.beta1, self.beta2, self.eps
+        a = self._sa
         # the big buffers of the route this step takes (allocated on first use: a run that never falls back to the plain
         # backward never pays for its 11 GB of saved activations)
         if live:
-            if not a.act_ws:
-                t1 = _Workspace.get('act', dev, ops.act_floats(P1))
-                t2 = _Workspace.get('live', dev, ops.live_ws_ints(P1), torch.int32)
-                a.act_ws, a.live_ws = t1.data_ptr(), t2.data_ptr()
-                self._keep += [t1, t2]
+            self._compacted_scratch(a, self._keep, dev)
         elif not a.act0:
-            t1 = _Workspace.get('act0', dev, ops.act_floats(P0))
+            t1 = _Workspace.get('act0', dev, ops.act_floats(n * S0))
             a.act0 = t1.data_ptr()
             self._keep.append(t1)
             if Ni > 0:
-                t2 = _Workspace.get('act1', dev, ops.act_floats(P1))
+                t2 = _Workspace.get('act1', dev, ops.act_floats(n * S1))
                 a.act1 = t2.data_ptr()
                 self._keep.append(t2)
         # a depth / opacity term appends its four gradient rows and loss4 to the block, regions like the others
         aux = self._aux_terms(n, depth, depth_weight, acc, acc_weight)
         row = (n + 63) // 64 * 64
-        block = torch.empty(self._block_floats + (4 * row + 64 if aux else 0), device=dev, dtype=torch.float32)
+        block, hold = self._fill_step(a, self._regions, self._block_floats + (4 * row + 64 if aux else 0), rays_o, rays_d, target,
+                                      leaf_tag, table, max_leaves, n_global)
         base = block.data_ptr()
-        for name, (off, _) in self._regions.items():
-            setattr(a, name, base + 4 * off)
-        ro, rd, tg = ops._f32(rays_o).reshape(-1, 3), ops._f32(rays_d).reshape(-1, 3), ops._f32(target)
-        a.rays_o, a.rays_d, a.target = ro.data_ptr(), rd.data_ptr(), tg.data_ptr()
-        hold = [ro, rd, tg]
         if t_rand is not None:
             t_rand = ops._f32(t_rand)
             assert t_rand.shape == (n, S0)
@@ -501,13 +531,6 @@ class Trainer:
         # (the same draws, in the same order, as the call-by-call route: render._forward_core)
         a.seed0 = _next_seed() if (self.perturb and t_rand is None) else 0
         a.seed1 = _next_seed() if (Ni > 0 and self.perturb and u is None) else 0
-        if leaf_tag is not None:
-            leaf_tag = leaf_tag.contiguous()
-            hold.append(leaf_tag)
-        a.leaf_tag = None if leaf_tag is None else leaf_tag.data_ptr()
-        a.table = None if table is None else table.data_ptr()
-        a.max_leaves = int(max_leaves)
-        a.grad_scale = 1.0 if n_global is None else float(n) / float(n_global)
         a.live = int(live)
         a.fwd_flags = (1 if (live and self.skip_dead_rgb and noise0 is None) else 0) | (_lib.STEP_TIGHTEN if self.tighten else 0)
         occ = self.occupancy
@@ -529,17 +552,14 @@ class Trainer:
             hold += [aux, self.aux_losses]
         self._hold = hold       # inputs stay referenced until the next step is prepared (the launches are asynchronous)
         out = _StepOut(block, self._regions, _OUT_NAMES_2 if Ni > 0 else _OUT_NAMES_1)
-        loss2 = block[self._regions['loss2'][0]:self._regions['loss2'][0] + 2]
-        return a, out, loss2, live
+        return a, out, _region(block, self._regions, 'loss2'), live
 
     def _occupancy_tick(self, marching=False):
         """Before a step with the grid set: refresh it when its turn has come (a grid without a density is never touched).  A marched
         step refreshes it from the marched network alone."""
         k = self.occupancy_steps - self.occupancy_warmup
         if self.occupancy.dens is not None and k >= 0 and k % self.occupancy_every == 0:
-            if ops.packed_tag(self.pc[0]) != ops.get_math():
-                self.repack()
-                self._sa_key = self._ma_key = None
+            self._follow_math()
             if marching:
                 which, _, pk = self._marched()
                 self.occupancy.update(self._kw, cells_per_call=self.occupancy_cells, _packed=[pk[0]], which='fine' if which else 'coarse')
@@ -554,75 +574,40 @@ class Trainer:
         step's uint8 buffer here: step() hands it out as bool once the forward is enqueued."""
         n = rays_o.shape[0]
         dev = rays_o.device
-        P = n * C
         ops.require_gpu(rays_o, rays_d, target, leaf_tag, table, march_u)
         self._check_occupancy()
-        tag = ops.get_math()
-        if ops.packed_tag(self.pc[0]) != tag:
-            self.repack()
-            self._sa_key = self._ma_key = None
-        which, _, pk = self._marched()
+        tag = self._follow_math()
         key = (n, K, C, str(dev), torch.cuda.current_stream(dev).cuda_stream, tag)
         if self._ma is None or self._ma_key != key:
-            a, x = _lib.StepArgs(), _lib.StepMarch()
+            # the row is a single pass of C samples, always compacted
+            a, self._march_regions, self._march_floats, self._march_keep = self._new_step_args(n, C, 0, dev)
+            x = _lib.StepMarch()
             self._ma, self._ma_key = (a, x), key
-            self._march_regions, self._march_floats = _step_regions(n, C, 0)
-            a.n, a.net_floats, a.math_mode = n, ops.NET_PARAMS, ops.mode_id()
-            a.params, a.grads, a.adam_m, a.adam_v = self.flat.data_ptr(), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr()
-            a.packed_fwd_c, a.packed_bwd_c = self.pc[0].data_ptr(), self.pc[1].data_ptr()
-            if self.pf is not None:
-                a.packed_fwd_f, a.packed_bwd_f = self.pf[0].data_ptr(), self.pf[1].data_ptr()
-            ws = _Workspace.dact(dev, ops.dact_floats(P) + P * 4)
-            a.dact_ws = ws.data_ptr()
-            a.draw_ws = ws.data_ptr() + 4 * ops.dact_floats(P)
-            a.partial_ws = _Workspace.partial(dev).data_ptr()
-            t1 = _Workspace.get('act', dev, ops.act_floats(P))
-            t2 = _Workspace.get('live', dev, ops.live_ws_ints(P), torch.int32)
+            self._compacted_scratch(a, self._march_keep, dev)
             t3 = _Workspace.get('march_list', dev, ops.step_march_ws_ints(n, C), torch.int32)
-            a.act_ws, a.live_ws = t1.data_ptr(), t2.data_ptr()
-            a.counts = self.live_counts.data_ptr()
+            self._march_keep.append(t3)
             a.live = 1
             x.list_ws = t3.data_ptr()
             x.counts = self.march_counts.data_ptr()
-            self._march_keep = [ws, t1, t2, t3]
         a, x = self._ma
-        a.lindisp, a.white_bkgd = int(bool(self.lindisp)), int(bool(self.white_bkgd))
-        a.ndc, a.H, a.W = int(bool(self.ndc)), int(self.H), int(self.W)
-        a.focal, a.near_plane, a.far_plane = float(self.K[0][0]), float(self.near), float(self.far)
-        a.beta1, a.beta2, a.eps = self.beta1, self.beta2, self.eps
-        block = torch.empty(self._march_floats, device=dev, dtype=torch.float32)
-        base = block.data_ptr()
-        for name, (off, _) in self._march_regions.items():
-            setattr(a, name, base + 4 * off)
-        ro, rd, tg = ops._f32(rays_o).reshape(-1, 3), ops._f32(rays_d).reshape(-1, 3), ops._f32(target)
-        a.rays_o, a.rays_d, a.target = ro.data_ptr(), rd.data_ptr(), tg.data_ptr()
+        block, hold = self._fill_step(a, self._march_regions, self._march_floats, rays_o, rays_d, target, leaf_tag, table, max_leaves,
+                                      n_global)
         kidx = torch.empty(n, C, device=dev, dtype=torch.int32)
         overflow = torch.empty(n, device=dev, dtype=torch.uint8)
-        hold = [ro, rd, tg, kidx, overflow, self.occupancy]
+        hold += [kidx, overflow, self.occupancy]
         if march_u is not None:
             march_u = ops._f32(march_u).reshape(-1)
             assert march_u.shape == (n,)
             hold.append(march_u)
-        x.K, x.C, x.which = K, C, which
+        x.K, x.C, x.which = K, C, self._marched()[0]
         x.u = None if march_u is None else march_u.data_ptr()
         x.seed = _next_seed() if (self.perturb and march_u is None) else 0
         x.kidx, x.overflow = kidx.data_ptr(), overflow.data_ptr()
-        if leaf_tag is not None:
-            leaf_tag = leaf_tag.contiguous()
-            hold.append(leaf_tag)
-        a.leaf_tag = None if leaf_tag is None else leaf_tag.data_ptr()
-        a.table = None if table is None else table.data_ptr()
-        a.max_leaves = int(max_leaves)
-        a.grad_scale = 1.0 if n_global is None else float(n) / float(n_global)
         a.fwd_flags = (1 if self.skip_dead_rgb else 0) | (_lib.STEP_TIGHTEN if self.tighten else 0)
         a.occ = ctypes.addressof(self.occupancy._c)
         self._hold = hold
         self._march_block = block      # (with _march_regions: the step's tensors, g_rgb included, for inspection)
-
-        def view(name):
-            off, shape = self._march_regions[name]
-            return block[off:off + math.prod(shape)].view(shape)
-
+        view = lambda name: _region(block, self._march_regions, name)      # noqa: E731
         out = {'rgb_map': view('rgb0'), 'disp_map': view('disp0'), 'acc_map': view('acc0'), 'depth_map': view('depth0'),
                'raw': view('raw0'), 'weights': view('w0'), 'z_vals': view('z0'), 'march_k': kidx, 'march_overflow': overflow}
         return a, x, out, view('loss2')
@@ -644,21 +629,51 @@ class Trainer:
         self.live.tick()
         self.last_step_live = live
 
+    def _host_update(self, sl, overlap):
+        """What follows the gradient off the fused step, over the slice `sl` of the flat buffer: the collectives the stepping ranks
+        issue (the fused route's two under `overlap`, so that every rank issues the same sequence), Adam, the repack."""
+        if self.world > 1:
+            Nn = ops.NET_PARAMS
+            if overlap:
+                parallel.wait_all(parallel.all_reduce_sum_async(self.grad[Nn:]), parallel.all_reduce_sum_async(self.grad[:Nn]))
+            else:
+                parallel.all_reduce_sum(self.grad[sl])
+        ops.adam_step(self.flat[sl], self.grad[sl], self.m[sl], self.v[sl], self.lr, self.adam_t, self.beta1, self.beta2, self.eps)
+        self.repack()
+
+    def _empty_step(self, sl, seeds, overlap):
+        """The step of a rank whose shard of a (tail) batch is empty, on every route: it renders nothing and leaves the grid alone, but
+        joins the collectives with a zero gradient over the slice `sl` the step would have trained, draws the `seeds` seeds the step
+        would have drawn, and takes the update.  -> (loss2, out)"""
+        self.grad[sl].zero_()
+        _burn_seeds(seeds)
+        self.aux_losses = self._aux_zero
+        self._host_update(sl, overlap)
+        return torch.zeros(2, device=self.grad.device), {}
+
     def step(self, rays_o, rays_d, target, leaf_tag=None, table=None, max_leaves=0, t_rand=None, u=None,
              n_global=None, decay=None, march_u=None, depth=None, depth_weight=None, acc=None, acc_weight=None):
         n = rays_o.shape[0]
         Nn = ops.NET_PARAMS
         two = self.N_importance > 0 and self.net_f is not None and self.net_f is not self.net_c
         overlap = self.world > 1 and two and self.overlap_allreduce and self.grad.numel() == 2 * Nn
-        fused = self.fused and n > 0
         KC = self._check_march()            # (read on every step, like perturb and white_bkgd)
         if KC is not None and self._aux_terms(n, depth, depth_weight, acc, acc_weight):
             raise ValueError('Trainer: the marched step has no depth / opacity terms (lambda_depth / lambda_acc with a target)')
         marching = KC is not None and self.occupancy_steps >= int(self.march_after)
+        everything = slice(0, self.grad.numel())
         self.adam_t += 1
         if self.occupancy is not None and n > 0:
             self._occupancy_tick(marching)
-        if marching and n > 0:
+        if n == 0:      # an empty batch takes its own path on every route
+            if marching:
+                which = self._marched()[0]
+                loss2, out = self._empty_step(slice(which * Nn, (which + 1) * Nn), 1 if (self.perturb and march_u is None) else 0, False)
+            else:
+                seeds = ((1 if self.raw_noise_std > 0. else 0) + (1 if (self.perturb and t_rand is None) else 0)
+                         + (1 if (self.N_importance > 0 and self.perturb and u is None) else 0))
+                loss2, out = self._empty_step(everything, seeds, overlap)
+        elif marching:
             a, x, out, loss2 = self._march_prepare(KC[0], KC[1], rays_o, rays_d, target, leaf_tag, table, max_leaves, march_u, n_global)
             a.lr, a.adam_t = float(self.lr), int(self.adam_t)
             self.aux_losses = self._aux_zero
@@ -671,20 +686,7 @@ class Trainer:
             out['march_overflow'] = out['march_overflow'].bool()
             self.live.tick()
             self.last_step_live = True
-        elif marching:
-            # a rank whose shard of a (tail) batch is empty joins the collective with a zero gradient and takes the update
-            which, net, _ = self._marched()
-            g = self.grad[which * Nn:(which + 1) * Nn]
-            g.zero_()
-            _burn_seeds(1 if (self.perturb and march_u is None) else 0)
-            loss2, out = torch.zeros(2, device=self.grad.device), {}
-            self.aux_losses = self._aux_zero
-            if self.world > 1:
-                parallel.all_reduce_sum(g)
-            sl = slice(which * Nn, (which + 1) * Nn)
-            ops.adam_step(self.flat[sl], g, self.m[sl], self.v[sl], self.lr, self.adam_t, self.beta1, self.beta2, self.eps)
-            self.repack()
-        elif fused:
+        elif self.fused:
             a, out, loss2, live = self._fused_prepare(rays_o, rays_d, target, leaf_tag, table, max_leaves, t_rand, u, n_global,
                                                       depth, depth_weight, acc, acc_weight)
             a.lr, a.adam_t = float(self.lr), int(self.adam_t)
@@ -706,23 +708,9 @@ class Trainer:
                 self._after_backward(live)
                 self._fused_call(a, _lib.STEP_UPDATE)
         else:
-            if n == 0:
-                # a rank whose shard of a (tail) batch is empty still joins the collective with a zero gradient
-                self.grad.zero_()
-                _burn_seeds((1 if self.raw_noise_std > 0. else 0) + (1 if (self.perturb and t_rand is None) else 0)
-                            + (1 if (self.N_importance > 0 and self.perturb and u is None) else 0))
-                loss2, out = torch.zeros(2, device=self.grad.device), {}
-                self.aux_losses = self._aux_zero
-            else:
-                loss2, out = self.forward_backward(rays_o, rays_d, target, leaf_tag, table, max_leaves, t_rand, u, n_global,
-                                                   depth, depth_weight, acc, acc_weight)
-            if self.world > 1:
-                if overlap:   # same two collectives as the fused route, so that every rank issues the same sequence
-                    parallel.wait_all(parallel.all_reduce_sum_async(self.grad[Nn:]), parallel.all_reduce_sum_async(self.grad[:Nn]))
-                else:
-                    parallel.all_reduce_sum(self.grad)
-            ops.adam_step(self.flat, self.grad, self.m, self.v, self.lr, self.adam_t, self.beta1, self.beta2, self.eps)
-            self.repack()
+            loss2, out = self.forward_backward(rays_o, rays_d, target, leaf_tag, table, max_leaves, t_rand, u, n_global,
+                                               depth, depth_weight, acc, acc_weight)
+            self._host_update(everything, overlap)
         if (self.decay if decay is None else decay):
             self.lr = self.lrate * (0.1 ** (self.global_iter / (self.lrate_decay * 1000)))
             self.global_iter += 1
