@@ -53,6 +53,11 @@ class StepMarch(C.Structure):
                 ('list_ws', P), ('counts', P)]
 
 
+class StepBkgd(C.Structure):
+    """fn_step_bkgd of include/fastnerf.h, field for field."""
+    _fields_ = [('bkgd', P), ('seed', U64), ('alpha', P), ('bkgd_used', P), ('target_ws', P), ('g_acc1', P), ('g_acc0', P)]
+
+
 class OccGrid(C.Structure):
     """fn_occ_grid of include/fastnerf.h, field for field."""
     _fields_ = [('words', P), ('lo', F * 3), ('inv', F * 3), ('n', C.c_int32 * 3), ('outside_occupied', C.c_int32)]
@@ -194,6 +199,11 @@ SIGNATURES = {
     'fastnerf_step_march_size': (L, []),
     'fastnerf_step_march_ws_ints': (L, [L, I]),
     'fastnerf_train_step_march': (I, [C.POINTER(StepArgs), C.POINTER(StepMarch), I, P]),
+    'fastnerf_step_bkgd_size': (L, []),
+    'fastnerf_bkgd_blend': (I, [L, P, U64, P, P, P, P, P, P, P, P, P]),
+    'fastnerf_bkgd_grad': (I, [L, P, P, P, P, P, P, P, P]),
+    'fastnerf_train_step_bkgd': (I, [C.POINTER(StepArgs), C.POINTER(StepAux), C.POINTER(StepBkgd), I, P]),
+    'fastnerf_train_step_march_bkgd': (I, [C.POINTER(StepArgs), C.POINTER(StepMarch), C.POINTER(StepBkgd), I, P]),
     'fastnerf_mlp_sigma_grad_ws_floats': (L, [I, L]),
     'fastnerf_mlp_sigma_grad': (I, [I, I, L, I, P, P, P, P, P, P, P, P, P]),
     'fastnerf_ray_grad_ws_floats': (L, [I, L, I]),
@@ -222,6 +232,8 @@ def lib():
             raise RuntimeError('fn_step_aux: the ctypes mirror does not match the library (stale libfastnerf.so?)')
         if l.fastnerf_step_march_size() != C.sizeof(StepMarch):
             raise RuntimeError('fn_step_march: the ctypes mirror does not match the library (stale libfastnerf.so?)')
+        if l.fastnerf_step_bkgd_size() != C.sizeof(StepBkgd):
+            raise RuntimeError('fn_step_bkgd: the ctypes mirror does not match the library (stale libfastnerf.so?)')
         _lib = l
     return _lib
 

@@ -601,6 +601,27 @@ extern "C" int64_t fastnerf_step_args_size(void) { return (int64_t)sizeof(fn_ste
 
 extern "C" int64_t fastnerf_step_aux_size(void) { return (int64_t)sizeof(fn_step_aux); }
 
+extern "C" int64_t fastnerf_step_bkgd_size(void) { return (int64_t)sizeof(fn_step_bkgd); }
+
+// the refusals of a step with per-ray background colours (bk != NULL), before anything else of the step is looked at
+static bool step_bkgd_ok(const fn_step_args* a, const fn_step_bkgd* bk, bool two, int phases, const char* fname) {
+  if (a->white_bkgd) {
+    fn::set_error("%s: white_bkgd != 0 cannot be combined with per-ray background colours (bkgd = ones is white)", fname);
+    return false;
+  }
+  const bool fwd = (phases & FN_STEP_FORWARD) != 0;
+  const bool maps = (phases & (FN_STEP_FORWARD | FN_STEP_BWD_FINE | FN_STEP_BWD_COARSE)) != 0;
+  if ((fwd && (!bk->bkgd_used || !bk->target_ws)) || (maps && (!bk->g_acc1 || (two && !bk->g_acc0)))) {
+    fn::set_error("%s: null member of fn_step_bkgd (bkgd_used, target_ws, g_acc1, g_acc0 with two passes)", fname);
+    return false;
+  }
+  if (fwd && ((bk->bkgd != nullptr) == (bk->seed != 0))) {
+    fn::set_error("%s: exactly one of fn_step_bkgd.bkgd and seed != 0", fname);
+    return false;
+  }
+  return true;
+}
+
 // the refusals of a step whose first forward runs over a list: it is a compacted step, without sigma noise; `what` / `who`: the caller's words
 static bool step_list_ok(const fn_step_args* a, const char* fname, const char* what, const char* who) {
   if (!a->live) {
@@ -641,15 +662,20 @@ static int step_update(const fn_step_args* a, int first, int count, fn_stream_t 
   return 0;
 }
 
-// aux: NULL, or the depth / opacity terms (a term is on when its target is set)
-static int train_step(const fn_step_args* a, const fn_step_aux* aux, int phases, fn_stream_t stream) {
-  const char* fname = "fastnerf_train_step";
+// aux: NULL, or the depth / opacity terms (a term is on when its target is set); bk: NULL, or the per-ray background colours
+static int train_step(const fn_step_args* a, const fn_step_aux* aux, const fn_step_bkgd* bk, int phases, fn_stream_t stream) {
+  const char* fname = bk ? "fastnerf_train_step_bkgd" : "fastnerf_train_step";
   if (aux && !aux->depth_target && !aux->acc_target) aux = nullptr;
   if (!a || a->math_mode < 0 || a->math_mode > 2 || a->n <= 0 || a->N_samples < 2 || a->N_importance < 0) {
     fn::set_error("%s: bad argument: args != NULL, math_mode in {0,1,2}, n>0, N_samples>=2, N_importance>=0", fname);
     return -1;
   }
   const bool two = a->N_importance > 0;
+  if (bk && !step_bkgd_ok(a, bk, two, phases, fname)) return -1;
+  if (bk && aux && aux->acc_target && (phases & FN_STEP_FORWARD) && (!aux->g_acc1 || (two && !aux->g_acc0))) {
+    fn::set_error("%s: null gradient buffer of the opacity term (its rows are added to the background's)", fname);
+    return -1;
+  }
   if (!a->params || !a->grads || !a->packed_fwd_c || !a->packed_bwd_c || (two && (!a->packed_fwd_f || !a->packed_bwd_f)) ||
       a->net_floats <= 0) {
     fn::set_error("%s: null network buffer", fname);
@@ -667,6 +693,14 @@ static int train_step(const fn_step_args* a, const fn_step_aux* aux, int phases,
     fn::set_error("%s: FN_STEP_TIGHTEN needs an occupancy grid (occ != NULL)", fname);
     return -1;
   }
+  const int passes = ((phases & FN_STEP_BWD_FINE) ? 1 : 0) | ((phases & FN_STEP_BWD_COARSE) ? 2 : 0);
+  // (every refusal before the first launch: a forward phase in the same call would have run by the time the backward looks)
+  if (passes && aux && ((aux->depth_target && (!aux->g_depth1 || (two && !aux->g_depth0))) ||
+                        (aux->acc_target && (!aux->g_acc1 || (two && !aux->g_acc0))))) {
+    fn::set_error("%s: null gradient buffer of a term whose target is set", bk ? fname : "fastnerf_train_step_aux");
+    return -1;
+  }
+  if ((phases & FN_STEP_UPDATE) && !step_update_ok(a, fname)) return -1;
   const int fwd_flags = a->fwd_flags & ~FN_STEP_TIGHTEN;   // the step's own bit does not travel on to the forward
   const float* params_c = a->params;
   const float* params_f = two ? a->params + a->net_floats : nullptr;
@@ -695,42 +729,56 @@ static int train_step(const fn_step_args* a, const fn_step_aux* aux, int phases,
                                           a->w0, a->depth0, a->z1, a->z_samples, a->z_std, a->raw1, save ? a->act1 : nullptr,
                                           a->rgb1, a->disp1, a->acc1, a->w1, a->depth1, save ? 0 : fwd_flags, stream)))
       return rc;
-    if ((rc = fastnerf_mse_leafmax(a->n, two ? a->rgb1 : a->rgb0, two ? a->rgb0 : nullptr, a->target, a->grad_scale, a->g_rgb,
-                                   two ? a->g_rgb0 : nullptr, a->loss2, a->leaf_tag, a->max_leaves, a->table, stream)))
+    // (bk: white_bkgd is 0 -- the forward left the bare maps; the colours go behind them and behind the target here)
+    if (bk && (rc = fastnerf_bkgd_blend(a->n, bk->bkgd, bk->seed, bk->alpha, two ? a->acc1 : a->acc0, two ? a->acc0 : nullptr,
+                                        two ? a->rgb1 : a->rgb0, two ? a->rgb0 : nullptr, a->target, bk->target_ws, bk->bkgd_used, stream)))
+      return rc;
+    if ((rc = fastnerf_mse_leafmax(a->n, two ? a->rgb1 : a->rgb0, two ? a->rgb0 : nullptr, bk ? bk->target_ws : a->target, a->grad_scale,
+                                   a->g_rgb, two ? a->g_rgb0 : nullptr, a->loss2, a->leaf_tag, a->max_leaves, a->table, stream)))
       return rc;
     if (aux && (rc = fastnerf_aux_loss(a->n, two ? a->depth1 : a->depth0, two ? a->acc1 : a->acc0, two ? a->depth0 : nullptr,
                                        two ? a->acc0 : nullptr, aux->depth_target, aux->depth_weight, aux->acc_target,
                                        aux->acc_weight, aux->lambda_depth, aux->lambda_acc, a->grad_scale, aux->g_depth1,
                                        aux->g_acc1, two ? aux->g_depth0 : nullptr, two ? aux->g_acc0 : nullptr, aux->loss4, stream)))
       return rc;
+    // what the blend sends back to acc, on top of the opacity term's rows when that term is on
+    if (bk) {
+      const bool add = aux && aux->acc_target;
+      if ((rc = fastnerf_bkgd_grad(a->n, bk->bkgd_used, a->g_rgb, two ? a->g_rgb0 : nullptr, add ? aux->g_acc1 : nullptr,
+                                   (add && two) ? aux->g_acc0 : nullptr, bk->g_acc1, two ? bk->g_acc0 : nullptr, stream)))
+        return rc;
+    }
   }
-  const int passes = ((phases & FN_STEP_BWD_FINE) ? 1 : 0) | ((phases & FN_STEP_BWD_COARSE) ? 2 : 0);
   if (passes) {
     fn_map_grads mg = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (aux) {
-      if ((aux->depth_target && (!aux->g_depth1 || (two && !aux->g_depth0))) || (aux->acc_target && (!aux->g_acc1 || (two && !aux->g_acc0)))) {
-        fn::set_error("fastnerf_train_step_aux: null gradient buffer of a term whose target is set");
-        return -1;
-      }
       // (the *0 members are read with two passes only: bwd_passes)
       if (aux->depth_target) { mg.g_depth1 = aux->g_depth1; mg.g_depth0 = aux->g_depth0; }
       if (aux->acc_target) { mg.g_acc1 = aux->g_acc1; mg.g_acc0 = aux->g_acc0; }
     }
+    if (bk) { mg.g_acc1 = bk->g_acc1; mg.g_acc0 = bk->g_acc0; }      // (they hold the opacity term's rows too: fastnerf_bkgd_grad)
     const RrBwd c = {a->math_mode, a->white_bkgd, passes, a->n, a->rays11, a->draw_ws, a->dact_ws, a->partial_ws, a->act_ws, a->live_ws, stream};
     const BwdPasses p = bwd_passes(a->N_samples, a->N_importance, a->g_rgb, a->g_rgb0, a->noise0, a->noise1, a->z0, a->raw0, a->act0, a->z1,
                                    a->raw1, a->act1, params_c, a->packed_fwd_c, a->packed_bwd_c, params_f, a->packed_fwd_f, a->packed_bwd_f,
                                    a->grads, two ? a->grads + a->net_floats : nullptr, a->acc0, a->depth0, a->acc1, a->depth1,
-                                   aux ? &mg : nullptr, a->counts ? a->counts : a->live_ws);
+                                   (aux || bk) ? &mg : nullptr, a->counts ? a->counts : a->live_ws);
     if ((rc = a->live ? rr_bwd_live(c, p) : rr_bwd(c, p))) return rc;
   }
-  if (phases & FN_STEP_UPDATE) return step_update_ok(a, fname) ? step_update(a, 0, two ? 2 : 1, stream) : -1;
+  if (phases & FN_STEP_UPDATE) return step_update(a, 0, two ? 2 : 1, stream);
   return 0;
 }
 
-extern "C" int fastnerf_train_step(const fn_step_args* a, int phases, fn_stream_t stream) { return train_step(a, nullptr, phases, stream); }
+extern "C" int fastnerf_train_step(const fn_step_args* a, int phases, fn_stream_t stream) {
+  return train_step(a, nullptr, nullptr, phases, stream);
+}
 
 extern "C" int fastnerf_train_step_aux(const fn_step_args* a, const fn_step_aux* aux, int phases, fn_stream_t stream) {
-  return train_step(a, aux, phases, stream);
+  return train_step(a, aux, nullptr, phases, stream);
+}
+
+extern "C" int fastnerf_train_step_bkgd(const fn_step_args* a, const fn_step_aux* aux, const fn_step_bkgd* bk, int phases,
+                                        fn_stream_t stream) {
+  return train_step(a, aux, bk, phases, stream);
 }
 
 // The marched step (include/fastnerf.h, "marched training"): one network on the packed rows of a jittered lattice.  The row is [n, C] in
@@ -744,12 +792,13 @@ extern "C" int64_t fastnerf_step_march_ws_ints(int64_t n, int C) {
   return march_ws_ints(n, C, false);
 }
 
-extern "C" int fastnerf_train_step_march(const fn_step_args* a, const fn_step_march* mx, int phases, fn_stream_t stream) {
-  const char* fname = "fastnerf_train_step_march";
+static int train_step_march(const fn_step_args* a, const fn_step_march* mx, const fn_step_bkgd* bk, int phases, fn_stream_t stream) {
+  const char* fname = bk ? "fastnerf_train_step_march_bkgd" : "fastnerf_train_step_march";
   if (!a || !mx || a->math_mode < 0 || a->math_mode > 2 || a->n <= 0 || mx->which < 0 || mx->which > 1) {
     fn::set_error("%s: bad argument: args and march != NULL, math_mode in {0,1,2}, n > 0, which in {0,1}", fname);
     return -1;
   }
+  if (bk && !step_bkgd_ok(a, bk, false, phases, fname)) return -1;
   const int K = mx->K, C = mx->C;
   const int64_t n = a->n;
   if (!march_kc_ok(K, C) || !march_n_ok(n, K, C)) {
@@ -798,16 +847,22 @@ extern "C" int fastnerf_train_step_march(const fn_step_args* a, const fn_step_ma
     if ((rc = fastnerf_raw2outputs_fwd(n, C, a->raw0, a->z0, a->rays11, nullptr, a->white_bkgd, a->rgb0, a->disp0, a->acc0, a->w0, a->depth0,
                                        stream)))
       return rc;
-    if ((rc = fastnerf_mse_leafmax(n, a->rgb0, nullptr, a->target, a->grad_scale, a->g_rgb, nullptr, a->loss2, a->leaf_tag, a->max_leaves,
-                                   a->table, stream)))
+    if (bk && (rc = fastnerf_bkgd_blend(n, bk->bkgd, bk->seed, bk->alpha, a->acc0, nullptr, a->rgb0, nullptr, a->target, bk->target_ws,
+                                        bk->bkgd_used, stream)))
+      return rc;
+    if ((rc = fastnerf_mse_leafmax(n, a->rgb0, nullptr, bk ? bk->target_ws : a->target, a->grad_scale, a->g_rgb, nullptr, a->loss2,
+                                   a->leaf_tag, a->max_leaves, a->table, stream)))
       return rc;
     // a truncated row has lost what lies behind the cut: its colour error does not train the field (loss2 stays the mean over all rays)
     if ((rc = fastnerf_march_mask(n, mx->overflow, a->g_rgb, stream))) return rc;
+    // (behind the mask: an overflowed ray's g_acc is +-0)
+    if (bk && (rc = fastnerf_bkgd_grad(n, bk->bkgd_used, a->g_rgb, nullptr, nullptr, nullptr, bk->g_acc1, nullptr, stream))) return rc;
   }
   if (bwd) {
     // the single pass, built directly (one pass: both members of BwdPasses name it); its counters are the coarse pair, as after a one-pass
     // fastnerf_train_step
-    const BwdPass pass = {C, a->z0, a->raw0, nullptr, a->g_rgb, PassMaps{}, params, pf, pb, nullptr,
+    const BwdPass pass = {C, a->z0, a->raw0, nullptr, a->g_rgb, bk ? PassMaps{a->acc0, a->depth0, nullptr, bk->g_acc1, nullptr} : PassMaps{},
+                          params, pf, pb, nullptr,
                           a->grads + off, (a->counts ? a->counts : a->live_ws) + 2};
     if ((rc = rr_bwd_live({a->math_mode, a->white_bkgd, 2, n, a->rays11, a->draw_ws, a->dact_ws, a->partial_ws, a->act_ws, a->live_ws, stream},
                           {false, pass, pass})))
@@ -815,4 +870,13 @@ extern "C" int fastnerf_train_step_march(const fn_step_args* a, const fn_step_ma
   }
   if (phases & FN_STEP_UPDATE) return step_update(a, mx->which, 1, stream);
   return 0;
+}
+
+extern "C" int fastnerf_train_step_march(const fn_step_args* a, const fn_step_march* mx, int phases, fn_stream_t stream) {
+  return train_step_march(a, mx, nullptr, phases, stream);
+}
+
+extern "C" int fastnerf_train_step_march_bkgd(const fn_step_args* a, const fn_step_march* mx, const fn_step_bkgd* bk, int phases,
+                                              fn_stream_t stream) {
+  return train_step_march(a, mx, bk, phases, stream);
 }

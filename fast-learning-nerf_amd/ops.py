@@ -628,6 +628,44 @@ def aux_loss(depth, acc, depth0=None, acc0=None, depth_target=None, depth_weight
     return loss4, g
 
 
+def bkgd_blend(rgb, acc, target, bkgd=None, seed=0, alpha=None, rgb0=None, acc0=None):
+    """Per-ray background colours behind the colour maps of one render and behind its target (fastnerf_bkgd_blend).  rgb [n,3] / acc [n]
+    are the image pass's maps composited with white_bkgd=False, rgb0 / acc0 the coarse pass's of a two-pass render; rgb and rgb0 are
+    blended IN PLACE: rgb += (1 - acc) b.  bkgd: [n,3] injected colours, or None with seed != 0: drawn from the 'bkgd' stream.  alpha:
+    [n] or None; the blended target is target * alpha + (1 - alpha) b, or the target's bits without an alpha.
+    -> (target_out [n,3], bkgd_used [n,3])."""
+    require_gpu(rgb, acc, target, bkgd, alpha, rgb0, acc0)
+    n, dev = rgb.shape[0], rgb.device
+    for t, shape in ((rgb, (n, 3)), (rgb0, (n, 3)), (acc, (n,)), (acc0, (n,))):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.shape == shape and t.device == dev), shape
+    assert (rgb0 is None) == (acc0 is None), 'rgb0 and acc0 go together'
+    target = _f32(target)
+    bkgd = None if bkgd is None else _f32(bkgd)
+    alpha = None if alpha is None else _f32(alpha).reshape(-1)
+    assert target.shape == (n, 3) and (bkgd is None or bkgd.shape == (n, 3)) and (alpha is None or alpha.shape == (n,))
+    target_out = torch.empty(n, 3, device=dev, dtype=torch.float32)
+    used = torch.empty(n, 3, device=dev, dtype=torch.float32)
+    check(lib().fastnerf_bkgd_blend(n, ptr(bkgd), int(seed), ptr(alpha), ptr(acc), ptr(acc0), ptr(rgb), ptr(rgb0), ptr(target),
+                                    ptr(target_out), ptr(used), stream()), 'fastnerf_bkgd_blend')
+    return target_out, used
+
+
+def bkgd_grad(bkgd_used, g_rgb, g_rgb0=None, add=None, add0=None):
+    """What bkgd_blend sends back to the opacity maps (fastnerf_bkgd_grad): g_acc[r] = (add[r] or 0) - (g_rgb[r] . bkgd_used[r]), [n], and
+    the same for the coarse pass from g_rgb0 / add0.  add / add0: another term's d(loss)/d(acc) rows (the opacity term's), or None.
+    -> (g_acc, g_acc0 or None): the rows that raw2outputs_bwd_full takes beside g_rgb (white_bkgd=False)."""
+    require_gpu(bkgd_used, g_rgb, g_rgb0, add, add0)
+    n, dev = g_rgb.shape[0], g_rgb.device
+    t = [None if x is None else _f32(x) for x in (bkgd_used, g_rgb, g_rgb0, add, add0)]
+    assert t[0].shape == (n, 3) and t[1].shape == (n, 3) and (t[2] is None or t[2].shape == (n, 3))
+    assert (t[3] is None or t[3].shape == (n,)) and (t[4] is None or t[4].shape == (n,))
+    g_acc = torch.empty(n, device=dev, dtype=torch.float32)
+    g_acc0 = None if g_rgb0 is None else torch.empty(n, device=dev, dtype=torch.float32)
+    check(lib().fastnerf_bkgd_grad(n, ptr(t[0]), ptr(t[1]), ptr(t[2]), ptr(t[3]), ptr(t[4]), ptr(g_acc), ptr(g_acc0), stream()),
+          'fastnerf_bkgd_grad')
+    return g_acc, g_acc0
+
+
 def sigma_noise(n, S0, S1, std, seed, device):
     """(noise0 [n, S0], noise1 [n, S1] or None when S1 == 0): N(0, std^2) sigma noise of both passes of one render_rays call
     (render.py:162), one launch into one allocation (csrc/train.hip gauss_noise_kernel)."""

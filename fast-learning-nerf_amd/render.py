@@ -546,7 +546,7 @@ def _render_rays_closure(ray_batch, rays11, network_fn, network_fine, network_qu
 
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
                 N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False, occupancy=None,
-                tighten=False, march=None, march_cap=128, retdepth=False, ert=None, ert_block=32):
+                tighten=False, march=None, march_cap=128, bkgd=None, retdepth=False, ert=None, ert_block=32):
     """render.py:195-305.  Two routes, chosen by the networks (after `.module` unwrapping):
 
     * fastnerf NeRF modules (8 x 256): positional encoding + MLP run fused inside the HIP kernels; `network_query_fn` is
@@ -606,7 +606,27 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     A `ray_batch` that requires grad receives the gradient of those maps w.r.t. the ray batch as the reference's plain-torch
     render_rays gives it: columns o, d (through the sample points and through dists * |d|) and viewdir; near / far (columns 6:8)
     get zeros on the fused route (they are constants there: `render` passes Python floats), and z is a constant of the backward.
-    Fused route: math modes 'fp32' and 'bf16x6' (NotImplementedError under 'bf16x3'), always through the saving backward."""
+    Fused route: math modes 'fp32' and 'bf16x6' (NotImplementedError under 'bf16x3'), always through the saving backward.
+
+    `bkgd` (a colour [3] or per-ray colours [n, 3]; ValueError with white_bkgd=True): the call runs with white_bkgd=False, then
+    rgb_map = rgb_map + (1 - acc_map)[:, None] * bkgd, and the same for rgb0 with acc0, in torch -- on every route, with `occupancy=`,
+    `ert=` and `march=` as well.  Under autograd that is plain arithmetic on maps that are differentiable already: parameters, rays and a
+    pose receive the background's gradient through acc_map.  bkgd = ones has the bits of white_bkgd=True.  `bkgd=None` (the default)
+    makes exactly the calls it made before."""
+    if bkgd is not None:
+        if white_bkgd:
+            raise ValueError('render_rays: bkgd cannot be combined with white_bkgd=True (bkgd = ones is the white background)')
+        ret = render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=retraw, lindisp=lindisp, perturb=perturb,
+                          N_importance=N_importance, network_fine=network_fine, white_bkgd=False, raw_noise_std=raw_noise_std,
+                          verbose=verbose, pytest=pytest, occupancy=occupancy, tighten=tighten, march=march, march_cap=march_cap,
+                          retdepth=retdepth, ert=ert, ert_block=ert_block)
+        b = torch.as_tensor(bkgd, dtype=ret['rgb_map'].dtype, device=ret['rgb_map'].device)
+        if b.shape != (3,) and b.shape != ret['rgb_map'].shape:
+            raise ValueError('render_rays: bkgd is a colour [3] or one colour per ray [n, 3]')
+        ret['rgb_map'] = ret['rgb_map'] + (1. - ret['acc_map'])[:, None] * b
+        if 'rgb0' in ret:
+            ret['rgb0'] = ret['rgb0'] + (1. - ret['acc0'])[:, None] * b
+        return ret
     net_c = _unwrap(network_fn)
     net_f = _unwrap(network_fine)
     fused = isinstance(net_c, NeRF)
@@ -718,9 +738,13 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
 
 
 def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
-    """render.py:12-24."""
+    """render.py:12-24.  Per-ray background colours (`bkgd` [N, 3]) are sliced with the chunk."""
     all_ret = {}
+    bkgd = kwargs.get('bkgd')
+    per_ray = torch.is_tensor(bkgd) and bkgd.dim() == 2
     for i in range(0, rays_flat.shape[0], chunk):
+        if per_ray:
+            kwargs = dict(kwargs, bkgd=bkgd[i:i + chunk])
         ret = render_rays(rays_flat[i:i + chunk], **kwargs)
         for k in ret:
             all_ret.setdefault(k, []).append(ret[k])
@@ -761,7 +785,12 @@ class _PoseRaysFn(torch.autograd.Function):
 def render(H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far=1., use_viewdirs=False,
            c2w_staticcam=None, **kwargs):
     """render.py:26-91 -> [rgb_map, disp_map, acc_map, extras].  A tensor `c2w` that requires grad receives the gradient of
-    every differentiable map (render_rays) through the rays (_PoseRaysFn); with ndc=True or c2w_staticcam that raises NotImplementedError."""
+    every differentiable map (render_rays) through the rays (_PoseRaysFn); with ndc=True or c2w_staticcam that raises NotImplementedError.
+    `bkgd=` (render_rays): a colour [3], or one colour per ray in the shape of the rays ([H, W, 3] or [N, 3])."""
+    bkgd = kwargs.get('bkgd')
+    if bkgd is not None and not (torch.is_tensor(bkgd) and bkgd.dim() == 1):
+        bkgd = torch.as_tensor(bkgd, dtype=torch.float32)
+        kwargs = dict(kwargs, bkgd=bkgd if bkgd.dim() == 1 else bkgd.reshape(-1, 3))
     if torch.is_tensor(c2w) and c2w.requires_grad and torch.is_grad_enabled():
         if ndc or c2w_staticcam is not None:
             raise NotImplementedError('render: a pose that requires grad is differentiated through plain pinhole rays only '

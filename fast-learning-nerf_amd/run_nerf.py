@@ -75,6 +75,7 @@ class _Args:
     N_samples = 64; N_importance = 0; perturb = 1.; use_viewdirs = True; i_embed = 0
     multires = 10; multires_views = 4; raw_noise_std = 0.
     dataset_type = 'blender'; white_bkgd = False; no_ndc = False; lindisp = False
+    random_bkgd = False      # (not in the reference's parser) RGBA training over a fresh background colour per ray
     n_epoch = 12; init_level = 3; rays_downscale = 1; subdivide_every = 1; subdivide_thres = 0.015
     randSamp_perc = 0.5; basedir = './logs'; expname = 'fastnerf'
 
@@ -259,11 +260,23 @@ class Trainer:
     march_overflow (bool [n]) (+ raw, weights, z_vals, march_k of the packed row).  `tighten=True` combines: the lattice spans the
     clamped interval.  ValueError: march without a grid, a grid with outside_occupied=True (every lattice point outside the box would be
     live and the rows would overflow), a depth / opacity term that is on, raw_noise_std > 0, forward_backward, a trainer off the fused
-    step.  No early ray termination while training."""
+    step.  No early ray termination while training.
+
+    Per-ray background colours (`bkgd`: None, 'random' or a colour of 3 floats; read on every step, like white_bkgd; include/fastnerf.h,
+    "per-ray background colours"): the step composites with white_bkgd=False, puts a colour b_r behind every ray of both passes,
+    rgb += (1 - acc) b, and -- with step(..., alpha=[n]), the alpha of an RGBA target whose colours are straight -- behind the target,
+    t' = t a + (1 - a) b; the loss and the leaf-error table see the blended maps and target.  'random' draws fresh colours every step
+    (one `_next_seed()` after the step's other draws), step(..., bkgd=[n,3]) injects them, a constant colour is every ray's.  Density
+    where the image is transparent then always costs, which a fixed colour cannot promise.  out['bkgd'] [n,3] holds the colours used;
+    out['rgb_map'] / out['rgb0'] are the blended maps.  What the blend sends back to the opacity maps, -(g_rgb . b), reaches the field
+    through the full-gradient compositing backward, added to the opacity term's rows when lambda_acc is on; like that term it makes every
+    sample with positive density of a ray that is not yet opaque live.  All routes take it: the fused step (plain, compacted, through a
+    grid, tighten), the marched step and the call-by-call route.  ValueError: together with white_bkgd (bkgd=(1, 1, 1) is white), an
+    alpha with no background on."""
 
     def __init__(self, render_kwargs_train, H, W, K, near, far, lrate=5e-4, lrate_decay=250, decay=True,
                  beta1=0.9, beta2=0.999, eps=1e-8, occupancy=None, occupancy_every=16, occupancy_warmup=256, occupancy_cells=None,
-                 lambda_depth=0., lambda_acc=0., tighten=False, march=None, march_cap=128, march_after=0):
+                 lambda_depth=0., lambda_acc=0., tighten=False, march=None, march_cap=128, march_after=0, bkgd=None):
         kw = render_kwargs_train
         self._kw = kw
         self.net_c = kw['network_fn']
@@ -311,6 +324,8 @@ class Trainer:
         self.march_counts = None if march is None else torch.zeros(2, device=self.flat.device, dtype=torch.int32)
         self._ma = None          # fn_step_args / fn_step_march of the marched step
         self._ma_key = None
+        self.bkgd = bkgd
+        self._bk = None          # fn_step_bkgd of the current step (None: no background)
         self._check_occupancy()
         self._check_march()
         self.repack()
@@ -372,14 +387,62 @@ class Trainer:
             t['lambda_depth'], t['lambda_acc'] = self.lambda_depth, self.lambda_acc
         return t
 
+    def _bkgd_terms(self, n, dev, alpha, bkgd):
+        """The background of this step: None when off, else a dict with `bkgd` (contiguous fp32 [n,3], or None: draw them, 'random')
+        and `alpha` (fp32 [n] or None).  A background is on when trainer.bkgd is set or colours are injected."""
+        setting = self.bkgd
+        if setting is None and bkgd is None:
+            if alpha is not None:
+                raise ValueError('Trainer: alpha= blends the target over a background colour: it needs bkgd= (trainer or step)')
+            return None
+        if self.white_bkgd:
+            raise ValueError('Trainer: bkgd cannot be combined with white_bkgd=True (bkgd=(1, 1, 1) is the white background)')
+        ops.require_gpu(alpha, bkgd)
+        if bkgd is not None:
+            bkgd = ops._f32(bkgd)
+            assert bkgd.shape == (n, 3), 'bkgd: [n, 3] colours'
+        elif not isinstance(setting, str):
+            colour = torch.as_tensor(setting, dtype=torch.float32).reshape(3)
+            bkgd = colour.to(dev).expand(n, 3).contiguous()
+        elif setting != 'random':
+            raise ValueError("Trainer: bkgd is None, 'random' or a colour of 3 floats, not {!r}".format(setting))
+        if alpha is not None:
+            alpha = ops._f32(alpha).reshape(-1)
+            assert alpha.numel() == n, 'alpha: [n]'
+        return {'bkgd': bkgd, 'alpha': alpha}
+
+    def _draws_bkgd(self, bkgd):
+        """Whether a step with these injected colours draws the seed of the 'bkgd' stream."""
+        return bkgd is None and isinstance(self.bkgd, str) and self.bkgd == 'random'
+
+    def _new_step_bkgd(self, bt, block, tail, n):
+        """fn_step_bkgd of a step whose block has 2 x [n,3] + 2 x [n] floats (_bkgd_floats) behind `tail`.  -> (struct, bkgd_used view)"""
+        row, row3 = (n + 63) // 64 * 64, (3 * n + 63) // 64 * 64
+        base = block.data_ptr()
+        k = _lib.StepBkgd()
+        k.bkgd = None if bt['bkgd'] is None else bt['bkgd'].data_ptr()
+        k.seed = _next_seed() if bt['bkgd'] is None else 0
+        k.alpha = None if bt['alpha'] is None else bt['alpha'].data_ptr()
+        k.bkgd_used, k.target_ws = base + 4 * tail, base + 4 * (tail + row3)
+        k.g_acc1, k.g_acc0 = base + 4 * (tail + 2 * row3), base + 4 * (tail + 2 * row3 + row)
+        at = lambda off, *shape: block[tail + off:tail + off + math.prod(shape)].view(shape)      # noqa: E731
+        # (the step's own tensors, for inspection: the blended target and the rows handed to the compositing backward)
+        self._bk_views = {'target': at(row3, n, 3), 'g_acc1': at(2 * row3, n), 'g_acc0': at(2 * row3 + row, n)}
+        return k, at(0, n, 3)
+
+    @staticmethod
+    def _bkgd_floats(n):
+        return 2 * ((3 * n + 63) // 64 * 64) + 2 * ((n + 63) // 64 * 64)
+
     def forward_backward(self, rays_o, rays_d, target, leaf_tag=None, table=None, max_leaves=0, t_rand=None, u=None,
-                         n_global=None, depth=None, depth_weight=None, acc=None, acc_weight=None):
+                         n_global=None, alpha=None, bkgd=None, depth=None, depth_weight=None, acc=None, acc_weight=None):
         if self.march is not None:
             raise ValueError('Trainer.forward_backward: the call-by-call route has no marched step; use step()')
         if self.occupancy is not None or self.tighten:
             raise ValueError('Trainer.forward_backward: the call-by-call route has no occupancy grid; use step()')
         n = rays_o.shape[0]
         dev = rays_o.device
+        bt = self._bkgd_terms(n, dev, alpha, bkgd)
         rays11 = ops.pack_rays(rays_o, rays_d, self.near, self.far, ndc=self.ndc, H=self.H, W=self.W,
                                focal=float(self.K[0][0]))
         if not self.use_viewdirs:
@@ -392,6 +455,10 @@ class Trainer:
                                    self.perturb, self.white_bkgd, t_rand, u, noise0, noise1, save=not live,
                                    packed_c=self.pc, packed_f=self.pf, skip_dead_rgb=live and self.skip_dead_rgb, act_ws=True)
         scale = 1.0 if n_global is None else float(n) / float(n_global)
+        if bt is not None:      # the same launches, in the same order, as fastnerf_train_step_bkgd makes
+            target, out['bkgd'] = ops.bkgd_blend(out['rgb_map'], out['acc_map'], target, bkgd=bt['bkgd'],
+                                                 seed=_next_seed() if bt['bkgd'] is None else 0, alpha=bt['alpha'],
+                                                 rgb0=out.get('rgb0'), acc0=out.get('acc0'))
         loss2, g, g0 = ops.mse_leafmax(out['rgb_map'], out.get('rgb0'), target, grad_scale=scale, leaf_tag=leaf_tag,
                                        max_leaves=max_leaves, table=table)
         maps = None
@@ -400,6 +467,11 @@ class Trainer:
         if aux:      # the same launch, behind the colour loss, as fastnerf_train_step_aux makes
             self.aux_losses, gm = ops.aux_loss(out['depth_map'], out['acc_map'], out.get('depth0'), out.get('acc0'), grad_scale=scale, **aux)
             maps = {k: t for k, t in gm.items() if t is not None}
+        if bt is not None:
+            ga1, ga0 = ops.bkgd_grad(out['bkgd'], g, g0, add=(maps or {}).get('g_acc1'), add0=(maps or {}).get('g_acc0'))
+            maps = dict(maps or {}, g_acc1=ga1)
+            if ga0 is not None:
+                maps['g_acc0'] = ga0
         _backward_core(saved, g, g0, counts=self.live_counts if live else None, maps=maps)
         self.net_c.collect_grads()          # (no-ops with view directions: the kernels write the parameters' gradients)
         if self.net_f is not None and self.net_f is not self.net_c:
@@ -475,12 +547,13 @@ class Trainer:
         return block, hold
 
     # ---- fused route: one fastnerf_train_step call per phase group ------------------------------------------------
-    def _fused_prepare(self, rays_o, rays_d, target, leaf_tag, table, max_leaves, t_rand, u, n_global, depth=None,
-                       depth_weight=None, acc=None, acc_weight=None):
-        """Fill fn_step_args (and fn_step_aux, self._aux, when a depth / opacity term is on) for this batch; returns (args, out
-        mapping, loss2, live)."""
+    def _fused_prepare(self, rays_o, rays_d, target, leaf_tag, table, max_leaves, t_rand, u, n_global, alpha=None, bkgd=None,
+                       depth=None, depth_weight=None, acc=None, acc_weight=None):
+        """Fill fn_step_args (and fn_step_aux, self._aux, when a depth / opacity term is on; fn_step_bkgd, self._bk, with a background)
+        for this batch; returns (args, out mapping, loss2, live)."""
         n = rays_o.shape[0]
         dev = rays_o.device
+        bt = self._bkgd_terms(n, dev, alpha, bkgd)
         S0, Ni = self.N_samples, self.N_importance
         S1 = S0 + Ni
         ops.require_gpu(rays_o, rays_d, target, leaf_tag, table, t_rand, u)
@@ -509,8 +582,9 @@ class Trainer:
         # a depth / opacity term appends its four gradient rows and loss4 to the block, regions like the others
         aux = self._aux_terms(n, depth, depth_weight, acc, acc_weight)
         row = (n + 63) // 64 * 64
-        block, hold = self._fill_step(a, self._regions, self._block_floats + (4 * row + 64 if aux else 0), rays_o, rays_d, target,
-                                      leaf_tag, table, max_leaves, n_global)
+        aux_floats = 4 * row + 64 if aux else 0
+        block, hold = self._fill_step(a, self._regions, self._block_floats + aux_floats + (self._bkgd_floats(n) if bt else 0), rays_o,
+                                      rays_d, target, leaf_tag, table, max_leaves, n_global)
         base = block.data_ptr()
         if t_rand is not None:
             t_rand = ops._f32(t_rand)
@@ -550,8 +624,15 @@ class Trainer:
             x.loss4 = self.aux_losses.data_ptr()
             x.lambda_depth, x.lambda_acc = aux['lambda_depth'], aux['lambda_acc']
             hold += [aux, self.aux_losses]
+        regions, names = self._regions, _OUT_NAMES_2 if Ni > 0 else _OUT_NAMES_1
+        self._bk = None
+        if bt:      # (the seed of 'random' is drawn here: after every other draw of the step)
+            tail = self._block_floats + aux_floats
+            self._bk, _ = self._new_step_bkgd(bt, block, tail, n)
+            regions, names = dict(regions, bkgd_used=(tail, (n, 3))), dict(names, bkgd='bkgd_used')
+            hold.append(bt)
         self._hold = hold       # inputs stay referenced until the next step is prepared (the launches are asynchronous)
-        out = _StepOut(block, self._regions, _OUT_NAMES_2 if Ni > 0 else _OUT_NAMES_1)
+        out = _StepOut(block, regions, names)
         return a, out, _region(block, self._regions, 'loss2'), live
 
     def _occupancy_tick(self, marching=False):
@@ -569,11 +650,12 @@ class Trainer:
         self.occupancy_steps += 1
 
     # ---- marched route: one fastnerf_train_step_march call per phase group ------------------------------------------
-    def _march_prepare(self, K, C, rays_o, rays_d, target, leaf_tag, table, max_leaves, march_u, n_global):
-        """Fill fn_step_args and fn_step_march for this batch; returns (args, march, out dict, loss2).  out['march_overflow'] is the
-        step's uint8 buffer here: step() hands it out as bool once the forward is enqueued."""
+    def _march_prepare(self, K, C, rays_o, rays_d, target, leaf_tag, table, max_leaves, march_u, n_global, alpha=None, bkgd=None):
+        """Fill fn_step_args and fn_step_march (and fn_step_bkgd, self._bk, with a background) for this batch; returns (args, march, out
+        dict, loss2).  out['march_overflow'] is the step's uint8 buffer here: step() hands it out as bool once the forward is enqueued."""
         n = rays_o.shape[0]
         dev = rays_o.device
+        bt = self._bkgd_terms(n, dev, alpha, bkgd)
         ops.require_gpu(rays_o, rays_d, target, leaf_tag, table, march_u)
         self._check_occupancy()
         tag = self._follow_math()
@@ -590,8 +672,8 @@ class Trainer:
             x.list_ws = t3.data_ptr()
             x.counts = self.march_counts.data_ptr()
         a, x = self._ma
-        block, hold = self._fill_step(a, self._march_regions, self._march_floats, rays_o, rays_d, target, leaf_tag, table, max_leaves,
-                                      n_global)
+        block, hold = self._fill_step(a, self._march_regions, self._march_floats + (self._bkgd_floats(n) if bt else 0), rays_o, rays_d,
+                                      target, leaf_tag, table, max_leaves, n_global)
         kidx = torch.empty(n, C, device=dev, dtype=torch.int32)
         overflow = torch.empty(n, device=dev, dtype=torch.uint8)
         hold += [kidx, overflow, self.occupancy]
@@ -610,13 +692,25 @@ class Trainer:
         view = lambda name: _region(block, self._march_regions, name)      # noqa: E731
         out = {'rgb_map': view('rgb0'), 'disp_map': view('disp0'), 'acc_map': view('acc0'), 'depth_map': view('depth0'),
                'raw': view('raw0'), 'weights': view('w0'), 'z_vals': view('z0'), 'march_k': kidx, 'march_overflow': overflow}
+        self._bk = None
+        if bt:      # (the seed of 'random' is drawn here: after the shift's)
+            self._bk, out['bkgd'] = self._new_step_bkgd(bt, block, self._march_floats, n)
+            hold.append(bt)
         return a, x, out, view('loss2')
 
     def _march_call(self, a, x, phases):
+        if self._bk is not None:      # (given in every phase call)
+            _lib.check(_lib.lib().fastnerf_train_step_march_bkgd(ctypes.byref(a), ctypes.byref(x), ctypes.byref(self._bk), int(phases),
+                                                                 _lib.stream()), 'fastnerf_train_step_march_bkgd')
+            return
         _lib.check(_lib.lib().fastnerf_train_step_march(ctypes.byref(a), ctypes.byref(x), int(phases), _lib.stream()),
                    'fastnerf_train_step_march')
 
     def _fused_call(self, a, phases):
+        if self._bk is not None:       # (like fn_step_aux, given in every phase call)
+            _lib.check(_lib.lib().fastnerf_train_step_bkgd(ctypes.byref(a), None if self._aux is None else ctypes.byref(self._aux),
+                                                           ctypes.byref(self._bk), int(phases), _lib.stream()), 'fastnerf_train_step_bkgd')
+            return
         if self._aux is not None:      # (given in every phase call: the data-parallel step splits them)
             _lib.check(_lib.lib().fastnerf_train_step_aux(ctypes.byref(a), ctypes.byref(self._aux), int(phases), _lib.stream()),
                        'fastnerf_train_step_aux')
@@ -652,7 +746,8 @@ class Trainer:
         return torch.zeros(2, device=self.grad.device), {}
 
     def step(self, rays_o, rays_d, target, leaf_tag=None, table=None, max_leaves=0, t_rand=None, u=None,
-             n_global=None, decay=None, march_u=None, depth=None, depth_weight=None, acc=None, acc_weight=None):
+             n_global=None, decay=None, march_u=None, alpha=None, bkgd=None, depth=None, depth_weight=None, acc=None,
+             acc_weight=None):
         n = rays_o.shape[0]
         Nn = ops.NET_PARAMS
         two = self.N_importance > 0 and self.net_f is not None and self.net_f is not self.net_c
@@ -666,15 +761,19 @@ class Trainer:
         if self.occupancy is not None and n > 0:
             self._occupancy_tick(marching)
         if n == 0:      # an empty batch takes its own path on every route
+            self._bkgd_terms(0, self.grad.device, alpha, bkgd)      # (its ValueErrors, like a step that renders)
+            bk_seed = 1 if self._draws_bkgd(bkgd) else 0
             if marching:
                 which = self._marched()[0]
-                loss2, out = self._empty_step(slice(which * Nn, (which + 1) * Nn), 1 if (self.perturb and march_u is None) else 0, False)
+                loss2, out = self._empty_step(slice(which * Nn, (which + 1) * Nn),
+                                              (1 if (self.perturb and march_u is None) else 0) + bk_seed, False)
             else:
                 seeds = ((1 if self.raw_noise_std > 0. else 0) + (1 if (self.perturb and t_rand is None) else 0)
-                         + (1 if (self.N_importance > 0 and self.perturb and u is None) else 0))
+                         + (1 if (self.N_importance > 0 and self.perturb and u is None) else 0) + bk_seed)
                 loss2, out = self._empty_step(everything, seeds, overlap)
         elif marching:
-            a, x, out, loss2 = self._march_prepare(KC[0], KC[1], rays_o, rays_d, target, leaf_tag, table, max_leaves, march_u, n_global)
+            a, x, out, loss2 = self._march_prepare(KC[0], KC[1], rays_o, rays_d, target, leaf_tag, table, max_leaves, march_u, n_global,
+                                                   alpha, bkgd)
             a.lr, a.adam_t = float(self.lr), int(self.adam_t)
             self.aux_losses = self._aux_zero
             if self.world == 1:
@@ -688,7 +787,7 @@ class Trainer:
             self.last_step_live = True
         elif self.fused:
             a, out, loss2, live = self._fused_prepare(rays_o, rays_d, target, leaf_tag, table, max_leaves, t_rand, u, n_global,
-                                                      depth, depth_weight, acc, acc_weight)
+                                                      alpha, bkgd, depth, depth_weight, acc, acc_weight)
             a.lr, a.adam_t = float(self.lr), int(self.adam_t)
             if self.world == 1:
                 self._fused_call(a, _lib.STEP_FORWARD | _lib.STEP_BWD_FINE | _lib.STEP_BWD_COARSE | _lib.STEP_UPDATE)
@@ -709,7 +808,7 @@ class Trainer:
                 self._fused_call(a, _lib.STEP_UPDATE)
         else:
             loss2, out = self.forward_backward(rays_o, rays_d, target, leaf_tag, table, max_leaves, t_rand, u, n_global,
-                                               depth, depth_weight, acc, acc_weight)
+                                               alpha=alpha, bkgd=bkgd, depth=depth, depth_weight=depth_weight, acc=acc, acc_weight=acc_weight)
             self._host_update(everything, overlap)
         if (self.decay if decay is None else decay):
             self.lr = self.lrate * (0.1 ** (self.global_iter / (self.lrate_decay * 1000)))
@@ -772,7 +871,9 @@ def load_dataset(args):
     """The data-loading branch of the reference's train() (run_nerf.py:160-241) for the two dataset types on this path:
     -> dict(images [n,H,W,3], poses [n,3,4], render_poses, hwf [H,W,focal], K, i_train, i_val, i_test, near, far).
     `args` needs dataset_type, datadir and the matching options (blender: half_res, testskip, white_bkgd; llff: factor,
-    spherify, llffhold, no_ndc); render_test swaps the render poses for the test poses like the reference."""
+    spherify, llffhold, no_ndc); render_test swaps the render poses for the test poses like the reference.
+    args.random_bkgd (no such flag in the reference's parser; default off): a blender set keeps its alpha, images [n,H,W,4] with
+    straight colours, for `train` to composite over a fresh colour per ray (Trainer(bkgd='random')); ValueError with white_bkgd."""
     K = None
     if args.dataset_type == 'llff':
         from .load_llff import load_llff_data
@@ -795,7 +896,10 @@ def load_dataset(args):
                                                                       getattr(args, 'testskip', 8))
         i_train, i_val, i_test = i_split
         near, far = 2., 6.
-        if args.white_bkgd:
+        if getattr(args, 'random_bkgd', False):
+            if args.white_bkgd:
+                raise ValueError('load_dataset: random_bkgd keeps the alpha channel for per-ray backgrounds; white_bkgd composites it away')
+        elif args.white_bkgd:
             images = images[..., :3] * images[..., -1:] + (1. - images[..., -1:])
         else:
             images = images[..., :3]
@@ -817,7 +921,8 @@ def train(images, poses, H, W, focal, args, near=2., far=6., device='cuda', log=
     """Epoch loop of run_nerf.py:train() (:337-546) on in-memory data: center-crop warm-up, per-epoch
     quadtree ray generation, fused steps with the on-device leaf-loss table, tree adjustment every
     `subdivide_every` epochs, checkpoints in the reference's file format.  images [n,H,W,3] (CPU or
-    GPU tensor), poses [n,3,4]."""
+    GPU tensor), poses [n,3,4].  args.random_bkgd: images [n,H,W,4] with straight colours (load_dataset); every step composites
+    prediction and target over a fresh colour per ray (Trainer(bkgd='random'), alpha taken at the rays' own pixels)."""
     dev = torch.device(device)
     K = np.array([[focal, 0, 0.5 * W], [0, focal, 0.5 * H], [0, 0, 1]])
     kw_train, kw_test, start_epoch, global_iter, grad_vars, optimizer = create_nerf(args, device=dev)
@@ -833,11 +938,26 @@ def train(images, poses, H, W, focal, args, near=2., far=6., device='cuda', log=
                       # marched training (needs occupancy_outside_occupied=False): steps from march_after on train the fine network alone
                       march=getattr(args, 'march', None), march_cap=getattr(args, 'march_cap', 128), march_after=getattr(args, 'march_after', 0),
                       occupancy_every=getattr(args, 'occupancy_every', 16), occupancy_warmup=getattr(args, 'occupancy_warmup', 256))
-    trainer = Trainer(kw_train, H, W, K, near, far, lrate=args.lrate, lrate_decay=args.lrate_decay, **occ_kw)
+    random_bkgd = bool(getattr(args, 'random_bkgd', False))
+    trainer = Trainer(kw_train, H, W, K, near, far, lrate=args.lrate, lrate_decay=args.lrate_decay, bkgd='random' if random_bkgd else None,
+                      **occ_kw)
     trainer.global_iter = global_iter
     if len(optimizer.state_dict()['state']) > 0:   # create_nerf restored a checkpoint (ours or the reference's)
         trainer.load_torch_optimizer(optimizer)
     images = torch.as_tensor(images, dtype=torch.float32)
+    alpha_img = None
+    if random_bkgd:      # the quadtree manager (and the leaf-error picks) see the straight colours; alpha travels beside them
+        if images.shape[-1] != 4:
+            raise ValueError('train: random_bkgd needs RGBA images [n,H,W,4] (load_dataset with args.random_bkgd)')
+        alpha_img = images[..., 3].contiguous().to(dev)
+        images = images[..., :3].contiguous()
+
+    def alpha_at(pix):
+        """alpha [N] at the pixels (image, row, col) of an epoch's rows, or None without random_bkgd."""
+        if alpha_img is None:
+            return None
+        p = pix.to(dev).long()
+        return alpha_img[p[:, 0], p[:, 1], p[:, 2]].contiguous()
     poses = torch.as_tensor(poses, dtype=torch.float32)[:, :3, :4]
     mgr = QuadTreeManager(H, W, K, images, poses, mseThres=0.0, max_depth=args.init_level, device=dev)
     # like the model, the subdivided trees of the checkpointed epoch are reloaded (run_nerf.py:338-345)
@@ -848,7 +968,7 @@ def train(images, poses, H, W, focal, args, near=2., far=6., device='cuda', log=
     rank, world = parallel.rank(), parallel.world_size()
     history = []
 
-    def run_batches(rays_o, rays_d, tgt, tags, decay, table, max_leaves, local_of=None):
+    def run_batches(rays_o, rays_d, tgt, tags, decay, table, max_leaves, local_of=None, alpha=None):
         """local_of = N: the tensors hold only THIS rank's rows of an epoch of N rows (gen_rays_device(shard=...)), batch after batch."""
         n_total = rays_o.shape[0] if local_of is None else local_of
         it = 0
@@ -865,7 +985,7 @@ def train(images, poses, H, W, focal, args, near=2., far=6., device='cuda', log=
             loss2, _ = trainer.step(rays_o[sl].contiguous(), rays_d[sl].contiguous(), tgt[sl].contiguous(),
                                     leaf_tag=None if tags is None else tags[sl].contiguous(),
                                     table=table, max_leaves=max_leaves, n_global=(b1 - b0) if world > 1 else None,
-                                    decay=decay)
+                                    decay=decay, alpha=None if alpha is None else alpha[sl].contiguous())
             it += 1
             if max_iters_per_epoch is not None and it >= max_iters_per_epoch:
                 break
@@ -883,7 +1003,7 @@ def train(images, poses, H, W, focal, args, near=2., far=6., device='cuda', log=
         pix = torch.cat([torch.cat([torch.full((randNum, 1), i, dtype=torch.int64), sel], 1)
                          for i in range(mgr.n_images)], 0)
         ro, rd, tgt = mgr.gather(pix)
-        loss2, it = run_batches(ro, rd, tgt, None, False, None, 0)
+        loss2, it = run_batches(ro, rd, tgt, None, False, None, 0, alpha=alpha_at(pix))
         log('warm-up: {} iters, fine/coarse mse {}'.format(it, loss2.tolist()))
 
     for epoch_id in range(start_epoch + 1, args.n_epoch + 1):
@@ -897,11 +1017,12 @@ def train(images, poses, H, W, focal, args, near=2., far=6., device='cuda', log=
         sharded_gen = world > 1 and not compat_rng and dev.type == 'cuda'
         ro, rd, tgt = mgr.gen_rays_v3_multiThread(down_scale=1, prob=False, randSamp_proc=args.randSamp_perc,
                                                   last_epoch=last, compat_rng=compat_rng,
-                                                  shard=(rank, world, N_rand) if sharded_gen else None)
+                                                  shard=(rank, world, N_rand) if sharded_gen else None, want_pix=random_bkgd)
         tags = mgr.result_leaf_tag
         max_leaves = mgr.max_leaves()
         table = torch.zeros(mgr.n_images * max_leaves, device=dev, dtype=torch.int32)
-        loss2, it = run_batches(ro, rd, tgt, tags, True, table, max_leaves, local_of=mgr.epoch_rows if sharded_gen else None)
+        loss2, it = run_batches(ro, rd, tgt, tags, True, table, max_leaves, local_of=mgr.epoch_rows if sharded_gen else None,
+                                alpha=alpha_at(mgr.result_pix) if random_bkgd else None)
         psnr = mse2psnr(loss2[:1].cpu())
         history.append((epoch_id, it, float(loss2[0]), float(psnr[0]), time.time() - t0))
         log('epoch {}: {} iters, fine mse {:.5f} psnr {:.2f}, {:.1f}s'.format(*history[-1]) +

@@ -596,13 +596,14 @@ class QuadTreeManager:
         return ro, rd, rgb
 
     def gen_rays_v3_multiThread(self, down_scale=16, prob=True, randSamp_proc=0.95, debug=False, last_epoch=False,
-                                compat_rng=True, shard=None):
+                                compat_rng=True, shard=None, want_pix=False):
         """tree.py:377-428.  compat_rng=True draws pixels with torch's global CPU generator in the
         reference's exact call order (per image, per leaf: randint rows, randint cols; then one
         randperm), so a seeded run selects identical pixels; compat_rng=False generates the whole epoch
-        in one device launch (gen_rays_device: same distribution).  Returns (origins, dirs, rgb) on the device."""
+        in one device launch (gen_rays_device: same distribution).  Returns (origins, dirs, rgb) on the device.  want_pix: the device
+        generator leaves the rows' pixels (image, row, col) in result_pix too, as the host picks always do."""
         if not compat_rng and self.device.type == 'cuda':
-            return self.gen_rays_device(down_scale, last_epoch, prob=prob, rand=randSamp_proc, shard=shard)
+            return self.gen_rays_device(down_scale, last_epoch, prob=prob, rand=randSamp_proc, shard=shard, want_pix=want_pix)
         if shard is not None:
             raise ValueError('shard= needs the device generator (compat_rng=False on a GPU): the reference-order host picks exist as a whole epoch only')
         pix = self.gen_pixels(down_scale, last_epoch, compat_rng, prob=prob, rand=randSamp_proc)

@@ -826,6 +826,47 @@ int fastnerf_occ_march_jitter(const fn_occ_grid* grid, const fn_occ_cascade* cas
 int fastnerf_march_mask(int64_t n, const uint8_t* overflow, float* g_rgb, fn_stream_t stream);
 int fastnerf_train_step_march(const fn_step_args* args, const fn_step_march* march, int phases, fn_stream_t stream);
 
+/* ---- per-ray background colours (csrc/bkgd.hip, render.cpp) --------------------------------------------------------------------------
+ * With ONE fixed background (white_bkgd) a pixel of that colour is explained as well by fog of that colour as by empty space.  Here
+ * every ray r gets its own colour b_r behind both the prediction and an RGBA target, fresh every step: density where the image is
+ * transparent then always costs.  The compositing runs with white_bkgd = 0 and knows nothing of it:
+ *   fastnerf_bkgd_blend   b_r = bkgd[r], or with bkgd == NULL (u01(w0), u01(w1), u01(w2)) of Philox block r (counter (r lo, r hi, 'bkgd' =
+ *                         0x626b6764, 0), key seed) -- exactly one of bkgd != NULL and seed != 0, -1 otherwise.  In place, for the image
+ *                         pass (rgb1, acc1) and, when given, the coarse pass (rgb0, acc0):
+ *                           rgb_k[r][c] = fadd(rgb_k[r][c], fmul(fsub(1, acc_k[r]), b_r[c]))
+ *                           target_out[r][c] = alpha ? fadd(fmul(target[r][c], alpha[r]), fmul(fsub(1, alpha[r]), b_r[c])) : target[r][c]
+ *                           bkgd_used[r] = b_r
+ *                         With b = 1 the colour line has the bits of the white branch of fastnerf_raw2outputs_fwd.
+ *   fastnerf_bkgd_grad    x = fadd(fadd(fmul(g0, b0), fmul(g1, b1)), fmul(g2, b2)) of g_rgb_k[r] and bkgd_used[r];
+ *                         g_acc_k[r] = add_k ? fsub(add_k[r], x) : -x      (add_k: another term's d(loss)/d(acc), e.g. the opacity term's;
+ *                         add_k == g_acc_k is allowed).  The row goes to fastnerf_raw2outputs_bwd_full beside g_rgb, white_bkgd = 0.
+ * One thread per ray, no atomics: bit-identical from call to call.  n == 0 returns 0.
+ *   fastnerf_train_step_bkgd / fastnerf_train_step_march_bkgd   fastnerf_train_step_aux / fastnerf_train_step_march with a background:
+ *     FN_STEP_FORWARD  the forward as before, fastnerf_bkgd_blend(bkgd, seed, alpha, ...) on its colour maps and the target into target_ws,
+ *                      fastnerf_mse_leafmax on the blended maps against target_ws (the leaf-error table sees what the loss sees),
+ *                      fastnerf_aux_loss when a term is on, (marched: fastnerf_march_mask, and only then) fastnerf_bkgd_grad into g_acc1 /
+ *                      g_acc0, with add_k = the opacity term's rows when that term is on.  An overflowed ray of a marched row so gets
+ *                      g_acc = +-0.
+ *     backward phases  g_acc1 / g_acc0 go to the full-gradient compositing backward of their pass beside the colour gradient.
+ *   fn_step_bkgd is given in EVERY phase call, like fn_step_aux.  bk == NULL: the entry point without _bkgd, launch for launch.
+ *   -1 before anything is enqueued, beside the refusals of those entry points: args->white_bkgd != 0 together with bk, a NULL member of
+ *   bk that the phases need (bkgd_used, target_ws, g_acc1 and with two passes g_acc0; forward: exactly one of bkgd / seed != 0). */
+typedef struct fn_step_bkgd {
+  const float* bkgd;                /* [n,3] or NULL: drawn from seed */
+  uint64_t seed;
+  const float* alpha;               /* [n] or NULL */
+  float *bkgd_used, *target_ws;     /* [n,3] each */
+  float *g_acc1, *g_acc0;           /* [n] each; g_acc0 unused with one pass */
+} fn_step_bkgd;
+int64_t fastnerf_step_bkgd_size(void);              /* sizeof(fn_step_bkgd): binding sanity check */
+int fastnerf_bkgd_blend(int64_t n, const float* bkgd, uint64_t seed, const float* alpha, const float* acc1, const float* acc0,
+                        float* rgb1, float* rgb0, const float* target, float* target_out, float* bkgd_used, fn_stream_t stream);
+int fastnerf_bkgd_grad(int64_t n, const float* bkgd_used, const float* g_rgb1, const float* g_rgb0, const float* add1, const float* add0,
+                       float* g_acc1, float* g_acc0, fn_stream_t stream);
+int fastnerf_train_step_bkgd(const fn_step_args* args, const fn_step_aux* aux, const fn_step_bkgd* bk, int phases, fn_stream_t stream);
+int fastnerf_train_step_march_bkgd(const fn_step_args* args, const fn_step_march* march, const fn_step_bkgd* bk, int phases,
+                                   fn_stream_t stream);
+
 /* ---- density gradient: d(sigma)/d(x) through the fused MLP (csrc/sigma_grad.hip) -------------------------------------------------
  * sigma[n,S] (may be NULL) = raw[..., 3] of the forward of `math_mode` (0 exact fp32, 1 split-bf16 "bf16x3", 2 "bf16x6") at the
  * points o + d*z of fastnerf_mlp_fwd, and grad[n,S,3] = its gradient with respect to the point.  Both are taken BEFORE the ReLU
