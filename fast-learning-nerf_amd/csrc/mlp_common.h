@@ -277,17 +277,48 @@ template <int CT> struct WRegs { uint4 b0[CT][3]; };   // k-step 0 (k-step 1 is 
 template <bool ON, int NT> struct WRegsSel { typedef NoChain type; };
 template <int NT> struct WRegsSel<true, NT> { typedef WRegs<2 * NT> type; };
 template <bool L16, int NT> using WRegsT = typename WRegsSel<L16, NT>::type;
+// ---- addressing of the bf16x6 k-loops: no address arithmetic beside the MFMAs (VALU time adds to matrix time: profiles/kloop_addr.md) ----
+//   LDS     32-bit byte addresses kept in registers for a whole segment, everything that varies with the row tile in the instruction's offset;
+//   weights one wave-uniform 64-bit base (scalar registers, advanced with scalar adds) + a 32-bit per-lane offset + the piece as the
+//           instruction's offset: the `saddr` form of global_load, explicit global pointers so that the selector can use it;
+//   saved rows likewise: scalar base + 32-bit per-lane offset (gemm_seg16, last k-step).
+typedef const __attribute__((address_space(3))) f32x4v* lds_f4p;
+typedef const __attribute__((address_space(1))) char* gbl_cp;
+__device__ __forceinline__ unsigned lds_addr(const float* p) {
+  return (unsigned)reinterpret_cast<size_t>((const __attribute__((address_space(3))) float*)p);
+}
+__device__ __forceinline__ gbl_cp uniform_gbl(const void* p) {   // a wave-uniform global pointer, as a scalar pair
+  const size_t v = reinterpret_cast<size_t>(p);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+  return (gbl_cp)(((size_t)hi << 32) | lo);
+}
+__device__ __forceinline__ float4 lds_read16(unsigned byte_addr) {
+  const f32x4v t = *reinterpret_cast<lds_f4p>(byte_addr);
+  return make_float4(t.x, t.y, t.z, t.w);
+}
+__device__ __forceinline__ uint4 gbl_read16(gbl_cp base, unsigned lane_off, int imm) {   // base wave-uniform
+  const u32x4v t = *reinterpret_cast<const __attribute__((address_space(1))) u32x4v*>(base + lane_off + imm);
+  return make_uint4(t.x, t.y, t.z, t.w);
+}
+__device__ __forceinline__ void gbl_store16_nt(__attribute__((address_space(1))) char* base, unsigned lane_off, const float4& v) {
+  if constexpr (ABL_NOSTORE) { if (v.x == 1.2345e-30f) *reinterpret_cast<__attribute__((address_space(1))) float*>(base + lane_off) = v.y; return; }
+  f32x4v t = {v.x, v.y, v.z, v.w};
+  __builtin_nontemporal_store(t, reinterpret_cast<__attribute__((address_space(1))) f32x4v*>(base + lane_off));
+}
+constexpr int X6_KSTEP_BYTES = 3 * 64 * 16, X6_PIECE_BYTES = 64 * 16;   // a column tile's k-step in the packing: three pieces of 64 lanes x 16 bytes
 // arguments as gemm<>'s: KS, b_ks0, nks in the 8-wide k units of the call sites, nt0 = the wave's first 32-column tile
 template <int CT>
 __device__ __forceinline__ void wprefetch(WRegs<CT>& w, const void* Bw, int KS, int b_ks0, int /*nks*/, int nt0, int lane) {
   const uint4* Bp = reinterpret_cast<const uint4*>(Bw);
+  const gbl_cp wb = uniform_gbl(Bp + ((int64_t)(nt0 * 2) * (KS / 4) + b_ks0 / 4) * 192);
   unsigned blane = (unsigned)lane * 16u;
   asm volatile("" : "+v"(blane));
 #pragma unroll
   for (int ct = 0; ct < CT; ++ct) {
-    const char* p = reinterpret_cast<const char*>(Bp + ((int64_t)(nt0 * 2 + ct) * (KS / 4) + b_ks0 / 4) * 192);
+    gbl_cp wc = wb + ct * ((KS / 4) * X6_KSTEP_BYTES);
+    asm volatile("" : "+s"(wc));
 #pragma unroll
-    for (int pl = 0; pl < X6_NPL; ++pl) w.b0[ct][pl] = *reinterpret_cast<const uint4*>((p + (pl * 64) * 16) + blane);
+    for (int pl = 0; pl < X6_NPL; ++pl) w.b0[ct][pl] = gbl_read16(wc, blane, pl * X6_PIECE_BYTES);
   }
 }
 __device__ __forceinline__ void wprefetch(NoChain&, const void*, int, int, int, int, int) {}
@@ -301,28 +332,44 @@ __device__ __forceinline__ void gemm_seg16(ACC& acc, const float* __restrict__ A
   const int r16 = lane & 15, kc = lane >> 4;
   constexpr int RS = AMODE == 0 ? 256 : (AMODE == 1 ? 64 : 32);
   const int m0 = wm * 64 + r16;
-  // row tile mt: row m0 + 16 mt; the swizzle term of H / E rows (m & 15) does not depend on mt
-  const float* arow0 = As + m0 * RS;
-  auto load_raw = [&](float4 (&a)[2], int mt, int ks) {
-    const int m = m0 + 16 * mt;
-    const int ax = (AMODE == 2) ? ((m >> 1) & 7) : (m & 15);
+  // Raw fragments.  Row tile mt is row m0 + 16 mt: the swizzle term of a row (H / E: m & 15, X2: (m >> 1) & 7) does not depend on mt, and only
+  // the low four bits of the slot index (s * 8 + kc * 2 + j) ^ ax take part in the XOR (ax < 16; s = a_ks0 + ks, and a_ks0 is even: 0 at
+  // every call site).  So four byte addresses per lane -- parity s & 1 x j, row base folded in -- are formed once per segment; the row tile
+  // is the instruction's offset (<= 48 KiB) and the pair of k-steps (s >> 1) * 256 bytes is added to the two registers of a parity once per
+  // two k-steps.
+  const int ax = (AMODE == 2) ? ((m0 >> 1) & 7) : (m0 & 15);
+  unsigned ae[2], ao[2];   // even / odd k-step, j = 0 / 1
+  {
+    const unsigned arow0 = lds_addr(As) + (unsigned)(m0 * RS * 4 + (a_ks0 >> 1) * 256);
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
-      a[j] = *reinterpret_cast<const float4*>(arow0 + mt * (16 * RS) + ((((a_ks0 + ks) * 8 + kc * 2 + j) ^ ax) << 2));
+    for (int j = 0; j < 2; ++j) {
+      ae[j] = arow0 + (unsigned)(((kc * 2 + j) ^ ax) << 4);
+      ao[j] = arow0 + (unsigned)(((8 + kc * 2 + j) ^ ax) << 4);
+      asm volatile("" : "+v"(ae[j]), "+v"(ao[j]));
+    }
+  }
+  auto load_raw = [&](float4 (&a)[2], int mt, const unsigned (&ad)[2]) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) a[j] = lds_read16(ad[j] + (unsigned)(mt * (16 * RS * 4)));
   };
-  const char* bptr[CT];   // (scalar-base weight loads: see gemm_seg6)
-#pragma unroll
-  for (int ct = 0; ct < CT; ++ct) bptr[ct] = reinterpret_cast<const char*>(Bp + ((int64_t)(nt0 * 2 + ct) * KS + b_ks0) * 192);
+  // Weights: the wave's first column tile at k-step b_ks0 is the scalar base; k-step and column tile are scalar adds to it, the piece is the
+  // instruction's offset, a lane adds lane * 16
+  const gbl_cp wb = uniform_gbl(Bp + ((int64_t)(nt0 * 2) * KS + b_ks0) * 192);
+  const int wstride = KS * X6_KSTEP_BYTES;   // column tile to column tile
   unsigned blane = (unsigned)lane * 16u;
   auto load_b = [&](uint4 (&b)[CT][3], int ks) {
     asm volatile("" : "+v"(blane));
+    const gbl_cp wk = wb + ks * X6_KSTEP_BYTES;
 #pragma unroll
-    for (int ct = 0; ct < CT; ++ct)
+    for (int ct = 0; ct < CT; ++ct) {
+      gbl_cp wc = wk + ct * wstride;
+      asm volatile("" : "+s"(wc));   // (a scalar pair: otherwise base + lane is formed once and the column tile added per lane, in 64 bits)
 #pragma unroll
       for (int pl = 0; pl < X6_NPL; ++pl) {
         if (pl >= ABL_WPIECES) { b[ct][pl] = b[ct][0]; continue; }
-        b[ct][pl] = *reinterpret_cast<const uint4*>((bptr[ct] + (ks * 192 + pl * 64) * 16) + blane);
+        b[ct][pl] = gbl_read16(wc, blane, pl * X6_PIECE_BYTES);
       }
+    }
   };
   const int klast = nks - 1;
   float4 r0[2], r1[2];          // raw fragments of units u + 1 (being split) and u + 2 (in flight)
@@ -334,42 +381,72 @@ __device__ __forceinline__ void gemm_seg16(ACC& acc, const float* __restrict__ A
   uint4 (&b0)[CT][3] = wr_.b0;
   uint4 b1[CT][3];
   if constexpr (!PRE) load_b(b0, 0);
-  load_raw(r0, 0, 0);
-  load_raw(r1, 1, 0);
+  load_raw(r0, 0, ae);
+  load_raw(r1, 1, ae);
   load_b(b1, klast > 0 ? 1 : 0);
 #pragma unroll
   for (int q = 0; q < 4; ++q) split_pair16(r0, pa, q);     // unit 0 is split up front; its registers then take unit 2
-  load_raw(r0, 2, 0);
+  load_raw(r0, 2, ae);
   __builtin_amdgcn_s_setprio(1);
-  // unit u = 4 ks + mt:   pieces  pa (u even) / pb (u odd);   splits raw r1 (u even) / r0 (u odd) = unit u + 1;   refills it with unit u + 3
-  // (clamped at the segment's last k-step: re-reads, never used)
-  auto kstep = [&](const uint4 (&b)[CT][3], int ks, auto par) __attribute__((always_inline)) {
+  // unit u = 4 ks + mt:   pieces  pa (u even) / pb (u odd);   splits raw r1 (u even) / r0 (u odd) = unit u + 1;   refills it with unit u + 3:
+  // row tile 3 of this k-step (addresses `cur`), then row tiles 0..2 of the next one (`nxt`; behind the segment's last k-step: re-reads of
+  // a k-step of the segment, never used)
+  auto kstep = [&](const uint4 (&b)[CT][3], const unsigned (&cur)[2], const unsigned (&nxt)[2], auto par) __attribute__((always_inline)) {
     constexpr int S0 = 1 + 4 * decltype(par)::value;   // one sched_group_barrier pipeline per unit of the loop body
-    const int kn = ks + 1 < klast ? ks + 1 : klast;   // k-step of units u + 3 / u + 4 once they wrap
-    unit16<CT, 0, S0 + 0>(acc, pa, b, r1, pb, [&]() { load_raw(r1, 3, ks); });
-    unit16<CT, 1, S0 + 1>(acc, pb, b, r0, pa, [&]() { load_raw(r0, 0, kn); });
-    unit16<CT, 2, S0 + 2>(acc, pa, b, r1, pb, [&]() { load_raw(r1, 1, kn); });
-    unit16<CT, 3, S0 + 3>(acc, pb, b, r0, pa, [&]() { load_raw(r0, 2, kn); });
+    unit16<CT, 0, S0 + 0>(acc, pa, b, r1, pb, [&]() { load_raw(r1, 3, cur); });
+    unit16<CT, 1, S0 + 1>(acc, pb, b, r0, pa, [&]() { load_raw(r0, 0, nxt); });
+    unit16<CT, 2, S0 + 2>(acc, pa, b, r1, pb, [&]() { load_raw(r1, 1, nxt); });
+    unit16<CT, 3, S0 + 3>(acc, pb, b, r0, pa, [&]() { load_raw(r0, 2, nxt); });
+  };
+  // the next pair of k-steps: 16 slots further in the row; not behind the segment's last k-step (the re-reads stay inside the segment)
+  auto advance = [&](unsigned (&ad)[2], int ks_next) {
+    const unsigned step = ks_next <= klast ? 256u : 0u;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) ad[j] += step;
   };
   constexpr std::integral_constant<int, 0> EVEN{};
   constexpr std::integral_constant<int, 1> ODD{};
-  const bool saving = AMODE == 0 && save_dst != nullptr;
+  // a saved segment streams the tile's rows out beside its last k-step; a tile with fewer than TM valid rows -- at most the last one of a
+  // launch -- runs the plain loop and copies its valid rows out behind it (wave-uniform)
+  const bool saved = AMODE == 0 && save_dst != nullptr;
+  const bool saving = saved && save_valid == TM;
 #pragma unroll 1
   for (int ks = 0; ks + 2 <= nks - (saving ? 1 : 0); ks += 2) {
-    kstep(b0, ks, EVEN);
+    kstep(b0, ae, ao, EVEN);
     load_b(b0, ks + 2 < klast ? ks + 2 : klast);
-    kstep(b1, ks + 1, ODD);
+    advance(ae, ks + 2);
+    kstep(b1, ao, ae, ODD);
     load_b(b1, ks + 3 < klast ? ks + 3 : klast);
+    advance(ao, ks + 3);
   }
   if (!saving) {
-    if (nks & 1) kstep(b0, klast, EVEN);          // (single-step segments: the 32 extra encoding channels)
+    if (nks & 1) kstep(b0, ae, ae, EVEN);          // (single-step segments: the 32 extra encoding channels)
+    if (saved) {
+#pragma unroll 1
+      for (int m = wave; m < save_valid; m += NWAVES) {
+        const float4 v = *reinterpret_cast<const float4*>(As + m * 256 + lane * 4);
+        store_nt(save_dst + (unsigned)(m * 256 + ((lane ^ (m & 15)) << 2)), v);
+      }
+    }
   } else {
     // nks is even (8) for every saved segment: k-step nks - 2 as above, then the LAST k-step with the tile's rows streamed out between
-    // its MFMAs (every load of the segment has been issued; rows beyond the valid count are clamped: rewritten with the same bytes)
-    kstep(b0, nks - 2, EVEN);
+    // its MFMAs (every load of the segment has been issued).  Row m = (MT * 4 + r) * NWAVES + wave of the burst: m & 15 = 4 r + wave, so the
+    // swizzled slot of a lane takes four values per wave (sv), the LDS read is one register + m * 1024 as the instruction's offset, the
+    // store a scalar base + sv[r].
+    kstep(b0, ae, ao, EVEN);
     constexpr int PA[6] = X6_PA, PB[6] = X6_PB;
     constexpr int NPROD = X6_NPROD, ROWS = TM / NWAVES, NM = NPROD * CT;
-    const int last_row = save_valid - 1;
+    static_assert(ROWS == 16 && NWAVES == 4, "the burst's swizzle classes: four rows per unit, m & 15 = 4 r + wave");
+    unsigned rd0 = lds_addr(As) + (unsigned)(wave * 1024 + lane * 16);
+    __attribute__((address_space(1))) char* sb0 = const_cast<__attribute__((address_space(1))) char*>(uniform_gbl(save_dst)) + wave * 1024;
+    asm volatile("" : "+v"(rd0));   // (so that the rows stay offsets / scalar adds: `wave` is no compile-time value)
+    asm volatile("" : "+s"(sb0));
+    unsigned sv[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      sv[r] = (unsigned)((lane ^ (4 * r + wave)) << 4);
+      asm volatile("" : "+v"(sv[r]));
+    }
     auto last_unit = [&](auto mtc, const Pieces16& pc, float4 (&ar)[2], Pieces16& pn) __attribute__((always_inline)) {
       constexpr int MT = decltype(mtc)::value;
 #pragma unroll
@@ -384,15 +461,15 @@ __device__ __forceinline__ void gemm_seg16(ACC& acc, const float* __restrict__ A
           }
 #pragma unroll
           for (int r = (i * (ROWS / 4)) / NM; r < ((i + 1) * (ROWS / 4)) / NM; ++r) {
-            int m = (MT * (ROWS / 4) + r) * NWAVES + wave;
-            m = m < last_row ? m : last_row;
-            const float4 v = *reinterpret_cast<const float4*>(As + m * 256 + lane * 4);
-            store_nt(save_dst + (unsigned)(m * 256 + ((lane ^ (m & 15)) << 2)), v);
+            const float4 v = lds_read16(rd0 + (unsigned)((MT * 4 + r) * NWAVES * 1024));
+            __attribute__((address_space(1))) char* sb = sb0 + (MT * 4 + r) * NWAVES * 1024;
+            asm volatile("" : "+s"(sb));
+            gbl_store16_nt(sb, sv[r], v);
           }
         }
     };
     last_unit(std::integral_constant<int, 0>{}, pa, r1, pb);
-    load_raw(r1, 3, klast);
+    load_raw(r1, 3, ao);
     last_unit(std::integral_constant<int, 1>{}, pb, r0, pa);
     last_unit(std::integral_constant<int, 2>{}, pa, r1, pb);
     last_unit(std::integral_constant<int, 3>{}, pb, r0, pa);

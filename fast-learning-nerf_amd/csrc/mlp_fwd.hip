@@ -151,7 +151,9 @@ mlp_fwd_kernel(int64_t P, int S, const float* __restrict__ rays, const float* __
     constexpr int KS5 = (BG ? 96 + 256 : 64 + 256) / 8;
     // ---- L0 : pe -> 256 -----------------------------------------------------------------
     float bv2[L16 ? 4 : 2];
-    load_bias<2>(bv2, params + lay.LB[0], wn, lane);
+    int lane0 = lane;
+    if constexpr (L16) asm volatile("" : "+v"(lane0));   // per tile: hoisted out of the tile loop, layer 0's bias accumulators are spilled to scratch
+    load_bias<2>(bv2, params + lay.LB[0], wn, lane0);
     init_acc<2, FOLD>(acc, bv2);
     gemm<MM, 2, 1>(acc, Es, 0, 8, wblock<MM>(packed, lay.PF[0]), PEP / 8, 0, wn * 2, wm, lane, dbg);
     if (BG) {
