@@ -80,6 +80,7 @@ SIGNATURES = {
     'fastnerf_last_error': (C.c_char_p, []),
     'fastnerf_device_cus': (I, []),
     'fastnerf_x6_pair_launches': (L, []),
+    'fastnerf_side_rebuild_passes': (L, []),
     'fastnerf_gen_rays': (I, [I, I, F, F, F, F, P, P, P, P]),
     'fastnerf_gen_rays_pixels': (I, [L, P, P, F, F, F, F, P, P, P]),
     'fastnerf_ndc_rays': (I, [L, I, I, D, F, P, P, P, P, P]),

@@ -35,6 +35,16 @@ inline int64_t dw_job_base(int j, int ncu, int pe_pad) {
 // floats of a net's partial buffer on a part with `ncu` CUs, sized for the widest layout (both *_partial_floats exports)
 inline int64_t dw_partial_floats(int ncu) { return dw_job_base(12, ncu, 96) + (int64_t)HEAD_MAX_WG * 388; }
 
+// ---- the rebuilding view job (bf16x6, 64-channel encoding, plain backward; mlp_bwd_dw.hip) ------------------------------------
+// The view job of a pass can form dYv, the gradient at the view layer's pre-activation, on chip from (hv, draw, Wr) instead of reading what dX
+// stored: 512 bytes a point that are then neither written nor read.  A caller whose call lets nothing else read dact_yv (the fused step,
+// render.cpp) asks for it with a SideRb:
+#define FN_DX_NO_DYV_STORE 1        // mlp_bwd_dx_kernel `flags`: dact_yv is not written
+struct SideRb {
+  int no_store;          // dX shall not store dYv
+  int poison;            // FASTNERF_SIDE_REBUILD=nan: dact_yv is filled with NaNs before the backward's first kernel
+};
+
 #define DW_TRUNK_JOBS 7
 struct DwTrunk {
   const float* dY[DW_TRUNK_JOBS];

@@ -5,7 +5,7 @@
 #include <atomic>
 
 int fn_launch_dx(int mm, int grid, hipStream_t st, int64_t P, const float* draw, const float* act, const float* params, const float* packed_bwd,
-                 float* dact, const NetLayout& L, const int* live_idx, const int* live_cnt, float* headws);   // mlp_bwd_dx.hip
+                 float* dact, const NetLayout& L, const int* live_idx, const int* live_cnt, float* headws, int flags);   // mlp_bwd_dx.hip
 
 // =========================================================================================
 // backward: dW = dY^T X  (split over workgroups by point chunk, partials reduced afterwards)
@@ -184,17 +184,24 @@ mlp_bwd_dw_kernel(int64_t P, const float* __restrict__ dY, int ldy, const float*
 // multiply the positional encoding: it is read and split once); bias sums are taken over dY only.
 // wg / nwg: this workgroup's chunk of the k-steps and the number of chunks (mlp_bwd_dw6_kernel: blockIdx.x / gridDim.x; the trunk
 // launch below: blockIdx.x / a function of the point count)
-template <int WO, int WI, int TO, int TI, bool BIAS, bool RANK1, int CTI2 = 0, int CTO2 = 0>
+// RBV (the view job, no live list): the dY tiles are REBUILT in the splitting lane instead of read -- dYv = (drgb . Wr) [hv > 0], dX's own expression
+// (dyv_value, mlp_common.h: bit-identical to what dX stores).  `dY` points at hv (same shape as dYv), wave 0 stages draw as a whole float4 (DR
+// beside DA, the same lanes, the same loads one pair of k-steps ahead) and a lane keeps the three Wr values of its channel; dYv is neither
+// written (dX) nor read.  Bias column sums are taken over the rebuilt values.
+template <int WO, int WI, int TO, int TI, bool BIAS, bool RANK1, int CTI2 = 0, int CTO2 = 0, bool RBV = false>
 __device__ __forceinline__ void dw6_body(const int64_t P, const float* __restrict__ dY, const float* __restrict__ X,
                                          const float* __restrict__ draw, float* __restrict__ partial_w, float* __restrict__ partial_b,
                                          float* __restrict__ partial_r, const int* __restrict__ live_idx,
-                                         const float* __restrict__ X2, const float* __restrict__ dY2, const int wg, const int nwg) {
+                                         const float* __restrict__ X2, const float* __restrict__ dY2, const int wg, const int nwg,
+                                         const float* __restrict__ rb_wr = nullptr) {
   constexpr int NO = WO * TO * 32, KI = WI * TI * 32;
   constexpr int CTO = WO * TO, CTI = WI * TI, NTILE = CTO + CTI;
   constexpr int NW = WO * WI;
   constexpr int TPW = (NTILE + NW - 1) / NW;         // tiles a wave splits per k-step
   extern __shared__ __attribute__((aligned(16))) uint4 S6[];   // [2][tile][piece h | m | l][lane]
   float* const DA = reinterpret_cast<float*>(S6 + 2 * NTILE * 192);   // RANK1: dalpha of the 16 points of a k-step, [2][16]
+  float4* const DR = reinterpret_cast<float4*>(DA + 32);              // RBV: draw of the 16 points of a k-step, [2][16]
+  static_assert(!RBV || (RANK1 && CTO2 == 0), "the view job: draw is staged, one gradient tensor");
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -244,6 +251,18 @@ __device__ __forceinline__ void dw6_body(const int64_t P, const float* __restric
   const unsigned boffy = (unsigned)(half8 * NO1 + col) * 4u, boffy2 = (unsigned)(half8 * NO2 + col) * 4u,
                  boffx = (unsigned)(half8 * KI1 + col) * 4u, boffx2 = (unsigned)(half8 * KI2 + col) * 4u;   // byte offsets of row 0
   struct Raw { float v[TPW][8]; };
+  float wr0[TPW], wr1[TPW], wr2[TPW];   // RBV: the Wr column of the lane's dYv channel, per slot
+  if constexpr (RBV) {
+#pragma unroll
+    for (int k = 0; k < TPW; ++k) {
+      const int t = k * NW + wave;
+      if (tisy[k] && (NTILE % NW == 0 || t < NTILE)) {
+        wr0[k] = rb_wr[t * 32 + col]; wr1[k] = rb_wr[128 + t * 32 + col]; wr2[k] = rb_wr[256 + t * 32 + col];
+      } else {
+        wr0[k] = wr1[k] = wr2[k] = 0.f;
+      }
+    }
+  }
   auto ldb = [](const float* base, unsigned byte_off) __attribute__((always_inline)) -> float {   // uniform base + 32-bit offset
     return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
   };
@@ -307,6 +326,15 @@ __device__ __forceinline__ void dw6_body(const int64_t P, const float* __restric
         float v[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = r.v[k][e];
+        if constexpr (RBV) {
+          if (tisy[k]) {   // r holds hv
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+              const float4 d = DR[(st & 1) * 16 + half8 + e];
+              v[e] = dyv_value(v[e], d.x, d.y, d.z, wr0[k], wr1[k], wr2[k]);
+            }
+          }
+        }
         if constexpr (!decltype(whole)::value) {
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] = e < nv ? v[e] : 0.f;
@@ -366,14 +394,24 @@ __device__ __forceinline__ void dw6_body(const int64_t P, const float* __restric
     load_raw(r0, 0, ANY);
     load_raw(r1, 1, ANY);
     // RANK1, wave 0, lanes 0..15: dalpha of the k-steps 2, 4, ... / 3, 5, ... on their way to DA, and the points after them
-    float dr0 = 0.f, dr1 = 0.f;
+    // (RBV: the whole float4 -- .w to DA as before, all of it to DR for the lanes that rebuild dYv)
+    typedef typename std::conditional<RBV, float4, float>::type DrawT;
+    auto ld_draw = [&](int64_t ix) __attribute__((always_inline)) -> DrawT {
+      if constexpr (RBV) return *reinterpret_cast<const float4*>(draw + ix * 4);
+      else return draw[ix * 4 + 3];
+    };
+    auto st_draw = [&](int slot, const DrawT& d) __attribute__((always_inline)) {
+      if constexpr (RBV) { DA[slot] = d.w; DR[slot] = d; }
+      else DA[slot] = d;
+    };
+    DrawT dr0 = DrawT(), dr1 = DrawT();
     int64_t ix0 = 0, ix1 = 0;
     const bool da_lane = RANK1 && wave == 0 && lane < 16;
     if (da_lane) {
-      DA[lane] = draw[load_ix(0) * 4 + 3];
-      DA[16 + lane] = draw[load_ix(1) * 4 + 3];
-      dr0 = draw[load_ix(2) * 4 + 3];
-      dr1 = draw[load_ix(3) * 4 + 3];
+      st_draw(lane, ld_draw(load_ix(0)));
+      st_draw(16 + lane, ld_draw(load_ix(1)));
+      dr0 = ld_draw(load_ix(2));
+      dr1 = ld_draw(load_ix(3));
       ix0 = load_ix(4);
       ix1 = load_ix(5);
     }
@@ -386,13 +424,13 @@ __device__ __forceinline__ void dw6_body(const int64_t P, const float* __restric
     };
     auto pair = [&](int d, auto whole) __attribute__((always_inline)) {
       const int st = 2 * d;
-      if (da_lane) { DA[lane] = dr0; dr0 = draw[ix0 * 4 + 3]; ix0 = load_ix(st + 6); }
+      if (da_lane) { st_draw(lane, dr0); dr0 = ld_draw(ix0); ix0 = load_ix(st + 6); }
       multiply(0);
       split_store(r1, 1, st + 1, whole);
       mix(std::integral_constant<int, 1>{});
       load_raw(r1, st + 3, whole);
       publish();
-      if (da_lane) { DA[16 + lane] = dr1; dr1 = draw[ix1 * 4 + 3]; ix1 = load_ix(st + 7); }
+      if (da_lane) { st_draw(16 + lane, dr1); dr1 = ld_draw(ix1); ix1 = load_ix(st + 7); }
       multiply(1);
       split_store(r0, 0, st + 2, whole);
       mix(std::integral_constant<int, 2>{});
@@ -444,6 +482,16 @@ mlp_bwd_dw6_kernel(int64_t P, const float* __restrict__ dY, const float* __restr
   if (live_idx) P = (int64_t)__builtin_amdgcn_readfirstlane(*live_cnt);
   dw6_body<WO, WI, TO, TI, BIAS, RANK1, CTI2, CTO2>(P, dY, X, draw, partial_w, partial_b, partial_r, live_idx, X2, dY2, (int)blockIdx.x,
                                                     (int)gridDim.x);
+}
+
+// the rebuilding view job (dw6_body RBV): hv where dYv was, Wr of the net
+template <int WO, int WI, int TO, int TI, bool BIAS, bool RANK1, int CTI2>
+__global__ void __launch_bounds__(WO * WI * 64, WO * WI / 4)
+mlp_bwd_dw6_rbv_kernel(int64_t P, const float* __restrict__ hv, const float* __restrict__ X, const float* __restrict__ draw,
+                       float* __restrict__ partial_w, float* __restrict__ partial_b, float* __restrict__ partial_r,
+                       const float* __restrict__ X2, const float* __restrict__ wr) {
+  dw6_body<WO, WI, TO, TI, BIAS, RANK1, CTI2, 0, true>(P, hv, X, draw, partial_w, partial_b, partial_r, nullptr, X2, nullptr, (int)blockIdx.x,
+                                                       (int)gridDim.x, wr);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -710,6 +758,23 @@ static int launch_dw(int64_t P, const float* dY, int ldy, const float* X, int ld
   }
 }
 
+// the rebuilding view job: launch_dw's partial layout and grid
+template <int WO, int WI, int TO, int TI, bool BIAS, bool RANK1, int CTI2>
+static int launch_dw_rbv(int64_t P, const float* hv, const float* X, const float* draw, float* base, int nwg, hipStream_t st, const float* X2,
+                         float* pr_at, const float* wr) {
+  constexpr int NO = WO * TO * 32, KI = WI * TI * 32;
+  float* pw = base;
+  float* pb = base + (int64_t)nwg * NO * KI;
+  float* pr = pr_at ? pr_at : pb + (BIAS ? (int64_t)nwg * NO : 0);
+  constexpr int lds6 = 2 * (WO * TO + WI * TI) * 3 * 1024 + 128 + 512;   // + DR: [2][16] float4
+  auto kern = mlp_bwd_dw6_rbv_kernel<WO, WI, TO, TI, BIAS, RANK1, CTI2>;
+  static fn::DevOnce once;
+  if (int rc = fn::set_dyn_lds(reinterpret_cast<const void*>(kern), once, lds6)) return rc;
+  hipLaunchKernelGGL(kern, dim3(nwg), dim3(WO * WI * 64), lds6, st, P, hv, X, draw, pw, pb, pr, X2, wr);
+  FN_LAUNCH_CHECK();
+  return 0;
+}
+
 static void add_seg(RedTable& T, int64_t src, int64_t wg_stride, int nwg, int rows, int cols, int64_t dst, int ld,
                     int valid_cols, int dyn = 0, int sc_cols = 0, int64_t sc_dst = 0) {
   RedSeg& s = T.s[T.n++];
@@ -759,10 +824,24 @@ static float* head_workspace(int64_t ntiles, hipStream_t st) {
 }
 }  // namespace fn
 
+// ---------------------------------------------------------------------------------------------------------------------
+// FASTNERF_SIDE_REBUILD, read at every call like FASTNERF_HEAD_FROM_DX: unset / anything else -- a caller that can (render.cpp, the fused step in
+// bf16x6 on the plain backward) lets the view job rebuild dYv and stops dX's store of it;  0 -- the reading route, the store on;  nan -- the
+// rebuilding route with dact_yv filled with NaNs first: nobody reads it.
+// ---------------------------------------------------------------------------------------------------------------------
+static std::atomic<int64_t> g_rebuild_passes{0};
+namespace fn {
+int side_rebuild_mode(void) {   // 0: off, 1: on, 2: on + poison
+  const char* e = getenv("FASTNERF_SIDE_REBUILD");
+  if (e && e[0] == '0') return 0;
+  return (e && e[0] == 'n') ? 2 : 1;
+}
+}  // namespace fn
+
 template <int MM>
 static int bwd_launch_t(int kind, int64_t n, int S, const float* draw, const float* act, const float* params,
                       const float* packed_bwd, float* dact, float* partial, float* grads, const int* live_idx,
-                      const int* live_cnt, fn_stream_t stream, DwDeferred* defer = nullptr) {
+                      const int* live_cnt, fn_stream_t stream, DwDeferred* defer = nullptr, const SideRb* rb = nullptr) {
   constexpr int MW = MM;
   const NetLayout& L = layout_of(kind);
   const int PEP = L.pe_pad;
@@ -773,7 +852,16 @@ static int bwd_launch_t(int kind, int64_t n, int S, const float* draw, const flo
   int grid = ncu * WG_PER_CU;
   if (ntiles < grid) grid = (int)ntiles;
   float* const headws = fn::head_workspace(ntiles, st);   // nullptr: the rgb-head / alpha-bias gradients take their own pass below
-  if (int rc_dx = fn_launch_dx(MM, grid, st, P, draw, act, params, packed_bwd, dact, L, live_idx, live_cnt, headws)) return rc_dx;
+  // the rebuilding view job (dw6_body RBV): bf16x6, the 64-channel encoding, no list
+  if (rb && (MM != MM_X6 || PEP != 64 || live_idx)) {
+    fn::set_error("mlp_bwd: the rebuilding view job needs bf16x6, the 64-channel encoding and no live list");
+    return -1;
+  }
+  if (rb) g_rebuild_passes.fetch_add(1, std::memory_order_relaxed);
+  if (rb && rb->poison) (void)hipMemsetAsync(dact + dact_yv(P), 0xFF, sizeof(float) * (size_t)P * 128, st);
+  if (int rc_dx = fn_launch_dx(MM, grid, st, P, draw, act, params, packed_bwd, dact, L, live_idx, live_cnt, headws,
+                               (rb && rb->no_store) ? FN_DX_NO_DYV_STORE : 0))
+    return rc_dx;
 
   // ---- dW jobs: every job writes per-chunk partials into its own region ------------------
   // (grids and chunk counts are functions of the point count alone -- one workgroup per CU and a fixed head-gradient grid for the jobs with
@@ -852,8 +940,11 @@ static int bwd_launch_t(int kind, int64_t n, int S, const float* draw, const flo
   if constexpr (MW == MM_X6) {
     // one job for both inputs of the view layer (h7 [P,256] | encoded direction [P,32]): dYv is read and split once; 12 waves,
     // partials [128][288] + bias [128] across the (adjacent) regions of jobs 10 and 11
-    if ((rc = launch_dw<4, 3, 1, 3, true, true, MW, 1, 0>(P, dact + dact_yv(P), 128, act + act_h(P, PEP, 7), 256, draw, region(10), nwg, st,
-                                                    live_idx, live_cnt, act + act_vpe(P, PEP), nullptr, pr_view))) return rc;
+    if (rb) rc = launch_dw_rbv<4, 3, 1, 3, true, true, 1>(P, act + act_hv(P, PEP), act + act_h(P, PEP, 7), draw, region(10), nwg, st, act + act_vpe(P, PEP),
+                                                          pr_view, params + L.RW);
+    else rc = launch_dw<4, 3, 1, 3, true, true, MW, 1, 0>(P, dact + dact_yv(P), 128, act + act_h(P, PEP, 7), 256, draw, region(10), nwg, st,
+                                                    live_idx, live_cnt, act + act_vpe(P, PEP), nullptr, pr_view);
+    if (rc) return rc;
     const int64_t b10 = dw_job_base(10, ncu, PEP);
     add_seg(T, b10, 128 * 288, nwg, 128, 288, L.VW, 283, 283, 0, 256, g_off);
     add_seg(T, b10 + (int64_t)nwg * 128 * 288, 128, nwg, 1, 128, L.VB, 128, 128);
@@ -918,11 +1009,19 @@ bool x6_pair_workspace(int64_t P_coarse, fn_stream_t stream, float** dact2, floa
 }
 
 // everything of fastnerf_mlp_x6_bwd but the trunk launch, the reduction and the unfold, which it records in *d (the caller's, one per pass)
+// rb: NULL, or the rebuilding view job (dw_pair.h SideRb)
 int x6_pair_pass(DwDeferred* d, int64_t n, int S, const float* draw, const float* act, const float* params, const float* packed_bwd,
-                 float* dact, float* partial, float* grads, fn_stream_t stream) {
+                 float* dact, float* partial, float* grads, fn_stream_t stream, const SideRb* rb) {
   FN_CHECK_ARG(d && n > 0 && S >= 1, "d != NULL, n>0, S>=1");
   FN_CHECK_ARG(draw && act && params && packed_bwd && dact && partial && grads, "null pointer");
-  return bwd_launch_t<MM_X6>(0, n, S, draw, act, params, packed_bwd, dact, partial, grads, nullptr, nullptr, stream, d);
+  return bwd_launch_t<MM_X6>(0, n, S, draw, act, params, packed_bwd, dact, partial, grads, nullptr, nullptr, stream, d, rb);
+}
+// fastnerf_mlp_x6_bwd(kind 0) with the rebuilding view job: a whole pass, trunk launch, reduction and unfold included
+int x6_bwd_rebuild(int64_t n, int S, const float* draw, const float* act, const float* params, const float* packed_bwd, float* dact,
+                   float* partial, float* grads, fn_stream_t stream, const SideRb* rb) {
+  FN_CHECK_ARG(n > 0 && S >= 1 && rb, "n>0, S>=1, rb != NULL");
+  FN_CHECK_ARG(draw && act && params && packed_bwd && dact && partial && grads, "null pointer");
+  return bwd_launch_t<MM_X6>(0, n, S, draw, act, params, packed_bwd, dact, partial, grads, nullptr, nullptr, stream, nullptr, rb);
 }
 
 // ONE trunk launch over both passes, then each net's reduction and unfold
@@ -949,6 +1048,8 @@ int x6_pair_finish(const DwDeferred* fine, const DwDeferred* coarse, fn_stream_t
 }  // namespace fn
 // paired trunk launches this process has enqueued: tells a caller (and tests/test_gpu_trunk_pair.py) which route its backward took
 extern "C" int64_t fastnerf_x6_pair_launches(void) { return fn::g_pair_launches.load(std::memory_order_relaxed); }
+// backward passes with a rebuilding view job this process has enqueued (tests/test_gpu_side_rebuild.py)
+extern "C" int64_t fastnerf_side_rebuild_passes(void) { return g_rebuild_passes.load(std::memory_order_relaxed); }
 
 static int bwd_launch(int kind, int64_t n, int S, const float* draw, const float* act, const float* params,
                       const float* packed_bwd, float* dact, float* partial, float* grads, const int* live_idx,

@@ -1,6 +1,7 @@
 // mlp_bwd_dx.hip -- the dY chain of the backward pass: one persistent kernel walks the layers in reverse with transposed packed weights and
 // leaves every layer's pre-activation gradient in HBM for the dW jobs (mlp_bwd_dw.hip launches it through fn_launch_dx).
 #include "mlp_common.h"
+#include "dw_pair.h"   // FN_DX_NO_DYV_STORE
 
 // =========================================================================================
 // backward: dX chain
@@ -99,7 +100,7 @@ __global__ void __launch_bounds__(NTHR, 2 * NTHR / 512 * WG_PER_CU)
 mlp_bwd_dx_kernel(int64_t P, const float* __restrict__ draw, const float* __restrict__ act,
                   const float* __restrict__ params, const float* __restrict__ packed_t, float* __restrict__ dact,
                   NetLayout lay, unsigned* __restrict__ sched, const int* __restrict__ live_idx,
-                  const int* __restrict__ live_cnt, float* __restrict__ headws) {
+                  const int* __restrict__ live_cnt, float* __restrict__ headws, int flags) {
   const int64_t PL = P;   // (live-list mode: see the forward kernel)
   if (live_idx) P = (int64_t)__builtin_amdgcn_readfirstlane(*live_cnt);
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -122,6 +123,7 @@ mlp_bwd_dx_kernel(int64_t P, const float* __restrict__ draw, const float* __rest
     {
       const int pm = tid >> 2, pq = tid & 3;
       const bool ok = pm < valid;
+      const bool keep = ok && !(flags & FN_DX_NO_DYV_STORE);   // (the view job rebuilds dYv from hv, draw and Wr: dw_pair.h)
       const int64_t pp = ok ? p0 + pm : P - 1;
       const float4 dr = *reinterpret_cast<const float4*>(draw + (live_idx ? (int64_t)live_idx[pp] : pp) * 4);
       if (pq == 0) Es[pm] = ok ? dr.w : 0.f;
@@ -138,13 +140,13 @@ mlp_bwd_dx_kernel(int64_t P, const float* __restrict__ draw, const float* __rest
         const float4 w1 = *reinterpret_cast<const float4*>(wr + 128 + k);
         const float4 w2 = *reinterpret_cast<const float4*>(wr + 256 + k);
         float4 o;
-        o.x = (h.x > 0.f) ? fmaf(dr.z, w2.x, fmaf(dr.y, w1.x, dr.x * w0.x)) : 0.f;
-        o.y = (h.y > 0.f) ? fmaf(dr.z, w2.y, fmaf(dr.y, w1.y, dr.x * w0.y)) : 0.f;
-        o.z = (h.z > 0.f) ? fmaf(dr.z, w2.z, fmaf(dr.y, w1.z, dr.x * w0.z)) : 0.f;
-        o.w = (h.w > 0.f) ? fmaf(dr.z, w2.w, fmaf(dr.y, w1.w, dr.x * w0.w)) : 0.f;
+        o.x = dyv_value(h.x, dr.x, dr.y, dr.z, w0.x, w1.x, w2.x);
+        o.y = dyv_value(h.y, dr.x, dr.y, dr.z, w0.y, w1.y, w2.y);
+        o.z = dyv_value(h.z, dr.x, dr.y, dr.z, w0.z, w1.z, w2.z);
+        o.w = dyv_value(h.w, dr.x, dr.y, dr.z, w0.w, w1.w, w2.w);
         if (!ok) o = make_float4(0.f, 0.f, 0.f, 0.f);
         *reinterpret_cast<float4*>(Hs + pm * 256 + ((((k >> 2) ^ (pm & 15))) << 2)) = o;
-        if (ok) store_nt(dyv + k, o);
+        if (keep) store_nt(dyv + k, o);
         // hv itself into the half of H that phase A leaves free (columns 128 + k, same swizzle): the head gradients below
         *reinterpret_cast<float4*>(Hs + pm * 256 + ((32 + ((k >> 2) ^ (pm & 15))) << 2)) = ok ? h : make_float4(0.f, 0.f, 0.f, 0.f);
       }
@@ -235,20 +237,21 @@ mlp_bwd_dx_kernel(int64_t P, const float* __restrict__ draw, const float* __rest
 
 template <int MM>
 static int launch_dx_t(int grid, hipStream_t st, int64_t P, const float* draw, const float* act, const float* params, const float* packed_bwd,
-                       float* dact, const NetLayout& L, const int* live_idx, const int* live_cnt, float* headws) {
+                       float* dact, const NetLayout& L, const int* live_idx, const int* live_cnt, float* headws, int flags) {
   static fn::DevOnce once;
   if (int rc = fn::set_dyn_lds(reinterpret_cast<const void*>(&mlp_bwd_dx_kernel<MM>), once, LDS_BYTES)) return rc;
   unsigned* sched = b_sched_pair();
   FN_CHECK_ARG(sched != nullptr, "scheduler counters (hipMalloc failed?)");
-  hipLaunchKernelGGL(mlp_bwd_dx_kernel<MM>, dim3(grid), dim3(NTHR), LDS_BYTES, st, P, draw, act, params, packed_bwd, dact, L, sched, live_idx, live_cnt, headws);
+  hipLaunchKernelGGL(mlp_bwd_dx_kernel<MM>, dim3(grid), dim3(NTHR), LDS_BYTES, st, P, draw, act, params, packed_bwd, dact, L, sched, live_idx, live_cnt, headws, flags);
   FN_LAUNCH_CHECK();
   return 0;
 }
 // headws: room for [ceil(P / TM)][388] per-tile rgb-head / alpha-bias partials (P the capacity in live-list mode), or nullptr: not formed
+// flags: 0, or FN_DX_NO_DYV_STORE
 int fn_launch_dx(int mm, int grid, hipStream_t st, int64_t P, const float* draw, const float* act, const float* params, const float* packed_bwd,
-                 float* dact, const NetLayout& L, const int* live_idx, const int* live_cnt, float* headws) {
-  return mm == MM_X6 ? launch_dx_t<MM_X6>(grid, st, P, draw, act, params, packed_bwd, dact, L, live_idx, live_cnt, headws)
-                     : launch_dx_t<MM_F32>(grid, st, P, draw, act, params, packed_bwd, dact, L, live_idx, live_cnt, headws);
+                 float* dact, const NetLayout& L, const int* live_idx, const int* live_cnt, float* headws, int flags) {
+  return mm == MM_X6 ? launch_dx_t<MM_X6>(grid, st, P, draw, act, params, packed_bwd, dact, L, live_idx, live_cnt, headws, flags)
+                     : launch_dx_t<MM_F32>(grid, st, P, draw, act, params, packed_bwd, dact, L, live_idx, live_cnt, headws, flags);
 }
 // The chain alone, on the grid the backward entry points give it (mlp_bwd_dw.hip, bwd_launch_t): for a caller that wants the
 // pre-activation gradients and no dW (sigma_grad.hip).
@@ -257,5 +260,5 @@ int fn_launch_dx_alone(int mm, int kind, int64_t P, const float* draw, const flo
   const int64_t ntiles = (P + TM - 1) / TM;
   int grid = fn::device_cus() * WG_PER_CU;
   if (ntiles < grid) grid = (int)ntiles;
-  return fn_launch_dx(mm, grid, st, P, draw, act, params, packed_bwd, dact, layout_of(kind), nullptr, nullptr, nullptr);
+  return fn_launch_dx(mm, grid, st, P, draw, act, params, packed_bwd, dact, layout_of(kind), nullptr, nullptr, nullptr, 0);
 }

@@ -96,6 +96,11 @@ __device__ __forceinline__ void split3_pair(float x0, float x1, unsigned& h, uns
   m = cvt_pk_bf16(r0, r1);
   l = cvt_pk_bf16(r0 - __uint_as_float(m << 16), r1 - __uint_as_float(m & 0xffff0000u));
 }
+// the gradient at the view layer's pre-activation (dX phase A writes it, the view job rebuilds it): (drgb . Wr[:, c]) [hv > 0]
+__device__ __forceinline__ float dyv_value(float h, float dx, float dy, float dz, float w0, float w1, float w2) {
+  return (h > 0.f) ? fmaf(dz, w2, fmaf(dy, w1, dx * w0)) : 0.f;
+}
+
 // =========================================================================================
 // tile GEMM pieces shared by fwd and bwd_dx
 // =========================================================================================

@@ -18,9 +18,14 @@ const char* occ_grid_fault(const fn_occ_grid* g);         // occupancy.hip
 // capture, no memory: take the unpaired route); pass -> everything of fastnerf_mlp_x6_bwd but the trunk launch, the reduction and the unfold, which
 // it records in *d; finish -> ONE trunk launch over both passes, then each net's reduction and unfold
 bool x6_pair_workspace(int64_t P_coarse, fn_stream_t stream, float** dact2, float** partial2);
+// rb != NULL: the pass's view job rebuilds dYv from hv, draw and Wr, and dX does not store it (dw_pair.h SideRb);
+// x6_bwd_rebuild: a whole unpaired pass of that kind;  side_rebuild_mode: FASTNERF_SIDE_REBUILD, 0 off / 1 on / 2 on with dact_yv poisoned
 int x6_pair_pass(DwDeferred* d, int64_t n, int S, const float* draw, const float* act, const float* params, const float* packed_bwd,
-                 float* dact, float* partial, float* grads, fn_stream_t stream);
+                 float* dact, float* partial, float* grads, fn_stream_t stream, const SideRb* rb);
 int x6_pair_finish(const DwDeferred* fine, const DwDeferred* coarse, fn_stream_t stream);
+int x6_bwd_rebuild(int64_t n, int S, const float* draw, const float* act, const float* params, const float* packed_bwd, float* dact,
+                   float* partial, float* grads, fn_stream_t stream, const SideRb* rb);
+int side_rebuild_mode(void);
 }
 
 // ---- the math modes: one row of MLP entry points per math_mode (0 exact fp32, 1 split-bf16 "bf16x3", 2 "bf16x6") -----------------
@@ -426,6 +431,7 @@ struct RrBwd {
   float *draw_ws, *dact_ws, *partial_ws, *act_ws;
   int32_t* live_ws;
   fn_stream_t stream;
+  int rebuild = 0;   // rr_bwd, bf16x6: 1 -- the view job rebuilds dYv and dX does not store it (train_step); 2 -- and dact_yv is poisoned first
 };
 static int comp_bwd(const RrBwd& c, const BwdPass& q) {
   const PassMaps& m = q.maps;
@@ -483,8 +489,12 @@ static int rr_bwd(const RrBwd& c, const BwdPasses& p) {
     return -1;
   }
   int rc;
+  const bool reb = c.rebuild && c.math_mode == 2;
+  const SideRb rb = {1, c.rebuild == 2};
   auto run = [&](const BwdPass& q) {
     if ((rc = comp_bwd(c, q))) return rc;
+    if (reb)
+      return fn::x6_bwd_rebuild(c.n, q.S, c.draw_ws, q.act, q.params, q.packed_bwd, c.dact_ws, c.partial_ws, q.grads, c.stream, &rb);
     return modes[c.math_mode].bwd(0, c.n, q.S, c.draw_ws, q.act, q.params, q.packed_bwd, c.dact_ws, c.partial_ws, q.grads, c.stream);
   };
   // Both passes in this call, bf16x6: the paired backward.  The trunk dW jobs of the two passes (7 jobs of 256 x 256 each) go into ONE
@@ -495,10 +505,13 @@ static int rr_bwd(const RrBwd& c, const BwdPasses& p) {
   if (p.two && c.passes == 3 && c.math_mode == 2 && fn::x6_pair_workspace(c.n * (int64_t)k.S, c.stream, &dact2, &partial2)) {
     DwDeferred d_fine, d_coarse;   // (this call's own: nothing of a call outlives it but the workspace)
     if ((rc = comp_bwd(c, f))) return rc;
-    if ((rc = fn::x6_pair_pass(&d_fine, c.n, f.S, c.draw_ws, f.act, f.params, f.packed_bwd, c.dact_ws, c.partial_ws, f.grads, c.stream)))
+    if ((rc = fn::x6_pair_pass(&d_fine, c.n, f.S, c.draw_ws, f.act, f.params, f.packed_bwd, c.dact_ws, c.partial_ws, f.grads, c.stream,
+                               reb ? &rb : nullptr)))
       return rc;
     if ((rc = comp_bwd(c, k))) return rc;
-    if ((rc = fn::x6_pair_pass(&d_coarse, c.n, k.S, c.draw_ws, k.act, k.params, k.packed_bwd, dact2, partial2, k.grads, c.stream))) return rc;
+    if ((rc = fn::x6_pair_pass(&d_coarse, c.n, k.S, c.draw_ws, k.act, k.params, k.packed_bwd, dact2, partial2, k.grads, c.stream,
+                               reb ? &rb : nullptr)))
+      return rc;
     return fn::x6_pair_finish(&d_fine, &d_coarse, c.stream);
   }
   if (p.two && (c.passes & 1) && (rc = run(f))) return rc;
@@ -702,6 +715,10 @@ static int train_step(const fn_step_args* a, const fn_step_aux* aux, const fn_st
   }
   if ((phases & FN_STEP_UPDATE) && !step_update_ok(a, fname)) return -1;
   const int fwd_flags = a->fwd_flags & ~FN_STEP_TIGHTEN;   // the step's own bit does not travel on to the forward
+  // The rebuilding view job (dw_pair.h SideRb) with dX's store of dYv off: the backward passes of a step in bf16x6 on the plain backward.  dact_ws
+  // is the step's own scratch and the view job of the same pass is the only reader of dact_yv in it -- fastnerf_ray_grad, which reads it too, is
+  // a call of its own behind a backward that stored (render.py), never part of a step.  FASTNERF_SIDE_REBUILD=0: the reading route.
+  const int rebuild = (passes && a->math_mode == 2 && !a->live) ? fn::side_rebuild_mode() : 0;
   const float* params_c = a->params;
   const float* params_f = two ? a->params + a->net_floats : nullptr;
   int rc;
@@ -757,7 +774,8 @@ static int train_step(const fn_step_args* a, const fn_step_aux* aux, const fn_st
       if (aux->acc_target) { mg.g_acc1 = aux->g_acc1; mg.g_acc0 = aux->g_acc0; }
     }
     if (bk) { mg.g_acc1 = bk->g_acc1; mg.g_acc0 = bk->g_acc0; }      // (they hold the opacity term's rows too: fastnerf_bkgd_grad)
-    const RrBwd c = {a->math_mode, a->white_bkgd, passes, a->n, a->rays11, a->draw_ws, a->dact_ws, a->partial_ws, a->act_ws, a->live_ws, stream};
+    const RrBwd c = {a->math_mode, a->white_bkgd, passes, a->n, a->rays11, a->draw_ws, a->dact_ws, a->partial_ws, a->act_ws, a->live_ws, stream,
+                     rebuild};
     const BwdPasses p = bwd_passes(a->N_samples, a->N_importance, a->g_rgb, a->g_rgb0, a->noise0, a->noise1, a->z0, a->raw0, a->act0, a->z1,
                                    a->raw1, a->act1, params_c, a->packed_fwd_c, a->packed_bwd_c, params_f, a->packed_fwd_f, a->packed_bwd_f,
                                    a->grads, two ? a->grads + a->net_floats : nullptr, a->acc0, a->depth0, a->acc1, a->depth1,

@@ -33,6 +33,12 @@ int fastnerf_device_cus(void);
 /* paired dW trunk launches (one launch for the trunk jobs of both passes of a bf16x6 step) this process has enqueued so far:
  * tells which route a backward took; the unpaired route computes the same gradients */
 int64_t fastnerf_x6_pair_launches(void);
+/* backward passes this process has enqueued whose view-layer dW job REBUILT dYv (the gradient at the view layer's pre-activation) on chip from
+ * hv, d(loss)/d(raw) and the rgb weights instead of reading it: the backward phases of fastnerf_train_step* in bf16x6 on the plain backward.
+ * dX then does not store dYv: after such a step the dYv region of dact_ws (the last 128 floats a point) holds nothing.  FASTNERF_SIDE_REBUILD=0
+ * in the environment, read at every call, selects the reading route with the store on; =nan fills the region with NaNs first.  The gradients
+ * are bit-identical on both routes.  Every other entry point stores and reads dYv as before. */
+int64_t fastnerf_side_rebuild_passes(void);
 
 /* ---- rays ------------------------------------------------------------- */
 /* get_rays (run_nerf_helpers.py:68-78): all H*W pixels of one camera.
