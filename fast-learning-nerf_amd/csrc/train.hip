@@ -202,6 +202,9 @@ extern "C" int fastnerf_aux_loss(int64_t n, const float* depth1, const float* ac
 extern "C" int fastnerf_adam_step(int64_t n, float* params, const float* grads, float* m, float* v, double lr,
                                   double beta1, double beta2, double eps, int step, fn_stream_t stream) {
   FN_CHECK_ARG(n > 0 && params && grads && m && v && step >= 1, "n>0, step>=1, non-null pointers");
+  FN_CHECK_ARG(((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) | reinterpret_cast<uintptr_t>(m) |
+                 reinterpret_cast<uintptr_t>(v)) & 15) == 0,
+               "params, grads, m, v: 16-byte aligned");      // adam_kernel reads them as float4
   const double bc1 = 1.0 - pow(beta1, (double)step);
   const double bc2 = 1.0 - pow(beta2, (double)step);
   const float step_size = (float)(lr / bc1);

@@ -146,7 +146,9 @@ int fastnerf_aux_loss(int64_t n, const float* depth1, const float* acc1, const f
                       const float* depth_target, const float* depth_weight, const float* acc_target, const float* acc_weight,
                       float lambda_depth, float lambda_acc, float grad_scale, float* g_depth1, float* g_acc1, float* g_depth0,
                       float* g_acc0, float* loss4, fn_stream_t stream);
-/* torch.optim.Adam step (run_nerf.py:99,494) over a flat buffer. */
+/* torch.optim.Adam step (run_nerf.py:99,494) over a flat buffer.  params, grads, m and v are read as float4: each must be 16-byte
+ * aligned (a slice of a flat buffer starts at a multiple of four floats), else the call returns an error and launches nothing; n
+ * itself may be any positive count. */
 int fastnerf_adam_step(int64_t n, float* params, const float* grads, float* m, float* v, double lr, double beta1,
                        double beta2, double eps, int step, fn_stream_t stream);
 
