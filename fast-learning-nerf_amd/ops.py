@@ -143,7 +143,19 @@ def net_floats(kind, what=0):
 
 
 def _f32(t):
+    """t as contiguous fp32: t itself, or a new tensor.  Bind a new one to a name until the call is enqueued: a temporary inside the
+    argument list is freed as soon as its pointer is taken, and the allocator hands its block to the next temporary of that list,
+    whose conversion then overwrites it before the kernel reads either."""
     return t.contiguous().float()
+
+
+def _need_f32(name, t, *shape):
+    """Refuse, before any launch, a tensor that the library would read as fp32 [*shape] and that is something else (ptr() only
+    checks contiguity: a float64 tensor would be read as twice as many fp32 values, a wrong shape beyond its end)."""
+    if t.dtype != torch.float32:
+        raise TypeError(f'{name} must be float32, got {t.dtype}')
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f'{name} must have shape {tuple(shape)}, got {tuple(t.shape)}')
 
 
 def gen_rays(H, W, K, c2w):
@@ -164,7 +176,8 @@ def gen_rays_pixels(pix, poses, K):
     n = pix.shape[0]
     ro = torch.empty(n, 3, device=pix.device, dtype=torch.float32)
     rd = torch.empty(n, 3, device=pix.device, dtype=torch.float32)
-    check(lib().fastnerf_gen_rays_pixels(n, ptr(pix.contiguous().int()), ptr(_f32(poses)), float(K[0][0]),
+    pix, poses = pix.contiguous().int(), _f32(poses)      # (named: see _f32)
+    check(lib().fastnerf_gen_rays_pixels(n, ptr(pix), ptr(poses), float(K[0][0]),
                                          float(K[1][1]), float(K[0][2]), float(K[1][2]), ptr(ro), ptr(rd), stream()),
           'fastnerf_gen_rays_pixels')
     return ro, rd
@@ -192,6 +205,7 @@ def pack_rays(rays_o, rays_d, near, far, ndc=False, H=0, W=0, focal=1.0):
 def sample_coarse(rays11, S, lindisp=False, perturb=False, t_rand=None, seed=0):
     require_gpu(rays11, t_rand)
     n = rays11.shape[0]
+    _need_f32('rays11', rays11, n, 11)
     z = torch.empty(n, S, device=rays11.device, dtype=torch.float32)
     if t_rand is not None:
         t_rand = _f32(t_rand)
@@ -326,7 +340,11 @@ def ray_grad(rays11, z, raw, noise, draw, act, dact, params, d_rays=None, accumu
 
 def raw2outputs_fwd(raw, z, rays11, noise=None, white_bkgd=False):
     require_gpu(raw, z, rays11, noise)
-    n, S = z.shape
+    n = rays11.shape[0]
+    _need_f32('rays11', rays11, n, 11)
+    S = z.shape[-1]
+    _need_f32('z', z, n, S)
+    _need_f32('raw', raw, n, S, 4)
     dev = z.device
     rgb = torch.empty(n, 3, device=dev, dtype=torch.float32)
     disp = torch.empty(n, device=dev, dtype=torch.float32)
@@ -562,7 +580,8 @@ def sample_pdf(bins, weights, Ni, det=False, u=None, seed=0):
     out = torch.empty(n, Ni, device=bins.device, dtype=torch.float32)
     if u is not None:
         u = _f32(u)
-    check(lib().fastnerf_sample_pdf(n, M, Ni, ptr(_f32(bins)), ptr(_f32(weights)), int(bool(det)), ptr(u), int(seed),
+    bins, weights = _f32(bins), _f32(weights)
+    check(lib().fastnerf_sample_pdf(n, M, Ni, ptr(bins), ptr(weights), int(bool(det)), ptr(u), int(seed),
                                     ptr(out), stream()), 'fastnerf_sample_pdf')
     return out
 
@@ -688,6 +707,7 @@ def pp_intersect_sphere(rays11, check_inside=True):
     check_inside=False skips the device->host read of the counter."""
     require_gpu(rays11)
     n = rays11.shape[0]
+    _need_f32('rays11', rays11, n, 11)
     fg_far = torch.empty(n, device=rays11.device, dtype=torch.float32)
     cnt = torch.zeros(1, device=rays11.device, dtype=torch.int32) if check_inside else None
     check(lib().fastnerf_pp_intersect_sphere(n, ptr(rays11), ptr(fg_far), ptr(cnt), stream()),
@@ -701,9 +721,11 @@ def pp_intersect_sphere(rays11, check_inside=True):
 def pp_fg_depths(fg_far, S, near=1e-4, perturb=True, t_rand=None, seed=0):
     require_gpu(fg_far, t_rand)
     n = fg_far.shape[0]
+    _need_f32('fg_far', fg_far, n)
     z = torch.empty(n, S, device=fg_far.device, dtype=torch.float32)
     if t_rand is not None:
         t_rand = _f32(t_rand)
+        assert t_rand.shape == (n, S)
     check(lib().fastnerf_pp_fg_depths(n, S, float(near), ptr(fg_far), int(bool(perturb) or t_rand is not None),
                                       ptr(t_rand), int(seed), ptr(z), stream()), 'fastnerf_pp_fg_depths')
     return z
@@ -741,7 +763,8 @@ def pp_sample_pdf(bins, weights, Ni, det=False, u=None, seed=0):
     out = torch.empty(n, Ni, device=bins.device, dtype=torch.float32)
     if u is not None:
         u = _f32(u)
-    check(lib().fastnerf_pp_sample_pdf(n, M, Ni, ptr(_f32(bins)), ptr(_f32(weights)), int(bool(det)), ptr(u), int(seed), ptr(out),
+    bins, weights = _f32(bins), _f32(weights)
+    check(lib().fastnerf_pp_sample_pdf(n, M, Ni, ptr(bins), ptr(weights), int(bool(det)), ptr(u), int(seed), ptr(out),
                                        stream()), 'fastnerf_pp_sample_pdf')
     return out
 
@@ -753,7 +776,8 @@ def pp_depth2pts_outside(ray_o, ray_d, depth):
     n, S = depth.shape
     pts = torch.empty(n, S, 4, device=depth.device, dtype=torch.float32)
     dr = torch.empty(n, S, device=depth.device, dtype=torch.float32)
-    check(lib().fastnerf_pp_depth2pts_outside(n, S, ptr(_f32(ray_o)), ptr(_f32(ray_d)), ptr(depth), ptr(pts), ptr(dr), stream()),
+    ray_o, ray_d = _f32(ray_o), _f32(ray_d)
+    check(lib().fastnerf_pp_depth2pts_outside(n, S, ptr(ray_o), ptr(ray_d), ptr(depth), ptr(pts), ptr(dr), stream()),
           'fastnerf_pp_depth2pts_outside')
     return pts, dr
 
@@ -775,8 +799,9 @@ def pp_composite_bwd(part, raw, z, rays11, g_rgb, fg_far=None, g_lambda=None):
     require_gpu(raw, z, rays11, g_rgb, fg_far, g_lambda)
     n, S = z.shape
     draw = torch.empty(n, S, 4, device=z.device, dtype=torch.float32)
-    check(lib().fastnerf_pp_composite_bwd(n, S, int(part), ptr(raw), ptr(z), ptr(rays11), ptr(fg_far), ptr(_f32(g_rgb)),
-                                          ptr(None if g_lambda is None else _f32(g_lambda)), ptr(draw), stream()),
+    g_rgb, g_lambda = _f32(g_rgb), None if g_lambda is None else _f32(g_lambda)
+    check(lib().fastnerf_pp_composite_bwd(n, S, int(part), ptr(raw), ptr(z), ptr(rays11), ptr(fg_far), ptr(g_rgb),
+                                          ptr(g_lambda), ptr(draw), stream()),
           'fastnerf_pp_composite_bwd')
     return draw
 
@@ -785,7 +810,8 @@ def leaf_sumcount(rgb, target, leaf_tag, max_leaves, sums, counts):
     """Accumulate per-(image, leaf) fp64 sums of |gt-pred| (rays x channels) and ray counts."""
     require_gpu(rgb, target, leaf_tag, sums, counts)
     assert sums.dtype == torch.float64 and counts.dtype == torch.int32
-    check(lib().fastnerf_leaf_sumcount(rgb.shape[0], ptr(_f32(rgb)), ptr(_f32(target)), ptr(leaf_tag), int(max_leaves),
+    rgb, target = _f32(rgb), _f32(target)
+    check(lib().fastnerf_leaf_sumcount(rgb.shape[0], ptr(rgb), ptr(target), ptr(leaf_tag), int(max_leaves),
                                        ptr(sums), ptr(counts), stream()), 'fastnerf_leaf_sumcount')
 
 
