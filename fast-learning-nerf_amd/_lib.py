@@ -58,6 +58,16 @@ class StepBkgd(C.Structure):
     _fields_ = [('bkgd', P), ('seed', U64), ('alpha', P), ('bkgd_used', P), ('target_ws', P), ('g_acc1', P), ('g_acc0', P)]
 
 
+class WeightGrads(C.Structure):
+    """fn_weight_grads of include/fastnerf.h, field for field."""
+    _fields_ = [('g_w1', P), ('g_w0', P)]
+
+
+class StepDist(C.Structure):
+    """fn_step_dist of include/fastnerf.h, field for field."""
+    _fields_ = [('lambda_dist', F)] + [(k, P) for k in ('ell1', 'ell0', 'g_w1', 'g_w0', 'loss2d')]
+
+
 class OccGrid(C.Structure):
     """fn_occ_grid of include/fastnerf.h, field for field."""
     _fields_ = [('words', P), ('lo', F * 3), ('inv', F * 3), ('n', C.c_int32 * 3), ('outside_occupied', C.c_int32)]
@@ -205,6 +215,13 @@ SIGNATURES = {
     'fastnerf_bkgd_grad': (I, [L, P, P, P, P, P, P, P, P]),
     'fastnerf_train_step_bkgd': (I, [C.POINTER(StepArgs), C.POINTER(StepAux), C.POINTER(StepBkgd), I, P]),
     'fastnerf_train_step_march_bkgd': (I, [C.POINTER(StepArgs), C.POINTER(StepMarch), C.POINTER(StepBkgd), I, P]),
+    'fastnerf_step_dist_size': (L, []),
+    'fastnerf_distortion': (I, [L, I, P, P, P, I, P, F, P, P, P, P]),
+    'fastnerf_distortion_mean': (I, [L, P, P, P, P]),
+    'fastnerf_render_rays_bwd_w': (I, [I, L, I, I, P, I] + [P] * 19 + [P] * 4 + [C.POINTER(MapGrads), C.POINTER(WeightGrads), P]),
+    'fastnerf_render_rays_bwd_live_w': (I, [I, L, I, I, P, I] + [P] * 22 + [P] * 4 + [C.POINTER(MapGrads), C.POINTER(WeightGrads), P]),
+    'fastnerf_train_step_dist': (I, [C.POINTER(StepArgs), C.POINTER(StepAux), C.POINTER(StepBkgd), C.POINTER(StepDist), I, P]),
+    'fastnerf_train_step_march_dist': (I, [C.POINTER(StepArgs), C.POINTER(StepMarch), C.POINTER(StepBkgd), C.POINTER(StepDist), I, P]),
     'fastnerf_mlp_sigma_grad_ws_floats': (L, [I, L]),
     'fastnerf_mlp_sigma_grad': (I, [I, I, L, I, P, P, P, P, P, P, P, P, P]),
     'fastnerf_ray_grad_ws_floats': (L, [I, L, I]),
@@ -235,6 +252,8 @@ def lib():
             raise RuntimeError('fn_step_march: the ctypes mirror does not match the library (stale libfastnerf.so?)')
         if l.fastnerf_step_bkgd_size() != C.sizeof(StepBkgd):
             raise RuntimeError('fn_step_bkgd: the ctypes mirror does not match the library (stale libfastnerf.so?)')
+        if l.fastnerf_step_dist_size() != C.sizeof(StepDist):
+            raise RuntimeError('fn_step_dist: the ctypes mirror does not match the library (stale libfastnerf.so?)')
         _lib = l
     return _lib
 

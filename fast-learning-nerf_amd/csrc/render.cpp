@@ -400,12 +400,15 @@ extern "C" int fastnerf_render_rays_fwd(int math_mode, int64_t n, int N_samples,
 // jobs never read draw, so pairing is untouched.
 struct PassMaps {
   const float *acc, *depth, *g_disp, *g_acc, *g_depth;
-  bool any() const { return g_disp || g_acc || g_depth; }
+  const float* g_w = nullptr;   // [n,S]: a gradient of the pass's weights themselves (fn_weight_grads: the distortion term)
+  bool any() const { return g_disp || g_acc || g_depth || g_w; }
 };
 // pass 1 = the pass that produces the image (the only pass when N_importance == 0, where it runs on the coarse buffers), 0 = the coarse pass
-static PassMaps pass_maps(const fn_map_grads* m, int pass, const float* acc, const float* depth) {
-  if (!m) return {acc, depth, nullptr, nullptr, nullptr};
-  return pass ? PassMaps{acc, depth, m->g_disp1, m->g_acc1, m->g_depth1} : PassMaps{acc, depth, m->g_disp0, m->g_acc0, m->g_depth0};
+static PassMaps pass_maps(const fn_map_grads* m, const fn_weight_grads* wg, int pass, const float* acc, const float* depth) {
+  PassMaps q = {acc, depth, nullptr, nullptr, nullptr};
+  if (m) q = pass ? PassMaps{acc, depth, m->g_disp1, m->g_acc1, m->g_depth1} : PassMaps{acc, depth, m->g_disp0, m->g_acc0, m->g_depth0};
+  if (wg) q.g_w = pass ? wg->g_w1 : wg->g_w0;
+  return q;
 }
 
 // One pass of a backward, in the style of RrFwd: its S samples, the forward's tensors over them, the gradients that come in, the network, and
@@ -436,7 +439,7 @@ struct RrBwd {
 static int comp_bwd(const RrBwd& c, const BwdPass& q) {
   const PassMaps& m = q.maps;
   if (!m.any()) return fastnerf_raw2outputs_bwd(c.n, q.S, q.raw, q.z, c.rays11, q.noise, c.white_bkgd, q.g_rgb, c.draw_ws, c.stream);
-  return fastnerf_raw2outputs_bwd_full(c.n, q.S, q.raw, q.z, c.rays11, q.noise, c.white_bkgd, m.acc, m.depth, q.g_rgb, m.g_disp, m.g_acc, nullptr,
+  return fastnerf_raw2outputs_bwd_full(c.n, q.S, q.raw, q.z, c.rays11, q.noise, c.white_bkgd, m.acc, m.depth, q.g_rgb, m.g_disp, m.g_acc, m.g_w,
                                        m.g_depth, c.draw_ws, c.stream);
 }
 
@@ -448,12 +451,13 @@ static BwdPasses bwd_passes(int N_samples, int N_importance, const float* g_rgb,
                             const float* z0, const float* raw0, const float* act0, const float* z1, const float* raw1, const float* act1,
                             const float* params_c, const float* packed_fwd_c, const float* packed_bwd_c, const float* params_f,
                             const float* packed_fwd_f, const float* packed_bwd_f, float* grads_c, float* grads_f, const float* acc0,
-                            const float* depth0, const float* acc1, const float* depth1, const fn_map_grads* mg, int32_t* counts) {
+                            const float* depth0, const float* acc1, const float* depth1, const fn_map_grads* mg, const fn_weight_grads* wg,
+                            int32_t* counts) {
   const bool two = N_importance > 0;
   return {two,
-          {N_samples + N_importance, z1, raw1, noise1, g_rgb, pass_maps(mg, 1, acc1, depth1), params_f, packed_fwd_f, packed_bwd_f, act1,
+          {N_samples + N_importance, z1, raw1, noise1, g_rgb, pass_maps(mg, wg, 1, acc1, depth1), params_f, packed_fwd_f, packed_bwd_f, act1,
            grads_f, counts},
-          {N_samples, z0, raw0, noise0, two ? g_rgb0 : g_rgb, pass_maps(mg, two ? 0 : 1, acc0, depth0), params_c, packed_fwd_c, packed_bwd_c,
+          {N_samples, z0, raw0, noise0, two ? g_rgb0 : g_rgb, pass_maps(mg, wg, two ? 0 : 1, acc0, depth0), params_c, packed_fwd_c, packed_bwd_c,
            act0, grads_c, counts ? counts + 2 : nullptr}};
 }
 
@@ -518,6 +522,19 @@ static int rr_bwd(const RrBwd& c, const BwdPasses& p) {
   return (c.passes & 2) ? run(k) : 0;
 }
 
+extern "C" int fastnerf_render_rays_bwd_w(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11,
+                                          int white_bkgd, const float* g_rgb, const float* g_rgb0, const float* noise0,
+                                          const float* noise1, const float* z0, const float* raw0, const float* act0,
+                                          const float* z1, const float* raw1, const float* act1, const float* params_c,
+                                          const float* packed_bwd_c, const float* params_f, const float* packed_bwd_f,
+                                          float* draw_ws, float* dact_ws, float* partial_ws, float* grads_c, float* grads_f,
+                                          const float* acc0, const float* depth0, const float* acc1, const float* depth1,
+                                          const fn_map_grads* maps, const fn_weight_grads* wg, fn_stream_t stream) {
+  return rr_bwd({math_mode, white_bkgd, 3, n, rays11, draw_ws, dact_ws, partial_ws, nullptr, nullptr, stream},
+                bwd_passes(N_samples, N_importance, g_rgb, g_rgb0, noise0, noise1, z0, raw0, act0, z1, raw1, act1, params_c, nullptr,
+                           packed_bwd_c, params_f, nullptr, packed_bwd_f, grads_c, grads_f, acc0, depth0, acc1, depth1, maps, wg, nullptr));
+}
+
 extern "C" int fastnerf_render_rays_bwd_maps(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11,
                                              int white_bkgd, const float* g_rgb, const float* g_rgb0, const float* noise0,
                                              const float* noise1, const float* z0, const float* raw0, const float* act0,
@@ -526,9 +543,9 @@ extern "C" int fastnerf_render_rays_bwd_maps(int math_mode, int64_t n, int N_sam
                                              float* draw_ws, float* dact_ws, float* partial_ws, float* grads_c, float* grads_f,
                                              const float* acc0, const float* depth0, const float* acc1, const float* depth1,
                                              const fn_map_grads* maps, fn_stream_t stream) {
-  return rr_bwd({math_mode, white_bkgd, 3, n, rays11, draw_ws, dact_ws, partial_ws, nullptr, nullptr, stream},
-                bwd_passes(N_samples, N_importance, g_rgb, g_rgb0, noise0, noise1, z0, raw0, act0, z1, raw1, act1, params_c, nullptr,
-                           packed_bwd_c, params_f, nullptr, packed_bwd_f, grads_c, grads_f, acc0, depth0, acc1, depth1, maps, nullptr));
+  return fastnerf_render_rays_bwd_w(math_mode, n, N_samples, N_importance, rays11, white_bkgd, g_rgb, g_rgb0, noise0, noise1, z0, raw0, act0,
+                                    z1, raw1, act1, params_c, packed_bwd_c, params_f, packed_bwd_f, draw_ws, dact_ws, partial_ws, grads_c,
+                                    grads_f, acc0, depth0, acc1, depth1, maps, nullptr, stream);
 }
 
 extern "C" int fastnerf_render_rays_bwd(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11,
@@ -572,6 +589,22 @@ static int rr_bwd_live(const RrBwd& c, const BwdPasses& p) {
   return (c.passes & 2) ? run(k) : 0;
 }
 
+extern "C" int fastnerf_render_rays_bwd_live_w(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11,
+                                               int white_bkgd, const float* g_rgb, const float* g_rgb0, const float* noise0,
+                                               const float* noise1, const float* z0, const float* raw0, const float* z1,
+                                               const float* raw1, const float* params_c, const float* packed_fwd_c,
+                                               const float* packed_bwd_c, const float* params_f, const float* packed_fwd_f,
+                                               const float* packed_bwd_f, float* draw_ws, float* act_ws, float* dact_ws,
+                                               float* partial_ws, int32_t* live_ws, float* grads_c, float* grads_f,
+                                               int32_t* counts_out, const float* acc0, const float* depth0, const float* acc1,
+                                               const float* depth1, const fn_map_grads* maps, const fn_weight_grads* wg,
+                                               fn_stream_t stream) {
+  return rr_bwd_live({math_mode, white_bkgd, 3, n, rays11, draw_ws, dact_ws, partial_ws, act_ws, live_ws, stream},
+                     bwd_passes(N_samples, N_importance, g_rgb, g_rgb0, noise0, noise1, z0, raw0, nullptr, z1, raw1, nullptr, params_c,
+                                packed_fwd_c, packed_bwd_c, params_f, packed_fwd_f, packed_bwd_f, grads_c, grads_f, acc0, depth0, acc1, depth1,
+                                maps, wg, counts_out ? counts_out : live_ws));
+}
+
 extern "C" int fastnerf_render_rays_bwd_live_maps(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11,
                                                   int white_bkgd, const float* g_rgb, const float* g_rgb0, const float* noise0,
                                                   const float* noise1, const float* z0, const float* raw0, const float* z1,
@@ -581,10 +614,10 @@ extern "C" int fastnerf_render_rays_bwd_live_maps(int math_mode, int64_t n, int 
                                                   float* partial_ws, int32_t* live_ws, float* grads_c, float* grads_f,
                                                   int32_t* counts_out, const float* acc0, const float* depth0, const float* acc1,
                                                   const float* depth1, const fn_map_grads* maps, fn_stream_t stream) {
-  return rr_bwd_live({math_mode, white_bkgd, 3, n, rays11, draw_ws, dact_ws, partial_ws, act_ws, live_ws, stream},
-                     bwd_passes(N_samples, N_importance, g_rgb, g_rgb0, noise0, noise1, z0, raw0, nullptr, z1, raw1, nullptr, params_c,
-                                packed_fwd_c, packed_bwd_c, params_f, packed_fwd_f, packed_bwd_f, grads_c, grads_f, acc0, depth0, acc1, depth1,
-                                maps, counts_out ? counts_out : live_ws));
+  return fastnerf_render_rays_bwd_live_w(math_mode, n, N_samples, N_importance, rays11, white_bkgd, g_rgb, g_rgb0, noise0, noise1, z0, raw0,
+                                         z1, raw1, params_c, packed_fwd_c, packed_bwd_c, params_f, packed_fwd_f, packed_bwd_f, draw_ws,
+                                         act_ws, dact_ws, partial_ws, live_ws, grads_c, grads_f, counts_out, acc0, depth0, acc1, depth1,
+                                         maps, nullptr, stream);
 }
 
 extern "C" int fastnerf_render_rays_bwd_live(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11, int white_bkgd,
@@ -615,6 +648,38 @@ extern "C" int64_t fastnerf_step_args_size(void) { return (int64_t)sizeof(fn_ste
 extern "C" int64_t fastnerf_step_aux_size(void) { return (int64_t)sizeof(fn_step_aux); }
 
 extern "C" int64_t fastnerf_step_bkgd_size(void) { return (int64_t)sizeof(fn_step_bkgd); }
+
+extern "C" int64_t fastnerf_step_dist_size(void) { return (int64_t)sizeof(fn_step_dist); }
+
+// the refusals of a step with the distortion term (dist != NULL, lambda_dist != 0), before anything of the step is launched.  w1 / w0: the
+// weights of the image pass / of the coarse pass of two (NULL with one pass), as the step's forward leaves them
+static bool step_dist_ok(const fn_step_dist* d, bool two, int phases, const float* w1, const float* w0, const char* fname) {
+  if (!(d->lambda_dist > 0.0f) || !(d->lambda_dist < __builtin_huge_valf())) {
+    fn::set_error("%s: bad argument: lambda_dist >= 0 and finite", fname);
+    return false;
+  }
+  const bool fwd = (phases & FN_STEP_FORWARD) != 0;
+  const bool any = (phases & (FN_STEP_FORWARD | FN_STEP_BWD_FINE | FN_STEP_BWD_COARSE)) != 0;
+  if ((any && (!d->g_w1 || (two && !d->g_w0))) || (fwd && (!d->ell1 || (two && !d->ell0) || !d->loss2d))) {
+    fn::set_error("%s: null member of fn_step_dist (g_w1, ell1, loss2d; g_w0, ell0 with two passes)", fname);
+    return false;
+  }
+  if (fwd && (!w1 || (two && !w0))) {
+    fn::set_error("%s: the distortion term needs the weights of its pass (w0, w1)", fname);
+    return false;
+  }
+  return true;
+}
+
+// the distortion term's launches of a forward phase, behind the loss launches: per pass l and coef * dl/dw, then the batch means
+static int step_dist_forward(const fn_step_args* a, const fn_step_dist* d, int S1, const float* w1, const float* z1, int S0, const float* w0,
+                             const float* z0, const uint8_t* skip, fn_stream_t stream) {
+  const float coef = (float)((double)a->grad_scale * (double)d->lambda_dist / (double)a->n);
+  if (int rc = fastnerf_distortion(a->n, S1, w1, z1, a->rays11, a->lindisp, skip, coef, nullptr, d->ell1, d->g_w1, stream)) return rc;
+  if (w0)
+    if (int rc = fastnerf_distortion(a->n, S0, w0, z0, a->rays11, a->lindisp, skip, coef, nullptr, d->ell0, d->g_w0, stream)) return rc;
+  return fastnerf_distortion_mean(a->n, d->ell1, w0 ? d->ell0 : nullptr, d->loss2d, stream);
+}
 
 // the refusals of a step with per-ray background colours (bk != NULL), before anything else of the step is looked at
 static bool step_bkgd_ok(const fn_step_args* a, const fn_step_bkgd* bk, bool two, int phases, const char* fname) {
@@ -675,9 +740,12 @@ static int step_update(const fn_step_args* a, int first, int count, fn_stream_t 
   return 0;
 }
 
-// aux: NULL, or the depth / opacity terms (a term is on when its target is set); bk: NULL, or the per-ray background colours
-static int train_step(const fn_step_args* a, const fn_step_aux* aux, const fn_step_bkgd* bk, int phases, fn_stream_t stream) {
-  const char* fname = bk ? "fastnerf_train_step_bkgd" : "fastnerf_train_step";
+// aux: NULL, or the depth / opacity terms (a term is on when its target is set); bk: NULL, or the per-ray background colours; dist: NULL,
+// or the distortion term (on when lambda_dist != 0)
+static int train_step(const fn_step_args* a, const fn_step_aux* aux, const fn_step_bkgd* bk, const fn_step_dist* dist, int phases,
+                      fn_stream_t stream) {
+  if (dist && dist->lambda_dist == 0.0f) dist = nullptr;
+  const char* fname = dist ? "fastnerf_train_step_dist" : bk ? "fastnerf_train_step_bkgd" : "fastnerf_train_step";
   if (aux && !aux->depth_target && !aux->acc_target) aux = nullptr;
   if (!a || a->math_mode < 0 || a->math_mode > 2 || a->n <= 0 || a->N_samples < 2 || a->N_importance < 0) {
     fn::set_error("%s: bad argument: args != NULL, math_mode in {0,1,2}, n>0, N_samples>=2, N_importance>=0", fname);
@@ -685,6 +753,7 @@ static int train_step(const fn_step_args* a, const fn_step_aux* aux, const fn_st
   }
   const bool two = a->N_importance > 0;
   if (bk && !step_bkgd_ok(a, bk, two, phases, fname)) return -1;
+  if (dist && !step_dist_ok(dist, two, phases, two ? a->w1 : a->w0, two ? a->w0 : nullptr, fname)) return -1;
   if (bk && aux && aux->acc_target && (phases & FN_STEP_FORWARD) && (!aux->g_acc1 || (two && !aux->g_acc0))) {
     fn::set_error("%s: null gradient buffer of the opacity term (its rows are added to the background's)", fname);
     return -1;
@@ -765,6 +834,9 @@ static int train_step(const fn_step_args* a, const fn_step_aux* aux, const fn_st
                                    (add && two) ? aux->g_acc0 : nullptr, bk->g_acc1, two ? bk->g_acc0 : nullptr, stream)))
         return rc;
     }
+    if (dist && (rc = step_dist_forward(a, dist, a->N_samples + a->N_importance, two ? a->w1 : a->w0, two ? a->z1 : a->z0, a->N_samples,
+                                        two ? a->w0 : nullptr, a->z0, nullptr, stream)))
+      return rc;
   }
   if (passes) {
     fn_map_grads mg = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -774,12 +846,13 @@ static int train_step(const fn_step_args* a, const fn_step_aux* aux, const fn_st
       if (aux->acc_target) { mg.g_acc1 = aux->g_acc1; mg.g_acc0 = aux->g_acc0; }
     }
     if (bk) { mg.g_acc1 = bk->g_acc1; mg.g_acc0 = bk->g_acc0; }      // (they hold the opacity term's rows too: fastnerf_bkgd_grad)
+    const fn_weight_grads wg = {dist ? dist->g_w1 : nullptr, dist ? dist->g_w0 : nullptr};
     const RrBwd c = {a->math_mode, a->white_bkgd, passes, a->n, a->rays11, a->draw_ws, a->dact_ws, a->partial_ws, a->act_ws, a->live_ws, stream,
                      rebuild};
     const BwdPasses p = bwd_passes(a->N_samples, a->N_importance, a->g_rgb, a->g_rgb0, a->noise0, a->noise1, a->z0, a->raw0, a->act0, a->z1,
                                    a->raw1, a->act1, params_c, a->packed_fwd_c, a->packed_bwd_c, params_f, a->packed_fwd_f, a->packed_bwd_f,
                                    a->grads, two ? a->grads + a->net_floats : nullptr, a->acc0, a->depth0, a->acc1, a->depth1,
-                                   (aux || bk) ? &mg : nullptr, a->counts ? a->counts : a->live_ws);
+                                   (aux || bk) ? &mg : nullptr, dist ? &wg : nullptr, a->counts ? a->counts : a->live_ws);
     if ((rc = a->live ? rr_bwd_live(c, p) : rr_bwd(c, p))) return rc;
   }
   if (phases & FN_STEP_UPDATE) return step_update(a, 0, two ? 2 : 1, stream);
@@ -787,16 +860,21 @@ static int train_step(const fn_step_args* a, const fn_step_aux* aux, const fn_st
 }
 
 extern "C" int fastnerf_train_step(const fn_step_args* a, int phases, fn_stream_t stream) {
-  return train_step(a, nullptr, nullptr, phases, stream);
+  return train_step(a, nullptr, nullptr, nullptr, phases, stream);
 }
 
 extern "C" int fastnerf_train_step_aux(const fn_step_args* a, const fn_step_aux* aux, int phases, fn_stream_t stream) {
-  return train_step(a, aux, nullptr, phases, stream);
+  return train_step(a, aux, nullptr, nullptr, phases, stream);
 }
 
 extern "C" int fastnerf_train_step_bkgd(const fn_step_args* a, const fn_step_aux* aux, const fn_step_bkgd* bk, int phases,
                                         fn_stream_t stream) {
-  return train_step(a, aux, bk, phases, stream);
+  return train_step(a, aux, bk, nullptr, phases, stream);
+}
+
+extern "C" int fastnerf_train_step_dist(const fn_step_args* a, const fn_step_aux* aux, const fn_step_bkgd* bk, const fn_step_dist* dist,
+                                        int phases, fn_stream_t stream) {
+  return train_step(a, aux, bk, dist, phases, stream);
 }
 
 // The marched step (include/fastnerf.h, "marched training"): one network on the packed rows of a jittered lattice.  The row is [n, C] in
@@ -810,13 +888,16 @@ extern "C" int64_t fastnerf_step_march_ws_ints(int64_t n, int C) {
   return march_ws_ints(n, C, false);
 }
 
-static int train_step_march(const fn_step_args* a, const fn_step_march* mx, const fn_step_bkgd* bk, int phases, fn_stream_t stream) {
-  const char* fname = bk ? "fastnerf_train_step_march_bkgd" : "fastnerf_train_step_march";
+static int train_step_march(const fn_step_args* a, const fn_step_march* mx, const fn_step_bkgd* bk, const fn_step_dist* dist, int phases,
+                            fn_stream_t stream) {
+  if (dist && dist->lambda_dist == 0.0f) dist = nullptr;
+  const char* fname = dist ? "fastnerf_train_step_march_dist" : bk ? "fastnerf_train_step_march_bkgd" : "fastnerf_train_step_march";
   if (!a || !mx || a->math_mode < 0 || a->math_mode > 2 || a->n <= 0 || mx->which < 0 || mx->which > 1) {
     fn::set_error("%s: bad argument: args and march != NULL, math_mode in {0,1,2}, n > 0, which in {0,1}", fname);
     return -1;
   }
   if (bk && !step_bkgd_ok(a, bk, false, phases, fname)) return -1;
+  if (dist && !step_dist_ok(dist, false, phases & ~FN_STEP_BWD_FINE, a->w0, nullptr, fname)) return -1;
   const int K = mx->K, C = mx->C;
   const int64_t n = a->n;
   if (!march_kc_ok(K, C) || !march_n_ok(n, K, C)) {
@@ -875,11 +956,15 @@ static int train_step_march(const fn_step_args* a, const fn_step_march* mx, cons
     if ((rc = fastnerf_march_mask(n, mx->overflow, a->g_rgb, stream))) return rc;
     // (behind the mask: an overflowed ray's g_acc is +-0)
     if (bk && (rc = fastnerf_bkgd_grad(n, bk->bkgd_used, a->g_rgb, nullptr, nullptr, nullptr, bk->g_acc1, nullptr, stream))) return rc;
+    // skip = overflow: a truncated row's weights are an artefact of the row too -- l = 0 and a zero g_w row
+    if (dist && (rc = step_dist_forward(a, dist, C, a->w0, a->z0, 0, nullptr, nullptr, mx->overflow, stream))) return rc;
   }
   if (bwd) {
     // the single pass, built directly (one pass: both members of BwdPasses name it); its counters are the coarse pair, as after a one-pass
     // fastnerf_train_step
-    const BwdPass pass = {C, a->z0, a->raw0, nullptr, a->g_rgb, bk ? PassMaps{a->acc0, a->depth0, nullptr, bk->g_acc1, nullptr} : PassMaps{},
+    PassMaps maps = bk ? PassMaps{a->acc0, a->depth0, nullptr, bk->g_acc1, nullptr} : PassMaps{};
+    if (dist) maps.g_w = dist->g_w1;
+    const BwdPass pass = {C, a->z0, a->raw0, nullptr, a->g_rgb, maps,
                           params, pf, pb, nullptr,
                           a->grads + off, (a->counts ? a->counts : a->live_ws) + 2};
     if ((rc = rr_bwd_live({a->math_mode, a->white_bkgd, 2, n, a->rays11, a->draw_ws, a->dact_ws, a->partial_ws, a->act_ws, a->live_ws, stream},
@@ -891,10 +976,15 @@ static int train_step_march(const fn_step_args* a, const fn_step_march* mx, cons
 }
 
 extern "C" int fastnerf_train_step_march(const fn_step_args* a, const fn_step_march* mx, int phases, fn_stream_t stream) {
-  return train_step_march(a, mx, nullptr, phases, stream);
+  return train_step_march(a, mx, nullptr, nullptr, phases, stream);
 }
 
 extern "C" int fastnerf_train_step_march_bkgd(const fn_step_args* a, const fn_step_march* mx, const fn_step_bkgd* bk, int phases,
                                               fn_stream_t stream) {
-  return train_step_march(a, mx, bk, phases, stream);
+  return train_step_march(a, mx, bk, nullptr, phases, stream);
+}
+
+extern "C" int fastnerf_train_step_march_dist(const fn_step_args* a, const fn_step_march* mx, const fn_step_bkgd* bk, const fn_step_dist* dist,
+                                              int phases, fn_stream_t stream) {
+  return train_step_march(a, mx, bk, dist, phases, stream);
 }

@@ -131,6 +131,25 @@ __global__ void __launch_bounds__(MSE_THREADS) aux_loss_kernel(
   }
 }
 
+// the batch means of the per-ray distortion losses of one or two passes (fastnerf_distortion_mean): aux_loss_kernel's reduction -- one
+// workgroup, a thread's rays in ascending order in fp64, the fixed butterfly; written, not accumulated
+__global__ void __launch_bounds__(MSE_THREADS) distortion_mean_kernel(int64_t n, const float* __restrict__ ell1,
+                                                                     const float* __restrict__ ell0, double inv_n,
+                                                                     float* __restrict__ loss2d) {
+  __shared__ double red[MSE_THREADS / 64];
+  double s1 = 0.0, s0 = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += MSE_THREADS) {
+    s1 += (double)ell1[i];
+    if (ell0) s0 += (double)ell0[i];
+  }
+  s1 = block_sum_d(s1, red);
+  s0 = block_sum_d(s0, red);
+  if (threadIdx.x == 0) {
+    loss2d[0] = (float)(s1 * inv_n);
+    loss2d[1] = (float)(s0 * inv_n);
+  }
+}
+
 __global__ void __launch_bounds__(256) adam_kernel(int64_t n4, int64_t n, float* __restrict__ p,
                                                     const float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, float b1, float b2, float omb1,
@@ -195,6 +214,13 @@ extern "C" int fastnerf_aux_loss(int64_t n, const float* depth1, const float* ac
   const double coef_a = (double)grad_scale * (double)lambda_acc * 2.0 * inv_n;
   hipLaunchKernelGGL(aux_loss_kernel, dim3(1), dim3(MSE_THREADS), 0, fn::S(stream), n, depth1, acc1, depth0, acc0, depth_target,
                      depth_weight, acc_target, acc_weight, coef_d, coef_a, inv_n, g_depth1, g_acc1, g_depth0, g_acc0, loss4);
+  FN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fastnerf_distortion_mean(int64_t n, const float* ell1, const float* ell0, float* loss2d, fn_stream_t stream) {
+  FN_CHECK_ARG(n > 0 && ell1 && loss2d, "n>0 and non-null ell1/loss2d");
+  hipLaunchKernelGGL(distortion_mean_kernel, dim3(1), dim3(MSE_THREADS), 0, fn::S(stream), n, ell1, ell0, 1.0 / (double)n, loss2d);
   FN_LAUNCH_CHECK();
   return 0;
 }

@@ -441,12 +441,29 @@ def _map_grads(map_grads, n):
     return [ptr(keep['acc0']), ptr(keep['depth0']), ptr(keep['acc1']), ptr(keep['depth1']), ctypes.byref(mg)], [keep, mg]
 
 
+def _weight_grads(weight_grads, n, N_samples, N_importance):
+    """weight_grads of render_rays_bwd / _bwd_live -> (None, []) when no weight gradient is set, else (byref(fn_weight_grads), tensors to
+    keep alive over the call).  'g_w1': the image pass's [n, N_samples + N_importance] ([n, N_samples] with one pass), 'g_w0': the coarse
+    pass's of two [n, N_samples]."""
+    if not weight_grads or all(weight_grads.get(k) is None for k in ('g_w1', 'g_w0')):
+        return None, []
+    assert not set(weight_grads) - {'g_w1', 'g_w0'}, set(weight_grads)
+    keep = {k: (None if weight_grads.get(k) is None else _f32(weight_grads[k])) for k in ('g_w1', 'g_w0')}
+    require_gpu(*keep.values())
+    assert keep['g_w1'] is None or tuple(keep['g_w1'].shape) == (n, N_samples + N_importance), tuple(keep['g_w1'].shape)
+    assert keep['g_w0'] is None or (N_importance > 0 and tuple(keep['g_w0'].shape) == (n, N_samples)), tuple(keep['g_w0'].shape)
+    wg = _lib.WeightGrads(ptr(keep['g_w1']), ptr(keep['g_w0']))
+    return ctypes.byref(wg), [keep, wg]
+
+
 def render_rays_bwd(rays11, white_bkgd, g_rgb, g_rgb0, noise0, noise1, z0, raw0, act0, z1, raw1, act1, params_c, packed_bwd_c,
-                    params_f, packed_bwd_f, draw_ws, dact_ws, partial, grads_c, grads_f, N_samples, N_importance, map_grads=None):
+                    params_f, packed_bwd_f, draw_ws, dact_ws, partial, grads_c, grads_f, N_samples, N_importance, map_grads=None,
+                    weight_grads=None):
     """One C-ABI call for the backward of render_rays w.r.t. the parameters of the (distinct) coarse / fine nets.
     map_grads: None, or a dict with d(loss)/d(disp, acc, depth) of the fine (1) and coarse (0) pass under MAP_GRAD_KEYS ([n] each,
     absent / None = zero; one pass: the *1 keys) and the forward's 'acc0', 'depth0', 'acc1', 'depth1' (needed for a g_disp*):
-    fastnerf_render_rays_bwd_maps.  A pass with a map gradient may have g_rgb / g_rgb0 None."""
+    fastnerf_render_rays_bwd_maps.  A pass with a map gradient may have g_rgb / g_rgb0 None.
+    weight_grads: None, or a dict with d(loss)/d(weights) under 'g_w1' / 'g_w0' (_weight_grads): fastnerf_render_rays_bwd_w."""
     require_gpu(rays11, g_rgb, g_rgb0, z0, raw0, act0, z1, raw1, act1, params_c, packed_bwd_c, params_f, packed_bwd_f, draw_ws,
                 dact_ws, partial, grads_c, grads_f)
     n = rays11.shape[0]
@@ -459,7 +476,10 @@ def render_rays_bwd(rays11, white_bkgd, g_rgb, g_rgb0, noise0, noise1, z0, raw0,
             ptr(noise0), ptr(noise1), ptr(z0), ptr(raw0), ptr(act0), ptr(z1), ptr(raw1), ptr(act1), ptr(params_c), ptr(packed_bwd_c),
             ptr(params_f), ptr(packed_bwd_f), ptr(draw_ws), ptr(dact_ws), ptr(partial), ptr(grads_c), ptr(grads_f)]
     maps, _keep = _map_grads(map_grads, n)
-    if maps is None:
+    wg, _keep_w = _weight_grads(weight_grads, n, int(N_samples), int(N_importance))
+    if wg is not None:
+        check(lib().fastnerf_render_rays_bwd_w(*args, *(maps or [None] * 5), wg, stream()), 'fastnerf_render_rays_bwd_w')
+    elif maps is None:
         check(lib().fastnerf_render_rays_bwd(*args, stream()), 'fastnerf_render_rays_bwd')
     else:
         check(lib().fastnerf_render_rays_bwd_maps(*args, *maps, stream()), 'fastnerf_render_rays_bwd_maps')
@@ -506,11 +526,11 @@ def live_ws_ints(P):
 
 def render_rays_bwd_live(rays11, white_bkgd, g_rgb, g_rgb0, noise0, noise1, z0, raw0, z1, raw1, params_c, packed_c,
                          params_f, packed_f, draw_ws, act_ws, dact_ws, partial, live_ws, grads_c, grads_f, N_samples,
-                         N_importance, counts=None, map_grads=None):
+                         N_importance, counts=None, map_grads=None, weight_grads=None):
     """One C-ABI call: backward of render_rays with exact zero-gradient point compaction, for a forward that saved
     nothing.  packed_c / packed_f: the (forward, backward) packed-weight pairs.  counts: optional int32[4] device
-    tensor receiving (live, total) of the fine and of the coarse pass.  map_grads: as render_rays_bwd
-    (fastnerf_render_rays_bwd_live_maps)."""
+    tensor receiving (live, total) of the fine and of the coarse pass.  map_grads, weight_grads: as render_rays_bwd
+    (fastnerf_render_rays_bwd_live_maps, fastnerf_render_rays_bwd_live_w)."""
     require_gpu(rays11, g_rgb, g_rgb0, z0, raw0, z1, raw1, params_c, params_f, draw_ws, act_ws, dact_ws, partial, live_ws,
                 grads_c, grads_f, counts)
     n = rays11.shape[0]
@@ -525,7 +545,10 @@ def render_rays_bwd_live(rays11, white_bkgd, g_rgb, g_rgb0, noise0, noise1, z0, 
             ptr(params_f), ptr(None if packed_f is None else packed_f[0]), ptr(None if packed_f is None else packed_f[1]),
             ptr(draw_ws), ptr(act_ws), ptr(dact_ws), ptr(partial), ptr(live_ws), ptr(grads_c), ptr(grads_f), ptr(counts)]
     maps, _keep = _map_grads(map_grads, n)
-    if maps is None:
+    wg, _keep_w = _weight_grads(weight_grads, n, int(N_samples), int(N_importance))
+    if wg is not None:
+        check(lib().fastnerf_render_rays_bwd_live_w(*args, *(maps or [None] * 5), wg, stream()), 'fastnerf_render_rays_bwd_live_w')
+    elif maps is None:
         check(lib().fastnerf_render_rays_bwd_live(*args, stream()), 'fastnerf_render_rays_bwd_live')
     else:
         check(lib().fastnerf_render_rays_bwd_live_maps(*args, *maps, stream()), 'fastnerf_render_rays_bwd_live_maps')
@@ -645,6 +668,40 @@ def aux_loss(depth, acc, depth0=None, acc0=None, depth_target=None, depth_weight
                                   ptr(g['g_depth1']), ptr(g['g_acc1']), ptr(g['g_depth0']), ptr(g['g_acc0']), ptr(loss4), stream()),
           'fastnerf_aux_loss')
     return loss4, g
+
+
+def distortion(w, z, rays11, lindisp=False, skip=None, coef=1.0, g_up=None, want=('ell', 'g_w')):
+    """The distortion loss of the weights of every ray and its gradient in them (fastnerf_distortion; include/fastnerf.h has the
+    definition).  w, z [n,S] (1 <= S <= 512), near / far = columns 6 / 7 of rays11.  skip: [n] bytes (uint8 or bool), a non-zero one gives
+    its ray l = 0 and a zero row.  -> (ell [n] or None, g_w [n,S] or None) as `want` names them; g_w = coef * (g_up[r] or 1) * dl_r/dw_i."""
+    require_gpu(w, z, rays11, skip, g_up)
+    w, z, rays11 = _f32(w), _f32(z), _f32(rays11)
+    n, S = z.shape
+    assert tuple(w.shape) == (n, S) and tuple(rays11.shape) == (n, 11), (tuple(w.shape), tuple(z.shape), tuple(rays11.shape))
+    assert want and not set(want) - {'ell', 'g_w'}, want
+    if skip is not None:
+        skip = skip.to(torch.uint8).contiguous()
+        assert skip.numel() == n
+    if g_up is not None:
+        g_up = _f32(g_up).reshape(-1)
+        assert g_up.numel() == n
+    ell = torch.empty(n, device=z.device, dtype=torch.float32) if 'ell' in want else None
+    g_w = torch.empty(n, S, device=z.device, dtype=torch.float32) if 'g_w' in want else None
+    check(lib().fastnerf_distortion(n, S, ptr(w), ptr(z), ptr(rays11), int(bool(lindisp)), ptr(skip), float(coef), ptr(g_up), ptr(ell),
+                                    ptr(g_w), stream()), 'fastnerf_distortion')
+    return ell, g_w
+
+
+def distortion_mean(ell1, ell0=None):
+    """The batch means of the per-ray distortion losses of the image pass and, when given, the coarse pass (fastnerf_distortion_mean):
+    -> loss2d [2] on the device (the second 0 without ell0); one workgroup, fixed order, fp64: bit-identical from call to call."""
+    require_gpu(ell1, ell0)
+    ell1 = _f32(ell1).reshape(-1)
+    ell0 = None if ell0 is None else _f32(ell0).reshape(-1)
+    assert ell0 is None or ell0.numel() == ell1.numel()
+    loss2d = torch.empty(2, device=ell1.device, dtype=torch.float32)
+    check(lib().fastnerf_distortion_mean(ell1.numel(), ptr(ell1), ptr(ell0), ptr(loss2d), stream()), 'fastnerf_distortion_mean')
+    return loss2d
 
 
 def bkgd_blend(rgb, acc, target, bkgd=None, seed=0, alpha=None, rgb0=None, acc0=None):

@@ -180,9 +180,21 @@ def _maps(o, N_importance):
                 depth_map=o['depth0'])
 
 
+def _dist_maps(out, rays11, lindisp):
+    """The per-ray distortion loss (ops.distortion) of the weights of a forward's image pass -> 'dist_map', and of the coarse pass of
+    two -> 'dist0'.  A marched row (its depths under 'march_z') is taken with skip = its overflow flags."""
+    if 'march_z' in out:
+        return {'dist_map': ops.distortion(out['weights'], out['march_z'], rays11, lindisp, skip=out['march_overflow'], want=('ell',))[0]}
+    d = {'dist_map': ops.distortion(out['weights'], out['z_vals'], rays11, lindisp, want=('ell',))[0]}
+    if 'weights0' in out:
+        d['dist0'] = ops.distortion(out['weights0'], out['z0'], rays11, lindisp, want=('ell',))[0]
+    return d
+
+
 def _forward_core(rays11, net_c, net_f, N_samples, N_importance, lindisp, perturb, white_bkgd, t_rand, u, noise0,
-                  noise1, save, packed_c=None, packed_f=None, skip_dead_rgb=False, act_ws=False):
-    """The fused forward.  Returns (outputs dict, saved-for-backward dict)."""
+                  noise1, save, packed_c=None, packed_f=None, skip_dead_rgb=False, act_ws=False, retdist=False):
+    """The fused forward.  Returns (outputs dict, saved-for-backward dict).  retdist: 'dist_map' (and 'dist0') among the outputs, and the
+    weights they were taken from among the saved tensors."""
     pc = packed_c if packed_c is not None else net_c.packed()
     fine = pf = None
     if N_importance > 0:
@@ -210,7 +222,13 @@ def _forward_core(rays11, net_c, net_f, N_samples, N_importance, lindisp, pertur
     if N_importance > 0:
         saved.update(z1=o['z1'], raw1=o['raw1'], act1=o['act1'], noise1=noise1, net_f=fine, pf=pf, acc1=o['acc1'].detach(),
                      depth1=o['depth1'].detach())
-    return _maps(o, N_importance), saved
+    out = _maps(o, N_importance)
+    if retdist:
+        out.update(_dist_maps(out, rays11, lindisp))
+        saved.update(lindisp=lindisp, w0=o['w0'].detach())
+        if N_importance > 0:
+            saved.update(w1=o['w1'].detach())
+    return out, saved
 
 
 def _forward_occ(rays11, net_c, net_f, N_samples, N_importance, lindisp, perturb, white_bkgd, t_rand, u, occupancy, skip_dead_rgb=False):
@@ -268,18 +286,31 @@ def _pass_maps(maps, k):
     return None if all(t is None for t in g) else g
 
 
-def _backward_core(saved, g_rgb, g_rgb0, out_c=None, out_f=None, counts=None, maps=None):
+def _dist_weight_grads(saved, g):
+    """The cotangents of 'dist_map' / 'dist0' -> d(loss)/d(weights) of their pass under 'g_w1' / 'g_w0' (ops._weight_grads), or None when
+    neither is set: the distortion kernel again, with the cotangent as its per-ray upstream gradient."""
+    two = saved['net_f'] is not None
+    wg = {}
+    for key, k, name in (('dist_map', '1' if two else '0', 'g_w1'), ('dist0', '0', 'g_w0')):
+        if g.get(key) is not None and (two or key == 'dist_map'):
+            wg[name] = ops.distortion(saved['w' + k], saved['z' + k], saved['rays11'], saved['lindisp'], g_up=g[key], want=('g_w',))[1]
+    return wg or None
+
+
+def _backward_core(saved, g_rgb, g_rgb0, out_c=None, out_f=None, counts=None, maps=None, weight_grads=None):
     """Writes d(loss)/d(params) of the coarse (and fine) net, given d(loss)/d(rgb maps), into
     out_c / out_f (flat, parameter order; default: the nets' flat_grad buffers).  A forward that saved no activations
     (saved['live']) is followed by the compacted backward; `counts` (int32[4], device) then receives the live / total
     point counts of the fine and the coarse pass.  `maps`: None, or d(loss)/d(disp, acc, depth) of the two passes under
-    ops.MAP_GRAD_KEYS (one pass: the *1 keys); without any, the calls are those of the colour loss alone."""
+    ops.MAP_GRAD_KEYS (one pass: the *1 keys); without any, the calls are those of the colour loss alone.  `weight_grads`: None, or
+    d(loss)/d(weights) of the passes under 'g_w1' / 'g_w0' (_dist_weight_grads)."""
     rays11 = saved['rays11']
     has1, has0 = _pass_maps(maps, '1') is not None, _pass_maps(maps, '0') is not None
     map_grads = None
     if has1 or has0:
         map_grads = dict({k: maps.get(k) for k in ops.MAP_GRAD_KEYS}, acc0=saved['acc0'], depth0=saved['depth0'],
                          acc1=saved.get('acc1'), depth1=saved.get('depth1'))
+    has1, has0 = has1 or (weight_grads or {}).get('g_w1') is not None, has0 or (weight_grads or {}).get('g_w0') is not None
     dev = rays11.device
     partial = _Workspace.partial(dev)
     net_c, net_f = saved['net_c'], saved['net_f']
@@ -300,7 +331,7 @@ def _backward_core(saved, g_rgb, g_rgb0, out_c=None, out_f=None, counts=None, ma
         ops.render_rays_bwd_live(rays11, saved['white'], g_a, g_b, saved['noise0'], saved.get('noise1'), saved['z0'], saved['raw0'],
                                  saved.get('z1'), saved.get('raw1'), net_c.flat, saved['pc'], None if Ni == 0 else net_f.flat,
                                  None if Ni == 0 else saved['pf'], draw_ws, act_ws, ws, partial, live_ws, out_c,
-                                 out_f if Ni > 0 else None, S0, Ni, counts=counts, map_grads=map_grads)
+                                 out_f if Ni > 0 else None, S0, Ni, counts=counts, map_grads=map_grads, weight_grads=weight_grads)
         return
     if net_f is None or net_f is not net_c:
         # one C-ABI call: compositing backward + MLP backward for the fine and the coarse pass
@@ -312,33 +343,37 @@ def _backward_core(saved, g_rgb, g_rgb0, out_c=None, out_f=None, counts=None, ma
         ops.render_rays_bwd(rays11, saved['white'], g_a, g_b, saved['noise0'], saved.get('noise1'), saved['z0'], saved['raw0'],
                             saved['act0'], saved.get('z1'), saved.get('raw1'), saved.get('act1'), net_c.flat, saved['pc'][1],
                             None if Ni == 0 else net_f.flat, None if Ni == 0 else saved['pf'][1], draw_ws, ws, partial, out_c,
-                            out_f if Ni > 0 else None, S0, Ni, map_grads=map_grads)
+                            out_f if Ni > 0 else None, S0, Ni, map_grads=map_grads, weight_grads=weight_grads)
         return
     # one shared network for both passes (N_importance > 0 without network_fine): accumulate the two gradients
-    _backward_passes(saved, g_rgb, g_rgb0, out_c, None, maps=maps)
+    _backward_passes(saved, g_rgb, g_rgb0, out_c, None, maps=maps, weight_grads=weight_grads)
 
 
-def _backward_passes(saved, g_rgb, g_rgb0, out_c, out_f, d_rays=None, maps=None):
+def _backward_passes(saved, g_rgb, g_rgb0, out_c, out_f, d_rays=None, maps=None, weight_grads=None):
     """The backward of a saving forward pass by pass -- raw2outputs_bwd -> mlp_bwd [-> ray_grad], the fine pass, then the coarse one --
     for what the one-call ops.render_rays_bwd cannot do: one shared network (the fine pass's gradient is added to the coarse
     pass's in out_c) and ray gradients (d_rays [n,11], overwritten: ops.ray_grad reads a pass's `dact` before the next pass
     overwrites it).  Same kernels, inputs and order as the one call, so the parameter gradients are bit-identical to its.  `maps` as
     in _backward_core: a pass with a map gradient goes through raw2outputs_bwd_full, and ops.ray_grad consumes its draw, so rays and
-    poses receive the depth / opacity terms (z is a constant of the backward, as in the reference)."""
+    poses receive the depth / opacity terms (z is a constant of the backward, as in the reference).  `weight_grads` as in _backward_core:
+    it travels beside the map gradients of its pass."""
     rays11 = saved['rays11']
     dev = rays11.device
     partial = _Workspace.partial(dev)
     net_c, net_f = saved['net_c'], saved['net_f']
     shared = net_f is net_c
+    wg = weight_grads or {}
     # (buffers k, colour gradient, map gradients: with one pass the coarse buffers carry the image pass, whose keys are the *1 ones)
-    passes = [('0', net_c, saved['pc'], g_rgb if net_f is None else g_rgb0, _pass_maps(maps, '1' if net_f is None else '0'), out_c)]
+    passes = [('0', net_c, saved['pc'], g_rgb if net_f is None else g_rgb0, _pass_maps(maps, '1' if net_f is None else '0'), out_c,
+               wg.get('g_w1' if net_f is None else 'g_w0'))]
     if net_f is not None:
-        passes.insert(0, ('1', net_f, saved['pf'], g_rgb, _pass_maps(maps, '1'), torch.empty_like(out_c) if shared else out_f))
-    for i, (k, net, packed, g, gm, out) in enumerate(passes):
+        passes.insert(0, ('1', net_f, saved['pf'], g_rgb, _pass_maps(maps, '1'), torch.empty_like(out_c) if shared else out_f, wg.get('g_w1')))
+    for i, (k, net, packed, g, gm, out, gw) in enumerate(passes):
         z, raw, noise, act = saved['z' + k], saved['raw' + k], saved['noise' + k], saved['act' + k]
-        if gm is not None:
+        if gm is not None or gw is not None:
+            gm = gm or (None, None, None)
             draw = ops.raw2outputs_bwd_full(raw, z, rays11, saved['acc' + k], saved['depth' + k], g_rgb=g, g_disp=gm[0], g_acc=gm[1],
-                                            g_depth=gm[2], noise=noise, white_bkgd=saved['white'])
+                                            g_w=gw, g_depth=gm[2], noise=noise, white_bkgd=saved['white'])
         else:
             if g is None:
                 g = torch.zeros(z.shape[0], 3, device=dev)
@@ -358,8 +393,9 @@ def _grad_views(flat):
     return list(flat_params.views(flat, param_slices()).values())
 
 
-def _fn_keys(two):
-    return ['rgb_map', 'disp_map', 'acc_map', 'raw', 'depth_map'] + (['rgb0', 'disp0', 'acc0', 'z_std', 'depth0'] if two else [])
+def _fn_keys(two, dist=False):
+    return (['rgb_map', 'disp_map', 'acc_map', 'raw', 'depth_map'] + (['rgb0', 'disp0', 'acc0', 'z_std', 'depth0'] if two else [])
+            + ((['dist_map'] + (['dist0'] if two else [])) if dist else []))
 
 
 _MAP_OF_KEY = {'disp_map': 'g_disp1', 'acc_map': 'g_acc1', 'depth_map': 'g_depth1', 'disp0': 'g_disp0', 'acc0': 'g_acc0',
@@ -369,7 +405,7 @@ _MAP_OF_KEY = {'disp_map': 'g_disp1', 'acc_map': 'g_acc1', 'depth_map': 'g_depth
 def _fn_outputs(ctx, out):
     """The outputs of the two autograd nodes: every map differentiable, `raw` and `z_std` not.  Cotangents are not materialised:
     a map no loss touches arrives as None in backward, so a loss on the colours alone reaches _backward_core with no map gradient."""
-    ctx.keys = _fn_keys('rgb0' in out)
+    ctx.keys = _fn_keys('rgb0' in out, 'dist_map' in out)
     outs = tuple(out[k] for k in ctx.keys)
     ctx.mark_non_differentiable(*[o for k, o in zip(ctx.keys, outs) if k in ('raw', 'z_std')])
     ctx.set_materialize_grads(False)
@@ -405,7 +441,8 @@ class _RenderRaysFn(torch.autograd.Function):
         out_c = torch.empty_like(saved['net_c'].flat)
         out_f = torch.empty_like(saved['net_f'].flat) if two else None
         counts = _Workspace.get('counts', out_c.device, 4, torch.int32) if saved.get('live') else None
-        _backward_core(saved, g.get('rgb_map'), g.get('rgb0'), out_c, out_f, counts=counts, maps=maps)
+        _backward_core(saved, g.get('rgb_map'), g.get('rgb0'), out_c, out_f, counts=counts, maps=maps,
+                       weight_grads=_dist_weight_grads(saved, g))
         if counts is not None:
             _POLICY.after_live_step(counts)
         _POLICY.tick()
@@ -436,7 +473,8 @@ class _RenderRaysRayGradFn(torch.autograd.Function):
         out_c = torch.empty_like(saved['net_c'].flat)      # (fresh buffers: see _RenderRaysFn.backward)
         out_f = torch.empty_like(saved['net_f'].flat) if two else None
         d_rays = torch.empty(saved['rays11'].shape[0], 11, device=out_c.device, dtype=torch.float32)
-        _backward_passes(saved, g.get('rgb_map'), g.get('rgb0'), out_c, out_f, d_rays=d_rays, maps=maps)
+        _backward_passes(saved, g.get('rgb_map'), g.get('rgb0'), out_c, out_f, d_rays=d_rays, maps=maps,
+                         weight_grads=_dist_weight_grads(saved, g))
         grads = saved['net_c'].param_grads_from(out_c) + (saved['net_f'].param_grads_from(out_f) if two else [])
         assert len(grads) == ctx.n_params
         width, dtype = ctx.ray_like
@@ -502,7 +540,7 @@ def _query_occupied(network_query_fn, net, rays11, z, viewdirs, occupancy):
 
 
 def _render_rays_closure(ray_batch, rays11, network_fn, network_fine, network_query_fn, N_samples, N_importance, retraw, lindisp,
-                         perturb, white_bkgd, t_rand, u, noise0, noise1, occupancy=None, retdepth=False):
+                         perturb, white_bkgd, t_rand, u, noise0, noise1, occupancy=None, retdepth=False, retdist=False):
     """render.py:195-305 for any torch network: sampling, inverse-CDF + merge and compositing run on the HIP kernels, the
     network runs as `network_query_fn(pts, viewdirs, net)` in torch, and autograd reaches its parameters through
     raw2outputs_full.  Random draws follow the fused route (same injected tensors, same host-RNG seed draws)."""
@@ -523,6 +561,8 @@ def _render_rays_closure(ray_batch, rays11, network_fn, network_fine, network_qu
         ret['rgb0'], ret['disp0'], ret['acc0'] = rgb, disp, acc
         if retdepth:
             ret['depth0'] = depth
+        if retdist:
+            ret['dist0'] = torch.ops.fastnerf.distortion(weights, z, rays11.detach(), lindisp, None)
         seed1 = _next_seed() if (perturb and u is None) else 0
         # sample_pdf(mid(z), weights[1:-1]) on the detached weights (render.py:279-283) + sort(cat)
         z1, _, z_std = ops.sample_pdf_merge(z, weights.detach().contiguous(), N_importance, det=(perturb == 0.), u=u, seed=seed1,
@@ -533,11 +573,14 @@ def _render_rays_closure(ray_batch, rays11, network_fn, network_fine, network_qu
         else:
             pts = rays_o[..., None, :] + rays_d[..., None, :] * z1[..., :, None]
             raw = network_query_fn(pts, viewdirs, network_fine if network_fine is not None else network_fn)
-        rgb, disp, acc, _, depth = _composite(raw, z1, rays11, noise1, white_bkgd)
+        z = z1
+        rgb, disp, acc, weights, depth = _composite(raw, z, rays11, noise1, white_bkgd)
         ret['z_std'] = z_std
     out = {'rgb_map': rgb, 'disp_map': disp, 'acc_map': acc}
     if retdepth:
         out['depth_map'] = depth
+    if retdist:
+        out['dist_map'] = torch.ops.fastnerf.distortion(weights, z, rays11.detach(), lindisp, None)
     if retraw:
         out['raw'] = raw
     out.update(ret)
@@ -546,7 +589,7 @@ def _render_rays_closure(ray_batch, rays11, network_fn, network_fine, network_qu
 
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
                 N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False, occupancy=None,
-                tighten=False, march=None, march_cap=128, bkgd=None, retdepth=False, ert=None, ert_block=32):
+                tighten=False, march=None, march_cap=128, bkgd=None, retdist=False, retdepth=False, ert=None, ert_block=32):
     """render.py:195-305.  Two routes, chosen by the networks (after `.module` unwrapping):
 
     * fastnerf NeRF modules (8 x 256): positional encoding + MLP run fused inside the HIP kernels; `network_query_fn` is
@@ -612,14 +655,19 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     rgb_map = rgb_map + (1 - acc_map)[:, None] * bkgd, and the same for rgb0 with acc0, in torch -- on every route, with `occupancy=`,
     `ert=` and `march=` as well.  Under autograd that is plain arithmetic on maps that are differentiable already: parameters, rays and a
     pose receive the background's gradient through acc_map.  bkgd = ones has the bits of white_bkgd=True.  `bkgd=None` (the default)
-    makes exactly the calls it made before."""
+    makes exactly the calls it made before.
+
+    `retdist=True` adds `dist_map` [n], the distortion loss of mip-NeRF 360 on the weights of every ray's image pass (ops.distortion;
+    include/fastnerf.h has the definition), and `dist0` for the coarse pass of two: differentiable w.r.t. the networks' parameters on both
+    routes, in all three math modes, through the weights alone (depths, near and far are constants).  A loss adds
+    lambda * (dist_map.mean() + dist0.mean()).  With `march=` the row is taken with its overflowed rays skipped (0 there)."""
     if bkgd is not None:
         if white_bkgd:
             raise ValueError('render_rays: bkgd cannot be combined with white_bkgd=True (bkgd = ones is the white background)')
         ret = render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=retraw, lindisp=lindisp, perturb=perturb,
                           N_importance=N_importance, network_fine=network_fine, white_bkgd=False, raw_noise_std=raw_noise_std,
                           verbose=verbose, pytest=pytest, occupancy=occupancy, tighten=tighten, march=march, march_cap=march_cap,
-                          retdepth=retdepth, ert=ert, ert_block=ert_block)
+                          retdepth=retdepth, ert=ert, ert_block=ert_block, retdist=retdist)
         b = torch.as_tensor(bkgd, dtype=ret['rgb_map'].dtype, device=ret['rgb_map'].device)
         if b.shape != (3,) and b.shape != ret['rgb_map'].shape:
             raise ValueError('render_rays: bkgd is a colour [3] or one colour per ray [n, 3]')
@@ -684,6 +732,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             ret['depth_map'] = out['depth_map']
         if retraw:
             ret['raw'], ret['march_z'], ret['march_k'] = out['raw'], out['march_z'], out['march_k']
+        if retdist:
+            ret.update(_dist_maps(out, rays11, lindisp))
         return ret
     n = rays11.shape[0]
     dev = rays11.device
@@ -700,12 +750,13 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             noise0, noise1 = ops.sigma_noise(n, N_samples, N_samples + N_importance if N_importance > 0 else 0, raw_noise_std, _next_seed(), dev)
     if not fused:
         return _render_rays_closure(ray_batch, rays11, network_fn, network_fine, network_query_fn, N_samples, N_importance, retraw,
-                                    lindisp, perturb, white_bkgd, t_rand, u, noise0, noise1, occupancy=occupancy, retdepth=retdepth)
+                                    lindisp, perturb, white_bkgd, t_rand, u, noise0, noise1, occupancy=occupancy, retdepth=retdepth,
+                                    retdist=retdist)
     cfg = dict(rays11=rays11, net_c=net_c, net_f=net_f, N_samples=N_samples, N_importance=N_importance,
                lindisp=lindisp, perturb=perturb, white_bkgd=white_bkgd, t_rand=t_rand, u=u, noise0=noise0,
                noise1=noise1,
                # nobody sees the colour logits of this call: tiles without a live sample may skip them (FN_FWD_SKIP_DEAD_RGB)
-               skip_dead_rgb=not retraw)
+               skip_dead_rgb=not retraw, retdist=retdist)
     params = list(net_c.parameters()) + (list(net_f.parameters()) if (net_f is not None and net_f is not net_c) else [])
     if ert is not None:
         out = _forward_ert(rays11, net_c, net_f, N_samples, N_importance, lindisp, perturb, white_bkgd, t_rand, u, ert, ert_block,
@@ -719,13 +770,15 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
                                       "ops.set_math): 'bf16x3' has no ray-gradient kernel")
         cfg['rays11'] = rays11.detach()
         outs = _RenderRaysRayGradFn.apply(cfg, ray_batch, *params)
-        out = dict(zip(_fn_keys(N_importance > 0), outs))
+        out = dict(zip(_fn_keys(N_importance > 0, retdist), outs))
     elif torch.is_grad_enabled() and any(p.requires_grad for p in params):
         outs = _RenderRaysFn.apply(cfg, *params)
-        out = dict(zip(_fn_keys(N_importance > 0), outs))
+        out = dict(zip(_fn_keys(N_importance > 0, retdist), outs))
     else:
         out, _ = _forward_core(save=False, **cfg)
     ret = {'rgb_map': out['rgb_map'], 'disp_map': out['disp_map'], 'acc_map': out['acc_map']}
+    if retdist:      # (the inference forwards through a grid / with early termination: from the weights they return)
+        ret.update({k: v for k, v in (out if 'dist_map' in out else _dist_maps(out, rays11, lindisp)).items() if k in ('dist_map', 'dist0')})
     if retdepth:
         ret['depth_map'] = out['depth_map']
     if retraw:

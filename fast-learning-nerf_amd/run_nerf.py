@@ -76,6 +76,7 @@ class _Args:
     multires = 10; multires_views = 4; raw_noise_std = 0.
     dataset_type = 'blender'; white_bkgd = False; no_ndc = False; lindisp = False
     random_bkgd = False      # (not in the reference's parser) RGBA training over a fresh background colour per ray
+    lambda_dist = 0.         # (not in the reference's parser) weight of the distortion loss on the ray weights (Trainer(lambda_dist=))
     n_epoch = 12; init_level = 3; rays_downscale = 1; subdivide_every = 1; subdivide_thres = 0.015
     randSamp_perc = 0.5; basedir = './logs'; expname = 'fastnerf'
 
@@ -272,11 +273,23 @@ class Trainer:
     through the full-gradient compositing backward, added to the opacity term's rows when lambda_acc is on; like that term it makes every
     sample with positive density of a ray that is not yet opaque live.  All routes take it: the fused step (plain, compacted, through a
     grid, tighten), the marched step and the call-by-call route.  ValueError: together with white_bkgd (bkgd=(1, 1, 1) is white), an
-    alpha with no background on."""
+    alpha with no background on.
+
+    Distortion loss (`lambda_dist`, read on every step; include/fastnerf.h, "distortion loss"): the step also minimises lambda_dist
+    (Ldist_fine + Ldist_coarse), Ldist = the batch mean of the mip-NeRF 360 distortion loss of a pass's weights over its normalised
+    intervals -- the term that removes floaters and half-transparent fog.  It reaches the field through the weights alone (depths, near
+    and far are constants), as d(loss)/d(weights) rows handed to the full-gradient compositing backward of its pass.  `dist_losses`:
+    device tensor [2] = (Ldist_fine, Ldist_coarse) of the last step, unscaled (the second 0 with one pass; zeros when off and after an
+    empty batch); out['dist_map'] (and out['dist0']) hold the per-ray values.  All routes take it: the fused step (plain, compacted,
+    through a grid, tighten), the marched step -- there on the packed row, an overflowed ray skipped -- and the call-by-call route;
+    nothing else of the marched step's restrictions is lifted.  Like the opacity term it makes every sample with positive density of a ray
+    that is not yet opaque live, so early compacted steps run over more points.  lambda_dist = 0 (the default): the step without it,
+    launch for launch.  ValueError for a negative or non-finite lambda_dist."""
 
     def __init__(self, render_kwargs_train, H, W, K, near, far, lrate=5e-4, lrate_decay=250, decay=True,
                  beta1=0.9, beta2=0.999, eps=1e-8, occupancy=None, occupancy_every=16, occupancy_warmup=256, occupancy_cells=None,
-                 lambda_depth=0., lambda_acc=0., tighten=False, march=None, march_cap=128, march_after=0, bkgd=None):
+                 lambda_depth=0., lambda_acc=0., tighten=False, march=None, march_cap=128, march_after=0, bkgd=None,
+                 lambda_dist=0.):
         kw = render_kwargs_train
         self._kw = kw
         self.net_c = kw['network_fn']
@@ -326,6 +339,11 @@ class Trainer:
         self._ma_key = None
         self.bkgd = bkgd
         self._bk = None          # fn_step_bkgd of the current step (None: no background)
+        self.lambda_dist = float(lambda_dist)
+        self._dist_zero = torch.zeros(2, device=self.flat.device, dtype=torch.float32)
+        self.dist_losses = self._dist_zero
+        self._dist = None        # fn_step_dist of the current step (None: the term is off)
+        self._check_dist()
         self._check_occupancy()
         self._check_march()
         self.repack()
@@ -434,6 +452,36 @@ class Trainer:
     def _bkgd_floats(n):
         return 2 * ((3 * n + 63) // 64 * 64) + 2 * ((n + 63) // 64 * 64)
 
+    def _check_dist(self):
+        """Whether the distortion term is on; ValueError for a weight that is no weight."""
+        if not (0. <= self.lambda_dist < float('inf')):
+            raise ValueError('Trainer: lambda_dist is a finite weight >= 0, not {!r}'.format(self.lambda_dist))
+        return self.lambda_dist != 0.
+
+    @staticmethod
+    def _dist_floats(n, S1, S0):
+        """The floats the distortion term appends to a step's block: ell1, ell0 [n], g_w1 [n,S1], g_w0 [n,S0] (S0 = 0: one pass), loss2d."""
+        r = lambda k: (k + 63) // 64 * 64      # noqa: E731
+        return 2 * r(n) + r(n * S1) + r(n * S0) + 64
+
+    def _new_step_dist(self, block, tail, n, S1, S0):
+        """fn_step_dist of a step whose block has _dist_floats(n, S1, S0) floats behind `tail`; dist_losses becomes its loss2d.
+        -> (struct, regions of its tensors)"""
+        r = lambda k: (k + 63) // 64 * 64      # noqa: E731
+        o_ell1, o_ell0, o_gw1 = tail, tail + r(n), tail + 2 * r(n)
+        o_gw0 = o_gw1 + r(n * S1)
+        o_loss = o_gw0 + r(n * S0)
+        base = block.data_ptr()
+        d = _lib.StepDist()
+        d.lambda_dist = self.lambda_dist
+        d.ell1, d.g_w1, d.loss2d = base + 4 * o_ell1, base + 4 * o_gw1, base + 4 * o_loss
+        regions = {'ell1': (o_ell1, (n,)), 'g_w1': (o_gw1, (n, S1))}
+        if S0:
+            d.ell0, d.g_w0 = base + 4 * o_ell0, base + 4 * o_gw0
+            regions.update(ell0=(o_ell0, (n,)), g_w0=(o_gw0, (n, S0)))
+        self.dist_losses = block[o_loss:o_loss + 2]
+        return d, regions
+
     def forward_backward(self, rays_o, rays_d, target, leaf_tag=None, table=None, max_leaves=0, t_rand=None, u=None,
                          n_global=None, alpha=None, bkgd=None, depth=None, depth_weight=None, acc=None, acc_weight=None):
         if self.march is not None:
@@ -472,7 +520,16 @@ class Trainer:
             maps = dict(maps or {}, g_acc1=ga1)
             if ga0 is not None:
                 maps['g_acc0'] = ga0
-        _backward_core(saved, g, g0, counts=self.live_counts if live else None, maps=maps)
+        wg = None
+        self.dist_losses = self._dist_zero
+        if self._check_dist():      # the same launches, behind the other terms', as fastnerf_train_step_dist makes
+            coef = ctypes.c_float(scale).value * ctypes.c_float(self.lambda_dist).value / n
+            out['dist_map'], gw1 = ops.distortion(out['weights'], out['z_vals'], rays11, self.lindisp, coef=coef)
+            wg = {'g_w1': gw1}
+            if 'weights0' in out:
+                out['dist0'], wg['g_w0'] = ops.distortion(out['weights0'], out['z0'], rays11, self.lindisp, coef=coef)
+            self.dist_losses = ops.distortion_mean(out['dist_map'], out.get('dist0'))
+        _backward_core(saved, g, g0, counts=self.live_counts if live else None, maps=maps, weight_grads=wg)
         self.net_c.collect_grads()          # (no-ops with view directions: the kernels write the parameters' gradients)
         if self.net_f is not None and self.net_f is not self.net_c:
             self.net_f.collect_grads()
@@ -583,7 +640,9 @@ class Trainer:
         aux = self._aux_terms(n, depth, depth_weight, acc, acc_weight)
         row = (n + 63) // 64 * 64
         aux_floats = 4 * row + 64 if aux else 0
-        block, hold = self._fill_step(a, self._regions, self._block_floats + aux_floats + (self._bkgd_floats(n) if bt else 0), rays_o,
+        bkgd_floats = self._bkgd_floats(n) if bt else 0
+        dist_floats = self._dist_floats(n, S1, S0 if Ni > 0 else 0) if self._check_dist() else 0
+        block, hold = self._fill_step(a, self._regions, self._block_floats + aux_floats + bkgd_floats + dist_floats, rays_o,
                                       rays_d, target, leaf_tag, table, max_leaves, n_global)
         base = block.data_ptr()
         if t_rand is not None:
@@ -631,6 +690,10 @@ class Trainer:
             self._bk, _ = self._new_step_bkgd(bt, block, tail, n)
             regions, names = dict(regions, bkgd_used=(tail, (n, 3))), dict(names, bkgd='bkgd_used')
             hold.append(bt)
+        self._dist, self.dist_losses = None, self._dist_zero
+        if dist_floats:
+            self._dist, dregions = self._new_step_dist(block, self._block_floats + aux_floats + bkgd_floats, n, S1, S0 if Ni > 0 else 0)
+            regions, names = dict(regions, **dregions), dict(names, dist_map='ell1', **({'dist0': 'ell0'} if Ni > 0 else {}))
         self._hold = hold       # inputs stay referenced until the next step is prepared (the launches are asynchronous)
         out = _StepOut(block, regions, names)
         return a, out, _region(block, self._regions, 'loss2'), live
@@ -672,7 +735,9 @@ class Trainer:
             x.list_ws = t3.data_ptr()
             x.counts = self.march_counts.data_ptr()
         a, x = self._ma
-        block, hold = self._fill_step(a, self._march_regions, self._march_floats + (self._bkgd_floats(n) if bt else 0), rays_o, rays_d,
+        bkgd_floats = self._bkgd_floats(n) if bt else 0
+        dist_floats = self._dist_floats(n, C, 0) if self._check_dist() else 0
+        block, hold = self._fill_step(a, self._march_regions, self._march_floats + bkgd_floats + dist_floats, rays_o, rays_d,
                                       target, leaf_tag, table, max_leaves, n_global)
         kidx = torch.empty(n, C, device=dev, dtype=torch.int32)
         overflow = torch.empty(n, device=dev, dtype=torch.uint8)
@@ -696,9 +761,20 @@ class Trainer:
         if bt:      # (the seed of 'random' is drawn here: after the shift's)
             self._bk, out['bkgd'] = self._new_step_bkgd(bt, block, self._march_floats, n)
             hold.append(bt)
+        self._dist, self.dist_losses = None, self._dist_zero
+        if dist_floats:
+            self._dist, dregions = self._new_step_dist(block, self._march_floats + bkgd_floats, n, C, 0)
+            self._march_dist_regions = dregions      # (with _march_block: g_w1 of the step, for inspection)
+            out['dist_map'] = _region(block, dregions, 'ell1')
         return a, x, out, view('loss2')
 
     def _march_call(self, a, x, phases):
+        if self._dist is not None:    # (given in every phase call, like fn_step_bkgd)
+            _lib.check(_lib.lib().fastnerf_train_step_march_dist(ctypes.byref(a), ctypes.byref(x),
+                                                                 None if self._bk is None else ctypes.byref(self._bk),
+                                                                 ctypes.byref(self._dist), int(phases), _lib.stream()),
+                       'fastnerf_train_step_march_dist')
+            return
         if self._bk is not None:      # (given in every phase call)
             _lib.check(_lib.lib().fastnerf_train_step_march_bkgd(ctypes.byref(a), ctypes.byref(x), ctypes.byref(self._bk), int(phases),
                                                                  _lib.stream()), 'fastnerf_train_step_march_bkgd')
@@ -707,6 +783,11 @@ class Trainer:
                    'fastnerf_train_step_march')
 
     def _fused_call(self, a, phases):
+        if self._dist is not None:     # (like fn_step_aux, given in every phase call)
+            _lib.check(_lib.lib().fastnerf_train_step_dist(ctypes.byref(a), None if self._aux is None else ctypes.byref(self._aux),
+                                                           None if self._bk is None else ctypes.byref(self._bk), ctypes.byref(self._dist),
+                                                           int(phases), _lib.stream()), 'fastnerf_train_step_dist')
+            return
         if self._bk is not None:       # (like fn_step_aux, given in every phase call)
             _lib.check(_lib.lib().fastnerf_train_step_bkgd(ctypes.byref(a), None if self._aux is None else ctypes.byref(self._aux),
                                                            ctypes.byref(self._bk), int(phases), _lib.stream()), 'fastnerf_train_step_bkgd')
@@ -742,6 +823,7 @@ class Trainer:
         self.grad[sl].zero_()
         _burn_seeds(seeds)
         self.aux_losses = self._aux_zero
+        self.dist_losses = self._dist_zero
         self._host_update(sl, overlap)
         return torch.zeros(2, device=self.grad.device), {}
 
@@ -753,6 +835,7 @@ class Trainer:
         two = self.N_importance > 0 and self.net_f is not None and self.net_f is not self.net_c
         overlap = self.world > 1 and two and self.overlap_allreduce and self.grad.numel() == 2 * Nn
         KC = self._check_march()            # (read on every step, like perturb and white_bkgd)
+        self._check_dist()
         if KC is not None and self._aux_terms(n, depth, depth_weight, acc, acc_weight):
             raise ValueError('Trainer: the marched step has no depth / opacity terms (lambda_depth / lambda_acc with a target)')
         marching = KC is not None and self.occupancy_steps >= int(self.march_after)
@@ -940,7 +1023,7 @@ def train(images, poses, H, W, focal, args, near=2., far=6., device='cuda', log=
                       occupancy_every=getattr(args, 'occupancy_every', 16), occupancy_warmup=getattr(args, 'occupancy_warmup', 256))
     random_bkgd = bool(getattr(args, 'random_bkgd', False))
     trainer = Trainer(kw_train, H, W, K, near, far, lrate=args.lrate, lrate_decay=args.lrate_decay, bkgd='random' if random_bkgd else None,
-                      **occ_kw)
+                      lambda_dist=float(getattr(args, 'lambda_dist', 0.)), **occ_kw)
     trainer.global_iter = global_iter
     if len(optimizer.state_dict()['state']) > 0:   # create_nerf restored a checkpoint (ours or the reference's)
         trainer.load_torch_optimizer(optimizer)

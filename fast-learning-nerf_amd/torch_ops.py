@@ -16,6 +16,8 @@ in this package.
                                                                                   differentiable w.r.t. raw through rgb
     torch.ops.fastnerf.raw2outputs_full(raw, z, rays11, noise, white_bkgd)     -> (rgb, disp, acc, weights, depth)   render.py:149-192
                                                                                   differentiable w.r.t. raw through all five
+    torch.ops.fastnerf.distortion(w, z, rays11, lindisp, skip)                 -> ell [n]            the distortion loss of mip-NeRF 360
+                                                                                  differentiable w.r.t. w (z, near, far are constants)
     torch.ops.fastnerf.sample_pdf_merge(z, weights, Ni, det, u, seed)          -> (z_all, z_samples, z_std)          run_nerf_helpers.py:112-155 + render.py:283
     torch.ops.fastnerf.mse_leafmax(rgb, rgb0, target, grad_scale, leaf_tag, max_leaves, table) -> (loss2, g_rgb, g_rgb0)   (table mutated)
     torch.ops.fastnerf.adam_step(params, grads, m, v, lr, step, beta1, beta2, eps)             -> ()  (params, m, v mutated)
@@ -170,6 +172,41 @@ def _r2o_full_backward(ctx, g_rgb, g_disp, g_acc, g_w, g_depth):
 raw2outputs_full.register_autograd(_r2o_full_backward, setup_context=_r2o_full_setup)
 
 
+@_lib_def('fastnerf::distortion', mutates_args=())
+def distortion(w: Tensor, z: Tensor, rays11: Tensor, lindisp: bool, skip: Optional[Tensor]) -> Tensor:
+    return ops.distortion(w.contiguous(), z.contiguous(), rays11.contiguous(), lindisp, skip, want=('ell',))[0]
+
+
+@distortion.register_fake
+def _(w, z, rays11, lindisp, skip):
+    return z.new_empty((z.shape[0],))
+
+
+@_lib_def('fastnerf::distortion_bwd', mutates_args=())
+def distortion_bwd(w: Tensor, z: Tensor, rays11: Tensor, lindisp: bool, skip: Optional[Tensor], g_ell: Tensor) -> Tensor:
+    return ops.distortion(w.contiguous(), z.contiguous(), rays11.contiguous(), lindisp, skip, g_up=g_ell.contiguous(), want=('g_w',))[1]
+
+
+@distortion_bwd.register_fake
+def _(w, z, rays11, lindisp, skip, g_ell):
+    return z.new_empty(z.shape)
+
+
+def _dist_setup(ctx, inputs, output):
+    w, z, rays11, lindisp, skip = inputs
+    ctx.save_for_backward(w, z, rays11, skip if skip is not None else w.new_empty(0, dtype=torch.uint8))
+    ctx.has_skip, ctx.lindisp = skip is not None, lindisp
+
+
+def _dist_backward(ctx, g_ell):
+    # the same kernel with the upstream gradient per ray: g_w[r][i] = g_ell[r] dl_r/dw_i (depths, near and far are constants)
+    w, z, rays11, skip = ctx.saved_tensors
+    return torch.ops.fastnerf.distortion_bwd(w, z, rays11, ctx.lindisp, skip if ctx.has_skip else None, g_ell), None, None, None, None
+
+
+distortion.register_autograd(_dist_backward, setup_context=_dist_setup)
+
+
 @_lib_def('fastnerf::sample_pdf_merge', mutates_args=())
 def sample_pdf_merge(z: Tensor, weights: Tensor, Ni: int, det: bool, u: Optional[Tensor], seed: int) -> Tuple[Tensor, Tensor, Tensor]:
     return ops.sample_pdf_merge(z, weights, Ni, det=det, u=u, seed=seed)
@@ -208,4 +245,4 @@ def _(draw):
 
 
 OPS = ['gen_rays_pixels', 'pack_rays', 'sample_coarse', 'posenc', 'mlp_fwd', 'raw2outputs', 'raw2outputs_bwd', 'raw2outputs_full',
-       'raw2outputs_bwd_full', 'sample_pdf_merge', 'mse_leafmax', 'adam_step', 'compact_live']
+       'raw2outputs_bwd_full', 'distortion', 'distortion_bwd', 'sample_pdf_merge', 'mse_leafmax', 'adam_step', 'compact_live']

@@ -875,6 +875,75 @@ int fastnerf_train_step_bkgd(const fn_step_args* args, const fn_step_aux* aux, c
 int fastnerf_train_step_march_bkgd(const fn_step_args* args, const fn_step_march* march, const fn_step_bkgd* bk, int phases,
                                    fn_stream_t stream);
 
+/* ---- distortion loss on the ray weights (csrc/distortion.hip, render.cpp) ------------------------------------------------------------
+ * The regulariser of mip-NeRF 360 (Barron et al. 2022, eq. 15) that pulls the weight of a ray together: it removes floaters and
+ * half-transparent fog, which the colour loss alone does not punish.  Per ray, with samples z_0 <= ... <= z_{S-1}, weights w_i >= 0 and
+ * near / far = columns 6 / 7 of its rays11 row as the forward left them (tightened bounds and marched rows included):
+ *   edges     e_i = z_i (i < S), e_S = max(far, z_{S-1}); interval i is [e_i, e_{i+1}].  In a marched row the interval of live sample b
+ *             ends at its closing entry; closing and padding slots carry w = 0.
+ *   t(x)      (x - near) / (far - near), or with lindisp (1/near - 1/x) / (1/near - 1/far)
+ *   delta_i = t(e_{i+1}) - t(e_i),   m_i = (t(e_i) + t(e_{i+1})) / 2
+ *   l       = sum_i sum_j w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 delta_i
+ * Differentiable in w only: depths, near and far are constants, as they are everywhere in this renderer.
+ *   fastnerf_distortion   w, z [n,S], 1 <= S <= 512.  ell [n] = l; g_w [n,S] = coef * (g_up ? g_up[r] : 1) * dl_r/dw_i.  ell and g_w may
+ *                         each be NULL, not both.  A ray whose far - near (with lindisp 1/near - 1/far) is not a positive finite number,
+ *                         or whose byte in skip [n] (may be NULL) is non-zero, gets l = +0 and a row of +0.  All-zero weights give +0
+ *                         throughout; repeated depths are legal.  One wave per ray, shuffle scans, no atomics: bit-identical from run to
+ *                         run.  Nothing cancels (distortion.hip): with the fp32 inputs taken as exact, l and every dl/dw_i have a
+ *                         relative error of at most (2 S + 32) 2^-24.  n == 0 returns 0.
+ *   fastnerf_distortion_mean  loss2d[0] = mean of ell1 [n], loss2d[1] = mean of ell0 [n] (0 when ell0 == NULL): one workgroup, fixed
+ *                         order, fp64, as fastnerf_aux_loss sums; written, not accumulated.
+ *   fn_weight_grads       d(loss)/d(weights) of the image pass (g_w1 [n, N_samples + N_importance]; the only pass's [n, N_samples] when
+ *                         N_importance == 0) and of the coarse pass of two (g_w0 [n, N_samples]), each may be NULL.
+ *   fastnerf_render_rays_bwd_w / _bwd_live_w   the _maps entry points with that struct in front of the stream: a pass whose member is
+ *                         set goes through fastnerf_raw2outputs_bwd_full with it as g_w, and counts as a pass with a gradient even
+ *                         when it has no other.  wg == NULL: the _maps entry point, launch for launch.
+ *   fastnerf_train_step_dist / fastnerf_train_step_march_dist   fastnerf_train_step_bkgd / fastnerf_train_step_march_bkgd (aux and bk may
+ *                         be NULL as there) with the term:
+ *     FN_STEP_FORWARD  behind the loss launches of the step: fastnerf_distortion on the image pass's (w, z) into ell1 / g_w1 and, with two
+ *                      passes, on the coarse pass's into ell0 / g_w0, coef = grad_scale * lambda_dist / n; then fastnerf_distortion_mean
+ *                      into loss2d.  The marched step runs it on the packed row with skip = overflow (a truncated row is an artefact of
+ *                      the row: fastnerf_march_mask).  The step's loss is loss2[0] + loss2[1] + lambda_dist (loss2d[0] + loss2d[1]) (+
+ *                      the other terms).
+ *     backward phases  g_w1 / g_w0 go to the compositing backward of their pass (fn_weight_grads).
+ *   fn_step_dist is given in EVERY phase call, like fn_step_aux.  dist == NULL or lambda_dist == 0: the entry point without _dist, launch
+ *   for launch.  -1 before anything is enqueued, beside the refusals of those entry points: a negative or non-finite lambda_dist, a NULL
+ *   member that the phases need (g_w1, ell1, loss2d; with two passes g_w0, ell0), missing weights buffers (w0, w1) in a forward phase.
+ *   As with the opacity term, every sample with positive density on a ray that has not saturated receives a gradient and becomes
+ *   live: early compacted steps run over more points than without the term. */
+typedef struct fn_weight_grads {
+  const float *g_w1, *g_w0;
+} fn_weight_grads;
+typedef struct fn_step_dist {
+  float lambda_dist;
+  float *ell1, *ell0;               /* [n] each out: the per-ray l of the image pass / the coarse pass of two */
+  float *g_w1, *g_w0;               /* [n, S] of their pass, out: coef * dl/dw */
+  float* loss2d;                    /* [2] out: the batch means of ell1, ell0 */
+} fn_step_dist;
+int64_t fastnerf_step_dist_size(void);              /* sizeof(fn_step_dist): binding sanity check */
+int fastnerf_distortion(int64_t n, int S, const float* w, const float* z, const float* rays11, int lindisp, const uint8_t* skip,
+                        float coef, const float* g_up, float* ell, float* g_w, fn_stream_t stream);
+int fastnerf_distortion_mean(int64_t n, const float* ell1, const float* ell0, float* loss2d, fn_stream_t stream);
+int fastnerf_render_rays_bwd_w(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11, int white_bkgd,
+                               const float* g_rgb, const float* g_rgb0, const float* noise0, const float* noise1, const float* z0,
+                               const float* raw0, const float* act0, const float* z1, const float* raw1, const float* act1,
+                               const float* params_c, const float* packed_bwd_c, const float* params_f, const float* packed_bwd_f,
+                               float* draw_ws, float* dact_ws, float* partial_ws, float* grads_c, float* grads_f, const float* acc0,
+                               const float* depth0, const float* acc1, const float* depth1, const fn_map_grads* maps,
+                               const fn_weight_grads* wg, fn_stream_t stream);
+int fastnerf_render_rays_bwd_live_w(int math_mode, int64_t n, int N_samples, int N_importance, const float* rays11, int white_bkgd,
+                                    const float* g_rgb, const float* g_rgb0, const float* noise0, const float* noise1, const float* z0,
+                                    const float* raw0, const float* z1, const float* raw1, const float* params_c,
+                                    const float* packed_fwd_c, const float* packed_bwd_c, const float* params_f,
+                                    const float* packed_fwd_f, const float* packed_bwd_f, float* draw_ws, float* act_ws, float* dact_ws,
+                                    float* partial_ws, int32_t* live_ws, float* grads_c, float* grads_f, int32_t* counts_out,
+                                    const float* acc0, const float* depth0, const float* acc1, const float* depth1,
+                                    const fn_map_grads* maps, const fn_weight_grads* wg, fn_stream_t stream);
+int fastnerf_train_step_dist(const fn_step_args* args, const fn_step_aux* aux, const fn_step_bkgd* bk, const fn_step_dist* dist,
+                             int phases, fn_stream_t stream);
+int fastnerf_train_step_march_dist(const fn_step_args* args, const fn_step_march* march, const fn_step_bkgd* bk,
+                                   const fn_step_dist* dist, int phases, fn_stream_t stream);
+
 /* ---- density gradient: d(sigma)/d(x) through the fused MLP (csrc/sigma_grad.hip) -------------------------------------------------
  * sigma[n,S] (may be NULL) = raw[..., 3] of the forward of `math_mode` (0 exact fp32, 1 split-bf16 "bf16x3", 2 "bf16x6") at the
  * points o + d*z of fastnerf_mlp_fwd, and grad[n,S,3] = its gradient with respect to the point.  Both are taken BEFORE the ReLU
