@@ -671,16 +671,6 @@ static bool step_dist_ok(const fn_step_dist* d, bool two, int phases, const floa
   return true;
 }
 
-// the distortion term's launches of a forward phase, behind the loss launches: per pass l and coef * dl/dw, then the batch means
-static int step_dist_forward(const fn_step_args* a, const fn_step_dist* d, int S1, const float* w1, const float* z1, int S0, const float* w0,
-                             const float* z0, const uint8_t* skip, fn_stream_t stream) {
-  const float coef = (float)((double)a->grad_scale * (double)d->lambda_dist / (double)a->n);
-  if (int rc = fastnerf_distortion(a->n, S1, w1, z1, a->rays11, a->lindisp, skip, coef, nullptr, d->ell1, d->g_w1, stream)) return rc;
-  if (w0)
-    if (int rc = fastnerf_distortion(a->n, S0, w0, z0, a->rays11, a->lindisp, skip, coef, nullptr, d->ell0, d->g_w0, stream)) return rc;
-  return fastnerf_distortion_mean(a->n, d->ell1, w0 ? d->ell0 : nullptr, d->loss2d, stream);
-}
-
 // the refusals of a step with per-ray background colours (bk != NULL), before anything else of the step is looked at
 static bool step_bkgd_ok(const fn_step_args* a, const fn_step_bkgd* bk, bool two, int phases, const char* fname) {
   if (a->white_bkgd) {
@@ -719,6 +709,45 @@ static int step_pack_rays(const fn_step_args* a, fn_stream_t stream) {
   if (int rc = fastnerf_pack_rays(a->n, a->rays_o, a->rays_d, a->near_plane, a->far_plane, a->ndc, a->H, a->W, a->focal, a->rays11, stream))
     return rc;
   return (a->fwd_flags & FN_STEP_TIGHTEN) ? fastnerf_occ_ray_bounds(a->occ, nullptr, a->n, a->rays11, 1, nullptr, nullptr, stream) : 0;
+}
+
+// One pass as the loss launches see it: its maps, weights and depths [n, S], and the colour gradient they leave for its backward.
+struct LossPass { float* rgb; const float *acc, *depth, *w, *z; int S; float* g_rgb; };
+// the pass in the *0 buffers of fn_step_args: the coarse pass of two, the image pass of one, the marched row
+static LossPass loss_pass0(const fn_step_args* a, int S, float* g_rgb) { return {a->rgb0, a->acc0, a->depth0, a->w0, a->z0, S, g_rgb}; }
+
+// The loss launches of a forward phase, behind its render, of both steps: blend -> mse_leafmax -> depth / opacity terms -> overflow mask -> what the
+// blend sends back to acc -> distortion.  p1: the image pass; p0: the coarse pass of two, {} with one.  aux / bk / dist: NULL = the term is off.  mask:
+// NULL, or the marched step's overflow flags (never with aux).  A new term is a few lines here; its checks stay with the callers', before any launch.
+static int step_losses(const fn_step_args* a, const LossPass& p1, const LossPass& p0, const fn_step_aux* aux, const fn_step_bkgd* bk,
+                       const fn_step_dist* dist, const uint8_t* mask, fn_stream_t stream) {
+  const bool two = p0.S > 0;
+  int rc;
+  // (bk: white_bkgd is 0 -- the forward left the bare maps; the colours go behind them and behind the target here)
+  if (bk &&
+      (rc = fastnerf_bkgd_blend(a->n, bk->bkgd, bk->seed, bk->alpha, p1.acc, p0.acc, p1.rgb, p0.rgb, a->target, bk->target_ws, bk->bkgd_used, stream)))
+    return rc;
+  if ((rc = fastnerf_mse_leafmax(a->n, p1.rgb, p0.rgb, bk ? bk->target_ws : a->target, a->grad_scale, p1.g_rgb, p0.g_rgb, a->loss2, a->leaf_tag,
+                                 a->max_leaves, a->table, stream)))
+    return rc;
+  if (aux && (rc = fastnerf_aux_loss(a->n, p1.depth, p1.acc, p0.depth, p0.acc, aux->depth_target, aux->depth_weight, aux->acc_target, aux->acc_weight,
+                                     aux->lambda_depth, aux->lambda_acc, a->grad_scale, aux->g_depth1, aux->g_acc1, two ? aux->g_depth0 : nullptr,
+                                     two ? aux->g_acc0 : nullptr, aux->loss4, stream)))
+    return rc;
+  // a truncated row has lost what lies behind the cut: its colour error does not train the field (loss2 stays the mean over all rays)
+  if (mask && (rc = fastnerf_march_mask(a->n, mask, p1.g_rgb, stream))) return rc;
+  // what the blend sends back to acc, on top of the opacity term's rows when that term is on (behind the mask: an overflowed ray's g_acc is +-0)
+  if (bk) {
+    const bool add = aux && aux->acc_target;
+    if ((rc = fastnerf_bkgd_grad(a->n, bk->bkgd_used, p1.g_rgb, p0.g_rgb, add ? aux->g_acc1 : nullptr, (add && two) ? aux->g_acc0 : nullptr,
+                                 bk->g_acc1, two ? bk->g_acc0 : nullptr, stream)))
+      return rc;
+  }
+  if (!dist) return 0;      // per pass l and coef * dl/dw (skip = mask: a truncated row's weights are an artefact too), then the batch means
+  const float coef = (float)((double)a->grad_scale * (double)dist->lambda_dist / (double)a->n);
+  if ((rc = fastnerf_distortion(a->n, p1.S, p1.w, p1.z, a->rays11, a->lindisp, mask, coef, nullptr, dist->ell1, dist->g_w1, stream))) return rc;
+  if (two && (rc = fastnerf_distortion(a->n, p0.S, p0.w, p0.z, a->rays11, a->lindisp, mask, coef, nullptr, dist->ell0, dist->g_w0, stream))) return rc;
+  return fastnerf_distortion_mean(a->n, dist->ell1, two ? dist->ell0 : nullptr, dist->loss2d, stream);
 }
 
 static bool step_update_ok(const fn_step_args* a, const char* fname) {
@@ -815,28 +844,9 @@ static int train_step(const fn_step_args* a, const fn_step_aux* aux, const fn_st
                                           a->w0, a->depth0, a->z1, a->z_samples, a->z_std, a->raw1, save ? a->act1 : nullptr,
                                           a->rgb1, a->disp1, a->acc1, a->w1, a->depth1, save ? 0 : fwd_flags, stream)))
       return rc;
-    // (bk: white_bkgd is 0 -- the forward left the bare maps; the colours go behind them and behind the target here)
-    if (bk && (rc = fastnerf_bkgd_blend(a->n, bk->bkgd, bk->seed, bk->alpha, two ? a->acc1 : a->acc0, two ? a->acc0 : nullptr,
-                                        two ? a->rgb1 : a->rgb0, two ? a->rgb0 : nullptr, a->target, bk->target_ws, bk->bkgd_used, stream)))
-      return rc;
-    if ((rc = fastnerf_mse_leafmax(a->n, two ? a->rgb1 : a->rgb0, two ? a->rgb0 : nullptr, bk ? bk->target_ws : a->target, a->grad_scale,
-                                   a->g_rgb, two ? a->g_rgb0 : nullptr, a->loss2, a->leaf_tag, a->max_leaves, a->table, stream)))
-      return rc;
-    if (aux && (rc = fastnerf_aux_loss(a->n, two ? a->depth1 : a->depth0, two ? a->acc1 : a->acc0, two ? a->depth0 : nullptr,
-                                       two ? a->acc0 : nullptr, aux->depth_target, aux->depth_weight, aux->acc_target,
-                                       aux->acc_weight, aux->lambda_depth, aux->lambda_acc, a->grad_scale, aux->g_depth1,
-                                       aux->g_acc1, two ? aux->g_depth0 : nullptr, two ? aux->g_acc0 : nullptr, aux->loss4, stream)))
-      return rc;
-    // what the blend sends back to acc, on top of the opacity term's rows when that term is on
-    if (bk) {
-      const bool add = aux && aux->acc_target;
-      if ((rc = fastnerf_bkgd_grad(a->n, bk->bkgd_used, a->g_rgb, two ? a->g_rgb0 : nullptr, add ? aux->g_acc1 : nullptr,
-                                   (add && two) ? aux->g_acc0 : nullptr, bk->g_acc1, two ? bk->g_acc0 : nullptr, stream)))
-        return rc;
-    }
-    if (dist && (rc = step_dist_forward(a, dist, a->N_samples + a->N_importance, two ? a->w1 : a->w0, two ? a->z1 : a->z0, a->N_samples,
-                                        two ? a->w0 : nullptr, a->z0, nullptr, stream)))
-      return rc;
+    const LossPass p0 = loss_pass0(a, a->N_samples, two ? a->g_rgb0 : a->g_rgb);
+    const LossPass p1 = {a->rgb1, a->acc1, a->depth1, a->w1, a->z1, a->N_samples + a->N_importance, a->g_rgb};
+    if ((rc = step_losses(a, two ? p1 : p0, two ? p0 : LossPass{}, aux, bk, dist, nullptr, stream))) return rc;
   }
   if (passes) {
     fn_map_grads mg = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -946,18 +956,7 @@ static int train_step_march(const fn_step_args* a, const fn_step_march* mx, cons
     if ((rc = fastnerf_raw2outputs_fwd(n, C, a->raw0, a->z0, a->rays11, nullptr, a->white_bkgd, a->rgb0, a->disp0, a->acc0, a->w0, a->depth0,
                                        stream)))
       return rc;
-    if (bk && (rc = fastnerf_bkgd_blend(n, bk->bkgd, bk->seed, bk->alpha, a->acc0, nullptr, a->rgb0, nullptr, a->target, bk->target_ws,
-                                        bk->bkgd_used, stream)))
-      return rc;
-    if ((rc = fastnerf_mse_leafmax(n, a->rgb0, nullptr, bk ? bk->target_ws : a->target, a->grad_scale, a->g_rgb, nullptr, a->loss2,
-                                   a->leaf_tag, a->max_leaves, a->table, stream)))
-      return rc;
-    // a truncated row has lost what lies behind the cut: its colour error does not train the field (loss2 stays the mean over all rays)
-    if ((rc = fastnerf_march_mask(n, mx->overflow, a->g_rgb, stream))) return rc;
-    // (behind the mask: an overflowed ray's g_acc is +-0)
-    if (bk && (rc = fastnerf_bkgd_grad(n, bk->bkgd_used, a->g_rgb, nullptr, nullptr, nullptr, bk->g_acc1, nullptr, stream))) return rc;
-    // skip = overflow: a truncated row's weights are an artefact of the row too -- l = 0 and a zero g_w row
-    if (dist && (rc = step_dist_forward(a, dist, C, a->w0, a->z0, 0, nullptr, nullptr, mx->overflow, stream))) return rc;
+    if ((rc = step_losses(a, loss_pass0(a, C, a->g_rgb), {}, nullptr, bk, dist, mx->overflow, stream))) return rc;
   }
   if (bwd) {
     // the single pass, built directly (one pass: both members of BwdPasses name it); its counters are the coarse pair, as after a one-pass

@@ -18,7 +18,7 @@ import torch
 
 from . import _lib, flat_params, ops, parallel
 from .model import NeRF, noview_slices
-from .render import LivePolicy, _Workspace, get_compact, _backward_core, _burn_seeds, _forward_core, _next_seed, render, render_path  # noqa: F401
+from .render import LivePolicy, _Workspace, get_compact, _backward_core, _forward_core, _next_seed, render, render_path  # noqa: F401
 from .run_nerf_helpers import get_embedder, img2mse, mse2psnr
 from .tree import QuadTreeManager
 
@@ -189,6 +189,14 @@ class _StepOut:
         return len(self._names)
 
 
+def _lay_out(shapes, regions, off):
+    """`regions` with (name, shape) of `shapes` appended from float `off` on, each on a 256-byte boundary.  -> (regions, the end)"""
+    for name, shape in shapes:
+        regions[name] = (off, shape)
+        off += (math.prod(shape) + 63) // 64 * 64
+    return regions, off
+
+
 def _step_regions(n, S0, Ni):
     """name -> (offset, shape) of the per-step tensors inside one fp32 block (every region starts on a 256-byte boundary),
     and the block's size."""
@@ -198,11 +206,42 @@ def _step_regions(n, S0, Ni):
     if Ni > 0:
         shapes += [('z1', (n, S1)), ('z_samples', (n, Ni)), ('z_std', (n,)), ('raw1', (n, S1, 4)), ('rgb1', (n, 3)),
                    ('disp1', (n,)), ('acc1', (n,)), ('w1', (n, S1)), ('depth1', (n,)), ('g_rgb0', (n, 3))]
-    regions, off = {}, 0
-    for name, shape in shapes:
-        regions[name] = (off, shape)
-        off += (math.prod(shape) + 63) // 64 * 64
-    return regions, off
+    return _lay_out(shapes, {}, 0)
+
+
+def _term_regions(base, size, n, S0, Ni, aux=False, bkgd=False, dist=False):
+    """The table `base` of `size` floats (_step_regions(n, S0, Ni); not built again, and handed back as it is when no term is on)
+    with the tensors of the optional terms that are on behind it, in the order aux | bkgd | dist: region '<term>.<member>' is what
+    the pointer member of that name of the term's struct (fn_step_aux / fn_step_bkgd / fn_step_dist) points to.  A new term is one
+    more list here.  -> (regions, the block's size)"""
+    shapes = []
+    if aux:
+        shapes += [('aux.' + k, (n,)) for k in ('g_depth1', 'g_acc1', 'g_depth0', 'g_acc0')] + [('aux.loss4', (4,))]
+    if bkgd:
+        shapes += [('bkgd.bkgd_used', (n, 3)), ('bkgd.target_ws', (n, 3)), ('bkgd.g_acc1', (n,)), ('bkgd.g_acc0', (n,))]
+    if dist:      # (the *0 rows of aux and bkgd, and ell0, are laid out with one pass too; g_w0 would be empty)
+        shapes += ([('dist.ell1', (n,)), ('dist.ell0', (n,)), ('dist.g_w1', (n, S0 + Ni))] + ([('dist.g_w0', (n, S0))] if Ni > 0 else [])
+                   + [('dist.loss2d', (2,))])
+    return _lay_out(shapes, dict(base), size) if shapes else (base, size)
+
+
+def _term_table(regions, term):
+    """The regions of one optional term under its members' names."""
+    return {name[len(term) + 1:]: r for name, r in regions.items() if name.startswith(term + '.')}
+
+
+def _term_struct(cls, term, block, regions, **members):
+    """The ctypes struct of a term: every pointer member that has a region points into `block`; `members`: the others."""
+    s, base = cls(), block.data_ptr()
+    for name, (off, _) in _term_table(regions, term).items():
+        setattr(s, name, base + 4 * off)
+    for name, value in members.items():
+        setattr(s, name, value)
+    return s
+
+
+def _ref(struct):
+    return None if struct is None else ctypes.byref(struct)
 
 
 _OUT_NAMES_2 = {'rgb_map': 'rgb1', 'disp_map': 'disp1', 'acc_map': 'acc1', 'raw': 'raw1', 'rgb0': 'rgb0', 'disp0': 'disp0',
@@ -322,7 +361,8 @@ class Trainer:
                       and (self.N_importance == 0 or (self.net_f is not None and self.net_f is not self.net_c)))
         self.overlap_allreduce = os.environ.get('FASTNERF_OVERLAP_ALLREDUCE', '1') != '0'
         self._sa = None          # fn_step_args of the fused path
-        self._sa_key = None
+        self._cache = {}         # route -> (key, fn_step_args, its regions, their size, keep-alive list): _begin_step
+        self._last = None        # (block, regions) of the last prepared step
         self.occupancy = occupancy
         self.occupancy_every, self.occupancy_warmup = max(1, int(occupancy_every)), int(occupancy_warmup)
         self.occupancy_cells = occupancy_cells
@@ -336,7 +376,6 @@ class Trainer:
         self.march, self.march_cap, self.march_after = march, march_cap, march_after
         self.march_counts = None if march is None else torch.zeros(2, device=self.flat.device, dtype=torch.int32)
         self._ma = None          # fn_step_args / fn_step_march of the marched step
-        self._ma_key = None
         self.bkgd = bkgd
         self._bk = None          # fn_step_bkgd of the current step (None: no background)
         self.lambda_dist = float(lambda_dist)
@@ -429,58 +468,32 @@ class Trainer:
             assert alpha.numel() == n, 'alpha: [n]'
         return {'bkgd': bkgd, 'alpha': alpha}
 
-    def _draws_bkgd(self, bkgd):
-        """Whether a step with these injected colours draws the seed of the 'bkgd' stream."""
-        return bkgd is None and isinstance(self.bkgd, str) and self.bkgd == 'random'
+    def _step_seeds(self, marching, t_rand=None, u=None, march_u=None, bkgd=None):
+        """The seeds of one step, drawn in the step's one order -- a dense step: sigma noise, coarse jitter, fine uniforms, background; a
+        marched step: shift, background (the draws of render._forward_core, then the background's) -- `_next_seed()` where the step
+        wants the draw, else 0.  t_rand / u / march_u / bkgd: what the caller injects instead.  A step on an empty batch calls this too
+        and drops the result: the host RNG moves alike."""
+        if marching:
+            wants = [('shift', self.perturb and march_u is None)]
+        else:
+            wants = [('noise', self.raw_noise_std > 0.), ('seed0', self.perturb and t_rand is None),
+                     ('seed1', self.N_importance > 0 and self.perturb and u is None)]
+        wants.append(('bkgd', bkgd is None and isinstance(self.bkgd, str) and self.bkgd == 'random'))
+        return {name: _next_seed() if want else 0 for name, want in wants}
 
-    def _new_step_bkgd(self, bt, block, tail, n):
-        """fn_step_bkgd of a step whose block has 2 x [n,3] + 2 x [n] floats (_bkgd_floats) behind `tail`.  -> (struct, bkgd_used view)"""
-        row, row3 = (n + 63) // 64 * 64, (3 * n + 63) // 64 * 64
-        base = block.data_ptr()
-        k = _lib.StepBkgd()
-        k.bkgd = None if bt['bkgd'] is None else bt['bkgd'].data_ptr()
-        k.seed = _next_seed() if bt['bkgd'] is None else 0
-        k.alpha = None if bt['alpha'] is None else bt['alpha'].data_ptr()
-        k.bkgd_used, k.target_ws = base + 4 * tail, base + 4 * (tail + row3)
-        k.g_acc1, k.g_acc0 = base + 4 * (tail + 2 * row3), base + 4 * (tail + 2 * row3 + row)
-        at = lambda off, *shape: block[tail + off:tail + off + math.prod(shape)].view(shape)      # noqa: E731
-        # (the step's own tensors, for inspection: the blended target and the rows handed to the compositing backward)
-        self._bk_views = {'target': at(row3, n, 3), 'g_acc1': at(2 * row3, n), 'g_acc0': at(2 * row3 + row, n)}
-        return k, at(0, n, 3)
-
-    @staticmethod
-    def _bkgd_floats(n):
-        return 2 * ((3 * n + 63) // 64 * 64) + 2 * ((n + 63) // 64 * 64)
+    # For inspection, of the last prepared step on either route (self._last: its block and regions): the table, the marched step's block,
+    # its distortion regions (g_w1), and the blended target and the rows the background hands to the compositing backward.
+    _regions = _march_regions = property(lambda self: self._last[1])
+    _march_block = property(lambda self: self._last[0])
+    _march_dist_regions = property(lambda self: _term_table(self._last[1], 'dist'))
+    _bk_views = property(lambda self: {k: _region(*self._last, 'bkgd.' + member)
+                                       for k, member in (('target', 'target_ws'), ('g_acc1', 'g_acc1'), ('g_acc0', 'g_acc0'))})
 
     def _check_dist(self):
         """Whether the distortion term is on; ValueError for a weight that is no weight."""
         if not (0. <= self.lambda_dist < float('inf')):
             raise ValueError('Trainer: lambda_dist is a finite weight >= 0, not {!r}'.format(self.lambda_dist))
         return self.lambda_dist != 0.
-
-    @staticmethod
-    def _dist_floats(n, S1, S0):
-        """The floats the distortion term appends to a step's block: ell1, ell0 [n], g_w1 [n,S1], g_w0 [n,S0] (S0 = 0: one pass), loss2d."""
-        r = lambda k: (k + 63) // 64 * 64      # noqa: E731
-        return 2 * r(n) + r(n * S1) + r(n * S0) + 64
-
-    def _new_step_dist(self, block, tail, n, S1, S0):
-        """fn_step_dist of a step whose block has _dist_floats(n, S1, S0) floats behind `tail`; dist_losses becomes its loss2d.
-        -> (struct, regions of its tensors)"""
-        r = lambda k: (k + 63) // 64 * 64      # noqa: E731
-        o_ell1, o_ell0, o_gw1 = tail, tail + r(n), tail + 2 * r(n)
-        o_gw0 = o_gw1 + r(n * S1)
-        o_loss = o_gw0 + r(n * S0)
-        base = block.data_ptr()
-        d = _lib.StepDist()
-        d.lambda_dist = self.lambda_dist
-        d.ell1, d.g_w1, d.loss2d = base + 4 * o_ell1, base + 4 * o_gw1, base + 4 * o_loss
-        regions = {'ell1': (o_ell1, (n,)), 'g_w1': (o_gw1, (n, S1))}
-        if S0:
-            d.ell0, d.g_w0 = base + 4 * o_ell0, base + 4 * o_gw0
-            regions.update(ell0=(o_ell0, (n,)), g_w0=(o_gw0, (n, S0)))
-        self.dist_losses = block[o_loss:o_loss + 2]
-        return d, regions
 
     def forward_backward(self, rays_o, rays_d, target, leaf_tag=None, table=None, max_leaves=0, t_rand=None, u=None,
                          n_global=None, alpha=None, bkgd=None, depth=None, depth_weight=None, acc=None, acc_weight=None):
@@ -545,7 +558,7 @@ class Trainer:
         tag = ops.get_math()
         if ops.packed_tag(self.pc[0]) != tag:
             self.repack()
-            self._sa_key = self._ma_key = None
+            self._cache.clear()
         return tag
 
     def _new_step_args(self, n, S0, Ni, dev):
@@ -603,67 +616,88 @@ class Trainer:
         a.grad_scale = 1.0 if n_global is None else float(n) / float(n_global)
         return block, hold
 
-    # ---- fused route: one fastnerf_train_step call per phase group ------------------------------------------------
+    def _begin_step(self, route, S0, Ni, extra, batch, given, alpha=None, bkgd=None, aux=(None,) * 4):
+        """What preparing a step is on both routes; _fused_prepare and _march_prepare add what differs.  In order: the background's terms,
+        the GPU check, the grid's refusals, the math mode; the arguments of `route` ('fused' | 'march'), cached under (n, *extra, device,
+        stream, math tag); the depth / opacity terms; the step's seeds (_step_seeds); one block laid out for the terms that are on
+        (_term_regions) and fn_step_args filled (_fill_step); self._aux / _bk / _dist (None: the term is off) pointing into the block, and
+        aux_losses / dist_losses as its views.  batch: (rays_o, rays_d, target, leaf_tag, table, max_leaves, n_global); given: what the
+        caller injects instead of draws, by _step_seeds' names; aux: (depth, depth_weight, acc, acc_weight).
+        -> (args, its keep-alive list, whether the args were built anew, block, regions, out key -> region of the terms' outputs, seeds,
+        hold: what stays referenced until the next step is prepared -- the launches are asynchronous -- for the route to append to)"""
+        n, dev = batch[0].shape[0], batch[0].device
+        bt = self._bkgd_terms(n, dev, alpha, bkgd)
+        ops.require_gpu(*batch[:5], *given.values())
+        self._check_occupancy()
+        key = (n,) + extra + (str(dev), torch.cuda.current_stream(dev).cuda_stream, self._follow_math())
+        c = self._cache.get(route)
+        fresh = c is None or c[0] != key
+        if fresh:
+            c = self._cache[route] = (key,) + self._new_step_args(n, S0, Ni, dev)
+        _, a, base, size, keep = c
+        aux = self._aux_terms(n, *aux)
+        seeds = self._step_seeds(route == 'march', bkgd=bkgd, **given)
+        dist = self._check_dist()
+        regions, size = _term_regions(base, size, n, S0, Ni, aux=bool(aux), bkgd=bt is not None, dist=dist)
+        block, hold = self._fill_step(a, base, size, *batch)
+        self._last = (block, regions)
+        self._aux = self._bk = self._dist = None
+        self.aux_losses, self.dist_losses = self._aux_zero, self._dist_zero
+        names = {}
+        if aux:
+            self._aux = _term_struct(_lib.StepAux, 'aux', block, regions, lambda_depth=aux['lambda_depth'], lambda_acc=aux['lambda_acc'],
+                                     **{k: _lib.ptr(aux.get(k)) for k in ('depth_target', 'depth_weight', 'acc_target', 'acc_weight')})
+            self.aux_losses = _region(block, regions, 'aux.loss4')
+            hold += [aux, self.aux_losses]
+        if bt is not None:
+            self._bk = _term_struct(_lib.StepBkgd, 'bkgd', block, regions, bkgd=_lib.ptr(bt['bkgd']), seed=seeds['bkgd'], alpha=_lib.ptr(bt['alpha']))
+            names['bkgd'] = 'bkgd.bkgd_used'
+            hold.append(bt)
+        if dist:
+            self._dist = _term_struct(_lib.StepDist, 'dist', block, regions, lambda_dist=self.lambda_dist)
+            self.dist_losses = _region(block, regions, 'dist.loss2d')
+            names.update(dist_map='dist.ell1', **({'dist0': 'dist.ell0'} if Ni > 0 else {}))
+        self._hold = hold
+        return a, keep, fresh, block, regions, names, seeds, hold
+
+    # ---- fused route: one fastnerf_train_step_dist call per phase group ---------------------------------------------
     def _fused_prepare(self, rays_o, rays_d, target, leaf_tag, table, max_leaves, t_rand, u, n_global, alpha=None, bkgd=None,
                        depth=None, depth_weight=None, acc=None, acc_weight=None):
-        """Fill fn_step_args (and fn_step_aux, self._aux, when a depth / opacity term is on; fn_step_bkgd, self._bk, with a background)
-        for this batch; returns (args, out mapping, loss2, live)."""
-        n = rays_o.shape[0]
-        dev = rays_o.device
-        bt = self._bkgd_terms(n, dev, alpha, bkgd)
+        """Fill fn_step_args (and the structs of the terms that are on: _begin_step) for this batch; returns (args, out mapping, loss2,
+        live)."""
+        n, dev = rays_o.shape[0], rays_o.device
         S0, Ni = self.N_samples, self.N_importance
-        S1 = S0 + Ni
-        ops.require_gpu(rays_o, rays_d, target, leaf_tag, table, t_rand, u)
-        tag = self._follow_math()
-        live = self.live.use_live(self.net_c, self.net_f, Ni)
-        if self.occupancy is not None or self.tighten:
-            self._check_occupancy()
-            live = True             # the grid's first forward feeds the compacted backward only
-        key = (n, str(dev), torch.cuda.current_stream(dev).cuda_stream, tag)
-        if self._sa is None or self._sa_key != key:
-            self._sa, self._regions, self._block_floats, self._keep = self._new_step_args(n, S0, Ni, dev)
-            self._sa_key = key
-        a = self._sa
-        # the big buffers of the route this step takes (allocated on first use: a run that never falls back to the plain
-        # backward never pays for its 11 GB of saved activations)
-        if live:
-            self._compacted_scratch(a, self._keep, dev)
-        elif not a.act0:
-            t1 = _Workspace.get('act0', dev, ops.act_floats(n * S0))
-            a.act0 = t1.data_ptr()
-            self._keep.append(t1)
-            if Ni > 0:
-                t2 = _Workspace.get('act1', dev, ops.act_floats(n * S1))
-                a.act1 = t2.data_ptr()
-                self._keep.append(t2)
-        # a depth / opacity term appends its four gradient rows and loss4 to the block, regions like the others
-        aux = self._aux_terms(n, depth, depth_weight, acc, acc_weight)
-        row = (n + 63) // 64 * 64
-        aux_floats = 4 * row + 64 if aux else 0
-        bkgd_floats = self._bkgd_floats(n) if bt else 0
-        dist_floats = self._dist_floats(n, S1, S0 if Ni > 0 else 0) if self._check_dist() else 0
-        block, hold = self._fill_step(a, self._regions, self._block_floats + aux_floats + bkgd_floats + dist_floats, rays_o,
-                                      rays_d, target, leaf_tag, table, max_leaves, n_global)
-        base = block.data_ptr()
         if t_rand is not None:
             t_rand = ops._f32(t_rand)
             assert t_rand.shape == (n, S0)
-            hold.append(t_rand)
         if u is not None:
             u = ops._f32(u)
             assert u.shape == (n, Ni)
-            hold.append(u)
-        a.t_rand = None if t_rand is None else t_rand.data_ptr()
-        a.u = None if u is None else u.data_ptr()
+        a, keep, _, block, regions, names, seeds, hold = self._begin_step(
+            'fused', S0, Ni, (), (rays_o, rays_d, target, leaf_tag, table, max_leaves, n_global), dict(t_rand=t_rand, u=u), alpha, bkgd,
+            (depth, depth_weight, acc, acc_weight))
+        self._sa = a
+        live = self.live.use_live(self.net_c, self.net_f, Ni)
+        if self.occupancy is not None or self.tighten:
+            live = True             # the grid's first forward feeds the compacted backward only
+        # the big buffers of the route this step takes (allocated on first use: a run that never falls back to the plain
+        # backward never pays for its 11 GB of saved activations)
+        if live:
+            self._compacted_scratch(a, keep, dev)
+        elif not a.act0:
+            t1 = _Workspace.get('act0', dev, ops.act_floats(n * S0))
+            a.act0 = t1.data_ptr()
+            keep.append(t1)
+            if Ni > 0:
+                t2 = _Workspace.get('act1', dev, ops.act_floats(n * (S0 + Ni)))
+                a.act1 = t2.data_ptr()
+                keep.append(t2)
+        a.t_rand, a.u = _lib.ptr(t_rand), _lib.ptr(u)
         noise0 = noise1 = None
         if self.raw_noise_std > 0.:
-            noise0, noise1 = ops.sigma_noise(n, S0, S1 if Ni > 0 else 0, self.raw_noise_std, _next_seed(), dev)
-            hold += [noise0, noise1]
-        a.noise0 = None if noise0 is None else noise0.data_ptr()
-        a.noise1 = None if noise1 is None else noise1.data_ptr()
-        # (the same draws, in the same order, as the call-by-call route: render._forward_core)
-        a.seed0 = _next_seed() if (self.perturb and t_rand is None) else 0
-        a.seed1 = _next_seed() if (Ni > 0 and self.perturb and u is None) else 0
+            noise0, noise1 = ops.sigma_noise(n, S0, S0 + Ni if Ni > 0 else 0, self.raw_noise_std, seeds['noise'], dev)
+        a.noise0, a.noise1 = _lib.ptr(noise0), _lib.ptr(noise1)
+        a.seed0, a.seed1 = seeds['seed0'], seeds['seed1']
         a.live = int(live)
         a.fwd_flags = (1 if (live and self.skip_dead_rgb and noise0 is None) else 0) | (_lib.STEP_TIGHTEN if self.tighten else 0)
         occ = self.occupancy
@@ -671,32 +705,10 @@ class Trainer:
             self.occupancy_counts = torch.zeros(4, device=self.flat.device, dtype=torch.int32)
         a.occ = None if occ is None else ctypes.addressof(occ._c)
         a.occ_counts = None if occ is None else self.occupancy_counts.data_ptr()
-        hold.append(occ)
-        self._aux, self.aux_losses = None, self._aux_zero
-        if aux:
-            tail = self._block_floats
-            self.aux_losses = block[tail + 4 * row:tail + 4 * row + 4]
-            x = self._aux = _lib.StepAux()
-            for k in ('depth_target', 'depth_weight', 'acc_target', 'acc_weight'):
-                setattr(x, k, None if aux.get(k) is None else aux[k].data_ptr())
-            x.g_depth1, x.g_acc1, x.g_depth0, x.g_acc0 = [base + 4 * (tail + i * row) for i in range(4)]
-            x.loss4 = self.aux_losses.data_ptr()
-            x.lambda_depth, x.lambda_acc = aux['lambda_depth'], aux['lambda_acc']
-            hold += [aux, self.aux_losses]
-        regions, names = self._regions, _OUT_NAMES_2 if Ni > 0 else _OUT_NAMES_1
-        self._bk = None
-        if bt:      # (the seed of 'random' is drawn here: after every other draw of the step)
-            tail = self._block_floats + aux_floats
-            self._bk, _ = self._new_step_bkgd(bt, block, tail, n)
-            regions, names = dict(regions, bkgd_used=(tail, (n, 3))), dict(names, bkgd='bkgd_used')
-            hold.append(bt)
-        self._dist, self.dist_losses = None, self._dist_zero
-        if dist_floats:
-            self._dist, dregions = self._new_step_dist(block, self._block_floats + aux_floats + bkgd_floats, n, S1, S0 if Ni > 0 else 0)
-            regions, names = dict(regions, **dregions), dict(names, dist_map='ell1', **({'dist0': 'ell0'} if Ni > 0 else {}))
-        self._hold = hold       # inputs stay referenced until the next step is prepared (the launches are asynchronous)
-        out = _StepOut(block, regions, names)
-        return a, out, _region(block, self._regions, 'loss2'), live
+        hold += [t_rand, u, noise0, noise1, occ]
+        base_names = _OUT_NAMES_2 if Ni > 0 else _OUT_NAMES_1
+        out = _StepOut(block, regions, dict(base_names, **names) if names else base_names)
+        return a, out, _region(block, regions, 'loss2'), live
 
     def _occupancy_tick(self, marching=False):
         """Before a step with the grid set: refresh it when its turn has come (a grid without a density is never touched).  A marched
@@ -712,91 +724,50 @@ class Trainer:
                                       _packed=[self.pc[0]] + ([self.pf[0]] if (self.pf is not None and self.net_f is not self.net_c) else []))
         self.occupancy_steps += 1
 
-    # ---- marched route: one fastnerf_train_step_march call per phase group ------------------------------------------
+    # ---- marched route: one fastnerf_train_step_march_dist call per phase group -----------------------------------
     def _march_prepare(self, K, C, rays_o, rays_d, target, leaf_tag, table, max_leaves, march_u, n_global, alpha=None, bkgd=None):
-        """Fill fn_step_args and fn_step_march (and fn_step_bkgd, self._bk, with a background) for this batch; returns (args, march, out
-        dict, loss2).  out['march_overflow'] is the step's uint8 buffer here: step() hands it out as bool once the forward is enqueued."""
-        n = rays_o.shape[0]
-        dev = rays_o.device
-        bt = self._bkgd_terms(n, dev, alpha, bkgd)
-        ops.require_gpu(rays_o, rays_d, target, leaf_tag, table, march_u)
-        self._check_occupancy()
-        tag = self._follow_math()
-        key = (n, K, C, str(dev), torch.cuda.current_stream(dev).cuda_stream, tag)
-        if self._ma is None or self._ma_key != key:
-            # the row is a single pass of C samples, always compacted
-            a, self._march_regions, self._march_floats, self._march_keep = self._new_step_args(n, C, 0, dev)
-            x = _lib.StepMarch()
-            self._ma, self._ma_key = (a, x), key
-            self._compacted_scratch(a, self._march_keep, dev)
-            t3 = _Workspace.get('march_list', dev, ops.step_march_ws_ints(n, C), torch.int32)
-            self._march_keep.append(t3)
-            a.live = 1
-            x.list_ws = t3.data_ptr()
-            x.counts = self.march_counts.data_ptr()
-        a, x = self._ma
-        bkgd_floats = self._bkgd_floats(n) if bt else 0
-        dist_floats = self._dist_floats(n, C, 0) if self._check_dist() else 0
-        block, hold = self._fill_step(a, self._march_regions, self._march_floats + bkgd_floats + dist_floats, rays_o, rays_d,
-                                      target, leaf_tag, table, max_leaves, n_global)
-        kidx = torch.empty(n, C, device=dev, dtype=torch.int32)
-        overflow = torch.empty(n, device=dev, dtype=torch.uint8)
-        hold += [kidx, overflow, self.occupancy]
+        """Fill fn_step_args and fn_step_march (and the structs of the terms that are on: _begin_step) for this batch; returns (args, march,
+        out dict, loss2).  out['march_overflow'] is the step's uint8 buffer here: step() hands it out as bool once the forward is enqueued."""
+        n, dev = rays_o.shape[0], rays_o.device
         if march_u is not None:
             march_u = ops._f32(march_u).reshape(-1)
             assert march_u.shape == (n,)
-            hold.append(march_u)
+        # the row is a single pass of C samples, always compacted
+        a, keep, fresh, block, regions, names, seeds, hold = self._begin_step(
+            'march', C, 0, (K, C), (rays_o, rays_d, target, leaf_tag, table, max_leaves, n_global), dict(march_u=march_u), alpha, bkgd)
+        if fresh:
+            x = _lib.StepMarch()
+            self._ma = (a, x)
+            self._compacted_scratch(a, keep, dev)
+            t3 = _Workspace.get('march_list', dev, ops.step_march_ws_ints(n, C), torch.int32)
+            keep.append(t3)
+            a.live = 1
+            x.list_ws = t3.data_ptr()
+            x.counts = self.march_counts.data_ptr()
+        x = self._ma[1]
+        kidx = torch.empty(n, C, device=dev, dtype=torch.int32)
+        overflow = torch.empty(n, device=dev, dtype=torch.uint8)
+        hold += [kidx, overflow, self.occupancy, march_u]
         x.K, x.C, x.which = K, C, self._marched()[0]
-        x.u = None if march_u is None else march_u.data_ptr()
-        x.seed = _next_seed() if (self.perturb and march_u is None) else 0
+        x.u, x.seed = _lib.ptr(march_u), seeds['shift']
         x.kidx, x.overflow = kidx.data_ptr(), overflow.data_ptr()
         a.fwd_flags = (1 if self.skip_dead_rgb else 0) | (_lib.STEP_TIGHTEN if self.tighten else 0)
         a.occ = ctypes.addressof(self.occupancy._c)
-        self._hold = hold
-        self._march_block = block      # (with _march_regions: the step's tensors, g_rgb included, for inspection)
-        view = lambda name: _region(block, self._march_regions, name)      # noqa: E731
+        view = lambda name: _region(block, regions, name)      # noqa: E731
         out = {'rgb_map': view('rgb0'), 'disp_map': view('disp0'), 'acc_map': view('acc0'), 'depth_map': view('depth0'),
                'raw': view('raw0'), 'weights': view('w0'), 'z_vals': view('z0'), 'march_k': kidx, 'march_overflow': overflow}
-        self._bk = None
-        if bt:      # (the seed of 'random' is drawn here: after the shift's)
-            self._bk, out['bkgd'] = self._new_step_bkgd(bt, block, self._march_floats, n)
-            hold.append(bt)
-        self._dist, self.dist_losses = None, self._dist_zero
-        if dist_floats:
-            self._dist, dregions = self._new_step_dist(block, self._march_floats + bkgd_floats, n, C, 0)
-            self._march_dist_regions = dregions      # (with _march_block: g_w1 of the step, for inspection)
-            out['dist_map'] = _region(block, dregions, 'ell1')
+        out.update((key, view(name)) for key, name in names.items())
         return a, x, out, view('loss2')
 
+    # The term structs are given in every phase call (the data-parallel step splits the phases).  NULL is "the term is off": the C side
+    # then makes the launches, and names itself in errors, as the entry point without that struct does.
     def _march_call(self, a, x, phases):
-        if self._dist is not None:    # (given in every phase call, like fn_step_bkgd)
-            _lib.check(_lib.lib().fastnerf_train_step_march_dist(ctypes.byref(a), ctypes.byref(x),
-                                                                 None if self._bk is None else ctypes.byref(self._bk),
-                                                                 ctypes.byref(self._dist), int(phases), _lib.stream()),
-                       'fastnerf_train_step_march_dist')
-            return
-        if self._bk is not None:      # (given in every phase call)
-            _lib.check(_lib.lib().fastnerf_train_step_march_bkgd(ctypes.byref(a), ctypes.byref(x), ctypes.byref(self._bk), int(phases),
-                                                                 _lib.stream()), 'fastnerf_train_step_march_bkgd')
-            return
-        _lib.check(_lib.lib().fastnerf_train_step_march(ctypes.byref(a), ctypes.byref(x), int(phases), _lib.stream()),
-                   'fastnerf_train_step_march')
+        _lib.check(_lib.lib().fastnerf_train_step_march_dist(ctypes.byref(a), ctypes.byref(x), _ref(self._bk), _ref(self._dist), int(phases),
+                                                             _lib.stream()), 'fastnerf_train_step_march_dist')
 
     def _fused_call(self, a, phases):
-        if self._dist is not None:     # (like fn_step_aux, given in every phase call)
-            _lib.check(_lib.lib().fastnerf_train_step_dist(ctypes.byref(a), None if self._aux is None else ctypes.byref(self._aux),
-                                                           None if self._bk is None else ctypes.byref(self._bk), ctypes.byref(self._dist),
-                                                           int(phases), _lib.stream()), 'fastnerf_train_step_dist')
-            return
-        if self._bk is not None:       # (like fn_step_aux, given in every phase call)
-            _lib.check(_lib.lib().fastnerf_train_step_bkgd(ctypes.byref(a), None if self._aux is None else ctypes.byref(self._aux),
-                                                           ctypes.byref(self._bk), int(phases), _lib.stream()), 'fastnerf_train_step_bkgd')
-            return
-        if self._aux is not None:      # (given in every phase call: the data-parallel step splits them)
-            _lib.check(_lib.lib().fastnerf_train_step_aux(ctypes.byref(a), ctypes.byref(self._aux), int(phases), _lib.stream()),
-                       'fastnerf_train_step_aux')
-            return
-        _lib.check(_lib.lib().fastnerf_train_step(ctypes.byref(a), int(phases), _lib.stream()), 'fastnerf_train_step')
+        _lib.check(_lib.lib().fastnerf_train_step_dist(ctypes.byref(a), _ref(self._aux), _ref(self._bk), _ref(self._dist), int(phases),
+                                                       _lib.stream()), 'fastnerf_train_step_dist')
 
     def _after_backward(self, live):
         if live:
@@ -816,12 +787,11 @@ class Trainer:
         ops.adam_step(self.flat[sl], self.grad[sl], self.m[sl], self.v[sl], self.lr, self.adam_t, self.beta1, self.beta2, self.eps)
         self.repack()
 
-    def _empty_step(self, sl, seeds, overlap):
+    def _empty_step(self, sl, overlap):
         """The step of a rank whose shard of a (tail) batch is empty, on every route: it renders nothing and leaves the grid alone, but
-        joins the collectives with a zero gradient over the slice `sl` the step would have trained, draws the `seeds` seeds the step
-        would have drawn, and takes the update.  -> (loss2, out)"""
+        joins the collectives with a zero gradient over the slice `sl` the step would have trained and takes the update (step() has drawn
+        the seeds the step would have drawn).  -> (loss2, out)"""
         self.grad[sl].zero_()
-        _burn_seeds(seeds)
         self.aux_losses = self._aux_zero
         self.dist_losses = self._dist_zero
         self._host_update(sl, overlap)
@@ -845,20 +815,16 @@ class Trainer:
             self._occupancy_tick(marching)
         if n == 0:      # an empty batch takes its own path on every route
             self._bkgd_terms(0, self.grad.device, alpha, bkgd)      # (its ValueErrors, like a step that renders)
-            bk_seed = 1 if self._draws_bkgd(bkgd) else 0
+            self._step_seeds(marching, t_rand, u, march_u, bkgd)      # (drawn like a step that renders, and dropped)
             if marching:
                 which = self._marched()[0]
-                loss2, out = self._empty_step(slice(which * Nn, (which + 1) * Nn),
-                                              (1 if (self.perturb and march_u is None) else 0) + bk_seed, False)
+                loss2, out = self._empty_step(slice(which * Nn, (which + 1) * Nn), False)
             else:
-                seeds = ((1 if self.raw_noise_std > 0. else 0) + (1 if (self.perturb and t_rand is None) else 0)
-                         + (1 if (self.N_importance > 0 and self.perturb and u is None) else 0) + bk_seed)
-                loss2, out = self._empty_step(everything, seeds, overlap)
+                loss2, out = self._empty_step(everything, overlap)
         elif marching:
             a, x, out, loss2 = self._march_prepare(KC[0], KC[1], rays_o, rays_d, target, leaf_tag, table, max_leaves, march_u, n_global,
                                                    alpha, bkgd)
             a.lr, a.adam_t = float(self.lr), int(self.adam_t)
-            self.aux_losses = self._aux_zero
             if self.world == 1:
                 self._march_call(a, x, _lib.STEP_FORWARD | _lib.STEP_BWD_COARSE | _lib.STEP_UPDATE)
             else:      # data parallel, not overlapped: one network, one collective over its half of the gradient
