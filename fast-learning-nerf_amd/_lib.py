@@ -226,6 +226,10 @@ SIGNATURES = {
     'fastnerf_mlp_sigma_grad': (I, [I, I, L, I, P, P, P, P, P, P, P, P, P]),
     'fastnerf_ray_grad_ws_floats': (L, [I, L, I]),
     'fastnerf_ray_grad': (I, [I, I, L, I, P, P, P, P, P, P, P, P, P, I, P, P]),
+    'fastnerf_pose_exp': (I, [I, P, P, P, P]),
+    'fastnerf_pose_exp_bwd': (I, [I, P, P, P, P, P]),
+    'fastnerf_pose_grad_ws_floats': (L, [L, I]),
+    'fastnerf_pose_grad': (I, [L, I, P, P, F, F, F, F, P, P, P, P]),
 }
 
 _lib = None

@@ -9,6 +9,7 @@
 #include <stdarg.h>
 #include "common.h"
 #include "depths.h"
+#include "pinhole.h"
 
 namespace fn {
 static thread_local std::string g_err;
@@ -38,16 +39,7 @@ struct Cam {
   float r[12];  // c2w 3x4 row-major
 };
 
-__device__ __forceinline__ void pixel_ray(float row, float col, float fx, float fy, float cx, float cy,
-                                          const float* __restrict__ c, float d[3]) {
-  const float dx = (col - cx) / fx;
-  const float dy = -(row - cy) / fy;
-  const float dz = -1.0f;
-#pragma unroll
-  for (int k = 0; k < 3; ++k)
-    d[k] = fadd(fadd(fmul(dx, c[4 * k + 0]), fmul(dy, c[4 * k + 1])), fmul(dz, c[4 * k + 2]));
-}
-
+// (pixel_ray: pinhole.h)
 __global__ void gen_rays_kernel(int H, int W, float fx, float fy, float cx, float cy, Cam cam,
                                 float* __restrict__ ro, float* __restrict__ rd) {
   const int64_t n = (int64_t)H * W;

@@ -338,6 +338,79 @@ def ray_grad(rays11, z, raw, noise, draw, act, dact, params, d_rays=None, accumu
     return d_rays.reshape(-1)[:n * 11].view(n, 11)
 
 
+# ---- pose table (csrc/pose.hip; include/fastnerf.h, "pose table") --------------------------------
+def _need_pix(pix):
+    """Refuse a pixel list that fastnerf_pose_grad would not read as int32 [n,3] rows (no value is read here: rows must name
+    existing images, as for gen_rays_pixels)."""
+    if pix.dtype != torch.int32:
+        raise TypeError(f'pix must be int32, got {pix.dtype}')
+    if pix.dim() != 2 or pix.shape[1] != 3:
+        raise ValueError(f'pix must have shape (n, 3), got {tuple(pix.shape)}')
+
+
+def pose_exp(base, xi=None, out=None):
+    """poses [n_img,3,4] = (exp(hat(omega)) R0 | t0 + tau) of the base poses [n_img,3,4] and xi [n_img,6] = (omega, tau)
+    (fastnerf_pose_exp).  xi=None, or a zero row, gives the base pose bit for bit."""
+    require_gpu(base, xi, out)
+    n_img = base.shape[0]
+    _need_f32('base', base, n_img, 3, 4)
+    if n_img < 1:
+        raise ValueError('pose_exp: at least one image')
+    if xi is not None:
+        _need_f32('xi', xi, n_img, 6)
+    if out is None:
+        out = torch.empty_like(base)
+    _need_f32('out', out, n_img, 3, 4)
+    check(lib().fastnerf_pose_exp(n_img, ptr(base), ptr(xi), ptr(out), stream()), 'fastnerf_pose_exp')
+    return out
+
+
+def pose_exp_bwd(base, xi, d_poses, d_xi=None):
+    """d_xi [n_img,6] = d(loss)/d(xi) from d_poses [n_img,3,4] = d(loss)/d(pose_exp(base, xi)) (fastnerf_pose_exp_bwd)."""
+    require_gpu(base, xi, d_poses, d_xi)
+    n_img = base.shape[0]
+    _need_f32('base', base, n_img, 3, 4)
+    if n_img < 1:
+        raise ValueError('pose_exp_bwd: at least one image')
+    if xi is not None:
+        _need_f32('xi', xi, n_img, 6)
+    _need_f32('d_poses', d_poses, n_img, 3, 4)
+    if d_xi is None:
+        d_xi = torch.empty(n_img, 6, device=base.device, dtype=torch.float32)
+    _need_f32('d_xi', d_xi, n_img, 6)
+    check(lib().fastnerf_pose_exp_bwd(n_img, ptr(base), ptr(xi), ptr(d_poses), ptr(d_xi), stream()), 'fastnerf_pose_exp_bwd')
+    return d_xi
+
+
+def pose_grad_ws_floats(n, n_img):
+    """Floats of scratch one pose_grad call over n rays of n_img images needs (0 for a small batch)."""
+    return int(check(lib().fastnerf_pose_grad_ws_floats(int(n), int(n_img)), 'fastnerf_pose_grad_ws_floats'))
+
+
+def pose_grad(pix, poses, K, d_rays, d_poses=None, ws=None):
+    """d_poses [n_img,3,4]: the gradient with respect to the poses of a loss whose gradient with respect to the pinhole rays of the
+    pixels pix [n,3] int32 = (image, row, col) is d_rays [n,11] (ops.ray_grad; columns 6:8 ignored) -- fastnerf_pose_grad, a
+    segmented sum without atomics.  An image without a ray gets zeros."""
+    require_gpu(pix, poses, d_rays, d_poses, ws)
+    n_img = poses.shape[0]
+    _need_f32('poses', poses, n_img, 3, 4)
+    if n_img < 1:
+        raise ValueError('pose_grad: at least one image')
+    _need_pix(pix)
+    n = pix.shape[0]
+    _need_f32('d_rays', d_rays, n, 11)
+    if d_poses is None:
+        d_poses = torch.empty(n_img, 3, 4, device=poses.device, dtype=torch.float32)
+    _need_f32('d_poses', d_poses, n_img, 3, 4)
+    need = pose_grad_ws_floats(n, n_img)
+    if ws is None and need > 0:
+        ws = torch.empty(need, device=poses.device, dtype=torch.float32)
+    assert need == 0 or (ws.dtype == torch.float32 and ws.numel() >= need)
+    check(lib().fastnerf_pose_grad(n, n_img, ptr(pix), ptr(poses), float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2]),
+                                   ptr(d_rays), ptr(ws), ptr(d_poses), stream()), 'fastnerf_pose_grad')
+    return d_poses
+
+
 def raw2outputs_fwd(raw, z, rays11, noise=None, white_bkgd=False):
     require_gpu(raw, z, rays11, noise)
     n = rays11.shape[0]

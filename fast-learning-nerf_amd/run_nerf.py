@@ -18,7 +18,7 @@ import torch
 
 from . import _lib, flat_params, ops, parallel
 from .model import NeRF, noview_slices
-from .render import LivePolicy, _Workspace, get_compact, _backward_core, _forward_core, _next_seed, render, render_path  # noqa: F401
+from .render import LivePolicy, _Workspace, get_compact, _backward_core, _backward_passes, _forward_core, _next_seed, render, render_path  # noqa: F401
 from .run_nerf_helpers import get_embedder, img2mse, mse2psnr
 from .tree import QuadTreeManager
 
@@ -77,6 +77,7 @@ class _Args:
     dataset_type = 'blender'; white_bkgd = False; no_ndc = False; lindisp = False
     random_bkgd = False      # (not in the reference's parser) RGBA training over a fresh background colour per ray
     lambda_dist = 0.         # (not in the reference's parser) weight of the distortion loss on the ray weights (Trainer(lambda_dist=))
+    refine_poses = False; pose_lrate = 1e-3      # (not in the reference's parser) refine the camera poses beside the field (Trainer(poses=))
     n_epoch = 12; init_level = 3; rays_downscale = 1; subdivide_every = 1; subdivide_thres = 0.015
     randSamp_perc = 0.5; basedir = './logs'; expname = 'fastnerf'
 
@@ -323,12 +324,23 @@ class Trainer:
     through a grid, tighten), the marched step -- there on the packed row, an overflowed ray skipped -- and the call-by-call route;
     nothing else of the marched step's restrictions is lifted.  Like the opacity term it makes every sample with positive density of a ray
     that is not yet opaque live, so early compacted steps run over more points.  lambda_dist = 0 (the default): the step without it,
-    launch for launch.  ValueError for a negative or non-finite lambda_dist."""
+    launch for launch.  ValueError for a negative or non-finite lambda_dist.
+
+    Pose refinement (`poses=` a poses.PoseTable, `pose_lrate`; include/fastnerf.h, "pose table"): step(None, None, target, pix=[n,3]
+    int (image, row, col)) makes the poses from the table and the rays from the pixels (ops.pose_exp, gen_rays_pixels), steps on the
+    call-by-call route with the saving backward forced and ops.ray_grad between the passes (forward_backward(d_rays=True); the fused
+    step reuses the buffers ray_grad reads), carries out['d_rays'] down to `pose_grad` [n_img,6] = d(loss)/d(xi) (ops.pose_grad,
+    ops.pose_exp_bwd), takes an Adam step on xi with moments of its own (`pose_m`, `pose_v`) at pose_lrate times the decay factor the
+    networks' rate has, then the networks' update.  The network gradients, the loss and the maps are those of the call-by-call step on
+    the same rays, bit for bit; every term above, leaf_tag / table, white_bkgd and networks without view directions pass through
+    unchanged.  An image without a ray in the batch has a zero gradient.  Without `poses=` nothing changes.  ValueError: pix without
+    poses= or poses= without pix, rays together with pix, occupancy= / tighten / march, data parallel.  NotImplementedError: ndc=True,
+    the math mode bf16x3 (no ray gradients)."""
 
     def __init__(self, render_kwargs_train, H, W, K, near, far, lrate=5e-4, lrate_decay=250, decay=True,
                  beta1=0.9, beta2=0.999, eps=1e-8, occupancy=None, occupancy_every=16, occupancy_warmup=256, occupancy_cells=None,
                  lambda_depth=0., lambda_acc=0., tighten=False, march=None, march_cap=128, march_after=0, bkgd=None,
-                 lambda_dist=0.):
+                 lambda_dist=0., poses=None, pose_lrate=1e-3):
         kw = render_kwargs_train
         self._kw = kw
         self.net_c = kw['network_fn']
@@ -382,10 +394,31 @@ class Trainer:
         self._dist_zero = torch.zeros(2, device=self.flat.device, dtype=torch.float32)
         self.dist_losses = self._dist_zero
         self._dist = None        # fn_step_dist of the current step (None: the term is off)
+        self.poses, self.pose_lrate = poses, float(pose_lrate)
+        self.pose_lr = self.pose_lrate
+        self.pose_grad = None    # d(loss)/d(xi) [n_img,6] of the last pose step
+        self.pose_m = self.pose_v = None
+        if poses is not None:
+            self.pose_m, self.pose_v = torch.zeros_like(poses.xi.data), torch.zeros_like(poses.xi.data)
         self._check_dist()
+        self._check_poses()
         self._check_occupancy()
         self._check_march()
         self.repack()
+
+    def _check_poses(self):
+        """The refusals of a trainer with a pose table, before any launch (read on every pose step, like the other settings)."""
+        if self.poses is None:
+            return
+        if self.occupancy is not None or self.tighten or self.march is not None:
+            raise ValueError('Trainer: poses= steps on the call-by-call route, which has no occupancy grid, tighten or march')
+        if self.world > 1:
+            raise ValueError('Trainer: poses= is not data parallel (world size {})'.format(self.world))
+        if self.ndc:
+            raise NotImplementedError('Trainer: poses= differentiates plain pinhole rays only (ndc=False)')
+        if ops.get_math() == 'bf16x3':
+            raise NotImplementedError("Trainer: poses= needs ray gradients, which exist in the math modes 'fp32' and 'bf16x6' only, "
+                                      "not in 'bf16x3'")
 
     def _check_occupancy(self):
         if self.occupancy is None:
@@ -496,7 +529,10 @@ class Trainer:
         return self.lambda_dist != 0.
 
     def forward_backward(self, rays_o, rays_d, target, leaf_tag=None, table=None, max_leaves=0, t_rand=None, u=None,
-                         n_global=None, alpha=None, bkgd=None, depth=None, depth_weight=None, acc=None, acc_weight=None):
+                         n_global=None, alpha=None, bkgd=None, d_rays=False, depth=None, depth_weight=None, acc=None, acc_weight=None):
+        """d_rays=True: the saving backward is forced and runs pass by pass with ops.ray_grad between the passes
+        (render._backward_passes); out['d_rays'] [n,11] is d(loss)/d(rays11).  The parameter gradients are those of the plain backward,
+        bit for bit."""
         if self.march is not None:
             raise ValueError('Trainer.forward_backward: the call-by-call route has no marched step; use step()')
         if self.occupancy is not None or self.tighten:
@@ -511,7 +547,7 @@ class Trainer:
         noise0 = noise1 = None
         if self.raw_noise_std > 0.:
             noise0, noise1 = ops.sigma_noise(n, self.N_samples, self.N_samples + self.N_importance, self.raw_noise_std, _next_seed(), dev)
-        live = self.live.use_live(self.net_c, self.net_f, self.N_importance)
+        live = not d_rays and self.live.use_live(self.net_c, self.net_f, self.N_importance)      # (the compacted backward has no ray gradients)
         out, saved = _forward_core(rays11, self.net_c, self.net_f, self.N_samples, self.N_importance, self.lindisp,
                                    self.perturb, self.white_bkgd, t_rand, u, noise0, noise1, save=not live,
                                    packed_c=self.pc, packed_f=self.pf, skip_dead_rgb=live and self.skip_dead_rgb, act_ws=True)
@@ -542,7 +578,13 @@ class Trainer:
             if 'weights0' in out:
                 out['dist0'], wg['g_w0'] = ops.distortion(out['weights0'], out['z0'], rays11, self.lindisp, coef=coef)
             self.dist_losses = ops.distortion_mean(out['dist_map'], out.get('dist0'))
-        _backward_core(saved, g, g0, counts=self.live_counts if live else None, maps=maps, weight_grads=wg)
+        if d_rays:
+            out['d_rays'] = torch.empty(n, 11, device=dev, dtype=torch.float32)
+            two = self.net_f is not None and self.net_f is not self.net_c
+            _backward_passes(saved, g, g0, self.net_c.flat_grad, self.net_f.flat_grad if two else None, d_rays=out['d_rays'], maps=maps,
+                             weight_grads=wg)
+        else:
+            _backward_core(saved, g, g0, counts=self.live_counts if live else None, maps=maps, weight_grads=wg)
         self.net_c.collect_grads()          # (no-ops with view directions: the kernels write the parameters' gradients)
         if self.net_f is not None and self.net_f is not self.net_c:
             self.net_f.collect_grads()
@@ -798,9 +840,13 @@ class Trainer:
         return torch.zeros(2, device=self.grad.device), {}
 
     def step(self, rays_o, rays_d, target, leaf_tag=None, table=None, max_leaves=0, t_rand=None, u=None,
-             n_global=None, decay=None, march_u=None, alpha=None, bkgd=None, depth=None, depth_weight=None, acc=None,
+             n_global=None, decay=None, march_u=None, alpha=None, bkgd=None, pix=None, depth=None, depth_weight=None, acc=None,
              acc_weight=None):
-        n = rays_o.shape[0]
+        if pix is not None or self.poses is not None:
+            pix = self._check_pose_step(rays_o, rays_d, pix)
+            n = pix.shape[0]
+        else:
+            n = rays_o.shape[0]
         Nn = ops.NET_PARAMS
         two = self.N_importance > 0 and self.net_f is not None and self.net_f is not self.net_c
         overlap = self.world > 1 and two and self.overlap_allreduce and self.grad.numel() == 2 * Nn
@@ -821,6 +867,16 @@ class Trainer:
                 loss2, out = self._empty_step(slice(which * Nn, (which + 1) * Nn), False)
             else:
                 loss2, out = self._empty_step(everything, overlap)
+            if pix is not None:
+                self._pose_update(pix, None, None)
+        elif pix is not None:
+            # the pose step: the call-by-call route with ray gradients, then the rays' gradient down to xi and an Adam step of its own
+            poses = ops.pose_exp(self.poses.base, self.poses.xi.data)
+            ro, rd = ops.gen_rays_pixels(pix, poses, self.K)
+            loss2, out = self.forward_backward(ro, rd, target, leaf_tag, table, max_leaves, t_rand, u, n_global, alpha=alpha, bkgd=bkgd,
+                                               depth=depth, depth_weight=depth_weight, acc=acc, acc_weight=acc_weight, d_rays=True)
+            self._pose_update(pix, poses, out['d_rays'])
+            self._host_update(everything, overlap)
         elif marching:
             a, x, out, loss2 = self._march_prepare(KC[0], KC[1], rays_o, rays_d, target, leaf_tag, table, max_leaves, march_u, n_global,
                                                    alpha, bkgd)
@@ -860,12 +916,40 @@ class Trainer:
                                                alpha=alpha, bkgd=bkgd, depth=depth, depth_weight=depth_weight, acc=acc, acc_weight=acc_weight)
             self._host_update(everything, overlap)
         if (self.decay if decay is None else decay):
-            self.lr = self.lrate * (0.1 ** (self.global_iter / (self.lrate_decay * 1000)))
+            factor = 0.1 ** (self.global_iter / (self.lrate_decay * 1000))
+            self.lr = self.lrate * factor
+            self.pose_lr = self.pose_lrate * factor
             self.global_iter += 1
         return loss2, out
 
+    def _check_pose_step(self, rays_o, rays_d, pix):
+        """The refusals of a pose step, before any launch -> pix as contiguous int32 [n,3]."""
+        if self.poses is None:
+            raise ValueError('Trainer.step: pix= names pixels of the images of a pose table: it needs Trainer(poses=)')
+        if pix is None:
+            raise ValueError('Trainer.step: a trainer with poses= makes its rays from the table: it needs pix=, not rays')
+        if rays_o is not None or rays_d is not None:
+            raise ValueError('Trainer.step: give rays or pix=, not both: with pix= the rays come from the pose table (rays_o = rays_d = None)')
+        self._check_poses()
+        from .poses import check_pix
+        return check_pix(pix)
+
+    def _pose_update(self, pix, poses, d_rays):
+        """d_rays -> d_poses -> self.pose_grad = d(loss)/d(xi), then Adam on xi with the table's own moments at pose_lr (pose_lrate times
+        the decay factor the networks' rate has).  An empty batch (poses None): a zero gradient, and the update Adam makes of it."""
+        xi = self.poses.xi.data
+        if poses is None:
+            self.pose_grad = torch.zeros_like(xi)
+        else:
+            d_poses = ops.pose_grad(pix, poses, self.K, d_rays)
+            self.pose_grad = ops.pose_exp_bwd(self.poses.base, xi, d_poses)
+        ops.adam_step(xi, self.pose_grad, self.pose_m, self.pose_v, self.pose_lr, self.adam_t, self.beta1, self.beta2, self.eps)
+
     def state_dict(self):
-        return {'m': self.m, 'v': self.v, 'adam_t': self.adam_t, 'global_iter': self.global_iter, 'lr': self.lr}
+        sd = {'m': self.m, 'v': self.v, 'adam_t': self.adam_t, 'global_iter': self.global_iter, 'lr': self.lr}
+        if self.poses is not None:
+            sd.update(pose_m=self.pose_m, pose_v=self.pose_v, pose_lr=self.pose_lr)
+        return sd
 
     # ---- interchange with torch.optim.Adam (the optimizer_state_dict of the reference's .tar, run_nerf.py:121,537) ----
     def _param_list(self):
@@ -885,9 +969,28 @@ class Trainer:
         self.adam_t, lr = flat_params.adam_state_from_torch(self._param_list(), self.m, self.v, opt)
         self.lr = float(lr)
 
+    def load_pose_checkpoint(self, ckpt):
+        """Take xi and its moments from a checkpoint of save_checkpoint (the loaded dict, or its path).  A checkpoint without a pose
+        table leaves the table untouched; one whose base poses are not this table's is a ValueError."""
+        if self.poses is None:
+            return False
+        if not isinstance(ckpt, dict):
+            ckpt = torch.load(ckpt, map_location=self.poses.xi.device, weights_only=False)
+        if 'pose_xi' not in ckpt:
+            return False
+        base = ckpt['pose_base'].to(self.poses.base.device)
+        if base.shape != self.poses.base.shape or not torch.equal(base, self.poses.base):
+            raise ValueError('Trainer.load_pose_checkpoint: the checkpoint refines other base poses than this table holds')
+        self.poses.xi.data.copy_(ckpt['pose_xi'])
+        self.pose_m.copy_(ckpt['pose_m']); self.pose_v.copy_(ckpt['pose_v'])
+        return True
+
     def load_state_dict(self, sd):
         self.m.copy_(sd['m']); self.v.copy_(sd['v'])
         self.adam_t, self.global_iter, self.lr = sd['adam_t'], sd['global_iter'], sd['lr']
+        if self.poses is not None and 'pose_m' in sd:      # (a state without them: the table's moments stay as they are)
+            self.pose_m.copy_(sd['pose_m']); self.pose_v.copy_(sd['pose_v'])
+            self.pose_lr = sd.get('pose_lr', self.pose_lr)
 
 
 def reference_state_dict(net):
@@ -907,11 +1010,14 @@ def save_checkpoint(args, epoch_id, trainer, kw_train, mgr):
     d = os.path.join(args.basedir, args.expname)
     os.makedirs(d, exist_ok=True)
     path = os.path.join(d, '{:03d}.tar'.format(epoch_id))
-    torch.save({'global_epoch': epoch_id, 'global_iter': trainer.global_iter,
-                'network_fn_state_dict': reference_state_dict(kw_train['network_fn']),
-                'network_fine_state_dict': (None if kw_train['network_fine'] is None    # N_importance = 0: run_nerf.py:536 fails
-                                            else reference_state_dict(kw_train['network_fine'])),   # on None.state_dict(); None is kept
-                'optimizer_state_dict': trainer.torch_optimizer_state_dict()}, path)
+    ckpt = {'global_epoch': epoch_id, 'global_iter': trainer.global_iter,
+            'network_fn_state_dict': reference_state_dict(kw_train['network_fn']),
+            'network_fine_state_dict': (None if kw_train['network_fine'] is None    # N_importance = 0: run_nerf.py:536 fails
+                                        else reference_state_dict(kw_train['network_fine'])),   # on None.state_dict(); None is kept
+            'optimizer_state_dict': trainer.torch_optimizer_state_dict()}
+    if trainer.poses is not None:      # the pose table beside them (keys the reference does not read)
+        ckpt.update(pose_xi=trainer.poses.xi.data, pose_base=trainer.poses.base, pose_m=trainer.pose_m, pose_v=trainer.pose_v)
+    torch.save(ckpt, path)
     mgr.save_trees(tree_pkl_path(args, epoch_id))
     return path
 
@@ -988,11 +1094,21 @@ def train(images, poses, H, W, focal, args, near=2., far=6., device='cuda', log=
                       march=getattr(args, 'march', None), march_cap=getattr(args, 'march_cap', 128), march_after=getattr(args, 'march_after', 0),
                       occupancy_every=getattr(args, 'occupancy_every', 16), occupancy_warmup=getattr(args, 'occupancy_warmup', 256))
     random_bkgd = bool(getattr(args, 'random_bkgd', False))
+    # args.refine_poses (no such flag in the reference's parser; default off): the poses are a PoseTable that every step refines beside
+    # the networks, at args.pose_lrate; the steps get the rows' pixels instead of rays.  The table is trainer.poses.
+    refine_poses = bool(getattr(args, 'refine_poses', False))
+    pose_kw = {}
+    if refine_poses:
+        from .poses import PoseTable
+        pose_kw = dict(poses=PoseTable(torch.as_tensor(poses, dtype=torch.float32)[:, :3, :4]).to(dev),
+                       pose_lrate=float(getattr(args, 'pose_lrate', 1e-3)))
     trainer = Trainer(kw_train, H, W, K, near, far, lrate=args.lrate, lrate_decay=args.lrate_decay, bkgd='random' if random_bkgd else None,
-                      lambda_dist=float(getattr(args, 'lambda_dist', 0.)), **occ_kw)
+                      lambda_dist=float(getattr(args, 'lambda_dist', 0.)), **occ_kw, **pose_kw)
     trainer.global_iter = global_iter
     if len(optimizer.state_dict()['state']) > 0:   # create_nerf restored a checkpoint (ours or the reference's)
         trainer.load_torch_optimizer(optimizer)
+        if refine_poses and create_nerf.last_ckpt_path is not None:
+            trainer.load_pose_checkpoint(create_nerf.last_ckpt_path)
     images = torch.as_tensor(images, dtype=torch.float32)
     alpha_img = None
     if random_bkgd:      # the quadtree manager (and the leaf-error picks) see the straight colours; alpha travels beside them
@@ -1017,8 +1133,11 @@ def train(images, poses, H, W, focal, args, near=2., far=6., device='cuda', log=
     rank, world = parallel.rank(), parallel.world_size()
     history = []
 
-    def run_batches(rays_o, rays_d, tgt, tags, decay, table, max_leaves, local_of=None, alpha=None):
-        """local_of = N: the tensors hold only THIS rank's rows of an epoch of N rows (gen_rays_device(shard=...)), batch after batch."""
+    def run_batches(rays_o, rays_d, tgt, tags, decay, table, max_leaves, local_of=None, alpha=None, pix=None):
+        """local_of = N: the tensors hold only THIS rank's rows of an epoch of N rows (gen_rays_device(shard=...)), batch after batch.
+        pix (refine_poses): the rows' pixels [N,3]; the steps get them instead of the rays."""
+        if pix is not None:
+            pix = pix.to(dev).int()
         n_total = rays_o.shape[0] if local_of is None else local_of
         it = 0
         lo = 0
@@ -1031,10 +1150,11 @@ def train(images, poses, H, W, focal, args, near=2., far=6., device='cuda', log=
                 sl = slice(lo, lo + cnt)
                 lo += cnt
             # (a rank's rows r::world of the global batch are a strided view: the kernels take contiguous buffers)
-            loss2, _ = trainer.step(rays_o[sl].contiguous(), rays_d[sl].contiguous(), tgt[sl].contiguous(),
-                                    leaf_tag=None if tags is None else tags[sl].contiguous(),
+            loss2, _ = trainer.step(None if pix is not None else rays_o[sl].contiguous(), None if pix is not None else rays_d[sl].contiguous(),
+                                    tgt[sl].contiguous(), leaf_tag=None if tags is None else tags[sl].contiguous(),
                                     table=table, max_leaves=max_leaves, n_global=(b1 - b0) if world > 1 else None,
-                                    decay=decay, alpha=None if alpha is None else alpha[sl].contiguous())
+                                    decay=decay, alpha=None if alpha is None else alpha[sl].contiguous(),
+                                    **({} if pix is None else {'pix': pix[sl].contiguous()}))
             it += 1
             if max_iters_per_epoch is not None and it >= max_iters_per_epoch:
                 break
@@ -1052,7 +1172,7 @@ def train(images, poses, H, W, focal, args, near=2., far=6., device='cuda', log=
         pix = torch.cat([torch.cat([torch.full((randNum, 1), i, dtype=torch.int64), sel], 1)
                          for i in range(mgr.n_images)], 0)
         ro, rd, tgt = mgr.gather(pix)
-        loss2, it = run_batches(ro, rd, tgt, None, False, None, 0, alpha=alpha_at(pix))
+        loss2, it = run_batches(ro, rd, tgt, None, False, None, 0, alpha=alpha_at(pix), pix=pix if refine_poses else None)
         log('warm-up: {} iters, fine/coarse mse {}'.format(it, loss2.tolist()))
 
     for epoch_id in range(start_epoch + 1, args.n_epoch + 1):
@@ -1066,12 +1186,12 @@ def train(images, poses, H, W, focal, args, near=2., far=6., device='cuda', log=
         sharded_gen = world > 1 and not compat_rng and dev.type == 'cuda'
         ro, rd, tgt = mgr.gen_rays_v3_multiThread(down_scale=1, prob=False, randSamp_proc=args.randSamp_perc,
                                                   last_epoch=last, compat_rng=compat_rng,
-                                                  shard=(rank, world, N_rand) if sharded_gen else None, want_pix=random_bkgd)
+                                                  shard=(rank, world, N_rand) if sharded_gen else None, want_pix=random_bkgd or refine_poses)
         tags = mgr.result_leaf_tag
         max_leaves = mgr.max_leaves()
         table = torch.zeros(mgr.n_images * max_leaves, device=dev, dtype=torch.int32)
         loss2, it = run_batches(ro, rd, tgt, tags, True, table, max_leaves, local_of=mgr.epoch_rows if sharded_gen else None,
-                                alpha=alpha_at(mgr.result_pix) if random_bkgd else None)
+                                alpha=alpha_at(mgr.result_pix) if random_bkgd else None, pix=mgr.result_pix if refine_poses else None)
         psnr = mse2psnr(loss2[:1].cpu())
         history.append((epoch_id, it, float(loss2[0]), float(psnr[0]), time.time() - t0))
         log('epoch {}: {} iters, fine mse {:.5f} psnr {:.2f}, {:.1f}s'.format(*history[-1]) +

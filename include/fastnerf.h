@@ -985,6 +985,43 @@ int fastnerf_ray_grad(int math_mode, int kind, int64_t n, int S, const float* ra
                       const float* noise, const float* draw, const float* act, const float* dact, const float* params, float* ws,
                       int accumulate, float* d_rays, fn_stream_t stream);
 
+/* ---- pose table: camera poses that training refines (csrc/pose.hip) ------------------------------------------------------------------
+ * Per image i a 6-vector xi_i = (omega_i, tau_i) beside a fixed base pose (R0_i | t0_i), all poses row-major 3x4 camera-to-world:
+ *   R_i = exp(hat(omega_i)) R0_i,   t_i = t0_i + tau_i
+ * (the camera turns about its own centre, in world axes, and moves independently).  Rays are the pinhole rays of
+ * fastnerf_gen_rays_pixels + fastnerf_pack_rays with ndc = 0:  dir = ((col - cx) / fx, -(row - cy) / fy, -1),  o = t,  d = R dir,
+ * v = d / |d|.
+ *
+ * fastnerf_pose_exp: poses_out [n_img,3,4] from base [n_img,3,4] and xi [n_img,6], one lane per image.  Rodrigues,
+ *   exp(hat(w)) = I + a K + b K^2,  K = hat(w),  a = sin(th) / th,  b = 1/2 (sin(th/2) / (th/2))^2,  th = |w|
+ * (b in the half-angle form, in which nothing cancels; a and b by series below th = 1e-3, so a(0) = 1 and b(0) = 1/2 exactly and
+ * nothing divides by zero).  xi == NULL, or an image whose omega is zero, returns that image's base rotation BIT FOR BIT, a zero
+ * component of tau that component of t0 bit for bit; every other t is the fp32 sum t0 + tau.
+ *
+ * fastnerf_pose_exp_bwd: d_xi [n_img,6] from d_poses [n_img,3,4] = d(loss)/d(poses_out):
+ *   d_tau   = column 3 of d_poses, copied
+ *   d_omega = J_l(omega)^T sum_k (A_k x G_k),   A = R R0 (rebuilt), G = d_poses[:, :, :3], both column by column,
+ *   J_l = I + b K + c K^2,   c = (th - sin(th)) / th^3   (by series below th = 0.5, where the difference would cancel)
+ * This is autograd of the matrix exponential composed with R0, at th = 0 too (J_l = I).
+ *
+ * fastnerf_pose_grad: d_poses [n_img,3,4] = the gradient of a loss with respect to the poses, given d_rays [n,11] = d(loss)/d(ray
+ * batch) (fastnerf_ray_grad) of the rays that pix [n,3] = (image, row, col) names; d and v are rebuilt from poses and pix:
+ *   g_d = d_d + (d_v - v (v . d_v)) / |d|
+ *   d_poses[img, j, k] = sum over the rays of img of g_d[j] dir[k]   (k < 3),     d_poses[img, j, 3] = sum of d_o[j]
+ * Columns 6:8 of d_rays are ignored; a batch without view directions has zeros in 8:11.  pix rows must name existing images, as for
+ * fastnerf_gen_rays_pixels.  A segmented sum without atomics: a ray's place in the sum depends on its row index alone, so the
+ * result is bit-identical from call to call; an image without a ray in the batch gets twelve +0, written; n == 0 writes n_img * 12
+ * zeros (when d_poses is given) and returns 0.  Any n: the batch is walked in chunks, never one thread per ray of a capped grid.
+ * ws: fastnerf_pose_grad_ws_floats(n, n_img) floats of scratch (0 for a small batch: NULL is then accepted).
+ *
+ * -1 before anything is enqueued: n_img < 1; n < 0; a NULL buffer other than xi (pose_grad: when n > 0; ws only when its size is
+ * not 0).  All stores are plain vector stores. */
+int fastnerf_pose_exp(int n_img, const float* base, const float* xi, float* poses_out, fn_stream_t stream);
+int fastnerf_pose_exp_bwd(int n_img, const float* base, const float* xi, const float* d_poses, float* d_xi, fn_stream_t stream);
+int64_t fastnerf_pose_grad_ws_floats(int64_t n, int n_img);
+int fastnerf_pose_grad(int64_t n, int n_img, const int32_t* pix, const float* poses, float fx, float fy, float cx, float cy,
+                       const float* d_rays, float* ws, float* d_poses, fn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,8 @@ A field is fitted to the analytic scene of synthetic.py for --train-iters steps,
 perturbed pose is pulled back to it by Adam on a 6-vector (axis-angle rotation + translation, applied on the left of the start pose)
 whose gradient comes through `render(H, W, K, c2w=pose)` -- get_rays / pack_rays, the fused render_rays and ops.ray_grad.
 Prints the rotation error (degrees) and the translation error per iteration.
+(The pose table that training refines, fastnerf.poses.PoseTable, uses the OTHER convention: there the camera turns about its own
+centre, t = t0 + tau; here the rotation is about the world origin and moves the camera centre with it.)
 
 usage: python tools/refine_pose.py [--iters 100] [--train-iters 300] [--size 24] [--rot-deg 4] [--trans 0.1] [--lr 0.01]"""
 import argparse
