@@ -68,6 +68,12 @@ class StepDist(C.Structure):
     _fields_ = [('lambda_dist', F)] + [(k, P) for k in ('ell1', 'ell0', 'g_w1', 'g_w0', 'loss2d')]
 
 
+class StepExpo(C.Structure):
+    """fn_step_expo of include/fastnerf.h, field for field ('lambda' is set by name: setattr / _term_struct)."""
+    _fields_ = ([('img', P), ('ab', P), ('n_img', I), ('lambda', F)]
+                + [(k, P) for k in ('e1', 'e0', 'ws', 'd_ab', 'counts', 'loss_reg')])
+
+
 class OccGrid(C.Structure):
     """fn_occ_grid of include/fastnerf.h, field for field."""
     _fields_ = [('words', P), ('lo', F * 3), ('inv', F * 3), ('n', C.c_int32 * 3), ('outside_occupied', C.c_int32)]
@@ -230,6 +236,13 @@ SIGNATURES = {
     'fastnerf_pose_exp_bwd': (I, [I, P, P, P, P, P]),
     'fastnerf_pose_grad_ws_floats': (L, [L, I]),
     'fastnerf_pose_grad': (I, [L, I, P, P, F, F, F, F, P, P, P, P]),
+    'fastnerf_step_expo_size': (L, []),
+    'fastnerf_expo_apply': (I, [L, I, P, P, P, P, P, P, P]),
+    'fastnerf_expo_grad_ws_floats': (L, [L, I]),
+    'fastnerf_expo_grad': (I, [L, I, P, P, F, F, P, P, P, P, P, P, P, P, P]),
+    'fastnerf_train_step_expo': (I, [C.POINTER(StepArgs), C.POINTER(StepAux), C.POINTER(StepBkgd), C.POINTER(StepDist), C.POINTER(StepExpo), I, P]),
+    'fastnerf_train_step_march_expo': (I, [C.POINTER(StepArgs), C.POINTER(StepMarch), C.POINTER(StepBkgd), C.POINTER(StepDist),
+                                           C.POINTER(StepExpo), I, P]),
 }
 
 _lib = None
@@ -258,6 +271,8 @@ def lib():
             raise RuntimeError('fn_step_bkgd: the ctypes mirror does not match the library (stale libfastnerf.so?)')
         if l.fastnerf_step_dist_size() != C.sizeof(StepDist):
             raise RuntimeError('fn_step_dist: the ctypes mirror does not match the library (stale libfastnerf.so?)')
+        if l.fastnerf_step_expo_size() != C.sizeof(StepExpo):
+            raise RuntimeError('fn_step_expo: the ctypes mirror does not match the library (stale libfastnerf.so?)')
         _lib = l
     return _lib
 

@@ -8,6 +8,7 @@
 // one lane per image; pose_grad is the one with work in it, a segmented sum without atomics.
 #include "common.h"
 #include "pinhole.h"
+#include "seg_reduce.h"
 
 // Rodrigues' coefficients of theta^2 = |omega|^2, each in a form in which nothing cancels and nothing divides by zero:
 //   a = sin(theta) / theta,   b = (1 - cos(theta)) / theta^2 = 1/2 (sin(theta/2) / (theta/2))^2,   c = (theta - sin(theta)) / theta^3
@@ -145,18 +146,7 @@ __global__ void pose_exp_bwd_kernel(int n_img, const float* __restrict__ base, c
 // wave's 64 by shuffles, the 4 waves in lane 0), and with C > 1 a second launch adds an image's C partial sums in chunk order.  Which
 // lane and which chunk a ray falls to depends on its row index alone: no atomics, bit-identical from call to call.  The walk reads the 4-byte
 // image index of every ray of the chunk (out of L2: n_img * n reads in all) and 44 + 8 more bytes of the rays that match.
-#define FN_POSE_GRAD_BLOCK 256
-#define FN_POSE_GRAD_MIN_CHUNK 1024      // rays per workgroup below which splitting further only adds partial sums
-#define FN_POSE_GRAD_MAX_GROUPS 1024     // n_img * C stays near this: four workgroups per CU
-
-static inline int pose_grad_chunks(int64_t n, int n_img) {
-  int64_t by_rays = (n + FN_POSE_GRAD_MIN_CHUNK - 1) / FN_POSE_GRAD_MIN_CHUNK;
-  int64_t by_groups = FN_POSE_GRAD_MAX_GROUPS / n_img;
-  int64_t c = by_rays < by_groups ? by_rays : by_groups;
-  return c < 1 ? 1 : (int)c;
-}
-
-__global__ void __launch_bounds__(FN_POSE_GRAD_BLOCK)
+__global__ void __launch_bounds__(FN_SEG_BLOCK)
 pose_grad_kernel(int64_t n, int64_t chunk, const int32_t* __restrict__ pix, const float* __restrict__ poses, float fx, float fy, float cx,
                  float cy, const float* __restrict__ d_rays, float* __restrict__ out) {
   const int img = blockIdx.x, c = blockIdx.y, C = gridDim.y;
@@ -167,7 +157,7 @@ pose_grad_kernel(int64_t n, int64_t chunk, const int32_t* __restrict__ pix, cons
   float acc[12];
 #pragma unroll
   for (int k = 0; k < 12; ++k) acc[k] = 0.0f;
-  for (int64_t i = lo + threadIdx.x; i < hi; i += FN_POSE_GRAD_BLOCK) {
+  for (int64_t i = lo + threadIdx.x; i < hi; i += FN_SEG_BLOCK) {
     if (pix[i * 3] != img) continue;
     float dir[3], d[3];
     pixel_dir((float)pix[i * 3 + 1], (float)pix[i * 3 + 2], fx, fy, cx, cy, dir);
@@ -190,27 +180,10 @@ pose_grad_kernel(int64_t n, int64_t chunk, const int32_t* __restrict__ pix, cons
       acc[4 * j + 3] = fadd(acc[4 * j + 3], g[j]);
     }
   }
-  // 256 -> 1 in a fixed tree
-  __shared__ float part[FN_POSE_GRAD_BLOCK / 64][12];
-#pragma unroll
-  for (int k = 0; k < 12; ++k) {
-    float x = acc[k];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x = fadd(x, __shfl_down(x, off, 64));
-    acc[k] = x;
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < 12; ++k) part[wave][k] = acc[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < 12) {
-    float x = part[0][threadIdx.x];
-#pragma unroll
-    for (int w = 1; w < FN_POSE_GRAD_BLOCK / 64; ++w) x = fadd(x, part[w][threadIdx.x]);
-    out[((int64_t)img * C + c) * 12 + threadIdx.x] = x;
-  }
+  // 256 -> 1 in the fixed tree of seg_reduce.h
+  __shared__ float part[FN_SEG_BLOCK / 64][12];
+  seg_wave_sums(acc, part);
+  if (threadIdx.x < 12) out[((int64_t)img * C + c) * 12 + threadIdx.x] = seg_total(part, threadIdx.x);
 }
 
 // d_poses[img, e] = the sum of the image's C partial sums in chunk order (C == 0: an empty batch, +0)
@@ -252,7 +225,7 @@ extern "C" int64_t fastnerf_pose_grad_ws_floats(int64_t n, int n_img) {
     fn::set_error("fastnerf_pose_grad_ws_floats: bad argument: n >= 0, n_img >= 1");
     return -1;
   }
-  const int C = n == 0 ? 0 : pose_grad_chunks(n, n_img);
+  const int C = n == 0 ? 0 : seg_chunks(n, n_img);
   return C > 1 ? (int64_t)n_img * C * 12 : 0;
 }
 
@@ -268,11 +241,11 @@ extern "C" int fastnerf_pose_grad(int64_t n, int n_img, const int32_t* pix, cons
     }
     return 0;
   }
-  const int C = pose_grad_chunks(n, n_img);
+  const int C = seg_chunks(n, n_img);
   FN_CHECK_ARG(pix && poses && d_rays && d_poses, "null pointer (pix, poses, d_rays, d_poses)");
   FN_CHECK_ARG(C == 1 || ws, "null pointer (ws: fastnerf_pose_grad_ws_floats(n, n_img) floats)");
   const int64_t chunk = (n + C - 1) / C;
-  hipLaunchKernelGGL(pose_grad_kernel, dim3(n_img, C), dim3(FN_POSE_GRAD_BLOCK), 0, fn::S(stream), n, chunk, pix, poses, fx, fy, cx, cy,
+  hipLaunchKernelGGL(pose_grad_kernel, dim3(n_img, C), dim3(FN_SEG_BLOCK), 0, fn::S(stream), n, chunk, pix, poses, fx, fy, cx, cy,
                      d_rays, C == 1 ? d_poses : ws);
   FN_LAUNCH_CHECK();
   if (C > 1) {

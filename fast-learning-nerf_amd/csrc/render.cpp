@@ -651,6 +651,22 @@ extern "C" int64_t fastnerf_step_bkgd_size(void) { return (int64_t)sizeof(fn_ste
 
 extern "C" int64_t fastnerf_step_dist_size(void) { return (int64_t)sizeof(fn_step_dist); }
 
+extern "C" int64_t fastnerf_step_expo_size(void) { return (int64_t)sizeof(fn_step_expo); }
+
+// the refusals of a step with the exposure table (ex != NULL), before anything of the step is launched; the struct is read in a forward phase only
+static bool step_expo_ok(const fn_step_args* a, const fn_step_expo* ex, bool two, int phases, const char* fname) {
+  if (ex->n_img < 1 || !(ex->lambda >= 0.0f) || !(ex->lambda < __builtin_huge_valf()) || a->n >= ((int64_t)1 << 31)) {
+    fn::set_error("%s: bad argument: n_img >= 1, lambda >= 0 and finite, n < 2^31", fname);
+    return false;
+  }
+  if ((phases & FN_STEP_FORWARD) &&
+      (!ex->img || !ex->ab || !ex->e1 || (two && !ex->e0) || !ex->ws || !ex->d_ab || !ex->counts || !ex->loss_reg)) {
+    fn::set_error("%s: null member of fn_step_expo (img, ab, e1, ws, d_ab, counts, loss_reg; e0 with two passes)", fname);
+    return false;
+  }
+  return true;
+}
+
 // the refusals of a step with the distortion term (dist != NULL, lambda_dist != 0), before anything of the step is launched.  w1 / w0: the
 // weights of the image pass / of the coarse pass of two (NULL with one pass), as the step's forward leaves them
 static bool step_dist_ok(const fn_step_dist* d, bool two, int phases, const float* w1, const float* w0, const char* fname) {
@@ -716,19 +732,23 @@ struct LossPass { float* rgb; const float *acc, *depth, *w, *z; int S; float* g_
 // the pass in the *0 buffers of fn_step_args: the coarse pass of two, the image pass of one, the marched row
 static LossPass loss_pass0(const fn_step_args* a, int S, float* g_rgb) { return {a->rgb0, a->acc0, a->depth0, a->w0, a->z0, S, g_rgb}; }
 
-// The loss launches of a forward phase, behind its render, of both steps: blend -> mse_leafmax -> depth / opacity terms -> overflow mask -> what the
-// blend sends back to acc -> distortion.  p1: the image pass; p0: the coarse pass of two, {} with one.  aux / bk / dist: NULL = the term is off.  mask:
-// NULL, or the marched step's overflow flags (never with aux).  A new term is a few lines here; its checks stay with the callers', before any launch.
+// The loss launches of a forward phase, behind its render, of both steps: blend -> exposure -> mse_leafmax -> depth / opacity terms -> overflow mask ->
+// what the exposure sends back to the table (and takes out of the colour gradient) -> what the blend sends back to acc -> distortion.  p1: the image
+// pass; p0: the coarse pass of two, {} with one.  aux / bk / dist / ex: NULL = the term is off.  mask: NULL, or the marched step's overflow flags (never
+// with aux).  A new term is a few lines here; its checks stay with the callers', before any launch.
 static int step_losses(const fn_step_args* a, const LossPass& p1, const LossPass& p0, const fn_step_aux* aux, const fn_step_bkgd* bk,
-                       const fn_step_dist* dist, const uint8_t* mask, fn_stream_t stream) {
+                       const fn_step_dist* dist, const fn_step_expo* ex, const uint8_t* mask, fn_stream_t stream) {
   const bool two = p0.S > 0;
   int rc;
   // (bk: white_bkgd is 0 -- the forward left the bare maps; the colours go behind them and behind the target here)
   if (bk &&
       (rc = fastnerf_bkgd_blend(a->n, bk->bkgd, bk->seed, bk->alpha, p1.acc, p0.acc, p1.rgb, p0.rgb, a->target, bk->target_ws, bk->bkgd_used, stream)))
     return rc;
-  if ((rc = fastnerf_mse_leafmax(a->n, p1.rgb, p0.rgb, bk ? bk->target_ws : a->target, a->grad_scale, p1.g_rgb, p0.g_rgb, a->loss2, a->leaf_tag,
-                                 a->max_leaves, a->table, stream)))
+  // (ex: the colour loss and the leaf table see the re-exposed maps e; rgb stays the scene's colour)
+  float* e0 = (ex && two) ? ex->e0 : nullptr;
+  if (ex && (rc = fastnerf_expo_apply(a->n, ex->n_img, ex->img, ex->ab, p1.rgb, p0.rgb, ex->e1, e0, stream))) return rc;
+  if ((rc = fastnerf_mse_leafmax(a->n, ex ? ex->e1 : p1.rgb, ex ? e0 : p0.rgb, bk ? bk->target_ws : a->target, a->grad_scale, p1.g_rgb, p0.g_rgb,
+                                 a->loss2, a->leaf_tag, a->max_leaves, a->table, stream)))
     return rc;
   if (aux && (rc = fastnerf_aux_loss(a->n, p1.depth, p1.acc, p0.depth, p0.acc, aux->depth_target, aux->depth_weight, aux->acc_target, aux->acc_weight,
                                      aux->lambda_depth, aux->lambda_acc, a->grad_scale, aux->g_depth1, aux->g_acc1, two ? aux->g_depth0 : nullptr,
@@ -736,6 +756,10 @@ static int step_losses(const fn_step_args* a, const LossPass& p1, const LossPass
     return rc;
   // a truncated row has lost what lies behind the cut: its colour error does not train the field (loss2 stays the mean over all rays)
   if (mask && (rc = fastnerf_march_mask(a->n, mask, p1.g_rgb, stream))) return rc;
+  // behind the mask (a masked ray has G = 0: nothing for the table) and in front of every reader of the colour gradient, which it rescales in place
+  if (ex && (rc = fastnerf_expo_grad(a->n, ex->n_img, ex->img, ex->ab, ex->lambda, a->grad_scale, ex->e1, e0, p1.g_rgb, p0.g_rgb, ex->ws, ex->d_ab,
+                                     ex->counts, ex->loss_reg, stream)))
+    return rc;
   // what the blend sends back to acc, on top of the opacity term's rows when that term is on (behind the mask: an overflowed ray's g_acc is +-0)
   if (bk) {
     const bool add = aux && aux->acc_target;
@@ -770,11 +794,11 @@ static int step_update(const fn_step_args* a, int first, int count, fn_stream_t 
 }
 
 // aux: NULL, or the depth / opacity terms (a term is on when its target is set); bk: NULL, or the per-ray background colours; dist: NULL,
-// or the distortion term (on when lambda_dist != 0)
-static int train_step(const fn_step_args* a, const fn_step_aux* aux, const fn_step_bkgd* bk, const fn_step_dist* dist, int phases,
-                      fn_stream_t stream) {
+// or the distortion term (on when lambda_dist != 0); ex: NULL, or the exposure table
+static int train_step(const fn_step_args* a, const fn_step_aux* aux, const fn_step_bkgd* bk, const fn_step_dist* dist, const fn_step_expo* ex,
+                      int phases, fn_stream_t stream) {
   if (dist && dist->lambda_dist == 0.0f) dist = nullptr;
-  const char* fname = dist ? "fastnerf_train_step_dist" : bk ? "fastnerf_train_step_bkgd" : "fastnerf_train_step";
+  const char* fname = ex ? "fastnerf_train_step_expo" : dist ? "fastnerf_train_step_dist" : bk ? "fastnerf_train_step_bkgd" : "fastnerf_train_step";
   if (aux && !aux->depth_target && !aux->acc_target) aux = nullptr;
   if (!a || a->math_mode < 0 || a->math_mode > 2 || a->n <= 0 || a->N_samples < 2 || a->N_importance < 0) {
     fn::set_error("%s: bad argument: args != NULL, math_mode in {0,1,2}, n>0, N_samples>=2, N_importance>=0", fname);
@@ -783,6 +807,7 @@ static int train_step(const fn_step_args* a, const fn_step_aux* aux, const fn_st
   const bool two = a->N_importance > 0;
   if (bk && !step_bkgd_ok(a, bk, two, phases, fname)) return -1;
   if (dist && !step_dist_ok(dist, two, phases, two ? a->w1 : a->w0, two ? a->w0 : nullptr, fname)) return -1;
+  if (ex && !step_expo_ok(a, ex, two, phases, fname)) return -1;
   if (bk && aux && aux->acc_target && (phases & FN_STEP_FORWARD) && (!aux->g_acc1 || (two && !aux->g_acc0))) {
     fn::set_error("%s: null gradient buffer of the opacity term (its rows are added to the background's)", fname);
     return -1;
@@ -846,7 +871,7 @@ static int train_step(const fn_step_args* a, const fn_step_aux* aux, const fn_st
       return rc;
     const LossPass p0 = loss_pass0(a, a->N_samples, two ? a->g_rgb0 : a->g_rgb);
     const LossPass p1 = {a->rgb1, a->acc1, a->depth1, a->w1, a->z1, a->N_samples + a->N_importance, a->g_rgb};
-    if ((rc = step_losses(a, two ? p1 : p0, two ? p0 : LossPass{}, aux, bk, dist, nullptr, stream))) return rc;
+    if ((rc = step_losses(a, two ? p1 : p0, two ? p0 : LossPass{}, aux, bk, dist, ex, nullptr, stream))) return rc;
   }
   if (passes) {
     fn_map_grads mg = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -870,21 +895,26 @@ static int train_step(const fn_step_args* a, const fn_step_aux* aux, const fn_st
 }
 
 extern "C" int fastnerf_train_step(const fn_step_args* a, int phases, fn_stream_t stream) {
-  return train_step(a, nullptr, nullptr, nullptr, phases, stream);
+  return train_step(a, nullptr, nullptr, nullptr, nullptr, phases, stream);
 }
 
 extern "C" int fastnerf_train_step_aux(const fn_step_args* a, const fn_step_aux* aux, int phases, fn_stream_t stream) {
-  return train_step(a, aux, nullptr, nullptr, phases, stream);
+  return train_step(a, aux, nullptr, nullptr, nullptr, phases, stream);
 }
 
 extern "C" int fastnerf_train_step_bkgd(const fn_step_args* a, const fn_step_aux* aux, const fn_step_bkgd* bk, int phases,
                                         fn_stream_t stream) {
-  return train_step(a, aux, bk, nullptr, phases, stream);
+  return train_step(a, aux, bk, nullptr, nullptr, phases, stream);
 }
 
 extern "C" int fastnerf_train_step_dist(const fn_step_args* a, const fn_step_aux* aux, const fn_step_bkgd* bk, const fn_step_dist* dist,
                                         int phases, fn_stream_t stream) {
-  return train_step(a, aux, bk, dist, phases, stream);
+  return train_step(a, aux, bk, dist, nullptr, phases, stream);
+}
+
+extern "C" int fastnerf_train_step_expo(const fn_step_args* a, const fn_step_aux* aux, const fn_step_bkgd* bk, const fn_step_dist* dist,
+                                        const fn_step_expo* ex, int phases, fn_stream_t stream) {
+  return train_step(a, aux, bk, dist, ex, phases, stream);
 }
 
 // The marched step (include/fastnerf.h, "marched training"): one network on the packed rows of a jittered lattice.  The row is [n, C] in
@@ -898,16 +928,20 @@ extern "C" int64_t fastnerf_step_march_ws_ints(int64_t n, int C) {
   return march_ws_ints(n, C, false);
 }
 
-static int train_step_march(const fn_step_args* a, const fn_step_march* mx, const fn_step_bkgd* bk, const fn_step_dist* dist, int phases,
-                            fn_stream_t stream) {
+static int train_step_march(const fn_step_args* a, const fn_step_march* mx, const fn_step_bkgd* bk, const fn_step_dist* dist,
+                            const fn_step_expo* ex, int phases, fn_stream_t stream) {
   if (dist && dist->lambda_dist == 0.0f) dist = nullptr;
-  const char* fname = dist ? "fastnerf_train_step_march_dist" : bk ? "fastnerf_train_step_march_bkgd" : "fastnerf_train_step_march";
+  const char* fname = ex     ? "fastnerf_train_step_march_expo"
+                      : dist ? "fastnerf_train_step_march_dist"
+                      : bk   ? "fastnerf_train_step_march_bkgd"
+                             : "fastnerf_train_step_march";
   if (!a || !mx || a->math_mode < 0 || a->math_mode > 2 || a->n <= 0 || mx->which < 0 || mx->which > 1) {
     fn::set_error("%s: bad argument: args and march != NULL, math_mode in {0,1,2}, n > 0, which in {0,1}", fname);
     return -1;
   }
   if (bk && !step_bkgd_ok(a, bk, false, phases, fname)) return -1;
   if (dist && !step_dist_ok(dist, false, phases & ~FN_STEP_BWD_FINE, a->w0, nullptr, fname)) return -1;
+  if (ex && !step_expo_ok(a, ex, false, phases, fname)) return -1;
   const int K = mx->K, C = mx->C;
   const int64_t n = a->n;
   if (!march_kc_ok(K, C) || !march_n_ok(n, K, C)) {
@@ -956,7 +990,7 @@ static int train_step_march(const fn_step_args* a, const fn_step_march* mx, cons
     if ((rc = fastnerf_raw2outputs_fwd(n, C, a->raw0, a->z0, a->rays11, nullptr, a->white_bkgd, a->rgb0, a->disp0, a->acc0, a->w0, a->depth0,
                                        stream)))
       return rc;
-    if ((rc = step_losses(a, loss_pass0(a, C, a->g_rgb), {}, nullptr, bk, dist, mx->overflow, stream))) return rc;
+    if ((rc = step_losses(a, loss_pass0(a, C, a->g_rgb), {}, nullptr, bk, dist, ex, mx->overflow, stream))) return rc;
   }
   if (bwd) {
     // the single pass, built directly (one pass: both members of BwdPasses name it); its counters are the coarse pair, as after a one-pass
@@ -975,15 +1009,20 @@ static int train_step_march(const fn_step_args* a, const fn_step_march* mx, cons
 }
 
 extern "C" int fastnerf_train_step_march(const fn_step_args* a, const fn_step_march* mx, int phases, fn_stream_t stream) {
-  return train_step_march(a, mx, nullptr, nullptr, phases, stream);
+  return train_step_march(a, mx, nullptr, nullptr, nullptr, phases, stream);
 }
 
 extern "C" int fastnerf_train_step_march_bkgd(const fn_step_args* a, const fn_step_march* mx, const fn_step_bkgd* bk, int phases,
                                               fn_stream_t stream) {
-  return train_step_march(a, mx, bk, nullptr, phases, stream);
+  return train_step_march(a, mx, bk, nullptr, nullptr, phases, stream);
 }
 
 extern "C" int fastnerf_train_step_march_dist(const fn_step_args* a, const fn_step_march* mx, const fn_step_bkgd* bk, const fn_step_dist* dist,
                                               int phases, fn_stream_t stream) {
-  return train_step_march(a, mx, bk, dist, phases, stream);
+  return train_step_march(a, mx, bk, dist, nullptr, phases, stream);
+}
+
+extern "C" int fastnerf_train_step_march_expo(const fn_step_args* a, const fn_step_march* mx, const fn_step_bkgd* bk, const fn_step_dist* dist,
+                                              const fn_step_expo* ex, int phases, fn_stream_t stream) {
+  return train_step_march(a, mx, bk, dist, ex, phases, stream);
 }

@@ -165,17 +165,38 @@ class NerfNet(nn.Module):
         return OrderedDict(zip(keys, res))
 
 
+def _short_name(path):
+    """An image's key in `autoexpo_params` (ddp_model.py:146-154): every '.' becomes '-' (a parameter's name may hold no dot), one trailing
+    '/' goes, and the last three components of the path stay: '/data/scene/train/rgb/0001.png' -> 'train/rgb/0001-png'."""
+    path = path.replace('.', '-')
+    if path.endswith('/'):
+        path = path[:-1]
+    return '/'.join(path.split('/')[-3:])
+
+
 class NerfNetWithAutoExpo(nn.Module):
-    """ddp_model.py:157-188 with optim_autoexpo=False (the configs on this path never enable it)."""
+    """ddp_model.py:157-188.  optim_autoexpo=True with `img_names`: one parameter (0.5, 0) per image in the ParameterDict
+    `autoexpo_params`, keyed by the last three components of the image's path with dots turned into '-'; forward(..., img_name=) of a known image also returns
+    ret['autoexpo'] = (scale, shift) = (|a| + 0.5, shift).  (The batched form, one table over the rays of many images, is
+    exposure.ExposureTable with CascadeTrainer(exposure=).)"""
 
     def __init__(self, args=None, optim_autoexpo=False, img_names=None, device='cuda'):
         super().__init__()
-        if optim_autoexpo:
-            raise NotImplementedError('optim_autoexpo is not used by the tanks-and-temples configs')
         self.nerf_net = NerfNet(args, device=device)
+        self.optim_autoexpo = bool(optim_autoexpo)
+        if self.optim_autoexpo:
+            if img_names is None:
+                raise ValueError('NerfNetWithAutoExpo: optim_autoexpo=True needs img_names')
+            self.img_names = [_short_name(x) for x in img_names]
+            self.autoexpo_params = nn.ParameterDict(OrderedDict(
+                (name, nn.Parameter(torch.tensor([0.5, 0.], device=device))) for name in self.img_names))
 
     def forward(self, ray_o, ray_d, fg_z_max, fg_z_vals, bg_z_vals, img_name=None):
-        return self.nerf_net(ray_o, ray_d, fg_z_max, fg_z_vals, bg_z_vals)
+        ret = self.nerf_net(ray_o, ray_d, fg_z_max, fg_z_vals, bg_z_vals)
+        if self.optim_autoexpo and img_name is not None and _short_name(img_name) in self.autoexpo_params:
+            p = self.autoexpo_params[_short_name(img_name)]
+            ret['autoexpo'] = (torch.abs(p[0]) + 0.5, p[1])
+        return ret
 
     def load_state_dict(self, state_dict, strict=True, **kwargs):
         """Accepts the reference's checkpoints: its nets are saved through nn.DataParallel (`module.` prefix, ddp_train_nerf.py:154).
@@ -264,9 +285,14 @@ class CascadeTrainer:
     """Fused train_step batch of ddp_train_nerf.py:347-404 over `cascade_samples` levels, each level
     with its own net + Adam (no LR decay in this fork), gradients all-reduced when world_size > 1.
     `perturb=False` (an extension: the reference always jitters) takes the unperturbed depths and the deterministic inverse-CDF
-    positions, so that a sharded run can be compared with the single-rank run on the union of the shards."""
+    positions, so that a sharded run can be compared with the single-rank run on the union of the shards.
+    `exposure=` (one exposure.ExposureTable per level, as the reference has one set of autoexposure parameters per cascade level;
+    include/fastnerf.h, "exposure table") with step(..., img=[n] int): each level's loss and leaf errors see its colours as the ray's image
+    exposed them, ops.expo_apply / ops.expo_grad around the level's ops.mse_leafmax, plus `lambda_autoexpo` times the L1 pull of its table
+    towards the identity; the table takes the level's Adam step with moments of its own.  `expo_grad[m]` / `expo_loss[m]`: d(loss)/d(ab)
+    and the unscaled pull of level m in the last step.  The returned colours stay the scene's.  Single process only."""
 
-    def __init__(self, nets, cascade_samples=(64, 128), lrate=5e-4, min_depth=1e-4, perturb=True):
+    def __init__(self, nets, cascade_samples=(64, 128), lrate=5e-4, min_depth=1e-4, perturb=True, exposure=None, lambda_autoexpo=1.0):
         self.nets = [getattr(n, 'nerf_net', n) for n in nets]
         self.cascade_samples = list(cascade_samples)
         self.lrate, self.min_depth, self.perturb = lrate, min_depth, bool(perturb)
@@ -274,9 +300,35 @@ class CascadeTrainer:
         self.m = [torch.zeros_like(n.flat) for n in self.nets]
         self.v = [torch.zeros_like(n.flat) for n in self.nets]
         self.t = [0] * len(self.nets)
+        self.exposure, self.lambda_autoexpo = (None if exposure is None else list(exposure)), float(lambda_autoexpo)
+        if self.exposure is not None:
+            if len(self.exposure) != len(self.nets):
+                raise ValueError('CascadeTrainer: exposure= is one table per level ({}), got {}'.format(len(self.nets), len(self.exposure)))
+            if not (0. <= self.lambda_autoexpo < float('inf')):
+                raise ValueError('CascadeTrainer: lambda_autoexpo is a finite weight >= 0, not {!r}'.format(self.lambda_autoexpo))
+            self.expo_m = [torch.zeros_like(t.ab.data) for t in self.exposure]
+            self.expo_v = [torch.zeros_like(t.ab.data) for t in self.exposure]
+            self.expo_grad, self.expo_loss = [None] * len(self.nets), [None] * len(self.nets)
+
+    def _check_img(self, img, n):
+        """The refusals of a step's img=, before any launch -> None without tables, else contiguous int32 [n]."""
+        from . import parallel
+        if self.exposure is None:
+            if img is not None:
+                raise ValueError('CascadeTrainer.step: img= names rows of exposure tables: it needs CascadeTrainer(exposure=)')
+            return None
+        if parallel.world_size() > 1:
+            raise ValueError('CascadeTrainer: exposure= is not data parallel (world size {})'.format(parallel.world_size()))
+        if img is None:
+            raise ValueError('CascadeTrainer.step: a trainer with exposure= needs the image of every ray: img=')
+        from .exposure import check_img
+        img = check_img(img)
+        if img.shape[0] != n:
+            raise ValueError('CascadeTrainer.step: img= holds {} rows for {} rays'.format(img.shape[0], n))
+        return img
 
     def step(self, ray_o, ray_d, target, rand=None, leaf_tag=None, table=None, max_leaves=0, n_global=None,
-             update=True, sumcount=None):
+             update=True, sumcount=None, img=None):
         """One batch through every cascade level.  `table`: the MAX table of nerf-ours' rule (int32 bit patterns);
         `sumcount=(sums fp64, counts int32)`: the nerf++ fork's MEAN rule (nerf++-ours/tree.py:609-632) -- the LAST level's colours
         of this batch are accumulated per (image, leaf) on the device, no host copy.  n_global: rays of the whole batch when this
@@ -284,6 +336,7 @@ class CascadeTrainer:
         empty still joins every collective."""
         from . import parallel
         n = ray_o.shape[0]
+        img = self._check_img(img, n)
         dist = parallel.world_size() > 1
         if n == 0 and not dist:        # an empty batch of a single process is a no-op: no Adam step on a zero gradient (moments would decay,
             self.last_depths = []      # t advance and the parameters drift by momentum)
@@ -323,16 +376,24 @@ class CascadeTrainer:
             rgb = fg_rgb + lam[:, None] * bg_rgb
             last = m == len(self.nets) - 1
             scale = 1.0 if n_global is None else float(n) / float(n_global)
-            loss2, g, _ = ops.mse_leafmax(rgb, None, target, grad_scale=scale, leaf_tag=leaf_tag if (last and table is not None) else None,
+            seen = rgb      # what the loss and the leaf errors see: the level's colours as the ray's image exposed them
+            if img is not None:
+                ab = self.exposure[m].ab.data
+                seen, _ = ops.expo_apply(rgb.contiguous(), img, ab)
+            loss2, g, _ = ops.mse_leafmax(seen, None, target, grad_scale=scale, leaf_tag=leaf_tag if (last and table is not None) else None,
                                           max_leaves=max_leaves, table=table if last else None)
             if last and sumcount is not None:
-                ops.leaf_sumcount(rgb, target, leaf_tag, max_leaves, sumcount[0], sumcount[1])
+                ops.leaf_sumcount(seen, target, leaf_tag, max_leaves, sumcount[0], sumcount[1])
+            if img is not None:      # g becomes the gradient with respect to rgb, in place
+                self.expo_grad[m], _, self.expo_loss[m] = ops.expo_grad(img, ab, self.lambda_autoexpo, scale, seen, g)
             _nerfnet_backward(net, saved, g)
             if dist:
                 parallel.all_reduce_sum(net.flat_grad)
             if update:
                 self.t[m] += 1
                 ops.adam_step(net.flat, net.flat_grad, self.m[m], self.v[m], self.lrate, self.t[m])
+                if img is not None:
+                    ops.adam_step(ab, self.expo_grad[m], self.expo_m[m], self.expo_v[m], self.lrate, self.t[m])
             losses.append(loss2[0])
             ret = outs
         return torch.stack(losses), rgb
@@ -425,14 +486,14 @@ def create_nerf(rank, args, device='cuda'):
     newest `*.pth` of basedir/expname (or args.ckpt_path) is reloaded unless args.no_reload.  Networks are initialised under
     torch.manual_seed(777) like the reference, so that every process starts from the same weights."""
     import os
-    if getattr(args, 'optim_autoexpo', False):
-        raise NotImplementedError('optim_autoexpo is dead code in the reference loop (train_step passes img_name=None)')
     torch.manual_seed(777)
     models = OrderedDict()
     models['cascade_level'] = args.cascade_level
     models['cascade_samples'] = [int(x.strip()) for x in args.cascade_samples.split(',')]
     for m in range(models['cascade_level']):
-        net = NerfNetWithAutoExpo(args, optim_autoexpo=False, device=device)
+        # (args.optim_autoexpo builds the reference's per-image parameters; its own loop passes img_name=None and never reads them)
+        net = NerfNetWithAutoExpo(args, optim_autoexpo=bool(getattr(args, 'optim_autoexpo', False)),
+                                  img_names=getattr(args, 'img_names', None), device=device)
         models['net_{}'.format(m)] = net
         models['optim_{}'.format(m)] = torch.optim.Adam(net.parameters(), lr=args.lrate)
     start = 0

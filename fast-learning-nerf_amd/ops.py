@@ -411,6 +411,82 @@ def pose_grad(pix, poses, K, d_rays, d_poses=None, ws=None):
     return d_poses
 
 
+# ---- exposure table (csrc/exposure.hip; include/fastnerf.h, "exposure table") ---------------------
+def _need_img(img, n):
+    """Refuse an image list that the exposure kernels would not read as int32 [n] (no value is read here: a row outside the table is
+    defined behaviour, the ray is left untouched)."""
+    if img.dtype != torch.int32:
+        raise TypeError(f'img must be int32, got {img.dtype}')
+    if tuple(img.shape) != (n,):
+        raise ValueError(f'img must have shape {(n,)}, got {tuple(img.shape)}')
+
+
+def _need_ab(ab):
+    if ab.dim() != 2 or ab.shape[0] < 1:
+        raise ValueError(f'ab must have shape (n_img >= 1, 2), got {tuple(ab.shape)}')
+    _need_f32('ab', ab, ab.shape[0], 2)
+    return ab.shape[0]
+
+
+def expo_apply(rgb, img, ab, rgb0=None, out=None, out0=None):
+    """e [n,3] = (rgb - shift_i) / scale_i, i = img[r], scale_i = |ab[i,0]| + 0.5, shift_i = ab[i,1] (fastnerf_expo_apply): the colours
+    the loss sees.  rgb0: the coarse pass's map of a two-pass render.  A ray whose img is outside the table keeps rgb's bits.
+    out / out0: [n,3] buffers to write instead of new ones.  -> (e, e0 or None)"""
+    require_gpu(rgb, img, ab, rgb0, out, out0)
+    n_img, n = _need_ab(ab), rgb.shape[0]
+    _need_f32('rgb', rgb, n, 3)
+    _need_img(img, n)
+    if rgb0 is not None:
+        _need_f32('rgb0', rgb0, n, 3)
+    e = torch.empty_like(rgb, memory_format=torch.contiguous_format) if out is None else out
+    e0 = None if rgb0 is None else (torch.empty_like(e) if out0 is None else out0)
+    for name, t in (('out', e), ('out0', e0)):
+        if t is not None:
+            _need_f32(name, t, n, 3)
+    check(lib().fastnerf_expo_apply(n, n_img, ptr(img), ptr(ab), ptr(rgb), ptr(rgb0), ptr(e), ptr(e0), stream()), 'fastnerf_expo_apply')
+    return e, e0
+
+
+def expo_grad_ws_floats(n, n_img):
+    """Floats of scratch one expo_grad call over n rays of n_img images needs."""
+    return int(check(lib().fastnerf_expo_grad_ws_floats(int(n), int(n_img)), 'fastnerf_expo_grad_ws_floats'))
+
+
+def expo_grad(img, ab, lam, grad_scale, e, g, e0=None, g0=None, d_ab=None, counts=None, ws=None, loss_reg=None):
+    """The backward of expo_apply under a loss whose gradient with respect to e / e0 is g / g0 [n,3] (fastnerf_expo_grad): g and g0 are
+    divided by their ray's scale IN PLACE (they become the gradient with respect to rgb / rgb0), and
+    -> (d_ab [n_img,2], counts [n_img] int32 = rays per image, loss_reg [1] = the batch mean of |scale - 1| + |shift|), d_ab with the
+    gradient of lam * grad_scale * loss_reg in it.  A segmented sum without atomics; an image without a ray gets an exact zero row.
+    d_ab / counts / ws / loss_reg: buffers to use instead of new ones."""
+    require_gpu(img, ab, e, g, e0, g0, d_ab, counts, ws, loss_reg)
+    n_img, n = _need_ab(ab), g.shape[0]
+    _need_img(img, n)
+    for name, t in (('e', e), ('g', g), ('e0', e0), ('g0', g0)):
+        if t is not None:
+            _need_f32(name, t, n, 3)
+    if (e0 is None) != (g0 is None):
+        raise ValueError('expo_grad: e0 and g0 go together')
+    if not (0. <= float(lam) < float('inf')):
+        raise ValueError(f'expo_grad: lam is a finite weight >= 0, not {lam!r}')
+    dev = ab.device
+    if d_ab is None:
+        d_ab = torch.empty(n_img, 2, device=dev, dtype=torch.float32)
+    _need_f32('d_ab', d_ab, n_img, 2)
+    if counts is None:
+        counts = torch.empty(n_img, device=dev, dtype=torch.int32)
+    assert counts.dtype == torch.int32 and tuple(counts.shape) == (n_img,)
+    need = expo_grad_ws_floats(n, n_img)
+    if ws is None and need > 0:
+        ws = torch.empty(need, device=dev, dtype=torch.float32)
+    assert need == 0 or (ws.dtype == torch.float32 and ws.numel() >= need)
+    if loss_reg is None:
+        loss_reg = torch.empty(1, device=dev, dtype=torch.float32)
+    _need_f32('loss_reg', loss_reg, 1)
+    check(lib().fastnerf_expo_grad(n, n_img, ptr(img), ptr(ab), float(lam), float(grad_scale), ptr(e), ptr(e0), ptr(g), ptr(g0), ptr(ws),
+                                   ptr(d_ab), ptr(counts), ptr(loss_reg), stream()), 'fastnerf_expo_grad')
+    return d_ab, counts, loss_reg
+
+
 def raw2outputs_fwd(raw, z, rays11, noise=None, white_bkgd=False):
     require_gpu(raw, z, rays11, noise)
     n = rays11.shape[0]

@@ -78,6 +78,7 @@ class _Args:
     random_bkgd = False      # (not in the reference's parser) RGBA training over a fresh background colour per ray
     lambda_dist = 0.         # (not in the reference's parser) weight of the distortion loss on the ray weights (Trainer(lambda_dist=))
     refine_poses = False; pose_lrate = 1e-3      # (not in the reference's parser) refine the camera poses beside the field (Trainer(poses=))
+    optim_autoexpo = False; lambda_autoexpo = 1.      # (nerf++-ours' parser) fit a per-image exposure beside the field (Trainer(exposure=))
     n_epoch = 12; init_level = 3; rays_downscale = 1; subdivide_every = 1; subdivide_thres = 0.015
     randSamp_perc = 0.5; basedir = './logs'; expname = 'fastnerf'
 
@@ -210,11 +211,12 @@ def _step_regions(n, S0, Ni):
     return _lay_out(shapes, {}, 0)
 
 
-def _term_regions(base, size, n, S0, Ni, aux=False, bkgd=False, dist=False):
+def _term_regions(base, size, n, S0, Ni, aux=False, bkgd=False, dist=False, expo=None):
     """The table `base` of `size` floats (_step_regions(n, S0, Ni); not built again, and handed back as it is when no term is on)
-    with the tensors of the optional terms that are on behind it, in the order aux | bkgd | dist: region '<term>.<member>' is what
-    the pointer member of that name of the term's struct (fn_step_aux / fn_step_bkgd / fn_step_dist) points to.  A new term is one
-    more list here.  -> (regions, the block's size)"""
+    with the tensors of the optional terms that are on behind it, in the order aux | bkgd | dist | expo: region '<term>.<member>' is
+    what the pointer member of that name of the term's struct (fn_step_aux / fn_step_bkgd / fn_step_dist / fn_step_expo) points to.  expo:
+    None, or (n_img, the floats of its scratch); its counts are int32 in a region of as many words.  A new term is one more list here.
+    -> (regions, the block's size)"""
     shapes = []
     if aux:
         shapes += [('aux.' + k, (n,)) for k in ('g_depth1', 'g_acc1', 'g_depth0', 'g_acc0')] + [('aux.loss4', (4,))]
@@ -223,6 +225,9 @@ def _term_regions(base, size, n, S0, Ni, aux=False, bkgd=False, dist=False):
     if dist:      # (the *0 rows of aux and bkgd, and ell0, are laid out with one pass too; g_w0 would be empty)
         shapes += ([('dist.ell1', (n,)), ('dist.ell0', (n,)), ('dist.g_w1', (n, S0 + Ni))] + ([('dist.g_w0', (n, S0))] if Ni > 0 else [])
                    + [('dist.loss2d', (2,))])
+    if expo:
+        shapes += ([('expo.e1', (n, 3))] + ([('expo.e0', (n, 3))] if Ni > 0 else [])
+                   + [('expo.ws', (expo[1],)), ('expo.d_ab', (expo[0], 2)), ('expo.counts', (expo[0],)), ('expo.loss_reg', (1,))])
     return _lay_out(shapes, dict(base), size) if shapes else (base, size)
 
 
@@ -335,12 +340,23 @@ class Trainer:
     the same rays, bit for bit; every term above, leaf_tag / table, white_bkgd and networks without view directions pass through
     unchanged.  An image without a ray in the batch has a zero gradient.  Without `poses=` nothing changes.  ValueError: pix without
     poses= or poses= without pix, rays together with pix, occupancy= / tighten / march, data parallel.  NotImplementedError: ndc=True,
-    the math mode bf16x3 (no ray gradients)."""
+    the math mode bf16x3 (no ray gradients).
+
+    Per-image exposure (`exposure=` an exposure.ExposureTable, `lambda_autoexpo`, `exposure_lrate`; include/fastnerf.h, "exposure
+    table"): step(..., img=[n] int), the image of every ray (with pix= the default is pix[:, 0]).  The colour loss and the leaf-error table
+    see e = (rgb - shift_i) / scale_i of both passes, i = img[r]; the step also minimises lambda_autoexpo times the batch mean of
+    |scale_i - 1| + |shift_i|; out['rgb_map'] / out['rgb0'] stay the scene's colours.  `expo_grad` [n_img,2] = d(loss)/d(table.ab),
+    `expo_counts` int32 [n_img] the rays per image and `expo_loss` [1] the unscaled penalty of the last step; then an Adam step on the
+    table with moments of its own (`expo_m`, `expo_v`) at exposure_lrate (None: the networks' rate) times the networks' decay factor.  An
+    image without a ray has a zero gradient; a ray whose img is outside the table is left as it is.  A fresh table (rows (0.5, 0))
+    reproduces the step without it bit for bit.  All routes take it: the fused step (plain, compacted, through a grid, tighten), the
+    marched step (an overflowed ray gives the table nothing), the call-by-call route and the pose step.  Without `exposure=` nothing
+    changes.  ValueError: exposure= without img / pix, img without exposure=, a negative or non-finite lambda_autoexpo, data parallel."""
 
     def __init__(self, render_kwargs_train, H, W, K, near, far, lrate=5e-4, lrate_decay=250, decay=True,
                  beta1=0.9, beta2=0.999, eps=1e-8, occupancy=None, occupancy_every=16, occupancy_warmup=256, occupancy_cells=None,
                  lambda_depth=0., lambda_acc=0., tighten=False, march=None, march_cap=128, march_after=0, bkgd=None,
-                 lambda_dist=0., poses=None, pose_lrate=1e-3):
+                 lambda_dist=0., poses=None, pose_lrate=1e-3, exposure=None, lambda_autoexpo=1.0, exposure_lrate=None):
         kw = render_kwargs_train
         self._kw = kw
         self.net_c = kw['network_fn']
@@ -400,11 +416,49 @@ class Trainer:
         self.pose_m = self.pose_v = None
         if poses is not None:
             self.pose_m, self.pose_v = torch.zeros_like(poses.xi.data), torch.zeros_like(poses.xi.data)
+        self.exposure, self.lambda_autoexpo, self.exposure_lrate = exposure, float(lambda_autoexpo), exposure_lrate
+        self.expo_lr = lrate if exposure_lrate is None else float(exposure_lrate)
+        self._exp = None         # fn_step_expo of the current step (None: no table)
+        self._img = None         # the rays' images handed to the next _fused_prepare, which takes them and leaves None
+        self.expo_grad = None    # d(loss)/d(ab) [n_img,2] of the last step with the table
+        self.expo_counts = None  # int32 [n_img]: the rays of every image in that step
+        self.expo_loss = torch.zeros(1, device=self.flat.device, dtype=torch.float32)
+        self.expo_m = self.expo_v = None
+        if exposure is not None:
+            self.expo_m, self.expo_v = torch.zeros_like(exposure.ab.data), torch.zeros_like(exposure.ab.data)
         self._check_dist()
         self._check_poses()
+        self._check_expo()
         self._check_occupancy()
         self._check_march()
         self.repack()
+
+    def _check_expo(self):
+        """Whether the trainer has an exposure table; its refusals, before any launch (read on every step, like the other settings)."""
+        if self.exposure is None:
+            return False
+        if not (0. <= self.lambda_autoexpo < float('inf')):
+            raise ValueError('Trainer: lambda_autoexpo is a finite weight >= 0, not {!r}'.format(self.lambda_autoexpo))
+        if self.world > 1:
+            raise ValueError('Trainer: exposure= is not data parallel (world size {})'.format(self.world))
+        return True
+
+    def _check_expo_step(self, img, pix, n):
+        """The refusals of a step's img=, before any launch -> None without a table, else the rays' images as contiguous int32 [n]
+        (the default with pix= is its first column)."""
+        if not self._check_expo():
+            if img is not None:
+                raise ValueError('Trainer.step: img= names rows of an exposure table: it needs Trainer(exposure=)')
+            return None
+        if img is None:
+            if pix is None:
+                raise ValueError('Trainer.step: a trainer with exposure= needs the image of every ray: img= (or pix=)')
+            img = pix[:, 0]
+        from .exposure import check_img
+        img = check_img(img)
+        if img.shape[0] != n:
+            raise ValueError('Trainer.step: img= holds {} rows for {} rays'.format(img.shape[0], n))
+        return img
 
     def _check_poses(self):
         """The refusals of a trainer with a pose table, before any launch (read on every pose step, like the other settings)."""
@@ -529,7 +583,8 @@ class Trainer:
         return self.lambda_dist != 0.
 
     def forward_backward(self, rays_o, rays_d, target, leaf_tag=None, table=None, max_leaves=0, t_rand=None, u=None,
-                         n_global=None, alpha=None, bkgd=None, d_rays=False, depth=None, depth_weight=None, acc=None, acc_weight=None):
+                         n_global=None, alpha=None, bkgd=None, d_rays=False, img=None, depth=None, depth_weight=None, acc=None,
+                         acc_weight=None):
         """d_rays=True: the saving backward is forced and runs pass by pass with ops.ray_grad between the passes
         (render._backward_passes); out['d_rays'] [n,11] is d(loss)/d(rays11).  The parameter gradients are those of the plain backward,
         bit for bit."""
@@ -539,6 +594,7 @@ class Trainer:
             raise ValueError('Trainer.forward_backward: the call-by-call route has no occupancy grid; use step()')
         n = rays_o.shape[0]
         dev = rays_o.device
+        img = self._check_expo_step(img, None, n)
         bt = self._bkgd_terms(n, dev, alpha, bkgd)
         rays11 = ops.pack_rays(rays_o, rays_d, self.near, self.far, ndc=self.ndc, H=self.H, W=self.W,
                                focal=float(self.K[0][0]))
@@ -556,14 +612,19 @@ class Trainer:
             target, out['bkgd'] = ops.bkgd_blend(out['rgb_map'], out['acc_map'], target, bkgd=bt['bkgd'],
                                                  seed=_next_seed() if bt['bkgd'] is None else 0, alpha=bt['alpha'],
                                                  rgb0=out.get('rgb0'), acc0=out.get('acc0'))
-        loss2, g, g0 = ops.mse_leafmax(out['rgb_map'], out.get('rgb0'), target, grad_scale=scale, leaf_tag=leaf_tag,
-                                       max_leaves=max_leaves, table=table)
+        e1, e0 = out['rgb_map'], out.get('rgb0')
+        if img is not None:      # the same launches, around the colour loss, as fastnerf_train_step_expo makes
+            ab = self.exposure.ab.data
+            e1, e0 = ops.expo_apply(e1, img, ab, rgb0=e0)
+        loss2, g, g0 = ops.mse_leafmax(e1, e0, target, grad_scale=scale, leaf_tag=leaf_tag, max_leaves=max_leaves, table=table)
         maps = None
         self.aux_losses = self._aux_zero
         aux = self._aux_terms(n, depth, depth_weight, acc, acc_weight)
         if aux:      # the same launch, behind the colour loss, as fastnerf_train_step_aux makes
             self.aux_losses, gm = ops.aux_loss(out['depth_map'], out['acc_map'], out.get('depth0'), out.get('acc0'), grad_scale=scale, **aux)
             maps = {k: t for k, t in gm.items() if t is not None}
+        if img is not None:      # g, g0 become the gradient with respect to the scene's colours, in place
+            self.expo_grad, self.expo_counts, self.expo_loss = ops.expo_grad(img, ab, self.lambda_autoexpo, scale, e1, g, e0=e0, g0=g0)
         if bt is not None:
             ga1, ga0 = ops.bkgd_grad(out['bkgd'], g, g0, add=(maps or {}).get('g_acc1'), add0=(maps or {}).get('g_acc0'))
             maps = dict(maps or {}, g_acc1=ga1)
@@ -658,13 +719,14 @@ class Trainer:
         a.grad_scale = 1.0 if n_global is None else float(n) / float(n_global)
         return block, hold
 
-    def _begin_step(self, route, S0, Ni, extra, batch, given, alpha=None, bkgd=None, aux=(None,) * 4):
+    def _begin_step(self, route, S0, Ni, extra, batch, given, alpha=None, bkgd=None, aux=(None,) * 4, img=None):
         """What preparing a step is on both routes; _fused_prepare and _march_prepare add what differs.  In order: the background's terms,
         the GPU check, the grid's refusals, the math mode; the arguments of `route` ('fused' | 'march'), cached under (n, *extra, device,
         stream, math tag); the depth / opacity terms; the step's seeds (_step_seeds); one block laid out for the terms that are on
-        (_term_regions) and fn_step_args filled (_fill_step); self._aux / _bk / _dist (None: the term is off) pointing into the block, and
-        aux_losses / dist_losses as its views.  batch: (rays_o, rays_d, target, leaf_tag, table, max_leaves, n_global); given: what the
-        caller injects instead of draws, by _step_seeds' names; aux: (depth, depth_weight, acc, acc_weight).
+        (_term_regions) and fn_step_args filled (_fill_step); self._aux / _bk / _dist / _exp (None: the term is off) pointing into the block,
+        and aux_losses / dist_losses / expo_grad / expo_counts / expo_loss as its views.  batch: (rays_o, rays_d, target, leaf_tag, table,
+        max_leaves, n_global); given: what the caller injects instead of draws, by _step_seeds' names; aux: (depth, depth_weight, acc,
+        acc_weight); img: None, or the rays' images (_check_expo_step).
         -> (args, its keep-alive list, whether the args were built anew, block, regions, out key -> region of the terms' outputs, seeds,
         hold: what stays referenced until the next step is prepared -- the launches are asynchronous -- for the route to append to)"""
         n, dev = batch[0].shape[0], batch[0].device
@@ -680,10 +742,14 @@ class Trainer:
         aux = self._aux_terms(n, *aux)
         seeds = self._step_seeds(route == 'march', bkgd=bkgd, **given)
         dist = self._check_dist()
-        regions, size = _term_regions(base, size, n, S0, Ni, aux=bool(aux), bkgd=bt is not None, dist=dist)
+        expo = None
+        if img is not None:
+            ab = self.exposure.ab.data
+            expo = (ab.shape[0], ops.expo_grad_ws_floats(n, ab.shape[0]))
+        regions, size = _term_regions(base, size, n, S0, Ni, aux=bool(aux), bkgd=bt is not None, dist=dist, expo=expo)
         block, hold = self._fill_step(a, base, size, *batch)
         self._last = (block, regions)
-        self._aux = self._bk = self._dist = None
+        self._aux = self._bk = self._dist = self._exp = None
         self.aux_losses, self.dist_losses = self._aux_zero, self._dist_zero
         names = {}
         if aux:
@@ -699,14 +765,23 @@ class Trainer:
             self._dist = _term_struct(_lib.StepDist, 'dist', block, regions, lambda_dist=self.lambda_dist)
             self.dist_losses = _region(block, regions, 'dist.loss2d')
             names.update(dist_map='dist.ell1', **({'dist0': 'dist.ell0'} if Ni > 0 else {}))
+        if expo:
+            self._exp = _term_struct(_lib.StepExpo, 'expo', block, regions, img=_lib.ptr(img), ab=_lib.ptr(ab), n_img=expo[0],
+                                     **{'lambda': self.lambda_autoexpo})
+            self.expo_grad, self.expo_loss = _region(block, regions, 'expo.d_ab'), _region(block, regions, 'expo.loss_reg')
+            self.expo_counts = _region(block, regions, 'expo.counts').view(torch.int32)
+            hold += [img, ab]
         self._hold = hold
         return a, keep, fresh, block, regions, names, seeds, hold
 
-    # ---- fused route: one fastnerf_train_step_dist call per phase group ---------------------------------------------
+    # ---- fused route: one fastnerf_train_step_expo call per phase group ---------------------------------------------
     def _fused_prepare(self, rays_o, rays_d, target, leaf_tag, table, max_leaves, t_rand, u, n_global, alpha=None, bkgd=None,
                        depth=None, depth_weight=None, acc=None, acc_weight=None):
         """Fill fn_step_args (and the structs of the terms that are on: _begin_step) for this batch; returns (args, out mapping, loss2,
-        live)."""
+        live).  The rays' images of a step with an exposure table come in self._img, which step() sets just before this call and which
+        is taken here, once: this signature is pinned to end in the depth / opacity arguments and is called positionally up to them
+        (tests/test_aux_loss_cpu.py, tests/test_gpu_step_terms.py), so it has no place for one more; a direct call sees None."""
+        img, self._img = self._img, None
         n, dev = rays_o.shape[0], rays_o.device
         S0, Ni = self.N_samples, self.N_importance
         if t_rand is not None:
@@ -717,7 +792,7 @@ class Trainer:
             assert u.shape == (n, Ni)
         a, keep, _, block, regions, names, seeds, hold = self._begin_step(
             'fused', S0, Ni, (), (rays_o, rays_d, target, leaf_tag, table, max_leaves, n_global), dict(t_rand=t_rand, u=u), alpha, bkgd,
-            (depth, depth_weight, acc, acc_weight))
+            (depth, depth_weight, acc, acc_weight), img)
         self._sa = a
         live = self.live.use_live(self.net_c, self.net_f, Ni)
         if self.occupancy is not None or self.tighten:
@@ -766,8 +841,8 @@ class Trainer:
                                       _packed=[self.pc[0]] + ([self.pf[0]] if (self.pf is not None and self.net_f is not self.net_c) else []))
         self.occupancy_steps += 1
 
-    # ---- marched route: one fastnerf_train_step_march_dist call per phase group -----------------------------------
-    def _march_prepare(self, K, C, rays_o, rays_d, target, leaf_tag, table, max_leaves, march_u, n_global, alpha=None, bkgd=None):
+    # ---- marched route: one fastnerf_train_step_march_expo call per phase group -----------------------------------
+    def _march_prepare(self, K, C, rays_o, rays_d, target, leaf_tag, table, max_leaves, march_u, n_global, alpha=None, bkgd=None, img=None):
         """Fill fn_step_args and fn_step_march (and the structs of the terms that are on: _begin_step) for this batch; returns (args, march,
         out dict, loss2).  out['march_overflow'] is the step's uint8 buffer here: step() hands it out as bool once the forward is enqueued."""
         n, dev = rays_o.shape[0], rays_o.device
@@ -776,7 +851,7 @@ class Trainer:
             assert march_u.shape == (n,)
         # the row is a single pass of C samples, always compacted
         a, keep, fresh, block, regions, names, seeds, hold = self._begin_step(
-            'march', C, 0, (K, C), (rays_o, rays_d, target, leaf_tag, table, max_leaves, n_global), dict(march_u=march_u), alpha, bkgd)
+            'march', C, 0, (K, C), (rays_o, rays_d, target, leaf_tag, table, max_leaves, n_global), dict(march_u=march_u), alpha, bkgd, img=img)
         if fresh:
             x = _lib.StepMarch()
             self._ma = (a, x)
@@ -804,12 +879,12 @@ class Trainer:
     # The term structs are given in every phase call (the data-parallel step splits the phases).  NULL is "the term is off": the C side
     # then makes the launches, and names itself in errors, as the entry point without that struct does.
     def _march_call(self, a, x, phases):
-        _lib.check(_lib.lib().fastnerf_train_step_march_dist(ctypes.byref(a), ctypes.byref(x), _ref(self._bk), _ref(self._dist), int(phases),
-                                                             _lib.stream()), 'fastnerf_train_step_march_dist')
+        _lib.check(_lib.lib().fastnerf_train_step_march_expo(ctypes.byref(a), ctypes.byref(x), _ref(self._bk), _ref(self._dist), _ref(self._exp),
+                                                             int(phases), _lib.stream()), 'fastnerf_train_step_march_expo')
 
     def _fused_call(self, a, phases):
-        _lib.check(_lib.lib().fastnerf_train_step_dist(ctypes.byref(a), _ref(self._aux), _ref(self._bk), _ref(self._dist), int(phases),
-                                                       _lib.stream()), 'fastnerf_train_step_dist')
+        _lib.check(_lib.lib().fastnerf_train_step_expo(ctypes.byref(a), _ref(self._aux), _ref(self._bk), _ref(self._dist), _ref(self._exp),
+                                                       int(phases), _lib.stream()), 'fastnerf_train_step_expo')
 
     def _after_backward(self, live):
         if live:
@@ -840,13 +915,14 @@ class Trainer:
         return torch.zeros(2, device=self.grad.device), {}
 
     def step(self, rays_o, rays_d, target, leaf_tag=None, table=None, max_leaves=0, t_rand=None, u=None,
-             n_global=None, decay=None, march_u=None, alpha=None, bkgd=None, pix=None, depth=None, depth_weight=None, acc=None,
-             acc_weight=None):
+             n_global=None, decay=None, march_u=None, alpha=None, bkgd=None, pix=None, img=None, depth=None, depth_weight=None,
+             acc=None, acc_weight=None):
         if pix is not None or self.poses is not None:
             pix = self._check_pose_step(rays_o, rays_d, pix)
             n = pix.shape[0]
         else:
             n = rays_o.shape[0]
+        img = self._check_expo_step(img, pix, n)
         Nn = ops.NET_PARAMS
         two = self.N_importance > 0 and self.net_f is not None and self.net_f is not self.net_c
         overlap = self.world > 1 and two and self.overlap_allreduce and self.grad.numel() == 2 * Nn
@@ -869,17 +945,20 @@ class Trainer:
                 loss2, out = self._empty_step(everything, overlap)
             if pix is not None:
                 self._pose_update(pix, None, None)
+            if img is not None:
+                self.expo_grad, self.expo_counts = torch.zeros_like(self.expo_m), torch.zeros_like(self.expo_m[:, 0], dtype=torch.int32)
+                self.expo_loss = torch.zeros_like(self.expo_loss)
         elif pix is not None:
             # the pose step: the call-by-call route with ray gradients, then the rays' gradient down to xi and an Adam step of its own
             poses = ops.pose_exp(self.poses.base, self.poses.xi.data)
             ro, rd = ops.gen_rays_pixels(pix, poses, self.K)
             loss2, out = self.forward_backward(ro, rd, target, leaf_tag, table, max_leaves, t_rand, u, n_global, alpha=alpha, bkgd=bkgd,
-                                               depth=depth, depth_weight=depth_weight, acc=acc, acc_weight=acc_weight, d_rays=True)
+                                               depth=depth, depth_weight=depth_weight, acc=acc, acc_weight=acc_weight, d_rays=True, img=img)
             self._pose_update(pix, poses, out['d_rays'])
             self._host_update(everything, overlap)
         elif marching:
             a, x, out, loss2 = self._march_prepare(KC[0], KC[1], rays_o, rays_d, target, leaf_tag, table, max_leaves, march_u, n_global,
-                                                   alpha, bkgd)
+                                                   alpha, bkgd, img)
             a.lr, a.adam_t = float(self.lr), int(self.adam_t)
             if self.world == 1:
                 self._march_call(a, x, _lib.STEP_FORWARD | _lib.STEP_BWD_COARSE | _lib.STEP_UPDATE)
@@ -891,6 +970,7 @@ class Trainer:
             self.live.tick()
             self.last_step_live = True
         elif self.fused:
+            self._img = img
             a, out, loss2, live = self._fused_prepare(rays_o, rays_d, target, leaf_tag, table, max_leaves, t_rand, u, n_global,
                                                       alpha, bkgd, depth, depth_weight, acc, acc_weight)
             a.lr, a.adam_t = float(self.lr), int(self.adam_t)
@@ -913,12 +993,17 @@ class Trainer:
                 self._fused_call(a, _lib.STEP_UPDATE)
         else:
             loss2, out = self.forward_backward(rays_o, rays_d, target, leaf_tag, table, max_leaves, t_rand, u, n_global,
-                                               alpha=alpha, bkgd=bkgd, depth=depth, depth_weight=depth_weight, acc=acc, acc_weight=acc_weight)
+                                               alpha=alpha, bkgd=bkgd, depth=depth, depth_weight=depth_weight, acc=acc, acc_weight=acc_weight,
+                                               img=img)
             self._host_update(everything, overlap)
+        if img is not None:      # Adam on the table with moments of its own, as _pose_update does for xi
+            ops.adam_step(self.exposure.ab.data, self.expo_grad, self.expo_m, self.expo_v, self.expo_lr, self.adam_t, self.beta1, self.beta2,
+                          self.eps)
         if (self.decay if decay is None else decay):
             factor = 0.1 ** (self.global_iter / (self.lrate_decay * 1000))
             self.lr = self.lrate * factor
             self.pose_lr = self.pose_lrate * factor
+            self.expo_lr = (self.lrate if self.exposure_lrate is None else float(self.exposure_lrate)) * factor
             self.global_iter += 1
         return loss2, out
 
@@ -949,6 +1034,8 @@ class Trainer:
         sd = {'m': self.m, 'v': self.v, 'adam_t': self.adam_t, 'global_iter': self.global_iter, 'lr': self.lr}
         if self.poses is not None:
             sd.update(pose_m=self.pose_m, pose_v=self.pose_v, pose_lr=self.pose_lr)
+        if self.exposure is not None:
+            sd.update(expo_m=self.expo_m, expo_v=self.expo_v, expo_lr=self.expo_lr)
         return sd
 
     # ---- interchange with torch.optim.Adam (the optimizer_state_dict of the reference's .tar, run_nerf.py:121,537) ----
@@ -985,12 +1072,32 @@ class Trainer:
         self.pose_m.copy_(ckpt['pose_m']); self.pose_v.copy_(ckpt['pose_v'])
         return True
 
+    def load_expo_checkpoint(self, ckpt):
+        """Take the exposure table and its moments from a checkpoint of save_checkpoint (the loaded dict, or its path).  A checkpoint
+        without one leaves the table untouched; one for another number of images is a ValueError."""
+        if self.exposure is None:
+            return False
+        ab = self.exposure.ab.data
+        if not isinstance(ckpt, dict):
+            ckpt = torch.load(ckpt, map_location=ab.device, weights_only=False)
+        if 'expo_ab' not in ckpt:
+            return False
+        if ckpt['expo_ab'].shape != ab.shape:
+            raise ValueError('Trainer.load_expo_checkpoint: the checkpoint holds exposures of {} images, this table of {}'.format(
+                ckpt['expo_ab'].shape[0], ab.shape[0]))
+        ab.copy_(ckpt['expo_ab'])
+        self.expo_m.copy_(ckpt['expo_m']); self.expo_v.copy_(ckpt['expo_v'])
+        return True
+
     def load_state_dict(self, sd):
         self.m.copy_(sd['m']); self.v.copy_(sd['v'])
         self.adam_t, self.global_iter, self.lr = sd['adam_t'], sd['global_iter'], sd['lr']
         if self.poses is not None and 'pose_m' in sd:      # (a state without them: the table's moments stay as they are)
             self.pose_m.copy_(sd['pose_m']); self.pose_v.copy_(sd['pose_v'])
             self.pose_lr = sd.get('pose_lr', self.pose_lr)
+        if self.exposure is not None and 'expo_m' in sd:
+            self.expo_m.copy_(sd['expo_m']); self.expo_v.copy_(sd['expo_v'])
+            self.expo_lr = sd.get('expo_lr', self.expo_lr)
 
 
 def reference_state_dict(net):
@@ -1017,6 +1124,8 @@ def save_checkpoint(args, epoch_id, trainer, kw_train, mgr):
             'optimizer_state_dict': trainer.torch_optimizer_state_dict()}
     if trainer.poses is not None:      # the pose table beside them (keys the reference does not read)
         ckpt.update(pose_xi=trainer.poses.xi.data, pose_base=trainer.poses.base, pose_m=trainer.pose_m, pose_v=trainer.pose_v)
+    if trainer.exposure is not None:      # and the exposure table
+        ckpt.update(expo_ab=trainer.exposure.ab.data, expo_m=trainer.expo_m, expo_v=trainer.expo_v)
     torch.save(ckpt, path)
     mgr.save_trees(tree_pkl_path(args, epoch_id))
     return path
@@ -1102,13 +1211,22 @@ def train(images, poses, H, W, focal, args, near=2., far=6., device='cuda', log=
         from .poses import PoseTable
         pose_kw = dict(poses=PoseTable(torch.as_tensor(poses, dtype=torch.float32)[:, :3, :4]).to(dev),
                        pose_lrate=float(getattr(args, 'pose_lrate', 1e-3)))
+    # args.optim_autoexpo, args.lambda_autoexpo (the reference's names, nerf++-ours ddp_train_nerf.py; default off): an ExposureTable with a
+    # row per image is fitted beside the networks; the steps get the image of every row.  The table is trainer.exposure.
+    autoexpo = bool(getattr(args, 'optim_autoexpo', False))
+    expo_kw = {}
+    if autoexpo:
+        from .exposure import ExposureTable
+        expo_kw = dict(exposure=ExposureTable(len(images)).to(dev), lambda_autoexpo=float(getattr(args, 'lambda_autoexpo', 1.)))
     trainer = Trainer(kw_train, H, W, K, near, far, lrate=args.lrate, lrate_decay=args.lrate_decay, bkgd='random' if random_bkgd else None,
-                      lambda_dist=float(getattr(args, 'lambda_dist', 0.)), **occ_kw, **pose_kw)
+                      lambda_dist=float(getattr(args, 'lambda_dist', 0.)), **occ_kw, **pose_kw, **expo_kw)
     trainer.global_iter = global_iter
     if len(optimizer.state_dict()['state']) > 0:   # create_nerf restored a checkpoint (ours or the reference's)
         trainer.load_torch_optimizer(optimizer)
         if refine_poses and create_nerf.last_ckpt_path is not None:
             trainer.load_pose_checkpoint(create_nerf.last_ckpt_path)
+        if autoexpo and create_nerf.last_ckpt_path is not None:
+            trainer.load_expo_checkpoint(create_nerf.last_ckpt_path)
     images = torch.as_tensor(images, dtype=torch.float32)
     alpha_img = None
     if random_bkgd:      # the quadtree manager (and the leaf-error picks) see the straight colours; alpha travels beside them
@@ -1133,11 +1251,13 @@ def train(images, poses, H, W, focal, args, near=2., far=6., device='cuda', log=
     rank, world = parallel.rank(), parallel.world_size()
     history = []
 
-    def run_batches(rays_o, rays_d, tgt, tags, decay, table, max_leaves, local_of=None, alpha=None, pix=None):
+    def run_batches(rays_o, rays_d, tgt, tags, decay, table, max_leaves, local_of=None, alpha=None, pix=None, img=None):
         """local_of = N: the tensors hold only THIS rank's rows of an epoch of N rows (gen_rays_device(shard=...)), batch after batch.
-        pix (refine_poses): the rows' pixels [N,3]; the steps get them instead of the rays."""
+        pix (refine_poses): the rows' pixels [N,3]; the steps get them instead of the rays.  img (optim_autoexpo): the rows' images [N]."""
         if pix is not None:
             pix = pix.to(dev).int()
+        if img is not None:
+            img = img.to(dev).int()
         n_total = rays_o.shape[0] if local_of is None else local_of
         it = 0
         lo = 0
@@ -1154,7 +1274,8 @@ def train(images, poses, H, W, focal, args, near=2., far=6., device='cuda', log=
                                     tgt[sl].contiguous(), leaf_tag=None if tags is None else tags[sl].contiguous(),
                                     table=table, max_leaves=max_leaves, n_global=(b1 - b0) if world > 1 else None,
                                     decay=decay, alpha=None if alpha is None else alpha[sl].contiguous(),
-                                    **({} if pix is None else {'pix': pix[sl].contiguous()}))
+                                    **({} if pix is None else {'pix': pix[sl].contiguous()}),
+                                    **({} if img is None else {'img': img[sl].contiguous()}))
             it += 1
             if max_iters_per_epoch is not None and it >= max_iters_per_epoch:
                 break
@@ -1172,7 +1293,8 @@ def train(images, poses, H, W, focal, args, near=2., far=6., device='cuda', log=
         pix = torch.cat([torch.cat([torch.full((randNum, 1), i, dtype=torch.int64), sel], 1)
                          for i in range(mgr.n_images)], 0)
         ro, rd, tgt = mgr.gather(pix)
-        loss2, it = run_batches(ro, rd, tgt, None, False, None, 0, alpha=alpha_at(pix), pix=pix if refine_poses else None)
+        loss2, it = run_batches(ro, rd, tgt, None, False, None, 0, alpha=alpha_at(pix), pix=pix if refine_poses else None,
+                                img=pix[:, 0] if autoexpo else None)
         log('warm-up: {} iters, fine/coarse mse {}'.format(it, loss2.tolist()))
 
     for epoch_id in range(start_epoch + 1, args.n_epoch + 1):
@@ -1186,12 +1308,13 @@ def train(images, poses, H, W, focal, args, near=2., far=6., device='cuda', log=
         sharded_gen = world > 1 and not compat_rng and dev.type == 'cuda'
         ro, rd, tgt = mgr.gen_rays_v3_multiThread(down_scale=1, prob=False, randSamp_proc=args.randSamp_perc,
                                                   last_epoch=last, compat_rng=compat_rng,
-                                                  shard=(rank, world, N_rand) if sharded_gen else None, want_pix=random_bkgd or refine_poses)
+                                                  shard=(rank, world, N_rand) if sharded_gen else None, want_pix=random_bkgd or refine_poses or autoexpo)
         tags = mgr.result_leaf_tag
         max_leaves = mgr.max_leaves()
         table = torch.zeros(mgr.n_images * max_leaves, device=dev, dtype=torch.int32)
         loss2, it = run_batches(ro, rd, tgt, tags, True, table, max_leaves, local_of=mgr.epoch_rows if sharded_gen else None,
-                                alpha=alpha_at(mgr.result_pix) if random_bkgd else None, pix=mgr.result_pix if refine_poses else None)
+                                alpha=alpha_at(mgr.result_pix) if random_bkgd else None, pix=mgr.result_pix if refine_poses else None,
+                                img=mgr.result_pix[:, 0] if autoexpo else None)
         psnr = mse2psnr(loss2[:1].cpu())
         history.append((epoch_id, it, float(loss2[0]), float(psnr[0]), time.time() - t0))
         log('epoch {}: {} iters, fine mse {:.5f} psnr {:.2f}, {:.1f}s'.format(*history[-1]) +

@@ -1022,6 +1022,64 @@ int64_t fastnerf_pose_grad_ws_floats(int64_t n, int n_img);
 int fastnerf_pose_grad(int64_t n, int n_img, const int32_t* pix, const float* poses, float fx, float fy, float cx, float cy,
                        const float* d_rays, float* ws, float* d_poses, fn_stream_t stream);
 
+/* ---- exposure table: per-image exposures that training fits beside the field (csrc/exposure.hip) -------------------------------------
+ * Per image i a row ab[i] = (a_i, shift_i) of ab [n_img,2]; scale_i = |a_i| + 0.5, so that the row (0.5, 0) is the identity (the
+ * reference's autoexposure parameters, nerf++-ours ddp_model.py:157-188).  img [n] int32 names the image of every ray.  For ray r of
+ * image i = img[r], per pass p (1: the pass that produces the image, 0: the coarse pass of two) and channel c:
+ *   e_p[r,c] = (rgb_p[r,c] - shift_i) / scale_i              one fsub, one IEEE division; rgb_p behind the background blend
+ *   L = mse(e_1, t) + mse(e_0, t) + lambda (1/n) sum_r (|scale_i(r) - 1| + |shift_i(r)|)
+ * (for a batch drawn from one image, the reference's loss).
+ *
+ * fastnerf_expo_apply: e1 / e0 [n,3] from rgb1 / rgb0 [n,3]; rgb0 and e0 are NULL with one pass.  One thread per ray.
+ *
+ * fastnerf_expo_grad: with G_p = dL/de_p in g1 / g0 [n,3] (what fastnerf_mse_leafmax leaves, grad_scale included),
+ *   g_p[r,c]  = G_p[r,c] / scale_i                           written over G_p IN PLACE: the colour gradient every later launch reads
+ *   d_shift_i = -sum_{r in i} sum_{p,c} g_p[r,c],     d_scale_i = -sum_{r in i} sum_{p,c} g_p[r,c] e_p[r,c]
+ *   d_ab[i,0] = sign(a_i) (d_scale_i + lambda grad_scale cnt_i/n sign(scale_i - 1))           sign(0) = 0, as torch.abs differentiates
+ *   d_ab[i,1] = d_shift_i + lambda grad_scale cnt_i/n sign(shift_i)
+ *   counts[i] = cnt_i, the number of rays of image i;   loss_reg[0] = sum_i (cnt_i/n) (|scale_i - 1| + |shift_i|), images in index order
+ * d_ab [n_img,2], counts [n_img] int32 and loss_reg [1] are written, not accumulated; an image without a ray gets an exact zero row.
+ * A segmented sum without atomics (the scheme of fastnerf_pose_grad): workgroup (image, chunk) walks a contiguous chunk of the batch
+ * and owns the rays of it that name its image, lane sums in ray order, a fixed tree over the 256 lanes, the chunks in chunk order in a
+ * finish launch; the chunk count is a function of (n, n_img) alone: bit-identical from call to call.  n == 0: the finish launch alone
+ * writes zeros.  ws: fastnerf_expo_grad_ws_floats(n, n_img) floats of scratch (0 only for n == 0).
+ *
+ * A ray whose img lies outside [0, n_img) is left untouched by both (e = rgb, g = G) and belongs to no image: the kernels read no
+ * table row for it.  With the identity row e has the bits of rgb and g those of G.
+ *
+ * -1 before anything is enqueued: n < 0 or n >= 2^31; n_img < 1; a negative or non-finite lambda; a NULL table or output; with n > 0 a
+ * NULL img, map, gradient or ws; rgb0 / e0 (apply) or e0 / g0 (grad) not both set or both NULL.  All stores are plain vector stores.
+ *
+ * fastnerf_train_step_expo / fastnerf_train_step_march_expo: fastnerf_train_step_dist / fastnerf_train_step_march_dist (aux, bk and dist
+ * may be NULL as there) with the term.  FN_STEP_FORWARD: the loss launches become  blend -> expo_apply -> mse_leafmax on e1 / e0 ->
+ * depth / opacity terms -> march mask -> expo_grad on g_rgb / g_rgb0 -> bkgd_grad -> distortion.  The leaf-error table sees e; rgb0 /
+ * rgb1 stay the scene's colours.  An overflowed marched ray has G = 0 and gives the table nothing, but counts in cnt.  The step's loss is
+ * loss2[0] + loss2[1] + lambda loss_reg[0] (+ the other terms).  fn_step_expo is read in a forward phase only.  ex == NULL: the _dist
+ * entry point, launch for launch.  -1 before anything is enqueued, beside the refusals of those entry points: n_img < 1, a negative or
+ * non-finite lambda, n >= 2^31, a NULL member in a forward phase (e0 with two passes only). */
+typedef struct fn_step_expo {
+  const int32_t* img;               /* [n] */
+  const float* ab;                  /* [n_img,2] */
+  int n_img;
+  float lambda;
+  float *e1, *e0;                   /* [n,3] each out: what the colour loss saw (e0 with two passes) */
+  float* ws;                        /* fastnerf_expo_grad_ws_floats(n, n_img) floats */
+  float* d_ab;                      /* [n_img,2] out */
+  int32_t* counts;                  /* [n_img] out */
+  float* loss_reg;                  /* [1] out */
+} fn_step_expo;
+int64_t fastnerf_step_expo_size(void);              /* sizeof(fn_step_expo): binding sanity check */
+int fastnerf_expo_apply(int64_t n, int n_img, const int32_t* img, const float* ab, const float* rgb1, const float* rgb0, float* e1,
+                        float* e0, fn_stream_t stream);
+int64_t fastnerf_expo_grad_ws_floats(int64_t n, int n_img);
+int fastnerf_expo_grad(int64_t n, int n_img, const int32_t* img, const float* ab, float lambda, float grad_scale, const float* e1,
+                       const float* e0, float* g1, float* g0, float* ws, float* d_ab, int32_t* counts, float* loss_reg,
+                       fn_stream_t stream);
+int fastnerf_train_step_expo(const fn_step_args* args, const fn_step_aux* aux, const fn_step_bkgd* bk, const fn_step_dist* dist,
+                             const fn_step_expo* ex, int phases, fn_stream_t stream);
+int fastnerf_train_step_march_expo(const fn_step_args* args, const fn_step_march* march, const fn_step_bkgd* bk,
+                                   const fn_step_dist* dist, const fn_step_expo* ex, int phases, fn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

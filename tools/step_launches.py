@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Kernel launches per training step, with every optional term of the step off or on (profiles/step_host.md).
 
-  step_launches.py run off|on <k>    k steps at the benchmark's shape (4096 rays, 64 + 128 samples, bf16x6, plain backward); `on`: depth /
-                                     opacity supervision, random per-ray backgrounds with an alpha, the distortion loss.  For
+  step_launches.py run off|on|expo <k>   k steps at the benchmark's shape (4096 rays, 64 + 128 samples, bf16x6, plain backward); `on`: depth /
+                                     opacity supervision, random per-ray backgrounds with an alpha, the distortion loss; `expo`: the terms
+                                     off and an exposure table of 100 images (profiles/exposure.md).  For
                                      rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o steps -- python tools/step_launches.py run on 4
   step_launches.py count DIR         launches per step from DIR's kernel trace: the dispatches from one pack_rays_kernel (the first launch of a
                                      step) to the next.  The first count includes what only a first step launches and the last one runs to the
@@ -28,7 +29,10 @@ def run(terms, k):
     args = fn.run_nerf.make_args(N_importance=128, N_samples=64, perturb=1.0, white_bkgd=not on, no_reload=True)
     torch.manual_seed(0)
     ktr = fn.run_nerf.create_nerf(args, device='cuda')[0]
-    tr = fn.run_nerf.Trainer(ktr, H, W, K, 2.0, 6.0, **(dict(lambda_depth=0.1, lambda_acc=0.1, lambda_dist=0.01, bkgd='random') if on else {}))
+    terms_kw = dict(lambda_depth=0.1, lambda_acc=0.1, lambda_dist=0.01, bkgd='random') if on else {}
+    if terms == 'expo':
+        terms_kw = dict(exposure=fn.exposure.ExposureTable(100).cuda())
+    tr = fn.run_nerf.Trainer(ktr, H, W, K, 2.0, 6.0, **terms_kw)
     g = torch.Generator().manual_seed(1)
     poses = torch.stack([fn.synthetic.pose_spherical(-180.0 + 3.6 * i, -30.0, 4.0)[:3, :4] for i in range(100)], 0).cuda()
     pix = torch.stack([torch.randint(0, 100, (N,), generator=g), torch.randint(0, H, (N,), generator=g), torch.randint(0, W, (N,), generator=g)], 1).int()
@@ -37,6 +41,8 @@ def run(terms, k):
     kw = {}
     if on:
         kw = dict(alpha=torch.rand(N, generator=g).cuda(), depth=(2 + 4 * torch.rand(N, generator=g)).cuda(), acc=torch.rand(N, generator=g).cuda())
+    if terms == 'expo':
+        kw = dict(img=pix[:, 0].contiguous().cuda())
     for _ in range(k):
         loss2, _ = tr.step(ro, rd, tgt, **kw)
     torch.cuda.synchronize()
