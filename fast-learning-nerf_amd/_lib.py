@@ -243,6 +243,9 @@ SIGNATURES = {
     'fastnerf_train_step_expo': (I, [C.POINTER(StepArgs), C.POINTER(StepAux), C.POINTER(StepBkgd), C.POINTER(StepDist), C.POINTER(StepExpo), I, P]),
     'fastnerf_train_step_march_expo': (I, [C.POINTER(StepArgs), C.POINTER(StepMarch), C.POINTER(StepBkgd), C.POINTER(StepDist),
                                            C.POINTER(StepExpo), I, P]),
+    'fastnerf_env_lookup': (I, [L, P, L, P, I, P, P]),
+    'fastnerf_env_grad_ws_bytes': (L, [I]),
+    'fastnerf_env_grad': (I, [L, P, L, I, P, P, P, P, P, P, P]),
 }
 
 _lib = None

@@ -487,6 +487,78 @@ def expo_grad(img, ab, lam, grad_scale, e, g, e0=None, g0=None, d_ab=None, count
     return d_ab, counts, loss_reg
 
 
+# ---- environment map (csrc/envmap.hip; include/fastnerf.h, "environment map") ---------------------
+def _need_table(table):
+    """Refuse a table that the kernels would not read as fp32 [R,R,3], R >= 2 -> R."""
+    if table.dim() != 3 or table.shape[0] != table.shape[1] or table.shape[0] < 2:
+        raise ValueError(f'table must have shape (R, R, 3) with R >= 2, got {tuple(table.shape)}')
+    _need_f32('table', table, table.shape[0], table.shape[0], 3)
+    return table.shape[0]
+
+
+def _need_dirs(dirs):
+    """Refuse directions that the kernels would not read as fp32 rows of three at a fixed stride -> (n, stride): a contiguous [n,3], or a
+    column view such as rays[:, 3:6] of a contiguous batch, which is read in place."""
+    if dirs.dtype != torch.float32:
+        raise TypeError(f'dirs must be float32, got {dirs.dtype}')
+    if dirs.dim() != 2 or dirs.shape[1] != 3:
+        raise ValueError(f'dirs must have shape (n, 3), got {tuple(dirs.shape)}')
+    n = dirs.shape[0]
+    if n <= 1 and dirs.stride(1) == 1:
+        return n, 3      # (a single row: its stride is never used)
+    if dirs.stride(1) != 1 or dirs.stride(0) < 3:
+        raise ValueError(f'dirs must be rows of three contiguous floats, got strides {tuple(dirs.stride())}')
+    return n, dirs.stride(0)
+
+
+def env_lookup(table, dirs, out=None):
+    """The environment map's colours [n,3] for directions dirs [n,3] of any length (fastnerf_env_lookup): the bilinear sample of the
+    octahedral table [R,R,3] with the mirror wrap at its border.  dirs may be a column view of a ray batch (rays[:, 3:6]).
+    out: an [n,3] buffer to write instead of a new one."""
+    require_gpu(table, dirs, out)
+    R = _need_table(table)
+    n, stride = _need_dirs(dirs)
+    if out is None:
+        out = torch.empty(n, 3, device=table.device, dtype=torch.float32)
+    _need_f32('out', out, n, 3)
+    check(lib().fastnerf_env_lookup(n, dirs.data_ptr() if n else None, stride, ptr(table), R, ptr(out), stream()), 'fastnerf_env_lookup')
+    return out
+
+
+def env_grad_ws_bytes(R):
+    """Bytes of scratch one env_grad call on an [R,R,3] table needs."""
+    return int(check(lib().fastnerf_env_grad_ws_bytes(int(R)), 'fastnerf_env_grad_ws_bytes'))
+
+
+def env_grad(R, dirs, g_rgb, acc, g_rgb0=None, acc0=None, d_table=None, ws=None):
+    """d_table [R,R,3]: what rgb += (1 - acc) env(dirs) (and the same for rgb0 / acc0 of a two-pass render) sends back to the table
+    under colour gradients g_rgb / g_rgb0 [n,3] (fastnerf_env_grad).  A scatter in 64-bit fixed point: the same bits whatever the order
+    of the rays.  d_table / ws (int64, R*R*3 words): buffers to use instead of new ones."""
+    require_gpu(dirs, g_rgb, acc, g_rgb0, acc0, d_table, ws)
+    R = int(R)
+    if R < 2:
+        raise ValueError(f'env_grad: R >= 2, got {R}')
+    n, stride = _need_dirs(dirs)
+    _need_f32('g_rgb', g_rgb, n, 3)
+    _need_f32('acc', acc, n)
+    if (g_rgb0 is None) != (acc0 is None):
+        raise ValueError('env_grad: g_rgb0 and acc0 go together')
+    if g_rgb0 is not None:
+        _need_f32('g_rgb0', g_rgb0, n, 3)
+        _need_f32('acc0', acc0, n)
+    dev = g_rgb.device
+    if d_table is None:
+        d_table = torch.empty(R, R, 3, device=dev, dtype=torch.float32)
+    _need_f32('d_table', d_table, R, R, 3)
+    if ws is None:
+        ws = torch.empty(R * R * 3, device=dev, dtype=torch.int64)
+    if ws.dtype != torch.int64 or not ws.is_contiguous() or ws.numel() * 8 < env_grad_ws_bytes(R):
+        raise ValueError(f'env_grad: ws must be contiguous int64 with at least {R * R * 3} words')
+    check(lib().fastnerf_env_grad(n, dirs.data_ptr() if n else None, stride, R, ptr(g_rgb), ptr(acc), ptr(g_rgb0), ptr(acc0), ptr(ws),
+                                  ptr(d_table), stream()), 'fastnerf_env_grad')
+    return d_table
+
+
 def raw2outputs_fwd(raw, z, rays11, noise=None, white_bkgd=False):
     require_gpu(raw, z, rays11, noise)
     n = rays11.shape[0]

@@ -589,7 +589,8 @@ def _render_rays_closure(ray_batch, rays11, network_fn, network_fine, network_qu
 
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
                 N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False, occupancy=None,
-                tighten=False, march=None, march_cap=128, bkgd=None, retdist=False, retdepth=False, ert=None, ert_block=32):
+                tighten=False, march=None, march_cap=128, bkgd=None, envmap=None, retdist=False, retdepth=False, ert=None,
+                ert_block=32):
     """render.py:195-305.  Two routes, chosen by the networks (after `.module` unwrapping):
 
     * fastnerf NeRF modules (8 x 256): positional encoding + MLP run fused inside the HIP kernels; `network_query_fn` is
@@ -657,10 +658,21 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     pose receive the background's gradient through acc_map.  bkgd = ones has the bits of white_bkgd=True.  `bkgd=None` (the default)
     makes exactly the calls it made before.
 
+    `envmap` (an envmap.EnvMap; ValueError with bkgd= or white_bkgd=True): a trained background behind every ray -- the call with
+    bkgd=envmap(ray_batch[:, 3:6]), the map's colours for the unnormalised directions of the batch ([N,8] or [N,11]; include/fastnerf.h,
+    "environment map"), on every route.  Under autograd the map's table receives its gradient; the directions get none.
+
     `retdist=True` adds `dist_map` [n], the distortion loss of mip-NeRF 360 on the weights of every ray's image pass (ops.distortion;
     include/fastnerf.h has the definition), and `dist0` for the coarse pass of two: differentiable w.r.t. the networks' parameters on both
     routes, in all three math modes, through the weights alone (depths, near and far are constants).  A loss adds
     lambda * (dist_map.mean() + dist0.mean()).  With `march=` the row is taken with its overflowed rays skipped (0 there)."""
+    if envmap is not None:
+        if bkgd is not None or white_bkgd:
+            raise ValueError('render_rays: envmap= is the background of every ray: it cannot be combined with bkgd= or white_bkgd=True')
+        ops.require_gpu(ray_batch)
+        if ray_batch.dim() != 2 or ray_batch.shape[-1] not in (8, 11):
+            raise ValueError('ray batches are [N,8] (o, d, near, far) or [N,11] (+ view directions), render.py:216-219')
+        bkgd = envmap(ray_batch[:, 3:6])
     if bkgd is not None:
         if white_bkgd:
             raise ValueError('render_rays: bkgd cannot be combined with white_bkgd=True (bkgd = ones is the white background)')
@@ -839,7 +851,11 @@ def render(H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far
            c2w_staticcam=None, **kwargs):
     """render.py:26-91 -> [rgb_map, disp_map, acc_map, extras].  A tensor `c2w` that requires grad receives the gradient of
     every differentiable map (render_rays) through the rays (_PoseRaysFn); with ndc=True or c2w_staticcam that raises NotImplementedError.
-    `bkgd=` (render_rays): a colour [3], or one colour per ray in the shape of the rays ([H, W, 3] or [N, 3])."""
+    `bkgd=` (render_rays): a colour [3], or one colour per ray in the shape of the rays ([H, W, 3] or [N, 3]).
+    `envmap=` (render_rays): looked up chunk by chunk from the rays' directions; ValueError with ndc=True (NDC directions are not the
+    scene's)."""
+    if kwargs.get('envmap') is not None and ndc:
+        raise ValueError('render: envmap= indexes the table by the ray direction: not with ndc=True (the NDC far plane is infinity)')
     bkgd = kwargs.get('bkgd')
     if bkgd is not None and not (torch.is_tensor(bkgd) and bkgd.dim() == 1):
         bkgd = torch.as_tensor(bkgd, dtype=torch.float32)

@@ -79,6 +79,7 @@ class _Args:
     lambda_dist = 0.         # (not in the reference's parser) weight of the distortion loss on the ray weights (Trainer(lambda_dist=))
     refine_poses = False; pose_lrate = 1e-3      # (not in the reference's parser) refine the camera poses beside the field (Trainer(poses=))
     optim_autoexpo = False; lambda_autoexpo = 1.      # (nerf++-ours' parser) fit a per-image exposure beside the field (Trainer(exposure=))
+    envmap = False; envmap_res = 64; envmap_lrate = 1e-2      # (not in the reference's parser) a trained background behind every ray (Trainer(envmap=))
     n_epoch = 12; init_level = 3; rays_downscale = 1; subdivide_every = 1; subdivide_thres = 0.015
     randSamp_perc = 0.5; basedir = './logs'; expname = 'fastnerf'
 
@@ -351,12 +352,26 @@ class Trainer:
     image without a ray has a zero gradient; a ray whose img is outside the table is left as it is.  A fresh table (rows (0.5, 0))
     reproduces the step without it bit for bit.  All routes take it: the fused step (plain, compacted, through a grid, tighten), the
     marched step (an overflowed ray gives the table nothing), the call-by-call route and the pose step.  Without `exposure=` nothing
-    changes.  ValueError: exposure= without img / pix, img without exposure=, a negative or non-finite lambda_autoexpo, data parallel."""
+    changes.  ValueError: exposure= without img / pix, img without exposure=, a negative or non-finite lambda_autoexpo, data parallel.
+
+    Environment map (`envmap=` an envmap.EnvMap, `envmap_lrate`; include/fastnerf.h, "environment map"): a trained background behind
+    every ray, for captures that look past the box.  Every step looks the colours up from rays_d (ops.env_lookup; on the pose route the
+    rays are made from pix first) and hands them in as the injected per-ray background above, so the step is the step with
+    bkgd=env(rays_d), launch for launch; out['bkgd'] holds them.  Once the colour gradients stand -- behind the forward phase of the fused
+    and the marched step, which are then called phase by phase, behind the loss launches of the call-by-call route; the exposure term
+    has rescaled them by then -- ops.env_grad scatters (1 - acc) g_rgb of both passes into `env_grad` [R,R,3] = d(loss)/d(table), and the
+    table takes an Adam step with moments of its own (`env_m`, `env_v`) at envmap_lrate (1e-2: a guess, not a tuned value) times the
+    networks' decay factor.  A marched ray whose row overflowed has g_rgb = 0 and gives the table exactly nothing.  The table does not
+    enter the pose gradient: a direction's colour is a constant of the ray.  All routes take it: the fused step (plain, compacted, through a
+    grid, tighten), the marched step, the call-by-call route, the pose step, with an exposure table.  Without `envmap=` nothing changes,
+    launch for launch.  ValueError, before any launch: together with bkgd= (trainer or step) or alpha= (a capture with alpha has no
+    background to learn), white_bkgd, ndc=True (the NDC far plane is infinity), data parallel, a table on another device."""
 
     def __init__(self, render_kwargs_train, H, W, K, near, far, lrate=5e-4, lrate_decay=250, decay=True,
                  beta1=0.9, beta2=0.999, eps=1e-8, occupancy=None, occupancy_every=16, occupancy_warmup=256, occupancy_cells=None,
                  lambda_depth=0., lambda_acc=0., tighten=False, march=None, march_cap=128, march_after=0, bkgd=None,
-                 lambda_dist=0., poses=None, pose_lrate=1e-3, exposure=None, lambda_autoexpo=1.0, exposure_lrate=None):
+                 lambda_dist=0., poses=None, pose_lrate=1e-3, exposure=None, lambda_autoexpo=1.0, exposure_lrate=None,
+                 envmap=None, envmap_lrate=1e-2):
         kw = render_kwargs_train
         self._kw = kw
         self.net_c = kw['network_fn']
@@ -426,9 +441,18 @@ class Trainer:
         self.expo_m = self.expo_v = None
         if exposure is not None:
             self.expo_m, self.expo_v = torch.zeros_like(exposure.ab.data), torch.zeros_like(exposure.ab.data)
+        self.envmap, self.envmap_lrate = envmap, float(envmap_lrate)
+        self.env_lr = self.envmap_lrate
+        self.env_grad = None     # d(loss)/d(table) [R,R,3] of the last step with the map
+        self.env_m = self.env_v = self._env_ws = None
+        if envmap is not None:
+            self.env_m, self.env_v = torch.zeros_like(envmap.table.data), torch.zeros_like(envmap.table.data)
+            self.env_grad = torch.zeros_like(envmap.table.data)
+            self._env_ws = torch.empty(envmap.table.numel(), device=envmap.table.device, dtype=torch.int64)
         self._check_dist()
         self._check_poses()
         self._check_expo()
+        self._check_env()
         self._check_occupancy()
         self._check_march()
         self.repack()
@@ -442,6 +466,43 @@ class Trainer:
         if self.world > 1:
             raise ValueError('Trainer: exposure= is not data parallel (world size {})'.format(self.world))
         return True
+
+    def _check_env(self, alpha=None, bkgd=None):
+        """Whether the trainer has an environment map; its refusals, before any launch (read on every step, like the other settings)."""
+        if self.envmap is None:
+            return False
+        if self.bkgd is not None or bkgd is not None:
+            raise ValueError('Trainer: envmap= is the background of every ray: it cannot be combined with bkgd= (trainer or step)')
+        if alpha is not None:
+            raise ValueError('Trainer: envmap= cannot be combined with alpha=: a capture with alpha has no background to learn')
+        if self.white_bkgd:
+            raise ValueError('Trainer: envmap= cannot be combined with white_bkgd=True')
+        if self.ndc:
+            raise ValueError('Trainer: envmap= indexes the table by the ray direction: not with ndc=True (the NDC far plane is infinity)')
+        if self.world > 1:
+            raise ValueError('Trainer: envmap= is not data parallel (world size {})'.format(self.world))
+        if self.envmap.table.device != self.flat.device:
+            raise ValueError('Trainer: the environment map is on {}, the networks on {}'.format(self.envmap.table.device, self.flat.device))
+        return True
+
+    def _env_lookup(self, rays_d):
+        """-> (dirs, the map's colours [n,3] for them): what the step injects as its per-ray background."""
+        ops.require_gpu(rays_d)
+        dirs = ops._f32(rays_d).reshape(-1, 3)
+        return dirs, ops.env_lookup(self.envmap.table.data, dirs)
+
+    def _env_backward(self, dirs, g_rgb, acc, g_rgb0=None, acc0=None):
+        """self.env_grad = d(loss)/d(table) from the step's colour gradients and opacity maps (of one pass or of two)."""
+        self.env_grad = ops.env_grad(self.envmap.res, dirs, g_rgb, acc, g_rgb0, acc0, d_table=self.env_grad, ws=self._env_ws)
+
+    def _env_backward_block(self, dirs):
+        """_env_backward on the regions of the step that was just prepared, behind its forward phase."""
+        block, regions = self._last
+        if 'g_rgb0' in regions:
+            self._env_backward(dirs, _region(block, regions, 'g_rgb'), _region(block, regions, 'acc1'), _region(block, regions, 'g_rgb0'),
+                               _region(block, regions, 'acc0'))
+        else:
+            self._env_backward(dirs, _region(block, regions, 'g_rgb'), _region(block, regions, 'acc0'))
 
     def _check_expo_step(self, img, pix, n):
         """The refusals of a step's img=, before any launch -> None without a table, else the rays' images as contiguous int32 [n]
@@ -595,6 +656,9 @@ class Trainer:
         n = rays_o.shape[0]
         dev = rays_o.device
         img = self._check_expo_step(img, None, n)
+        env_dirs = None
+        if self._check_env(alpha, bkgd):
+            env_dirs, bkgd = self._env_lookup(rays_d)
         bt = self._bkgd_terms(n, dev, alpha, bkgd)
         rays11 = ops.pack_rays(rays_o, rays_d, self.near, self.far, ndc=self.ndc, H=self.H, W=self.W,
                                focal=float(self.K[0][0]))
@@ -625,6 +689,8 @@ class Trainer:
             maps = {k: t for k, t in gm.items() if t is not None}
         if img is not None:      # g, g0 become the gradient with respect to the scene's colours, in place
             self.expo_grad, self.expo_counts, self.expo_loss = ops.expo_grad(img, ab, self.lambda_autoexpo, scale, e1, g, e0=e0, g0=g0)
+        if env_dirs is not None:      # the colour gradients stand: what the blend sends back to the table
+            self._env_backward(env_dirs, g, out['acc_map'], g0, out.get('acc0') if g0 is not None else None)
         if bt is not None:
             ga1, ga0 = ops.bkgd_grad(out['bkgd'], g, g0, add=(maps or {}).get('g_acc1'), add0=(maps or {}).get('g_acc0'))
             maps = dict(maps or {}, g_acc1=ga1)
@@ -923,6 +989,7 @@ class Trainer:
         else:
             n = rays_o.shape[0]
         img = self._check_expo_step(img, pix, n)
+        env = self._check_env(alpha, bkgd)
         Nn = ops.NET_PARAMS
         two = self.N_importance > 0 and self.net_f is not None and self.net_f is not self.net_c
         overlap = self.world > 1 and two and self.overlap_allreduce and self.grad.numel() == 2 * Nn
@@ -948,6 +1015,8 @@ class Trainer:
             if img is not None:
                 self.expo_grad, self.expo_counts = torch.zeros_like(self.expo_m), torch.zeros_like(self.expo_m[:, 0], dtype=torch.int32)
                 self.expo_loss = torch.zeros_like(self.expo_loss)
+            if env:
+                self.env_grad.zero_()
         elif pix is not None:
             # the pose step: the call-by-call route with ray gradients, then the rays' gradient down to xi and an Adam step of its own
             poses = ops.pose_exp(self.poses.base, self.poses.xi.data)
@@ -957,10 +1026,16 @@ class Trainer:
             self._pose_update(pix, poses, out['d_rays'])
             self._host_update(everything, overlap)
         elif marching:
+            if env:
+                env_dirs, bkgd = self._env_lookup(rays_d)
             a, x, out, loss2 = self._march_prepare(KC[0], KC[1], rays_o, rays_d, target, leaf_tag, table, max_leaves, march_u, n_global,
                                                    alpha, bkgd, img)
             a.lr, a.adam_t = float(self.lr), int(self.adam_t)
-            if self.world == 1:
+            if env:      # (world == 1: _check_env) phase by phase, the table's gradient behind the forward phase
+                self._march_call(a, x, _lib.STEP_FORWARD)
+                self._env_backward_block(env_dirs)
+                self._march_call(a, x, _lib.STEP_BWD_COARSE | _lib.STEP_UPDATE)
+            elif self.world == 1:
                 self._march_call(a, x, _lib.STEP_FORWARD | _lib.STEP_BWD_COARSE | _lib.STEP_UPDATE)
             else:      # data parallel, not overlapped: one network, one collective over its half of the gradient
                 self._march_call(a, x, _lib.STEP_FORWARD | _lib.STEP_BWD_COARSE)
@@ -970,11 +1045,18 @@ class Trainer:
             self.live.tick()
             self.last_step_live = True
         elif self.fused:
+            if env:
+                env_dirs, bkgd = self._env_lookup(rays_d)
             self._img = img
             a, out, loss2, live = self._fused_prepare(rays_o, rays_d, target, leaf_tag, table, max_leaves, t_rand, u, n_global,
                                                       alpha, bkgd, depth, depth_weight, acc, acc_weight)
             a.lr, a.adam_t = float(self.lr), int(self.adam_t)
-            if self.world == 1:
+            if env:      # (world == 1: _check_env) phase by phase, the table's gradient behind the forward phase
+                self._fused_call(a, _lib.STEP_FORWARD)
+                self._env_backward_block(env_dirs)
+                self._fused_call(a, _lib.STEP_BWD_FINE | _lib.STEP_BWD_COARSE | _lib.STEP_UPDATE)
+                self._after_backward(live)
+            elif self.world == 1:
                 self._fused_call(a, _lib.STEP_FORWARD | _lib.STEP_BWD_FINE | _lib.STEP_BWD_COARSE | _lib.STEP_UPDATE)
                 self._after_backward(live)
             else:
@@ -999,11 +1081,15 @@ class Trainer:
         if img is not None:      # Adam on the table with moments of its own, as _pose_update does for xi
             ops.adam_step(self.exposure.ab.data, self.expo_grad, self.expo_m, self.expo_v, self.expo_lr, self.adam_t, self.beta1, self.beta2,
                           self.eps)
+        if env:      # and on the environment map
+            ops.adam_step(self.envmap.table.data, self.env_grad, self.env_m, self.env_v, self.env_lr, self.adam_t, self.beta1, self.beta2,
+                          self.eps)
         if (self.decay if decay is None else decay):
             factor = 0.1 ** (self.global_iter / (self.lrate_decay * 1000))
             self.lr = self.lrate * factor
             self.pose_lr = self.pose_lrate * factor
             self.expo_lr = (self.lrate if self.exposure_lrate is None else float(self.exposure_lrate)) * factor
+            self.env_lr = self.envmap_lrate * factor
             self.global_iter += 1
         return loss2, out
 
@@ -1036,6 +1122,8 @@ class Trainer:
             sd.update(pose_m=self.pose_m, pose_v=self.pose_v, pose_lr=self.pose_lr)
         if self.exposure is not None:
             sd.update(expo_m=self.expo_m, expo_v=self.expo_v, expo_lr=self.expo_lr)
+        if self.envmap is not None:
+            sd.update(env_m=self.env_m, env_v=self.env_v, env_lr=self.env_lr)
         return sd
 
     # ---- interchange with torch.optim.Adam (the optimizer_state_dict of the reference's .tar, run_nerf.py:121,537) ----
@@ -1089,6 +1177,23 @@ class Trainer:
         self.expo_m.copy_(ckpt['expo_m']); self.expo_v.copy_(ckpt['expo_v'])
         return True
 
+    def load_env_checkpoint(self, ckpt):
+        """Take the environment map and its moments from a checkpoint of save_checkpoint (the loaded dict, or its path).  A checkpoint
+        without one leaves the table untouched; one of another resolution is a ValueError."""
+        if self.envmap is None:
+            return False
+        table = self.envmap.table.data
+        if not isinstance(ckpt, dict):
+            ckpt = torch.load(ckpt, map_location=table.device, weights_only=False)
+        if 'env_table' not in ckpt:
+            return False
+        if ckpt['env_table'].shape != table.shape:
+            raise ValueError('Trainer.load_env_checkpoint: the checkpoint holds a map of resolution {}, this one has {}'.format(
+                ckpt['env_table'].shape[0], table.shape[0]))
+        table.copy_(ckpt['env_table'])
+        self.env_m.copy_(ckpt['env_m']); self.env_v.copy_(ckpt['env_v'])
+        return True
+
     def load_state_dict(self, sd):
         self.m.copy_(sd['m']); self.v.copy_(sd['v'])
         self.adam_t, self.global_iter, self.lr = sd['adam_t'], sd['global_iter'], sd['lr']
@@ -1098,6 +1203,9 @@ class Trainer:
         if self.exposure is not None and 'expo_m' in sd:
             self.expo_m.copy_(sd['expo_m']); self.expo_v.copy_(sd['expo_v'])
             self.expo_lr = sd.get('expo_lr', self.expo_lr)
+        if self.envmap is not None and 'env_m' in sd:
+            self.env_m.copy_(sd['env_m']); self.env_v.copy_(sd['env_v'])
+            self.env_lr = sd.get('env_lr', self.env_lr)
 
 
 def reference_state_dict(net):
@@ -1126,6 +1234,8 @@ def save_checkpoint(args, epoch_id, trainer, kw_train, mgr):
         ckpt.update(pose_xi=trainer.poses.xi.data, pose_base=trainer.poses.base, pose_m=trainer.pose_m, pose_v=trainer.pose_v)
     if trainer.exposure is not None:      # and the exposure table
         ckpt.update(expo_ab=trainer.exposure.ab.data, expo_m=trainer.expo_m, expo_v=trainer.expo_v)
+    if trainer.envmap is not None:      # and the environment map
+        ckpt.update(env_table=trainer.envmap.table.data, env_m=trainer.env_m, env_v=trainer.env_v)
     torch.save(ckpt, path)
     mgr.save_trees(tree_pkl_path(args, epoch_id))
     return path
@@ -1218,8 +1328,15 @@ def train(images, poses, H, W, focal, args, near=2., far=6., device='cuda', log=
     if autoexpo:
         from .exposure import ExposureTable
         expo_kw = dict(exposure=ExposureTable(len(images)).to(dev), lambda_autoexpo=float(getattr(args, 'lambda_autoexpo', 1.)))
+    # args.envmap, args.envmap_res, args.envmap_lrate (no such flags in the reference's parser; default off): an EnvMap is fitted beside the
+    # networks as the background of every ray, and the test-time kwargs render over it.  The map is trainer.envmap.
+    env_kw = {}
+    if bool(getattr(args, 'envmap', False)):
+        from .envmap import EnvMap
+        env_kw = dict(envmap=EnvMap(res=int(getattr(args, 'envmap_res', 64))).to(dev), envmap_lrate=float(getattr(args, 'envmap_lrate', 1e-2)))
+        kw_test['envmap'] = env_kw['envmap']
     trainer = Trainer(kw_train, H, W, K, near, far, lrate=args.lrate, lrate_decay=args.lrate_decay, bkgd='random' if random_bkgd else None,
-                      lambda_dist=float(getattr(args, 'lambda_dist', 0.)), **occ_kw, **pose_kw, **expo_kw)
+                      lambda_dist=float(getattr(args, 'lambda_dist', 0.)), **occ_kw, **pose_kw, **expo_kw, **env_kw)
     trainer.global_iter = global_iter
     if len(optimizer.state_dict()['state']) > 0:   # create_nerf restored a checkpoint (ours or the reference's)
         trainer.load_torch_optimizer(optimizer)
@@ -1227,6 +1344,8 @@ def train(images, poses, H, W, focal, args, near=2., far=6., device='cuda', log=
             trainer.load_pose_checkpoint(create_nerf.last_ckpt_path)
         if autoexpo and create_nerf.last_ckpt_path is not None:
             trainer.load_expo_checkpoint(create_nerf.last_ckpt_path)
+        if env_kw and create_nerf.last_ckpt_path is not None:
+            trainer.load_env_checkpoint(create_nerf.last_ckpt_path)
     images = torch.as_tensor(images, dtype=torch.float32)
     alpha_img = None
     if random_bkgd:      # the quadtree manager (and the leaf-error picks) see the straight colours; alpha travels beside them

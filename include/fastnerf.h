@@ -1080,6 +1080,38 @@ int fastnerf_train_step_expo(const fn_step_args* args, const fn_step_aux* aux, c
 int fastnerf_train_step_march_expo(const fn_step_args* args, const fn_step_march* march, const fn_step_bkgd* bk,
                                    const fn_step_dist* dist, const fn_step_expo* ex, int phases, fn_stream_t stream);
 
+/* ---- environment map: a trained background behind every ray (csrc/envmap.hip) ----------------------------------------------------------
+ * A table of colours indexed by ray direction alone, composited behind the volume as rgb += (1 - acc) env(d) through the per-ray
+ * background colours above, and trained beside the field.  The map is octahedral: one square table T [R,R,3] fp32 (row j = y, column
+ * i = x), 2 <= R <= 16384.  Only + - * / and comparisons; every operation below is rounded on its own (no contraction, one IEEE
+ * division), so a float32 restatement matches bit for bit.  For a direction d = (dx, dy, dz) of ANY length:
+ *   s = (|dx| + |dy|) + |dz|;   s zero or not finite: p = (0, 0);   otherwise px = dx / s, py = dy / s
+ *   dz < 0:  (px, py) = ((1 - |py|) sg(px), (1 - |px|) sg(py)),  sg(t) = t >= 0 ? 1 : -1  (-0 gives +1; both sides use the old px, py)
+ *   x = ((px * 0.5 + 0.5) * (float)R) - 0.5,  i0 = floor(x),  fx = x - i0;   y, j0, fy alike from py
+ *   neighbours (i0, j0), (i0+1, j0), (i0, j0+1), (i0+1, j0+1), each through the mirror wrap -- the octahedral map's own identification of
+ *   its border, so the map has no seam: oi = i outside [0,R), oj = j outside [0,R); clamp both; oi: j = R-1-j; oj: i = R-1-i
+ *   w00 = (1-fx)(1-fy), w10 = fx (1-fy), w01 = (1-fx) fy, w11 = fx fy
+ *   colour[c] = (w00 T00[c] + w10 T10[c]) + (w01 T01[c] + w11 T11[c])
+ *
+ * fastnerf_env_lookup: out [n,3] from dirs, read as dirs[r*stride + 0..2] (columns 3:6 of an [n,11] batch are read in place with
+ * stride 11).  One thread per ray in a walk of the whole batch (any n), plain stores.
+ *
+ * fastnerf_env_grad: d_table [R,R,3] (written, not accumulated) from the step's colour gradients and opacity maps; g_rgb0 and acc0 are
+ * NULL with one pass.  Per ray and channel
+ *   g = (1 - acc1[r]) g_rgb1[r,c] + (1 - acc0[r]) g_rgb0[r,c]
+ * and the four terms w_k g go to their texels.  Every term is rounded once, q = llrint((double)term * 2^50), and added with a 64-bit
+ * integer vector atomic into ws [R*R*3] int64 (fastnerf_env_grad_ws_bytes(R) bytes, 8-byte aligned, zeroed by the call); a finishing
+ * launch writes d_table[t] = (float)((double)ws[t] * 2^-50).  Integer addition is associative: the bits do not depend on arrival order,
+ * on the order of the rays, or on how a batch is split; the sum is exact while a texel's sum stays below 2^13.  Non-finite gradients
+ * are out of contract.  Directions get no gradient.
+ *
+ * -1 before anything is enqueued: R < 2 or R > 16384; n < 0; stride < 3; with n > 0 a NULL buffer; a NULL d_table; g_rgb0 and acc0 not
+ * both set or both NULL.  n == 0: the lookup returns 0 at once, the gradient writes R*R*3 zeros. */
+int fastnerf_env_lookup(int64_t n, const float* dirs, int64_t stride, const float* table, int R, float* out, fn_stream_t stream);
+int64_t fastnerf_env_grad_ws_bytes(int R);
+int fastnerf_env_grad(int64_t n, const float* dirs, int64_t stride, int R, const float* g_rgb1, const float* acc1, const float* g_rgb0,
+                      const float* acc0, void* ws, float* d_table, fn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
