@@ -243,6 +243,13 @@ SIGNATURES = {
     'fastnerf_train_step_expo': (I, [C.POINTER(StepArgs), C.POINTER(StepAux), C.POINTER(StepBkgd), C.POINTER(StepDist), C.POINTER(StepExpo), I, P]),
     'fastnerf_train_step_march_expo': (I, [C.POINTER(StepArgs), C.POINTER(StepMarch), C.POINTER(StepBkgd), C.POINTER(StepDist),
                                            C.POINTER(StepExpo), I, P]),
+    'fastnerf_occ_cascade_own': (I, [C.POINTER(OccCascade), I, I, P, P, P, P]),
+    'fastnerf_occ_cascade_points': (I, [C.POINTER(OccCascade), P, C.POINTER(L), L, L, U64, P, P]),
+    'fastnerf_occ_cascade_update': (I, [C.POINTER(OccCascade), P, P, P, C.POINTER(L), L, L, C.POINTER(F), C.POINTER(P), P]),
+    'fastnerf_train_step_cascade': (I, [C.POINTER(StepArgs), C.POINTER(StepAux), C.POINTER(StepBkgd), C.POINTER(StepDist), C.POINTER(StepExpo),
+                                        C.POINTER(OccCascade), I, P]),
+    'fastnerf_train_step_march_cascade': (I, [C.POINTER(StepArgs), C.POINTER(StepMarch), C.POINTER(StepBkgd), C.POINTER(StepDist),
+                                              C.POINTER(StepExpo), C.POINTER(OccCascade), I, P]),
     'fastnerf_env_lookup': (I, [L, P, L, P, I, P, P]),
     'fastnerf_env_grad_ws_bytes': (L, [I]),
     'fastnerf_env_grad': (I, [L, P, L, I, P, P, P, P, P, P, P]),

@@ -35,6 +35,9 @@
 //   The marched render (fastnerf_march_list) is one more, MarchDev: the entries of one segment of the packed rows of march.hip, evaluated
 //   when the slot's lattice index is >= 0.  The lookup itself (descriptors, occ_point, the host checks) lives in occ_lookup.h, which
 //   march.hip shares.
+//   Training through a cascade (fastnerf_occ_cascade_own / _points / _update, at the end of the file): OwnDev is one more descriptor of the
+//   count / scatter kernels -- entry q is cell q of a level, kept when no inner level covers it -- and the refresh kernels walk the
+//   concatenation of the levels' own lists with the point and density arithmetic of the single grid (occ_cell_point, occ_dens_next).
 // All of them are memory bound and small next to the MLP they spare: one lane per cell / point / four consecutive samples, a
 // ray's 44 bytes come through the cache for all its samples.
 #include "common.h"
@@ -69,6 +72,15 @@ struct ErtDev {
 struct MarchDev {
   const int32_t* kidx;
   uint32_t s0, w;
+};
+
+// The own cells of one level of a training cascade (fastnerf_occ_cascade_own): entry q is cell q of the level, evaluated when no box
+// of `box` holds it.  box[j] = (first, last) index per axis of the cells that inner level j covers -- worked out on the host in
+// float64 from the levels' fp32 geometry, so the device compares integers only.  No ray, no depth, no bits are read.
+struct OwnDev {
+  int n[3];
+  int nbox;
+  int box[FN_OCC_MAX_LEVELS - 1][6];
 };
 
 __device__ __forceinline__ bool occ_point(const OccAll&, float, float, float) { return true; }
@@ -134,20 +146,18 @@ __global__ void __launch_bounds__(OCC_BLOCK) occ_query_kernel(G g, int64_t n, co
 
 __device__ __forceinline__ int occ_axis_cell(float x, float lo, float inv) { return (int)floorf(fmul(fsub(x, lo), inv)); }
 
-// One point inside each of the cells c0 .. c0+n-1: x = lo + (index + jitter) / inv per axis, each operation rounded to fp32,
-// jitter = 0.5 (seed == 0) or a Philox draw in [0, 1) keyed by (seed, cell).  Where fp32 rounding puts that point into a
+// One point inside cell c of a grid with this geometry, as a rays11 row: x = lo + (index + jitter) / inv per axis, each operation rounded
+// to fp32, jitter = 0.5 (jit == 0) or a Philox draw in [0, 1) keyed by (seed, cell).  Where fp32 rounding puts that point into a
 // neighbouring cell (index + jitter rounds up to index + 1, or the sum lands on a face), the jitter is clamped towards the
 // cell's centre -- halved distance to 0.5 per attempt, 0.5 itself at the end -- until occ_point's arithmetic gives the cell back.
-__global__ void __launch_bounds__(OCC_BLOCK) occ_cell_points_kernel(OccDev g, int64_t c0, int64_t n, uint32_t k0, uint32_t k1, int jit,
-                                                                    float* __restrict__ rays11) {
-  const int64_t q = (int64_t)blockIdx.x * OCC_BLOCK + threadIdx.x;
-  if (q >= n) return;
-  const uint32_t c = (uint32_t)(c0 + q);
-  const uint32_t r = c / (uint32_t)g.n[2];
+// The one definition behind fastnerf_occ_cell_points and fastnerf_occ_cascade_points: a level's cell gets the bits its grid gives it.
+__device__ __forceinline__ void occ_cell_point(const float* lo, const float* inv, const int* n, uint32_t c, uint32_t k0, uint32_t k1, int jit,
+                                               float* __restrict__ row) {
+  const uint32_t r = c / (uint32_t)n[2];
   int idx[3];
-  idx[2] = (int)(c - r * (uint32_t)g.n[2]);
-  idx[0] = (int)(r / (uint32_t)g.n[1]);
-  idx[1] = (int)(r - (uint32_t)idx[0] * (uint32_t)g.n[1]);
+  idx[2] = (int)(c - r * (uint32_t)n[2]);
+  idx[0] = (int)(r / (uint32_t)n[1]);
+  idx[1] = (int)(r - (uint32_t)idx[0] * (uint32_t)n[1]);
   float u[3] = {0.5f, 0.5f, 0.5f};
   if (jit) {
     uint32_t o[4];
@@ -156,19 +166,38 @@ __global__ void __launch_bounds__(OCC_BLOCK) occ_cell_points_kernel(OccDev g, in
     u[1] = u01(o[1]);
     u[2] = u01(o[2]);
   }
-  float* row = rays11 + q * 11;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     float j = u[a], x = 0.f;
     for (int it = 0; it < 26; ++it) {
-      x = fadd(g.lo[a], __fdiv_rn(fadd((float)idx[a], j), g.inv[a]));
-      if (occ_axis_cell(x, g.lo[a], g.inv[a]) == idx[a]) break;
+      x = fadd(lo[a], __fdiv_rn(fadd((float)idx[a], j), inv[a]));
+      if (occ_axis_cell(x, lo[a], inv[a]) == idx[a]) break;
       j = it < 24 ? fadd(0.5f, fmul(fsub(j, 0.5f), 0.5f)) : 0.5f;
     }
     row[a] = x;
   }
 #pragma unroll
   for (int a = 3; a < 11; ++a) row[a] = 0.f;
+}
+
+// the cells c0 .. c0+n-1 of one grid
+__global__ void __launch_bounds__(OCC_BLOCK) occ_cell_points_kernel(OccDev g, int64_t c0, int64_t n, uint32_t k0, uint32_t k1, int jit,
+                                                                    float* __restrict__ rays11) {
+  const int64_t q = (int64_t)blockIdx.x * OCC_BLOCK + threadIdx.x;
+  if (q >= n) return;
+  occ_cell_point(g.lo, g.inv, g.n, (uint32_t)(c0 + q), k0, k1, jit, rays11 + q * 11);
+}
+
+// dens' = max(dens * decay, relu(sigma_c), relu(sigma_f)) with the logits of row q; relu maps a NaN to 0
+__device__ __forceinline__ float occ_dens_next(float v, const float* __restrict__ raw_c, const float* __restrict__ raw_f, int64_t q, float decay) {
+  float s = raw_c[q * 4 + 3];
+  s = s > 0.f ? s : 0.f;
+  if (raw_f) {
+    const float t = raw_f[q * 4 + 3];
+    s = t > s ? t : s;
+  }
+  const float old = fmul(v, decay);
+  return s > old ? s : old;
 }
 
 // sigma of cell c0 + q is raw_c[q * 4 + 3] (and raw_f's, the larger of the two counts); relu maps a NaN to 0.
@@ -181,14 +210,7 @@ __global__ void __launch_bounds__(OCC_BLOCK) occ_update_kernel(const float* __re
     float v = dens[c];
     const int64_t q = c - c0;
     if (q >= 0 && q < n) {
-      float s = raw_c[q * 4 + 3];
-      s = s > 0.f ? s : 0.f;
-      if (raw_f) {
-        const float t = raw_f[q * 4 + 3];
-        s = t > s ? t : s;
-      }
-      const float old = fmul(v, decay);
-      v = s > old ? s : old;
+      v = occ_dens_next(v, raw_c, raw_f, q, decay);
       dens[c] = v;
     }
     b = v > thr;
@@ -225,6 +247,15 @@ __device__ __forceinline__ bool occ_live(const ErtDev<G>& e, const float* __rest
 }
 __device__ __forceinline__ bool occ_live(const MarchDev& e, const float* __restrict__, const float* __restrict__, uint32_t, int64_t p) {
   return e.kidx[p] >= 0;
+}
+// cell p of the level is its own: no inner level's box of covered cells holds it (e.nbox is uniform)
+__device__ __forceinline__ bool occ_live(const OwnDev& e, const float* __restrict__, const float* __restrict__, uint32_t, int64_t p) {
+  const uint32_t q = (uint32_t)p, r = q / (uint32_t)e.n[2];
+  const int k = (int)(q - r * (uint32_t)e.n[2]), i = (int)(r / (uint32_t)e.n[1]), j = (int)(r - (uint32_t)i * (uint32_t)e.n[1]);
+  bool covered = false;
+  for (int b = 0; b < e.nbox; ++b)
+    covered |= (i >= e.box[b][0]) & (i <= e.box[b][1]) & (j >= e.box[b][2]) & (j <= e.box[b][3]) & (k >= e.box[b][4]) & (k <= e.box[b][5]);
+  return !covered;
 }
 
 // bits 0..3: entries p0 .. p0+3 of the pass are evaluated
@@ -472,6 +503,160 @@ extern "C" int fastnerf_march_list(int64_t n, int C, int s0, int s1, const int32
   const MarchDev m = {kidx, (uint32_t)s0, (uint32_t)(s1 - s0)};
   occ_classify_launch(m, n * (int64_t)(s1 - s0), C, (const float*)nullptr, (const float*)nullptr, live_idx, count_out, raw, ws, fn::S(stream));
   if (total) hipLaunchKernelGGL(march_total_kernel, dim3(1), dim3(1), 0, fn::S(stream), (const int32_t*)count_out, s0 == 0 ? 1 : 0, lattice, total);
+  FN_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- training through a cascade (include/fastnerf.h, "cascade, trained"): the own cells of a level, and the refresh over their concatenation
+namespace {
+
+#define OCC_TRAIN_ARG "cascade: 1 <= levels <= 8; every level: 1 <= n[i] <= 4096, finite lo, finite inv > 0"
+
+// The concatenation of the levels' own lists, level 0 first: position p in [off[l], off[l+1]) is cell own[p] of level l.
+struct OccSpan {
+  const int32_t* own;
+  int64_t off[FN_OCC_MAX_LEVELS + 1];
+};
+
+struct OccDensDev {
+  float* dens[FN_OCC_MAX_LEVELS];
+  float decay[FN_OCC_MAX_LEVELS];
+  uint32_t ncells[FN_OCC_MAX_LEVELS];
+};
+
+// one rays11 row per position q0 .. q0+n-1: the point fastnerf_occ_cell_points makes for that level's grid and that cell.  l and
+// g.levels are uniform (scalar loads of the level's geometry); a lane takes the level its position falls into.
+__global__ void __launch_bounds__(OCC_BLOCK) occ_cascade_points_kernel(OccCascadeDev g, OccSpan s, int64_t q0, int64_t n, uint32_t k0, uint32_t k1,
+                                                                       int jit, float* __restrict__ rays11) {
+  const int64_t q = (int64_t)blockIdx.x * OCC_BLOCK + threadIdx.x;
+  if (q >= n) return;
+  const int64_t p = q0 + q;
+  const uint32_t c = (uint32_t)s.own[p];
+  for (int l = 0; l < g.levels; ++l)
+    if (p >= s.off[l] && p < s.off[l + 1]) occ_cell_point(g.g[l].lo, g.g[l].inv, g.g[l].n, c, k0, k1, jit, rays11 + q * 11);
+}
+
+// dens = max(dens * decay, relu(sigma_c), relu(sigma_f)) of the cell of each position: every cell stands once in the concatenation, so
+// every store has one writer.  (c < ncells holds for a list made by fastnerf_occ_cascade_own; a foreign list cannot write outside dens)
+__global__ void __launch_bounds__(OCC_BLOCK) occ_cascade_update_kernel(OccDensDev d, OccSpan s, int levels, const float* __restrict__ raw_c,
+                                                                       const float* __restrict__ raw_f, int64_t q0, int64_t n) {
+  const int64_t q = (int64_t)blockIdx.x * OCC_BLOCK + threadIdx.x;
+  if (q >= n) return;
+  const int64_t p = q0 + q;
+  const uint32_t c = (uint32_t)s.own[p];
+  for (int l = 0; l < levels; ++l)
+    if (p >= s.off[l] && p < s.off[l + 1] && c < d.ncells[l]) d.dens[l][c] = occ_dens_next(d.dens[l][c], raw_c, raw_f, q, d.decay[l]);
+}
+
+// the geometry of a training cascade (the bits are not read: words may be NULL)
+bool occ_train_dev(const fn_occ_cascade* c, OccCascadeDev* o) {
+  if (!c || c->levels < 1 || c->levels > FN_OCC_MAX_LEVELS) return false;
+  *o = OccCascadeDev{};
+  for (int l = 0; l < c->levels; ++l) {
+    OccDev d;
+    if (!occ_geom(&c->level[l], &d)) return false;
+    for (int a = 0; a < 3; ++a) {
+      if (d.n[a] > 4096) return false;
+      o->g[l].lo[a] = d.lo[a];
+      o->g[l].inv[a] = d.inv[a];
+      o->g[l].n[a] = d.n[a];
+    }
+    o->words[l] = d.words;
+  }
+  o->levels = c->levels;
+  return true;
+}
+
+// offsets[levels + 1] (host): 0 = offsets[0] <= offsets[1] <= ..., no level longer than its grid, and [q0, q0 + n) inside
+bool occ_span(const OccCascadeDev& g, const int32_t* own, const int64_t* offsets, int64_t q0, int64_t n, OccSpan* s) {
+  if (!offsets || offsets[0] != 0 || q0 < 0 || n < 0) return false;
+  *s = OccSpan{};
+  s->own = own;
+  for (int l = 0; l < g.levels; ++l) {
+    const int64_t len = offsets[l + 1] - offsets[l];
+    if (len < 0 || len > (int64_t)g.g[l].n[0] * g.g[l].n[1] * g.g[l].n[2]) return false;
+    s->off[l + 1] = offsets[l + 1];
+  }
+  return q0 <= offsets[g.levels] && n <= offsets[g.levels] - q0;
+}
+
+}  // namespace
+
+extern "C" int fastnerf_occ_cascade_own(const fn_occ_cascade* cascade, int level, int dilate, int32_t* list, int32_t* count_out, int32_t* ws,
+                                        fn_stream_t stream) {
+  OccCascadeDev g;
+  FN_CHECK_ARG(occ_train_dev(cascade, &g), OCC_TRAIN_ARG);
+  FN_CHECK_ARG(level >= 0 && level < g.levels && dilate >= 0 && dilate <= 4096, "0 <= level < levels, 0 <= dilate <= 4096");
+  FN_CHECK_ARG(list && count_out && ws, "non-null pointers");
+  // Per inner level j and axis a, in float64 with every product and sum rounded on its own (this file is compiled without
+  // contraction): w = 1 / inv, hi = lo + n w; cell i of `level` is covered on the axis when
+  //   lo_l + (i - m) w_l >= lo_j + w_j   and   lo_l + (i + 1 + m) w_l <= hi_j - w_j,   m = dilate + 1.
+  // Both sides are monotone in i, so the covered indices of an axis are one interval [first, last].
+  const OccLevel& L = g.g[level];
+  OwnDev e = {};
+  const int m = dilate + 1;
+  for (int a = 0; a < 3; ++a) e.n[a] = L.n[a];
+  for (int j = 0; j < level; ++j) {
+    const OccLevel& J = g.g[j];
+    int* box = e.box[e.nbox];
+    bool any = true;
+    for (int a = 0; a < 3 && any; ++a) {
+      const double wl = 1.0 / (double)L.inv[a], wj = 1.0 / (double)J.inv[a];
+      const double lol = (double)L.lo[a], loj = (double)J.lo[a];
+      const double hij = loj + (double)J.n[a] * wj;
+      const double A = loj + wj, B = hij - wj;
+      int first = L.n[a], last = -1;
+      for (int i = 0; i < L.n[a]; ++i) {
+        const double left = lol + (double)(i - m) * wl, right = lol + (double)(i + 1 + m) * wl;
+        if (left >= A && right <= B) {
+          if (i < first) first = i;
+          last = i;
+        }
+      }
+      box[2 * a] = first;
+      box[2 * a + 1] = last;
+      any = last >= first;
+    }
+    if (any) ++e.nbox;
+  }
+  occ_classify_launch(e, (int64_t)L.n[0] * L.n[1] * L.n[2], 1, (const float*)nullptr, (const float*)nullptr, list, count_out, (float*)nullptr, ws,
+                      fn::S(stream));
+  FN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fastnerf_occ_cascade_points(const fn_occ_cascade* cascade, const int32_t* own, const int64_t* offsets, int64_t q0, int64_t n,
+                                           uint64_t seed, float* rays11, fn_stream_t stream) {
+  OccCascadeDev g;
+  OccSpan s;
+  FN_CHECK_ARG(occ_train_dev(cascade, &g), OCC_TRAIN_ARG);
+  FN_CHECK_ARG(occ_span(g, own, offsets, q0, n, &s), "offsets[0] = 0, ascending, no level longer than its grid; 0 <= q0, q0 + n <= offsets[levels]");
+  if (n == 0) return 0;
+  FN_CHECK_ARG(own && rays11, "non-null pointers");
+  hipLaunchKernelGGL(occ_cascade_points_kernel, dim3(occ_blocks(n)), dim3(OCC_BLOCK), 0, fn::S(stream), g, s, q0, n, (uint32_t)seed,
+                     (uint32_t)(seed >> 32), seed != 0 ? 1 : 0, rays11);
+  FN_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fastnerf_occ_cascade_update(const fn_occ_cascade* cascade, const float* raw_c, const float* raw_f, const int32_t* own,
+                                           const int64_t* offsets, int64_t q0, int64_t n, const float* decay, float* const* dens,
+                                           fn_stream_t stream) {
+  OccCascadeDev g;
+  OccSpan s;
+  FN_CHECK_ARG(occ_train_dev(cascade, &g), OCC_TRAIN_ARG);
+  FN_CHECK_ARG(occ_span(g, own, offsets, q0, n, &s), "offsets[0] = 0, ascending, no level longer than its grid; 0 <= q0, q0 + n <= offsets[levels]");
+  FN_CHECK_ARG(decay && dens, "non-null decay / dens");
+  OccDensDev d = {};
+  for (int l = 0; l < g.levels; ++l) {
+    FN_CHECK_ARG(dens[l] && decay[l] >= 0.f && decay[l] <= 1.f, "every level: non-null dens, 0 <= decay <= 1");
+    d.dens[l] = dens[l];
+    d.decay[l] = decay[l];
+    d.ncells[l] = (uint32_t)((int64_t)g.g[l].n[0] * g.g[l].n[1] * g.g[l].n[2]);
+  }
+  if (n == 0) return 0;
+  FN_CHECK_ARG(own && raw_c, "non-null pointers");
+  hipLaunchKernelGGL(occ_cascade_update_kernel, dim3(occ_blocks(n)), dim3(OCC_BLOCK), 0, fn::S(stream), d, s, g.levels, raw_c, raw_f, q0, n);
   FN_LAUNCH_CHECK();
   return 0;
 }

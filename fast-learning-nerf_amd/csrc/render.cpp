@@ -719,12 +719,25 @@ static bool step_list_ok(const fn_step_args* a, const char* fname, const char* w
   return true;
 }
 
+// a step through a cascade: it stands where a->occ would, so a->occ is NULL, and every level is usable -- before anything is enqueued
+static bool step_cascade_ok(const fn_step_args* a, const fn_occ_cascade* cascade, const char* fname) {
+  if (a->occ) {
+    fn::set_error("%s: bad argument: a cascade needs args->occ == NULL (one of the two)", fname);
+    return false;
+  }
+  if (const char* fault = fn::occ_cascade_fault(cascade)) {
+    fn::set_error("%s: bad argument: %s", fname, fault);
+    return false;
+  }
+  return true;
+}
+
 // the rays of the batch -> rays11; with FN_STEP_TIGHTEN near / far of every ray are then clamped to what the grid's bits, as they are
-// now, leave occupied.  rays11 persists to the backward.
-static int step_pack_rays(const fn_step_args* a, fn_stream_t stream) {
+// now, leave occupied (cascade != NULL: the cascade's, a->occ being NULL then).  rays11 persists to the backward.
+static int step_pack_rays(const fn_step_args* a, const fn_occ_cascade* cascade, fn_stream_t stream) {
   if (int rc = fastnerf_pack_rays(a->n, a->rays_o, a->rays_d, a->near_plane, a->far_plane, a->ndc, a->H, a->W, a->focal, a->rays11, stream))
     return rc;
-  return (a->fwd_flags & FN_STEP_TIGHTEN) ? fastnerf_occ_ray_bounds(a->occ, nullptr, a->n, a->rays11, 1, nullptr, nullptr, stream) : 0;
+  return (a->fwd_flags & FN_STEP_TIGHTEN) ? fastnerf_occ_ray_bounds(cascade ? nullptr : a->occ, cascade, a->n, a->rays11, 1, nullptr, nullptr, stream) : 0;
 }
 
 // One pass as the loss launches see it: its maps, weights and depths [n, S], and the colour gradient they leave for its backward.
@@ -794,16 +807,22 @@ static int step_update(const fn_step_args* a, int first, int count, fn_stream_t 
 }
 
 // aux: NULL, or the depth / opacity terms (a term is on when its target is set); bk: NULL, or the per-ray background colours; dist: NULL,
-// or the distortion term (on when lambda_dist != 0); ex: NULL, or the exposure table
+// or the distortion term (on when lambda_dist != 0); ex: NULL, or the exposure table; cascade: NULL, or the occupancy cascade that takes
+// the place of a->occ at each of its sites (step_cascade_ok: a->occ is NULL then)
 static int train_step(const fn_step_args* a, const fn_step_aux* aux, const fn_step_bkgd* bk, const fn_step_dist* dist, const fn_step_expo* ex,
-                      int phases, fn_stream_t stream) {
+                      const fn_occ_cascade* cascade, int phases, fn_stream_t stream) {
   if (dist && dist->lambda_dist == 0.0f) dist = nullptr;
-  const char* fname = ex ? "fastnerf_train_step_expo" : dist ? "fastnerf_train_step_dist" : bk ? "fastnerf_train_step_bkgd" : "fastnerf_train_step";
+  const char* fname = cascade ? "fastnerf_train_step_cascade"
+                      : ex    ? "fastnerf_train_step_expo"
+                      : dist  ? "fastnerf_train_step_dist"
+                      : bk    ? "fastnerf_train_step_bkgd"
+                              : "fastnerf_train_step";
   if (aux && !aux->depth_target && !aux->acc_target) aux = nullptr;
   if (!a || a->math_mode < 0 || a->math_mode > 2 || a->n <= 0 || a->N_samples < 2 || a->N_importance < 0) {
     fn::set_error("%s: bad argument: args != NULL, math_mode in {0,1,2}, n>0, N_samples>=2, N_importance>=0", fname);
     return -1;
   }
+  if (cascade && !step_cascade_ok(a, cascade, fname)) return -1;
   const bool two = a->N_importance > 0;
   if (bk && !step_bkgd_ok(a, bk, two, phases, fname)) return -1;
   if (dist && !step_dist_ok(dist, two, phases, two ? a->w1 : a->w0, two ? a->w0 : nullptr, fname)) return -1;
@@ -817,7 +836,7 @@ static int train_step(const fn_step_args* a, const fn_step_aux* aux, const fn_st
     fn::set_error("%s: null network buffer", fname);
     return -1;
   }
-  if (a->occ) {
+  if (a->occ || cascade) {
     // the grid removes samples from the FIRST forward of a compacted step; the plain backward has no list to run over, and sigma
     // noise is added before the relu: a sample with zero sigma is not dead then
     if (!step_list_ok(a, fname, "an occupancy grid needs the compacted step", "an occupancy grid")) return -1;
@@ -850,9 +869,17 @@ static int train_step(const fn_step_args* a, const fn_step_aux* aux, const fn_st
       fn::set_error("%s: null batch / output buffer", fname);
       return -1;
     }
-    if ((rc = step_pack_rays(a, stream))) return rc;
+    if ((rc = step_pack_rays(a, cascade, stream))) return rc;
     const bool save = !a->live;
-    if (a->occ) {
+    if (cascade) {      // the grid's call below, argument for argument: rr_fwd_occ is the one body of both
+      if ((rc = fastnerf_render_rays_fwd_occ_cascade(a->math_mode, a->n, a->N_samples, a->N_importance, a->rays11, a->lindisp,
+                                                     (a->perturb || a->t_rand) ? 1 : 0, a->perturb ? 0 : 1, a->white_bkgd, a->t_rand, a->u,
+                                                     a->seed0, a->seed1, params_c, a->packed_fwd_c, params_f, a->packed_fwd_f, cascade,
+                                                     a->live_ws + 4, a->occ_counts ? a->occ_counts : a->live_ws, a->z0, a->raw0, a->rgb0,
+                                                     a->disp0, a->acc0, a->w0, a->depth0, a->z1, a->z_samples, a->z_std, a->raw1, a->rgb1,
+                                                     a->disp1, a->acc1, a->w1, a->depth1, fwd_flags, stream)))
+        return rc;
+    } else if (a->occ) {
       // live_ws: [4] counters of the backward | list | scan scratch -- the forward's list and scratch are dead before the backward
       // writes its own; without occ_counts the forward's counters land in the backward's (which overwrites them)
       if ((rc = fastnerf_render_rays_fwd_occ(a->math_mode, a->n, a->N_samples, a->N_importance, a->rays11, a->lindisp,
@@ -895,26 +922,31 @@ static int train_step(const fn_step_args* a, const fn_step_aux* aux, const fn_st
 }
 
 extern "C" int fastnerf_train_step(const fn_step_args* a, int phases, fn_stream_t stream) {
-  return train_step(a, nullptr, nullptr, nullptr, nullptr, phases, stream);
+  return train_step(a, nullptr, nullptr, nullptr, nullptr, nullptr, phases, stream);
 }
 
 extern "C" int fastnerf_train_step_aux(const fn_step_args* a, const fn_step_aux* aux, int phases, fn_stream_t stream) {
-  return train_step(a, aux, nullptr, nullptr, nullptr, phases, stream);
+  return train_step(a, aux, nullptr, nullptr, nullptr, nullptr, phases, stream);
 }
 
 extern "C" int fastnerf_train_step_bkgd(const fn_step_args* a, const fn_step_aux* aux, const fn_step_bkgd* bk, int phases,
                                         fn_stream_t stream) {
-  return train_step(a, aux, bk, nullptr, nullptr, phases, stream);
+  return train_step(a, aux, bk, nullptr, nullptr, nullptr, phases, stream);
 }
 
 extern "C" int fastnerf_train_step_dist(const fn_step_args* a, const fn_step_aux* aux, const fn_step_bkgd* bk, const fn_step_dist* dist,
                                         int phases, fn_stream_t stream) {
-  return train_step(a, aux, bk, dist, nullptr, phases, stream);
+  return train_step(a, aux, bk, dist, nullptr, nullptr, phases, stream);
 }
 
 extern "C" int fastnerf_train_step_expo(const fn_step_args* a, const fn_step_aux* aux, const fn_step_bkgd* bk, const fn_step_dist* dist,
                                         const fn_step_expo* ex, int phases, fn_stream_t stream) {
-  return train_step(a, aux, bk, dist, ex, phases, stream);
+  return train_step(a, aux, bk, dist, ex, nullptr, phases, stream);
+}
+
+extern "C" int fastnerf_train_step_cascade(const fn_step_args* a, const fn_step_aux* aux, const fn_step_bkgd* bk, const fn_step_dist* dist,
+                                           const fn_step_expo* ex, const fn_occ_cascade* cascade, int phases, fn_stream_t stream) {
+  return train_step(a, aux, bk, dist, ex, cascade, phases, stream);
 }
 
 // The marched step (include/fastnerf.h, "marched training"): one network on the packed rows of a jittered lattice.  The row is [n, C] in
@@ -929,9 +961,10 @@ extern "C" int64_t fastnerf_step_march_ws_ints(int64_t n, int C) {
 }
 
 static int train_step_march(const fn_step_args* a, const fn_step_march* mx, const fn_step_bkgd* bk, const fn_step_dist* dist,
-                            const fn_step_expo* ex, int phases, fn_stream_t stream) {
+                            const fn_step_expo* ex, const fn_occ_cascade* cascade, int phases, fn_stream_t stream) {
   if (dist && dist->lambda_dist == 0.0f) dist = nullptr;
-  const char* fname = ex     ? "fastnerf_train_step_march_expo"
+  const char* fname = cascade ? "fastnerf_train_step_march_cascade"
+                      : ex   ? "fastnerf_train_step_march_expo"
                       : dist ? "fastnerf_train_step_march_dist"
                       : bk   ? "fastnerf_train_step_march_bkgd"
                              : "fastnerf_train_step_march";
@@ -939,6 +972,7 @@ static int train_step_march(const fn_step_args* a, const fn_step_march* mx, cons
     fn::set_error("%s: bad argument: args and march != NULL, math_mode in {0,1,2}, n > 0, which in {0,1}", fname);
     return -1;
   }
+  if (cascade && !step_cascade_ok(a, cascade, fname)) return -1;
   if (bk && !step_bkgd_ok(a, bk, false, phases, fname)) return -1;
   if (dist && !step_dist_ok(dist, false, phases & ~FN_STEP_BWD_FINE, a->w0, nullptr, fname)) return -1;
   if (ex && !step_expo_ok(a, ex, false, phases, fname)) return -1;
@@ -948,12 +982,12 @@ static int train_step_march(const fn_step_args* a, const fn_step_march* mx, cons
     fn::set_error("%s: bad argument: 2 <= K < 2^24, 2 <= C <= 512, n * C < 2^31, n * K < 2^31", fname);
     return -1;
   }
-  if (!a->occ) {
+  if (!a->occ && !cascade) {
     fn::set_error("%s: the march walks an occupancy grid (occ != NULL)", fname);
     return -1;
   }
   if (!step_list_ok(a, fname, "the marched step is a compacted step", "the march")) return -1;
-  if (const char* fault = fn::occ_grid_fault(a->occ)) {
+  if (const char* fault = cascade ? nullptr : fn::occ_grid_fault(a->occ)) {
     fn::set_error("%s: bad argument: %s", fname, fault);
     return -1;
   }
@@ -981,9 +1015,9 @@ static int train_step_march(const fn_step_args* a, const fn_step_march* mx, cons
   if (phases & FN_STEP_FORWARD) {
     const MarchWs ws = march_ws(mx->list_ws, n, C);      // (fastnerf_step_march_ws_ints: no transmittance)
     const MarchRow row = {a->math_mode, K, C, a->fwd_flags & ~FN_STEP_TIGHTEN, n, a->rays11, params, pf, a->z0, a->raw0, mx->kidx, mx->counts, stream};
-    if ((rc = step_pack_rays(a, stream))) return rc;
+    if ((rc = step_pack_rays(a, cascade, stream))) return rc;
     if ((rc = march_round(row, ws, 0, C, false, [&] {
-           return fastnerf_occ_march_jitter(a->occ, nullptr, n, K, a->lindisp, a->rays11, C, 0, C, 1, nullptr, 0.f, mx->u, mx->seed, ws.state,
+           return fastnerf_occ_march_jitter(cascade ? nullptr : a->occ, cascade, n, K, a->lindisp, a->rays11, C, 0, C, 1, nullptr, 0.f, mx->u, mx->seed, ws.state,
                                             a->z0, mx->kidx, mx->overflow, stream);
          })))
       return rc;
@@ -1009,20 +1043,25 @@ static int train_step_march(const fn_step_args* a, const fn_step_march* mx, cons
 }
 
 extern "C" int fastnerf_train_step_march(const fn_step_args* a, const fn_step_march* mx, int phases, fn_stream_t stream) {
-  return train_step_march(a, mx, nullptr, nullptr, nullptr, phases, stream);
+  return train_step_march(a, mx, nullptr, nullptr, nullptr, nullptr, phases, stream);
 }
 
 extern "C" int fastnerf_train_step_march_bkgd(const fn_step_args* a, const fn_step_march* mx, const fn_step_bkgd* bk, int phases,
                                               fn_stream_t stream) {
-  return train_step_march(a, mx, bk, nullptr, nullptr, phases, stream);
+  return train_step_march(a, mx, bk, nullptr, nullptr, nullptr, phases, stream);
 }
 
 extern "C" int fastnerf_train_step_march_dist(const fn_step_args* a, const fn_step_march* mx, const fn_step_bkgd* bk, const fn_step_dist* dist,
                                               int phases, fn_stream_t stream) {
-  return train_step_march(a, mx, bk, dist, nullptr, phases, stream);
+  return train_step_march(a, mx, bk, dist, nullptr, nullptr, phases, stream);
 }
 
 extern "C" int fastnerf_train_step_march_expo(const fn_step_args* a, const fn_step_march* mx, const fn_step_bkgd* bk, const fn_step_dist* dist,
                                               const fn_step_expo* ex, int phases, fn_stream_t stream) {
-  return train_step_march(a, mx, bk, dist, ex, phases, stream);
+  return train_step_march(a, mx, bk, dist, ex, nullptr, phases, stream);
+}
+
+extern "C" int fastnerf_train_step_march_cascade(const fn_step_args* a, const fn_step_march* mx, const fn_step_bkgd* bk, const fn_step_dist* dist,
+                                                 const fn_step_expo* ex, const fn_occ_cascade* cascade, int phases, fn_stream_t stream) {
+  return train_step_march(a, mx, bk, dist, ex, cascade, phases, stream);
 }

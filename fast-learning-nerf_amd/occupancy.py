@@ -14,13 +14,21 @@ Training (opt-in): a grid made by `OccupancyGrid.for_training` starts fully occu
 `grid.update` as training goes: dens = max(dens * decay, relu(sigma)) at a jittered point INSIDE each cell, bit = dens >
 threshold, dilated.  render_rays(..., occupancy=grid) with gradients enabled still raises: the autograd route has no grid.
 
-Cascade (rendering only): `OccupancyCascade` is an ordered list of 1 to 8 such grids, innermost first -- usually the fine grid
+Cascade: `OccupancyCascade` is an ordered list of 1 to 8 such grids, innermost first -- usually the fine grid
 over the object and coarser grids over larger boxes around it.  A sample takes the bit of the FIRST grid whose box contains it
 (each grid's own index arithmetic), and `outside_occupied` of the cascade when none does.  Space outside the inner box is then
 skipped because it was looked at and found empty, not because it was assumed empty.
 
     cascade = fastnerf.occupancy.OccupancyCascade.from_network(render_kwargs_test, levels=3)
     render_kwargs_test['occupancy'] = cascade
+
+Training through a cascade (opt-in): `OccupancyCascade.for_training(levels=3)` -- or any cascade whose grids all carry a density, with
+one `dilate` and at most 4096 cells per axis -- goes wherever a training grid goes: run_nerf.Trainer(..., occupancy=cascade), with
+`tighten` and `march=`.  Its refresh (`cascade.update`) runs over the OWN cells of the levels only: a cell of level l that lies, with
+a margin of dilate + 1 cells of its own and one cell of the inner level, inside the box of ONE level j < l is never read by a lookup
+and is left at density 0 (`cascade.own_cells(l)`; the rule in float64: include/fastnerf.h, "cascade, trained").  One cursor rotates
+over the concatenation of the levels' own lists, so `cells_per_call` bounds the cost of a refresh whatever the number of levels, and
+every chunk is one network launch whatever mix of levels it holds.
 
 Per-ray bounds (opt-in): `grid.ray_bounds(ray_batch)` / `grid.tighten(ray_batch)` (grids and cascades; csrc/ray_bounds.hip) clamp near
 and far of every ray to the part of [near, far] outside which the lookup above calls no sample occupied, so that the coarse depths are
@@ -54,6 +62,47 @@ def _network_volume(render_kwargs, N, bound, which='both', chunk=1024 * 64):
                               use_viewdirs=render_kwargs.get('use_viewdirs'))
         vol = v if vol is None else torch.maximum(vol, v)
     return vol
+
+
+def _update_nets(render_kwargs, which, who):
+    """The networks an `update` evaluates: [coarse], [fine] or [coarse, fine] (`which`; the coarse one when there is no fine one)."""
+    from .model import NeRF
+    if which not in ('both', 'fine', 'coarse'):
+        raise ValueError("which is 'both', 'fine' or 'coarse'")
+    nets = [getattr(render_kwargs['network_fn'], 'module', render_kwargs['network_fn'])]
+    fine = render_kwargs.get('network_fine')
+    fine = getattr(fine, 'module', fine)
+    if fine is not None and fine is not nets[0]:
+        if which == 'both':
+            nets.append(fine)
+        elif which == 'fine':
+            nets = [fine]
+    if not all(isinstance(m, NeRF) for m in nets):
+        raise TypeError('%s.update runs the fused HIP forward: it needs fastnerf NeRF networks' % who)
+    return nets
+
+
+def _rotate(cursor, primed, total, cells_per_call):
+    """The slice of `total` entries a refresh takes: ([(a, b), ...] one or two ascending ranges, the next cursor).  Everything while
+    not primed or without a budget (the cursor stays); else cells_per_call entries from the cursor on, wrapping round."""
+    if cells_per_call is None or not primed or int(cells_per_call) >= total:
+        return [(0, total)], cursor
+    k = max(1, int(cells_per_call))
+    a, b = cursor, cursor + k
+    return [(a, min(b, total))] + ([(0, b - total)] if b > total else []), b % total
+
+
+def _training_fault(levels):
+    """None when `levels` (objects with dens, dilate, shape) make a training cascade; else why not.  A cascade in which no or only
+    some levels carry a density is a rendering cascade (''), which is no error."""
+    have = [g.dens is not None for g in levels]
+    if not all(have):
+        return ''
+    if len({int(g.dilate) for g in levels}) != 1:
+        return 'the levels of a training cascade share one dilate, got %s' % ([int(g.dilate) for g in levels],)
+    if max(max(g.shape) for g in levels) > OccupancyCascade.MAX_TRAIN_N:
+        return 'a training cascade has at most %d cells per axis on every level' % OccupancyCascade.MAX_TRAIN_N
+    return None
 
 
 class _RayBounds:
@@ -248,32 +297,14 @@ class OccupancyGrid(_RayBounds):
 
         which: 'both' (default), or 'coarse' / 'fine' as in from_network: the density then follows that network alone (the coarse
         one when there is no fine one) -- what a trainer that marches one network refreshes its grid from."""
-        from .model import NeRF
         if self.dens is None:
             raise ValueError('update() needs a grid with a density: OccupancyGrid.for_training(...)')
-        if which not in ('both', 'fine', 'coarse'):
-            raise ValueError("which is 'both', 'fine' or 'coarse'")
-        nets = [getattr(render_kwargs['network_fn'], 'module', render_kwargs['network_fn'])]
-        fine = render_kwargs.get('network_fine')
-        fine = getattr(fine, 'module', fine)
-        if fine is not None and fine is not nets[0]:
-            if which == 'both':
-                nets.append(fine)
-            elif which == 'fine':
-                nets = [fine]
-        if not all(isinstance(m, NeRF) for m in nets):
-            raise TypeError('OccupancyGrid.update runs the fused HIP forward: it needs fastnerf NeRF networks')
+        nets = _update_nets(render_kwargs, which, 'OccupancyGrid')
         packed = _packed if _packed is not None else [m.packed()[0] for m in nets]
         seed = self.updates + 1 if seed is None else int(seed)
         total = self.ncells
-        if cells_per_call is None or not self.primed or int(cells_per_call) >= total:
-            ranges = [(0, total)]
-            self.primed = True
-        else:
-            k = max(1, int(cells_per_call))
-            a, b = self.cursor, self.cursor + k
-            ranges = [(a, min(b, total))] + ([(0, b - total)] if b > total else [])
-            self.cursor = b % total
+        ranges, self.cursor = _rotate(self.cursor, self.primed, total, cells_per_call)
+        self.primed = True
         dev = self.dens.device
         n0 = min(self.CHUNK, max(r[1] - r[0] for r in ranges))
         rays11 = torch.empty(n0, 11, device=dev, dtype=torch.float32)
@@ -321,9 +352,15 @@ class OccupancyCascade(_RayBounds):
     level by level with each grid's own index arithmetic; the first grid whose box contains it decides, and the sample takes that
     cell's bit.  A point that no box contains -- every non-finite point -- takes `outside_occupied` (None = the last grid's); the
     grids' own `outside_occupied` flags are not read.  The boxes need not be nested or concentric.  A cascade of one grid is that
-    grid, bit for bit.  render / render_path / render_rays take it wherever they take a grid; training does not
-    (run_nerf.Trainer raises)."""
+    grid, bit for bit.  render / render_path / render_rays take it wherever they take a grid.
+
+    A cascade whose grids ALL carry a density (for_training, or made by hand from OccupancyGrid.for_training grids) is a training
+    cascade: run_nerf.Trainer takes it as `occupancy=`, and `update` refreshes it over the own cells of its levels (`own_cells`).
+    Its levels share one `dilate` and have at most 4096 cells per axis (ValueError otherwise).  Any other cascade is for rendering
+    only (`dens` is None; run_nerf.Trainer raises)."""
     MAX_LEVELS = _lib.OCC_MAX_LEVELS
+    MAX_TRAIN_N = 4096      # cells per axis of a level that is trained through: the own-cell margins rest on it
+    CHUNK = 1 << 19         # positions per network launch of update()
 
     def __init__(self, grids, outside_occupied=None):
         grids = list(grids)
@@ -340,10 +377,67 @@ class OccupancyCascade(_RayBounds):
         for l, g in enumerate(grids):      # copies of the levels' descriptors: the words stay the grids' own
             C.memmove(C.byref(self._c.level[l]), C.byref(g._c), C.sizeof(_lib.OccGrid))
         self._c.level[len(grids) - 1].outside_occupied = int(self.outside_occupied)
+        # the training cascade's state (unused for a rendering cascade): `updates`, `cursor`, `primed` as on a grid, the cursor
+        # running over the concatenation of the levels' own lists
+        self.updates, self.cursor, self.primed = 0, 0, False
+        self._own = None
+        fault = _training_fault(grids)
+        if fault:
+            raise ValueError(fault)
+        if fault is None:      # once: the boxes do not move
+            dev = grids[0].words.device
+            lists = [ops.occ_cascade_own(self._c, l, grids[0].dilate, dev) for l in range(len(grids))]
+            self._own = torch.cat(lists)
+            self._offsets = (C.c_int64 * (len(grids) + 1))(*np.concatenate([[0], np.cumsum([x.numel() for x in lists])]).tolist())
 
     @property
     def levels(self):
         return len(self.grids)
+
+    @property
+    def dens(self):
+        """The levels' densities (a tuple) of a training cascade, None for a rendering cascade."""
+        return None if self._own is None else tuple(g.dens for g in self.grids)
+
+    @property
+    def dilate(self):
+        return self.grids[0].dilate
+
+    @property
+    def offsets(self):
+        """levels + 1 ints: own_cells(l) is positions offsets[l] .. offsets[l+1] of the concatenation `update` walks."""
+        self._need_training()
+        return [int(v) for v in self._offsets]
+
+    def _need_training(self):
+        if self._own is None:
+            raise ValueError('this OccupancyCascade has levels without a density: make one to train through with '
+                             'OccupancyCascade.for_training(...), or from OccupancyGrid.for_training grids')
+
+    def own_cells(self, l):
+        """Ascending int32 cell indices (c = (i*ny + j)*nz + k) of the cells of level l that a lookup can read, plus the margin
+        dilation needs: every cell that is not covered by ONE inner level (include/fastnerf.h, "cascade, trained")."""
+        self._need_training()
+        return self._own[self._offsets[l]:self._offsets[l + 1]]
+
+    @classmethod
+    def for_training(cls, levels=3, N=128, bound=1.2, growth=2.0, threshold=0., dilate=1, decay=0.95, outside_occupied=True,
+                     device='cuda'):
+        """A cascade to train through (run_nerf.Trainer(..., occupancy=cascade)): level l is OccupancyGrid.for_training over
+        [-bound * growth^l, bound * growth^l)^3.  N: a cell count, one per level, or one (nx, ny, nz) per level."""
+        levels = int(levels)
+        if not 1 <= levels <= cls.MAX_LEVELS:
+            raise ValueError('an occupancy cascade has 1 to %d levels, got %d' % (cls.MAX_LEVELS, levels))
+        Ns = list(N) if isinstance(N, (list, tuple, np.ndarray)) else [N] * levels
+        if len(Ns) != levels or not all(np.ndim(v) == 0 or (np.ndim(v) == 1 and len(v) == 3) for v in Ns):
+            raise ValueError('N is a cell count, one per level, or one (nx, ny, nz) per level: got %r for %d levels' % (N, levels))
+        if not float(growth) > 0.:
+            raise ValueError('growth must be > 0')
+        if max(int(s) for v in Ns for s in np.atleast_1d(v)) > cls.MAX_TRAIN_N:
+            raise ValueError('a training cascade has at most %d cells per axis on every level' % cls.MAX_TRAIN_N)
+        grids = [OccupancyGrid.for_training(N=Ns[l], bound=bound * float(growth) ** l, threshold=threshold, dilate=dilate, decay=decay,
+                                            outside_occupied=outside_occupied, device=device) for l in range(levels)]
+        return cls(grids, outside_occupied)
 
     @classmethod
     def from_network(cls, render_kwargs, levels=3, N=256, bound=1.2, growth=2.0, threshold=0., dilate=1, which='both',
@@ -374,17 +468,66 @@ class OccupancyCascade(_RayBounds):
             if 'levels' not in f.files:
                 raise ValueError('%s holds a single occupancy grid: load it with OccupancyGrid.load' % path)
             grids = [OccupancyGrid._from_fields(f, 'l%d_' % l, device) for l in range(int(f['levels']))]
-            return cls(grids, bool(f['outside_occupied']))
+            c = cls(grids, bool(f['outside_occupied']))
+            if 'updates' in f.files:      # (a file from before cascades were trained through has none: a fresh cursor)
+                c.updates, c.cursor, c.primed = int(f['updates']), int(f['cursor']), bool(f['primed'])
+            return c
 
     def save(self, path):
         """.npz: levels (int64), outside_occupied (of the cascade), and per level i the fields of OccupancyGrid.save prefixed
         `l{i}_`: l0_words (uint32; cell (i,j,k) = bit c & 31 of word c >> 5, c = (i*ny + j)*nz + k), l0_shape, l0_lo, l0_hi,
-        l0_outside_occupied, l1_words, ...  OccupancyGrid.load refuses such a file."""
+        l0_outside_occupied, l1_words, ...; a training cascade adds its own updates, cursor, primed (the levels' training fields
+        ride with the levels).  OccupancyGrid.load refuses such a file."""
         fields = dict(levels=np.asarray(self.levels, np.int64), outside_occupied=np.asarray(self.outside_occupied))
+        if self._own is not None:
+            fields.update(updates=np.asarray(self.updates, np.int64), cursor=np.asarray(self.cursor, np.int64), primed=np.asarray(self.primed))
         for l, g in enumerate(self.grids):
             fields.update({'l%d_%s' % (l, k): v for k, v in g._fields().items()})
         with open(path, 'wb') as fh:
             np.savez(fh, **fields)
+
+    # ---- training ---------------------------------------------------------------------------------------------------
+    def update(self, render_kwargs, seed=None, cells_per_call=None, which='both', _packed=None):
+        """OccupancyGrid.update over the cascade's own cells: for each position of the concatenated own lists the point
+        OccupancyGrid.update samples in that level's cell (same Philox key (seed, cell); fastnerf_occ_cascade_points), the non-saving
+        forward of the network(s) on the chunk -- one launch per network and chunk, whatever levels the chunk spans -- then dens =
+        max(dens * decay, relu(sigma)) at each position's level and cell (fastnerf_occ_cascade_update), and the bits and their dilation
+        per level.  An own cell ends with the bits of density its grid's own update(seed) gives it; a covered cell keeps dens = 0.
+
+        cells_per_call: refresh that many positions, a slice that rotates through the concatenation (level 0 first) from call to
+        call; the first call takes everything.  seed, which: as for a grid (default seed = 1 + the cascade's `updates`)."""
+        self._need_training()
+        nets = _update_nets(render_kwargs, which, 'OccupancyCascade')
+        packed = _packed if _packed is not None else [m.packed()[0] for m in nets]
+        seed = self.updates + 1 if seed is None else int(seed)
+        total = int(self._offsets[self.levels])
+        ranges, self.cursor = _rotate(self.cursor, self.primed, total, cells_per_call)
+        self.primed = True
+        dev = self._own.device
+        # the levels' densities and decays as they are now (a grid's decay may be set, its density rebound, between refreshes)
+        dens = [g.dens for g in self.grids]
+        if any(d is None or d.numel() != g.ncells or d.dtype != torch.float32 or not d.is_contiguous() or d.device != dev
+               for d, g in zip(dens, self.grids)):
+            raise ValueError('every level of a training cascade keeps a contiguous float32 density of its own size on the cascade\'s device')
+        dens_ptrs = (C.c_void_p * self.levels)(*[d.data_ptr() for d in dens])
+        decays = (C.c_float * self.levels)(*[float(g.decay) for g in self.grids])
+        n0 = min(int(self.CHUNK), max(r[1] - r[0] for r in ranges))
+        rays11 = torch.empty(n0, 11, device=dev, dtype=torch.float32)
+        z = torch.zeros(n0, 1, device=dev, dtype=torch.float32)
+        raws = [torch.empty(n0, 1, 4, device=dev, dtype=torch.float32) for _ in nets]
+        with torch.no_grad():
+            for lo, hi in ranges:
+                for q0 in range(lo, hi, n0):
+                    n = min(n0, hi - q0)
+                    ops.occ_cascade_points(self._c, self._own, self._offsets, q0, rays11[:n], seed)
+                    for m, pk, raw in zip(nets, packed, raws):
+                        ops.mlp_fwd(rays11[:n], z[:n], m.flat, pk, raw=raw[:n])
+                    ops.occ_cascade_update(self._c, raws[0], raws[1] if len(raws) > 1 else None, self._own, self._offsets, q0, n,
+                                           decays, dens_ptrs)
+            for g in self.grids:      # the bits of every cell of every level and their dilation, once
+                ws = torch.empty(2 * g.words.numel(), device=dev, dtype=torch.int32) if g.dilate > 0 else None
+                ops.occ_update(None, None, 0, 0, g.shape, g.decay, g.threshold, g.dilate, g.dens, g.words, ws)
+        self.updates += 1
 
     # ---- inspection -------------------------------------------------------------------------------------------------
     def query(self, points):

@@ -1262,6 +1262,42 @@ def occ_update(raw_c, raw_f, c0, n, shape, decay, threshold, dilate, dens, words
                                     ptr(dens), ptr(words), ptr(ws), stream()), 'fastnerf_occ_update')
 
 
+def occ_cascade_own(ccascade, level, dilate, device):
+    """The own cells of level `level` of a training cascade (ccascade a _lib.OccCascade): ascending int32 cell indices
+    (fastnerf_occ_cascade_own).  One host read of the count: it runs once, when the cascade is made."""
+    g = ccascade.level[int(level)]
+    ncells = int(g.n[0]) * int(g.n[1]) * int(g.n[2])
+    if not 0 < ncells < 2 ** 31:
+        raise ValueError('a level has 1 to 2^31 - 1 cells')
+    lst = torch.empty(ncells, device=device, dtype=torch.int32)
+    cnt = torch.empty(2, device=device, dtype=torch.int32)
+    ws = torch.empty(int(lib().fastnerf_compact_ws_ints(ncells)), device=device, dtype=torch.int32)
+    check(lib().fastnerf_occ_cascade_own(ccascade, int(level), int(dilate), ptr(lst), ptr(cnt), ptr(ws), stream()), 'fastnerf_occ_cascade_own')
+    return lst[:int(cnt[0])].clone()
+
+
+def occ_cascade_points(ccascade, own, offsets, q0, rays11, seed=0):
+    """One point per position q0 .. q0 + len(rays11) - 1 of the concatenated own lists (`own` int32 on the device, `offsets` a ctypes
+    int64 array of levels + 1 entries): the point occ_cell_points makes for that level's grid and that cell."""
+    require_gpu(own, rays11)
+    assert rays11.dim() == 2 and rays11.shape[1] == 11 and rays11.is_contiguous() and rays11.dtype == torch.float32
+    assert own.dtype == torch.int32 and own.is_contiguous() and own.numel() >= int(offsets[ccascade.levels])
+    check(lib().fastnerf_occ_cascade_points(ccascade, ptr(own), offsets, int(q0), rays11.shape[0], int(seed), ptr(rays11), stream()),
+          'fastnerf_occ_cascade_points')
+    return rays11
+
+
+def occ_cascade_update(ccascade, raw_c, raw_f, own, offsets, q0, n, decay, dens):
+    """dens = max(dens * decay, relu(sigma of raw_c), relu(sigma of raw_f)) at the level and cell of the positions q0 .. q0 + n - 1.
+    decay: ctypes float array, dens: ctypes void-pointer array, one entry per level (the caller keeps the tensors alive)."""
+    require_gpu(raw_c, raw_f, own)
+    for r in (raw_c, raw_f):
+        assert r is None or (r.dtype == torch.float32 and r.is_contiguous() and r.numel() >= 4 * int(n))
+    assert own.dtype == torch.int32 and own.is_contiguous() and own.numel() >= int(offsets[ccascade.levels])
+    check(lib().fastnerf_occ_cascade_update(ccascade, ptr(raw_c), ptr(raw_f), ptr(own), offsets, int(q0), int(n), decay, dens, stream()),
+          'fastnerf_occ_cascade_update')
+
+
 def mlp_fwd_list(rays11, z, params, packed_fwd, raw, live_idx, live_cnt, flags=0):
     """Inference forward over a point list (current math mode): raw[live_idx[j]] = logits of point live_idx[j], j < live_cnt[0]."""
     require_gpu(rays11, z, params, packed_fwd, raw, live_idx, live_cnt)

@@ -266,8 +266,11 @@ class Trainer:
     sum is the gradient of the global-batch mean) -> Adam over both nets in one launch -> LR decay
     with the reference's pre-increment rule (run_nerf.py:498-508).
 
-    occupancy (opt-in; an occupancy.OccupancyGrid, usually OccupancyGrid.for_training(); an OccupancyCascade raises
-    ValueError: it is for rendering): the first forward of each pass
+    occupancy (opt-in; an occupancy.OccupancyGrid, usually OccupancyGrid.for_training(), or a training OccupancyCascade, usually
+    OccupancyCascade.for_training(): wherever "grid" stands below, on the fused, `tighten` and `march=` routes and with every term,
+    the cascade's lookup takes the grid's place (fastnerf_train_step_cascade / _march_cascade), its refresh runs over the own cells
+    of its levels, `occupancy_cells` of them per refresh, and a one-level cascade is its grid bit for bit; a cascade in which some
+    level has no density raises ValueError: it is for rendering): the first forward of each pass
     evaluates the networks on the samples in occupied cells only; a sample in an empty cell gets raw = (0, 0, 0, 0), whose
     d(loss)/d(raw) is exactly zero, so the compacted backward needs no change.  The first `occupancy_warmup` steps leave the
     grid untouched; from then on a grid with a density is refreshed (`grid.update`) every `occupancy_every` steps, by at most
@@ -540,11 +543,10 @@ class Trainer:
             if self.tighten:
                 raise ValueError('Trainer: tighten=True clamps near / far to an occupancy grid: it needs occupancy=')
             return
-        from .occupancy import OccupancyCascade
-        if isinstance(self.occupancy, OccupancyCascade):
-            raise ValueError('Trainer: training takes a single OccupancyGrid, not an OccupancyCascade: the fused step has room for one '
-                             'grid (fn_step_args.occ), and refreshing a cascade would evaluate both networks on levels x N^3 cells per '
-                             'refresh, more than the first forward it could shorten; build the cascade for rendering after training')
+        if self._cascade() is not None and self.occupancy.dens is None:
+            raise ValueError('Trainer: this OccupancyCascade has levels without a density, so it cannot be refreshed while the networks '
+                             'train: make the cascade with OccupancyCascade.for_training(...), or from OccupancyGrid.for_training grids '
+                             'with one dilate; build a cascade from the networks (from_network) for rendering after training')
         if self.raw_noise_std > 0.:
             raise ValueError('Trainer: an occupancy grid cannot be combined with raw_noise_std > 0 (sigma noise is added before the '
                              'relu, so a sample with zero sigma is not dead)')
@@ -554,6 +556,11 @@ class Trainer:
         if get_compact() == '0' or not self.live.available(self.net_c, self.net_f, self.N_importance):
             raise ValueError('Trainer: an occupancy grid needs the compacted step (FASTNERF_COMPACT=0 or one network shared by '
                              'both passes rules it out): the plain backward has no list')
+
+    def _cascade(self):
+        """fn_occ_cascade of the step when `occupancy` is a cascade (fn_step_args.occ is NULL then), else None."""
+        from .occupancy import OccupancyCascade
+        return self.occupancy._c if isinstance(self.occupancy, OccupancyCascade) else None
 
     def _check_march(self):
         """(K, C) of the marched step, or None when march is off; ValueError for a configuration that cannot march."""
@@ -886,7 +893,7 @@ class Trainer:
         occ = self.occupancy
         if occ is not None and self.occupancy_counts is None:      # a grid set after construction
             self.occupancy_counts = torch.zeros(4, device=self.flat.device, dtype=torch.int32)
-        a.occ = None if occ is None else ctypes.addressof(occ._c)
+        a.occ = None if (occ is None or self._cascade() is not None) else ctypes.addressof(occ._c)
         a.occ_counts = None if occ is None else self.occupancy_counts.data_ptr()
         hold += [t_rand, u, noise0, noise1, occ]
         base_names = _OUT_NAMES_2 if Ni > 0 else _OUT_NAMES_1
@@ -935,7 +942,7 @@ class Trainer:
         x.u, x.seed = _lib.ptr(march_u), seeds['shift']
         x.kidx, x.overflow = kidx.data_ptr(), overflow.data_ptr()
         a.fwd_flags = (1 if self.skip_dead_rgb else 0) | (_lib.STEP_TIGHTEN if self.tighten else 0)
-        a.occ = ctypes.addressof(self.occupancy._c)
+        a.occ = None if self._cascade() is not None else ctypes.addressof(self.occupancy._c)
         view = lambda name: _region(block, regions, name)      # noqa: E731
         out = {'rgb_map': view('rgb0'), 'disp_map': view('disp0'), 'acc_map': view('acc0'), 'depth_map': view('depth0'),
                'raw': view('raw0'), 'weights': view('w0'), 'z_vals': view('z0'), 'march_k': kidx, 'march_overflow': overflow}
@@ -945,10 +952,20 @@ class Trainer:
     # The term structs are given in every phase call (the data-parallel step splits the phases).  NULL is "the term is off": the C side
     # then makes the launches, and names itself in errors, as the entry point without that struct does.
     def _march_call(self, a, x, phases):
+        c = self._cascade()
+        if c is not None:
+            return _lib.check(_lib.lib().fastnerf_train_step_march_cascade(ctypes.byref(a), ctypes.byref(x), _ref(self._bk), _ref(self._dist),
+                                                                           _ref(self._exp), ctypes.byref(c), int(phases), _lib.stream()),
+                              'fastnerf_train_step_march_cascade')
         _lib.check(_lib.lib().fastnerf_train_step_march_expo(ctypes.byref(a), ctypes.byref(x), _ref(self._bk), _ref(self._dist), _ref(self._exp),
                                                              int(phases), _lib.stream()), 'fastnerf_train_step_march_expo')
 
     def _fused_call(self, a, phases):
+        c = self._cascade()
+        if c is not None:
+            return _lib.check(_lib.lib().fastnerf_train_step_cascade(ctypes.byref(a), _ref(self._aux), _ref(self._bk), _ref(self._dist),
+                                                                     _ref(self._exp), ctypes.byref(c), int(phases), _lib.stream()),
+                              'fastnerf_train_step_cascade')
         _lib.check(_lib.lib().fastnerf_train_step_expo(ctypes.byref(a), _ref(self._aux), _ref(self._bk), _ref(self._dist), _ref(self._exp),
                                                        int(phases), _lib.stream()), 'fastnerf_train_step_expo')
 
@@ -1305,9 +1322,15 @@ def train(images, poses, H, W, focal, args, near=2., far=6., device='cuda', log=
     kw_test.update(bds_dict)
     occ_kw = {}
     if getattr(args, 'occupancy_train', False):     # opt-in (no such flag in the reference's parser): train through an occupancy grid
-        from .occupancy import OccupancyGrid
-        occ_kw = dict(occupancy=OccupancyGrid.for_training(N=getattr(args, 'occupancy_N', 128), bound=getattr(args, 'occupancy_bound', 1.2),
-                                                           outside_occupied=getattr(args, 'occupancy_outside_occupied', True), device=dev),
+        from .occupancy import OccupancyCascade, OccupancyGrid
+        geom = dict(N=getattr(args, 'occupancy_N', 128), bound=getattr(args, 'occupancy_bound', 1.2),
+                    outside_occupied=getattr(args, 'occupancy_outside_occupied', True), device=dev)
+        # args.occupancy_levels (default: a single grid): a cascade of that many levels, level l over occupancy_bound * occupancy_growth^l;
+        # occupancy_N is then a cell count, a list of one per level, or a list of (nx, ny, nz) per level
+        levels = getattr(args, 'occupancy_levels', None)
+        occ = (OccupancyGrid.for_training(**geom) if not levels else
+               OccupancyCascade.for_training(levels=int(levels), growth=float(getattr(args, 'occupancy_growth', 2.0)), **geom))
+        occ_kw = dict(occupancy=occ,
                       tighten=getattr(args, 'occupancy_tighten', False),     # (matters with occupancy_outside_occupied=False)
                       # marched training (needs occupancy_outside_occupied=False): steps from march_after on train the fine network alone
                       march=getattr(args, 'march', None), march_cap=getattr(args, 'march_cap', 128), march_after=getattr(args, 'march_after', 0),

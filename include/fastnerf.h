@@ -588,7 +588,9 @@ int fastnerf_occ_classify(const fn_occ_grid* grid, int64_t n, int S, const float
  * decides, and the sample takes that cell's bit.  A point no level contains -- every non-finite point -- takes `outside_occupied` of
  * the LAST level; the `outside_occupied` of the other levels is not read.  A cascade of one level is that grid, bit for bit.  The
  * struct lives on the HOST; level[l].words are device pointers.  fn_occ_grid and fn_step_args keep their sizes: the cascade has
- * entry points of its own (rendering only; fn_step_args.occ stays a single grid).
+ * entry points of its own.  Training takes a cascade too, as one more trailing pointer of the step (fastnerf_train_step_cascade /
+ * fastnerf_train_step_march_cascade below; fn_step_args.occ stays a single grid and is NULL then), refreshed over the own cells of
+ * its levels ("cascade, trained" below).
  *   fastnerf_occ_query_cascade     the arguments and the result of fastnerf_occ_query
  *   fastnerf_occ_classify_cascade  the contract of fastnerf_occ_classify: ascending list, device count, zero logits for the other
  *                                  samples, the same ws, the same three launches without atomics
@@ -620,6 +622,40 @@ int fastnerf_occ_classify_cascade(const fn_occ_cascade* cascade, int64_t n, int 
 int fastnerf_occ_cell_points(const fn_occ_grid* grid, int64_t c0, int64_t n, uint64_t seed, float* rays11, fn_stream_t stream);
 int fastnerf_occ_update(const float* raw_c, const float* raw_f, int64_t c0, int64_t n, int64_t nx, int64_t ny, int64_t nz,
                         float decay, float threshold, int dilate, float* dens, uint32_t* words, uint32_t* ws, fn_stream_t stream);
+/* ---- cascade, trained: a cascade whose levels each carry a density, refreshed over the cells a lookup can read.  A lookup gives a
+ * point to the FIRST level whose box contains it, so a cell of level l well inside the box of a level j < l is never read.
+ * Own cells.  In float64, from each level's fp32 lo, inv and n: w = 1 / (double)inv, hi = lo + n w, every product and sum rounded on
+ * its own.  Cell (i0, i1, i2) of level l is COVERED when there is ONE level j < l with, on every axis a and m = dilate + 1,
+ *   lo_l[a] + (i_a - m) w_l[a] >= lo_j[a] + w_j[a]     and     lo_l[a] + (i_a + 1 + m) w_l[a] <= hi_j[a] - w_j[a];
+ * every other cell is an OWN cell of l.  Level 0 owns all its cells; a cell covered only by a union of inner boxes is own
+ * (conservative; the boxes need not be nested).  With n[a] <= 4096 the fp32 index of a point is within 0.001 cell of the real one,
+ * so a point whose cell at level l is covered lies 0.99 w_j inside box j and is decided by a level <= j: a covered cell is never
+ * read, and the margin m keeps every cell within `dilate` of a readable one sampled.
+ *   fastnerf_occ_cascade_own     list[0 .. count) = the ascending cell indices of `level`'s own cells, count_out = (count, cells
+ *                                of the level) on the device.  list: room for every cell of the level; ws:
+ *                                fastnerf_compact_ws_ints(cells).  The covered intervals are worked out on the host; the device
+ *                                runs the count / scan / scatter of fastnerf_occ_classify with that predicate: no atomics, the
+ *                                same bits from call to call.  words are not read.
+ * The refresh runs over the CONCATENATION of the levels' own lists, level 0 first: own[offsets[l] .. offsets[l+1]) is level l's list,
+ * offsets[levels + 1] on the host.
+ *   fastnerf_occ_cascade_points  one rays11 row per position q0 .. q0+n-1: the point fastnerf_occ_cell_points makes for that
+ *                                level's grid and that cell, bit for bit (same Philox key (seed, cell), same clamping, seed == 0
+ *                                gives centres).  One launch serves a range that spans levels.
+ *   fastnerf_occ_cascade_update  dens_l[cell] = max(dens_l[cell] * decay[l], relu(sigma_c), relu(sigma_f)) for the positions q0 ..
+ *                                q0+n-1 (raw_c / raw_f [n,4] as for fastnerf_occ_update; a NaN counts as 0).  decay[levels] and
+ *                                dens[levels] (device pointers) are HOST arrays.  A cell stands once in the concatenation: plain
+ *                                stores, no atomics.  The bits and their dilation follow per level from fastnerf_occ_update(n = 0);
+ *                                a covered cell keeps dens = 0, so its bit is clear.
+ * -1 before anything is enqueued: levels outside 1 .. 8, a level with n[a] outside 1 .. 4096, a non-finite lo or inv <= 0; level or
+ * dilate out of range; offsets that do not start at 0, descend, or give a level more entries than it has cells; a range outside the
+ * concatenation; a NULL pointer that would be read. */
+int fastnerf_occ_cascade_own(const fn_occ_cascade* cascade, int level, int dilate, int32_t* list, int32_t* count_out, int32_t* ws,
+                             fn_stream_t stream);
+int fastnerf_occ_cascade_points(const fn_occ_cascade* cascade, const int32_t* own, const int64_t* offsets, int64_t q0, int64_t n,
+                                uint64_t seed, float* rays11, fn_stream_t stream);
+int fastnerf_occ_cascade_update(const fn_occ_cascade* cascade, const float* raw_c, const float* raw_f, const int32_t* own,
+                                const int64_t* offsets, int64_t q0, int64_t n, const float* decay, float* const* dens,
+                                fn_stream_t stream);
 /* NeRF.forward + Embedder.embed (model.py:38-63) of the points live_idx[0 .. *live_cnt) only, inference (nothing saved):
  * raw[live_idx[j]*4 .. +3] = the logits the plain forward gives that point; no other element of raw is written.  kind 0 only.
  * flags as fastnerf_mlp_fwd_flags_ex, a tile being 64 consecutive list entries.  _ex: exact fp32, bf16: split-bf16 (x3),
@@ -1079,6 +1115,18 @@ int fastnerf_train_step_expo(const fn_step_args* args, const fn_step_aux* aux, c
                              const fn_step_expo* ex, int phases, fn_stream_t stream);
 int fastnerf_train_step_march_expo(const fn_step_args* args, const fn_step_march* march, const fn_step_bkgd* bk,
                                    const fn_step_dist* dist, const fn_step_expo* ex, int phases, fn_stream_t stream);
+/* The two steps through an occupancy CASCADE: fastnerf_train_step_expo / fastnerf_train_step_march_expo with the cascade as one more
+ * trailing pointer; fn_step_args keeps its size.  cascade == NULL is exactly that call.  cascade != NULL needs args->occ == NULL (-1
+ * before anything is enqueued otherwise, as for a level that fails the checks of fastnerf_occ_query_cascade), and each place where the
+ * step reads args->occ takes the cascade's twin, which shares its body: fastnerf_occ_ray_bounds (FN_STEP_TIGHTEN),
+ * fastnerf_render_rays_fwd_occ_cascade, the check of the descriptor, fastnerf_occ_march_jitter.  Every refusal of the grid's route
+ * holds: the compacted step only (live != 0), no sigma noise, live_ws; FN_STEP_TIGHTEN needs one of the two.  A cascade of one level
+ * is the step through that grid, bit for bit. */
+int fastnerf_train_step_cascade(const fn_step_args* args, const fn_step_aux* aux, const fn_step_bkgd* bk, const fn_step_dist* dist,
+                                const fn_step_expo* ex, const fn_occ_cascade* cascade, int phases, fn_stream_t stream);
+int fastnerf_train_step_march_cascade(const fn_step_args* args, const fn_step_march* march, const fn_step_bkgd* bk,
+                                      const fn_step_dist* dist, const fn_step_expo* ex, const fn_occ_cascade* cascade, int phases,
+                                      fn_stream_t stream);
 
 /* ---- environment map: a trained background behind every ray (csrc/envmap.hip) ----------------------------------------------------------
  * A table of colours indexed by ray direction alone, composited behind the volume as rgb += (1 - acc) env(d) through the per-ray
