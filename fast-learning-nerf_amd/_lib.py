@@ -253,6 +253,8 @@ SIGNATURES = {
     'fastnerf_env_lookup': (I, [L, P, L, P, I, P, P]),
     'fastnerf_env_grad_ws_bytes': (L, [I]),
     'fastnerf_env_grad': (I, [L, P, L, I, P, P, P, P, P, P, P]),
+    'fastnerf_band_apply': (I, [I, P, P, P, P, P]),
+    'fastnerf_band_grad': (I, [I, P, P, P, P]),
 }
 
 _lib = None

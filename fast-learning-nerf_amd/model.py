@@ -99,7 +99,56 @@ class NeRF(flat_params.FlatNet):
     def _kernel_views(flat):
         return flat_params.views(flat, param_slices())
 
+    # ---- band weights: the kernels run the network whose encoding columns are the parameters' times w (bands.py) -------------
+    _bands = None          # (w_pos [63], w_view [27]) on the device while band weights are set
+    _band_host = None      # ... and on the host: an unchanged pair is not uploaded again
+    _band_pool = None      # create_nerf: the dict its two networks share, so that their effective buffers are one allocation
+    _band_slot = None      # ... and this network's slice of it
+
+    def set_bands(self, w_pos, w_view, sync=True):
+        """-> whether the weights differ from those that were set (they are uploaded only then).  sync=False leaves making `flat`
+        current to the caller's next packed(refresh=True).  Weigh the columns of the point and direction encodings by w_pos [63] / w_view [27] (finite, in [0, 1]; bands.BandSchedule
+        makes them): from now on `flat` / `flat_grad` are buffers of their own that hold the EFFECTIVE network -- the parameters with
+        the encoding columns of layer 0, the skip layer and the view layer times w (ops.band_apply, run before every re-pack) -- and
+        its gradient, while `param_flat` / `param_grad` stay what parameters() and their .grad view; `param_grads_from` and
+        `collect_grads` carry a kernel gradient to the parameters (ops.band_grad).  Everything that reads `flat` and `packed()` sees
+        the weighted field.  A column at weight 0 is neither read (its effective weights are 0) nor moved (its gradient is 0).
+        ValueError for a network without view directions (its `flat` is derived already) and for weights that are none."""
+        if not self.use_viewdirs:
+            raise ValueError('NeRF.set_bands: a network without view directions already runs on a derived kernel network; band weights '
+                             'need use_viewdirs=True')
+        from .bands import check_weights
+        host = check_weights(w_pos, w_view)
+        if self._bands is None:
+            dev = self.param_flat.device
+            pool = self._band_pool
+            if pool is None:
+                self.flat, self.flat_grad = torch.empty_like(self.param_flat), torch.zeros_like(self.param_grad)
+            else:
+                if pool.get('flat') is None:
+                    pool['flat'], pool['grad'] = torch.empty_like(pool['params']), torch.zeros_like(pool['params'])
+                self.flat, self.flat_grad = pool['flat'][self._band_slot], pool['grad'][self._band_slot]
+            self._bands = tuple(torch.empty_like(w, device=dev) for w in host)
+            self._band_host = None
+        changed = self._band_host is None or not all(torch.equal(a, b) for a, b in zip(host, self._band_host))
+        if changed:
+            for d, h in zip(self._bands, host):
+                d.copy_(h)
+            self._band_host = host
+        if sync:
+            self._sync_kernel_net()
+        return changed
+
+    def clear_bands(self):
+        """Back to the network without band weights: `flat` / `flat_grad` are the parameters' buffers again (re-pack before the next
+        use of a cached packed(refresh=False))."""
+        if self._bands is not None:
+            self._bands = self._band_host = None
+            self.flat, self.flat_grad = self.param_flat, self.param_grad
+
     def _sync_kernel_net(self):
+        if self._bands is not None:
+            ops.band_apply(self._bands[0], self._bands[1], self.param_flat, self.flat)
         if self.use_viewdirs:
             return
         with torch.no_grad():
@@ -116,6 +165,8 @@ class NeRF(flat_params.FlatNet):
 
     def param_grads_from(self, kernel_grad):
         """Gradients in parameters() order from a gradient buffer the kernels wrote (standard layout)."""
+        if self._bands is not None:      # the effective network's gradient -> the parameters': the encoding columns times w, on a copy
+            kernel_grad = ops.band_grad(self._bands[0], self._bands[1], kernel_grad.clone())
         k = self._kernel_views(kernel_grad)
         if self.use_viewdirs:
             return [k[name] for name, _, _ in param_slices()]
@@ -139,6 +190,9 @@ class NeRF(flat_params.FlatNet):
 
     def collect_grads(self):
         """After a backward that wrote `flat_grad`: make the parameters' .grad (views of `param_grad`) current."""
+        if self._bands is not None:
+            self.param_grad.copy_(self.flat_grad)
+            ops.band_grad(self._bands[0], self._bands[1], self.param_grad)
         if self.use_viewdirs:
             return
         with torch.no_grad():

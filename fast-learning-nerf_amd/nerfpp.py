@@ -292,7 +292,9 @@ class CascadeTrainer:
     towards the identity; the table takes the level's Adam step with moments of its own.  `expo_grad[m]` / `expo_loss[m]`: d(loss)/d(ab)
     and the unscaled pull of level m in the last step.  The returned colours stay the scene's.  Single process only."""
 
-    def __init__(self, nets, cascade_samples=(64, 128), lrate=5e-4, min_depth=1e-4, perturb=True, exposure=None, lambda_autoexpo=1.0):
+    def __init__(self, nets, cascade_samples=(64, 128), lrate=5e-4, min_depth=1e-4, perturb=True, exposure=None, lambda_autoexpo=1.0, bands=None):
+        if bands is not None:      # (band weights exist for model.NeRF networks on run_nerf.Trainer's routes; nerf++ nets are out of scope)
+            raise ValueError('CascadeTrainer: bands= is not implemented for nerf++ networks (run_nerf.Trainer(bands=) trains model.NeRF)')
         self.nets = [getattr(n, 'nerf_net', n) for n in nets]
         self.cascade_samples = list(cascade_samples)
         self.lrate, self.min_depth, self.perturb = lrate, min_depth, bool(perturb)

@@ -559,6 +559,56 @@ def env_grad(R, dirs, g_rgb, acc, g_rgb0=None, acc0=None, d_table=None, ws=None)
     return d_table
 
 
+# ---- band weights (csrc/bands.hip; include/fastnerf.h, "band weights") ---------------------------
+BAND_VIEW_COLS = 27
+
+
+def band_pos_cols(kind=0):
+    """Columns of the point encoding of a net of this kind: 63, or 84 for kind 2."""
+    return 84 if int(kind) == 2 else 63
+
+
+def _need_bands(kind, w_pos, w_view, *buffers):
+    """Refuse, before any launch, what fastnerf_band_apply / _grad would misread: a kind outside 0..2, weights that are not contiguous
+    fp32 [in_pe] / [27], net buffers that are not contiguous fp32 of the kind's size, tensors on different devices."""
+    kind = int(kind)
+    if kind not in (0, 1, 2):
+        raise ValueError(f'kind must be 0, 1 or 2, got {kind}')
+    require_gpu(w_pos, w_view, *buffers)
+    _need_f32('w_pos', w_pos, band_pos_cols(kind))
+    _need_f32('w_view', w_view, BAND_VIEW_COLS)
+    n = net_floats(kind, 0)
+    for name, t in zip(('the first net buffer', 'the second net buffer'), buffers):
+        _need_f32(name, t, n)
+    for name, t in (('w_pos', w_pos), ('w_view', w_view)) + tuple(zip(('the first net buffer', 'the second net buffer'), buffers)):
+        if not t.is_contiguous():
+            raise ValueError(f'{name} must be contiguous, got strides {tuple(t.stride())}')
+        if t.device != buffers[0].device:
+            raise ValueError(f'{name} is on {t.device}, the net on {buffers[0].device}')
+    return kind
+
+
+def band_apply(w_pos, w_view, master, effective=None, kind=0):
+    """effective (a new buffer when None) = the network whose encoding columns are the master's times the band weights
+    (fastnerf_band_apply): LW[0][:, :in_pe] and LW[5][:, :in_pe] times w_pos [in_pe], VW[:, 256:283] times w_view [27], every other
+    float copied bit for bit.  master and effective: flat fp32 nets of layout `kind`, two buffers."""
+    if effective is None:
+        effective = torch.empty_like(master)
+    kind = _need_bands(kind, w_pos, w_view, master, effective)
+    if master.data_ptr() == effective.data_ptr():
+        raise ValueError('band_apply: master and effective must be two buffers')
+    check(lib().fastnerf_band_apply(kind, ptr(w_pos), ptr(w_view), ptr(master), ptr(effective), stream()), 'fastnerf_band_apply')
+    return effective
+
+
+def band_grad(w_pos, w_view, grads, kind=0):
+    """In place: the encoding columns of a flat gradient buffer of the effective network times the band weights, which makes it the
+    master's gradient (fastnerf_band_grad).  No other float is touched."""
+    kind = _need_bands(kind, w_pos, w_view, grads)
+    check(lib().fastnerf_band_grad(kind, ptr(w_pos), ptr(w_view), ptr(grads), stream()), 'fastnerf_band_grad')
+    return grads
+
+
 def raw2outputs_fwd(raw, z, rays11, noise=None, white_bkgd=False):
     require_gpu(raw, z, rays11, noise)
     n = rays11.shape[0]

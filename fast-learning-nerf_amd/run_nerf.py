@@ -80,6 +80,7 @@ class _Args:
     refine_poses = False; pose_lrate = 1e-3      # (not in the reference's parser) refine the camera poses beside the field (Trainer(poses=))
     optim_autoexpo = False; lambda_autoexpo = 1.      # (nerf++-ours' parser) fit a per-image exposure beside the field (Trainer(exposure=))
     envmap = False; envmap_res = 64; envmap_lrate = 1e-2      # (not in the reference's parser) a trained background behind every ray (Trainer(envmap=))
+    band_window = None; band_start = 0; band_end = 0; band_view = True      # (not in the reference's parser) coarse-to-fine encoding: 'cosine' | 'linear' ramp of the band weights over steps band_start .. band_end (Trainer(bands=))
     n_epoch = 12; init_level = 3; rays_downscale = 1; subdivide_every = 1; subdivide_thres = 0.015
     randSamp_perc = 0.5; basedir = './logs'; expname = 'fastnerf'
 
@@ -154,6 +155,10 @@ def create_nerf(args, device='cuda'):
     render_kwargs_test['raw_noise_std'] = 0.
     create_nerf.flat_all, create_nerf.grad_all = flat_all, grad_all
     model._flat_all, model._grad_all = flat_all, grad_all
+    if args.use_viewdirs:      # NeRF.set_bands: the effective buffers of the two networks are one allocation too, laid out like flat_all
+        pool = {'params': flat_all}
+        for i, net in enumerate([model] + ([model_fine] if two else [])):
+            net._band_pool, net._band_slot = pool, slice(i * N, (i + 1) * N)
     return render_kwargs_train, render_kwargs_test, start_epoch, start_iter, grad_vars, optimizer
 
 
@@ -368,13 +373,26 @@ class Trainer:
     enter the pose gradient: a direction's colour is a constant of the ray.  All routes take it: the fused step (plain, compacted, through a
     grid, tighten), the marched step, the call-by-call route, the pose step, with an exposure table.  Without `envmap=` nothing changes,
     launch for launch.  ValueError, before any launch: together with bkgd= (trainer or step) or alpha= (a capture with alpha has no
-    background to learn), white_bkgd, ndc=True (the NDC far plane is infinity), data parallel, a table on another device."""
+    background to learn), white_bkgd, ndc=True (the NDC far plane is infinity), data parallel, a table on another device.
+
+    Band weights (`bands=` a bands.BandSchedule; include/fastnerf.h, "band weights"; DESIGN.md, "Band weights"): coarse-to-fine positional
+    encodings.  Before every step the networks get the schedule's column weights for that step (NeRF.set_bands; the step index is the
+    number of steps taken, `adam_t`; uploaded only when they changed).  The kernels then run on the effective networks -- the parameters
+    with the encoding columns of layer 0, the skip layer and the view layer times w -- so the fused and the marched step are called without
+    FN_STEP_UPDATE on the effective buffers and `_band_update` follows: ops.band_grad into `grad` (the parameters' gradient), Adam on `flat`
+    (the parameters) with `m` / `v`, the next step's weights, ops.band_apply and the re-pack; the call-by-call and the pose route end in
+    `_host_update`, which calls the same.  Every term, table, grid and route above passes through untouched.  `flat`, `grad`, `m`, `v`, the
+    networks' state dicts and the checkpoints are always the parameters'.  Once `bands.done(step)` the weights are cleared and the trainer
+    is the trainer without bands=, launch for launch.  save_checkpoint adds `band_schedule` / `band_weights`; load_band_checkpoint takes
+    them.  Networks whose weights were set by hand (NeRF.set_bands on both) train the same way.  Without `bands=` nothing changes.
+    ValueError, before any launch: data parallel, one network shared by both passes, networks without view directions or of another
+    class, weights on one of the two networks only."""
 
     def __init__(self, render_kwargs_train, H, W, K, near, far, lrate=5e-4, lrate_decay=250, decay=True,
                  beta1=0.9, beta2=0.999, eps=1e-8, occupancy=None, occupancy_every=16, occupancy_warmup=256, occupancy_cells=None,
                  lambda_depth=0., lambda_acc=0., tighten=False, march=None, march_cap=128, march_after=0, bkgd=None,
                  lambda_dist=0., poses=None, pose_lrate=1e-3, exposure=None, lambda_autoexpo=1.0, exposure_lrate=None,
-                 envmap=None, envmap_lrate=1e-2):
+                 envmap=None, envmap_lrate=1e-2, bands=None):
         kw = render_kwargs_train
         self._kw = kw
         self.net_c = kw['network_fn']
@@ -452,12 +470,16 @@ class Trainer:
             self.env_m, self.env_v = torch.zeros_like(envmap.table.data), torch.zeros_like(envmap.table.data)
             self.env_grad = torch.zeros_like(envmap.table.data)
             self._env_ws = torch.empty(envmap.table.numel(), device=envmap.table.device, dtype=torch.int64)
+        self.bands = bands       # a bands.BandSchedule (None: the full encoding); _band_tick sets the networks' weights from it
+        self._band_open = None   # the first step at which the schedule was seen done: from there on nothing is evaluated
         self._check_dist()
         self._check_poses()
         self._check_expo()
         self._check_env()
+        self._check_bands()
         self._check_occupancy()
         self._check_march()
+        self._band_tick(self.adam_t)
         self.repack()
 
     def _check_expo(self):
@@ -506,6 +528,73 @@ class Trainer:
                                _region(block, regions, 'acc0'))
         else:
             self._env_backward(dirs, _region(block, regions, 'g_rgb'), _region(block, regions, 'acc0'))
+
+    # ---- band weights (bands.py; NeRF.set_bands) ---------------------------------------------------------------------------
+    def _nets(self):
+        return [self.net_c] + ([self.net_f] if (self.net_f is not None and self.net_f is not self.net_c) else [])
+
+    def _check_bands(self):
+        """The refusals of a trainer with a band schedule, before any launch (read on every step, like the other settings)."""
+        if self.bands is None:
+            return
+        if self.world > 1:
+            raise ValueError('Trainer: bands= is not data parallel (world size {})'.format(self.world))
+        if not all(isinstance(net, NeRF) and net.use_viewdirs for net in self._nets()):
+            raise ValueError('Trainer: bands= weighs the encodings of model.NeRF networks with view directions (not nerf++ nets, not '
+                             'use_viewdirs=False)')
+        if self.N_importance > 0 and len(self._nets()) < 2:
+            raise ValueError('Trainer: bands= needs two distinct networks for two passes, not one network shared by both')
+
+    def _banded(self):
+        """Whether the networks run with band weights (all of them or none): the step then leaves the update to _band_update."""
+        on = [getattr(net, '_bands', None) is not None for net in self._nets()]
+        if any(on) and not all(on):
+            raise ValueError('Trainer: band weights are set on one of the two networks only: set them on both (or on neither)')
+        if on[0] and self.world > 1:
+            raise ValueError('Trainer: networks with band weights do not train data parallel (world size {})'.format(self.world))
+        return on[0]
+
+    def _kernel_buffers(self):
+        """(params, grads) the step's kernels read and write, both networks in one buffer each: the parameters' own, or with band weights
+        the effective networks' (NeRF.set_bands lays them out alike)."""
+        if not self._banded():
+            return self.flat, self.grad
+        pool = self.net_c._band_pool
+        if pool is None or self.net_c.flat.data_ptr() != pool['flat'].data_ptr() or pool['flat'].numel() != self.flat.numel():
+            raise ValueError('Trainer: band weights need the networks of create_nerf (one effective buffer for both)')
+        return pool['flat'], pool['grad']
+
+    def _band_tick(self, step):
+        """The networks' band weights for step `step` (0-based: the steps taken so far) from the schedule -- uploaded only when they
+        changed; once the schedule is done the weights are cleared and the trainer is the trainer without bands=.  -> whether the
+        effective networks changed (the caller repacks)."""
+        if self.bands is None or (self._band_open is not None and step >= self._band_open):
+            return False
+        if self.bands.done(step):
+            self._band_open = step
+            changed = any(net._bands is not None for net in self._nets())
+            for net in self._nets():
+                net.clear_bands()
+            return changed
+        self._band_open = None
+        w = self.bands.weights(step)
+        return any([net.set_bands(*w, sync=False) for net in self._nets()])
+
+    def _band_update(self, sl, collected=False):
+        """The update of a step whose kernels ran on the effective networks (called without STEP_UPDATE), over the slice `sl` of the flat
+        buffer: the effective gradient to the parameters' (ops.band_grad; collected: the route has done that), Adam on the parameters
+        with the trainer's moments, the next step's weights, then the effective networks anew (ops.band_apply) and their packings."""
+        Nn = ops.NET_PARAMS
+        nets = [net for i, net in enumerate(self._nets()) if sl.start <= i * Nn < sl.stop]
+        if not collected:
+            for net in nets:
+                net.collect_grads()
+        ops.adam_step(self.flat[sl], self.grad[sl], self.m[sl], self.v[sl], self.lr, self.adam_t, self.beta1, self.beta2, self.eps)
+        if self._band_tick(self.adam_t):
+            self.repack()
+        else:
+            for net in nets:
+                net.packed(refresh=True)
 
     def _check_expo_step(self, img, pix, n):
         """The refusals of a step's img=, before any launch -> None without a table, else the rays' images as contiguous int32 [n]
@@ -719,7 +808,7 @@ class Trainer:
                              weight_grads=wg)
         else:
             _backward_core(saved, g, g0, counts=self.live_counts if live else None, maps=maps, weight_grads=wg)
-        self.net_c.collect_grads()          # (no-ops with view directions: the kernels write the parameters' gradients)
+        self.net_c.collect_grads()          # (no-ops with view directions and no band weights: the kernels write the parameters' gradients)
         if self.net_f is not None and self.net_f is not self.net_c:
             self.net_f.collect_grads()
         if live:
@@ -745,7 +834,8 @@ class Trainer:
         a = _lib.StepArgs()
         a.n, a.net_floats, a.math_mode = n, ops.NET_PARAMS, ops.mode_id()
         a.N_samples, a.N_importance = S0, Ni
-        a.params, a.grads, a.adam_m, a.adam_v = self.flat.data_ptr(), self.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr()
+        params, grads = self._kernel_buffers()
+        a.params, a.grads, a.adam_m, a.adam_v = params.data_ptr(), grads.data_ptr(), self.m.data_ptr(), self.v.data_ptr()
         a.packed_fwd_c, a.packed_bwd_c = self.pc[0].data_ptr(), self.pc[1].data_ptr()
         if self.pf is not None:
             a.packed_fwd_f, a.packed_bwd_f = self.pf[0].data_ptr(), self.pf[1].data_ptr()
@@ -806,7 +896,7 @@ class Trainer:
         bt = self._bkgd_terms(n, dev, alpha, bkgd)
         ops.require_gpu(*batch[:5], *given.values())
         self._check_occupancy()
-        key = (n,) + extra + (str(dev), torch.cuda.current_stream(dev).cuda_stream, self._follow_math())
+        key = (n,) + extra + (str(dev), torch.cuda.current_stream(dev).cuda_stream, self._follow_math(), self._banded())
         c = self._cache.get(route)
         fresh = c is None or c[0] != key
         if fresh:
@@ -977,7 +1067,10 @@ class Trainer:
 
     def _host_update(self, sl, overlap):
         """What follows the gradient off the fused step, over the slice `sl` of the flat buffer: the collectives the stepping ranks
-        issue (the fused route's two under `overlap`, so that every rank issues the same sequence), Adam, the repack."""
+        issue (the fused route's two under `overlap`, so that every rank issues the same sequence), Adam, the repack.  With band
+        weights (world == 1; the parameters' gradient stands): _band_update, the sequence the fused routes run then."""
+        if self._banded():
+            return self._band_update(sl, collected=True)
         if self.world > 1:
             Nn = ops.NET_PARAMS
             if overlap:
@@ -1016,6 +1109,12 @@ class Trainer:
             raise ValueError('Trainer: the marched step has no depth / opacity terms (lambda_depth / lambda_acc with a target)')
         marching = KC is not None and self.occupancy_steps >= int(self.march_after)
         everything = slice(0, self.grad.numel())
+        self._check_bands()
+        if self._band_tick(self.adam_t):      # this step's band weights (unchanged, as a rule: the last update has set them)
+            self.repack()
+        # with band weights the kernels run on the effective networks and the update is _band_update's (world == 1: _check_bands)
+        banded = self._banded()
+        update = 0 if banded else _lib.STEP_UPDATE
         self.adam_t += 1
         if self.occupancy is not None and n > 0:
             self._occupancy_tick(marching)
@@ -1051,13 +1150,15 @@ class Trainer:
             if env:      # (world == 1: _check_env) phase by phase, the table's gradient behind the forward phase
                 self._march_call(a, x, _lib.STEP_FORWARD)
                 self._env_backward_block(env_dirs)
-                self._march_call(a, x, _lib.STEP_BWD_COARSE | _lib.STEP_UPDATE)
+                self._march_call(a, x, _lib.STEP_BWD_COARSE | update)
             elif self.world == 1:
-                self._march_call(a, x, _lib.STEP_FORWARD | _lib.STEP_BWD_COARSE | _lib.STEP_UPDATE)
+                self._march_call(a, x, _lib.STEP_FORWARD | _lib.STEP_BWD_COARSE | update)
             else:      # data parallel, not overlapped: one network, one collective over its half of the gradient
                 self._march_call(a, x, _lib.STEP_FORWARD | _lib.STEP_BWD_COARSE)
                 parallel.all_reduce_sum(self.grad[x.which * Nn:(x.which + 1) * Nn])
                 self._march_call(a, x, _lib.STEP_UPDATE)
+            if banded:
+                self._band_update(slice(x.which * Nn, (x.which + 1) * Nn))
             out['march_overflow'] = out['march_overflow'].bool()
             self.live.tick()
             self.last_step_live = True
@@ -1071,10 +1172,10 @@ class Trainer:
             if env:      # (world == 1: _check_env) phase by phase, the table's gradient behind the forward phase
                 self._fused_call(a, _lib.STEP_FORWARD)
                 self._env_backward_block(env_dirs)
-                self._fused_call(a, _lib.STEP_BWD_FINE | _lib.STEP_BWD_COARSE | _lib.STEP_UPDATE)
+                self._fused_call(a, _lib.STEP_BWD_FINE | _lib.STEP_BWD_COARSE | update)
                 self._after_backward(live)
             elif self.world == 1:
-                self._fused_call(a, _lib.STEP_FORWARD | _lib.STEP_BWD_FINE | _lib.STEP_BWD_COARSE | _lib.STEP_UPDATE)
+                self._fused_call(a, _lib.STEP_FORWARD | _lib.STEP_BWD_FINE | _lib.STEP_BWD_COARSE | update)
                 self._after_backward(live)
             else:
                 # data parallel: the fine net's gradient (the second half of the flat buffer) is final after the fine pass and is
@@ -1090,6 +1191,8 @@ class Trainer:
                     parallel.all_reduce_sum(self.grad)
                 self._after_backward(live)
                 self._fused_call(a, _lib.STEP_UPDATE)
+            if banded:
+                self._band_update(everything)
         else:
             loss2, out = self.forward_backward(rays_o, rays_d, target, leaf_tag, table, max_leaves, t_rand, u, n_global,
                                                alpha=alpha, bkgd=bkgd, depth=depth, depth_weight=depth_weight, acc=acc, acc_weight=acc_weight,
@@ -1160,6 +1263,10 @@ class Trainer:
         parameters, e.g. the optimizer create_nerf restored from a reference checkpoint."""
         self.adam_t, lr = flat_params.adam_state_from_torch(self._param_list(), self.m, self.v, opt)
         self.lr = float(lr)
+        if self.bands is not None:      # (as in load_state_dict)
+            self._band_open = None
+            self._band_tick(self.adam_t)
+            self.repack()
 
     def load_pose_checkpoint(self, ckpt):
         """Take xi and its moments from a checkpoint of save_checkpoint (the loaded dict, or its path).  A checkpoint without a pose
@@ -1223,6 +1330,26 @@ class Trainer:
         if self.envmap is not None and 'env_m' in sd:
             self.env_m.copy_(sd['env_m']); self.env_v.copy_(sd['env_v'])
             self.env_lr = sd.get('env_lr', self.env_lr)
+        if self.bands is not None:      # the step count moved: the band weights of the step that comes next, on the networks as they are
+            self._band_open = None
+            self._band_tick(self.adam_t)
+            self.repack()
+
+    def load_band_checkpoint(self, ckpt):
+        """Take the band schedule from a checkpoint of save_checkpoint (the loaded dict, or its path): the trainer then ramps as the
+        run that wrote it did; the weights of the next step follow from the step count (load_torch_optimizer / load_state_dict first).
+        A checkpoint without a schedule leaves the trainer untouched."""
+        if not isinstance(ckpt, dict):
+            ckpt = torch.load(ckpt, map_location=self.flat.device, weights_only=False)
+        if 'band_schedule' not in ckpt:
+            return False
+        from .bands import BandSchedule
+        self.bands = BandSchedule.from_settings(ckpt['band_schedule'], ckpt.get('band_weights'))
+        self._check_bands()
+        self._band_open = None
+        self._band_tick(self.adam_t)
+        self.repack()
+        return True
 
 
 def reference_state_dict(net):
@@ -1253,6 +1380,9 @@ def save_checkpoint(args, epoch_id, trainer, kw_train, mgr):
         ckpt.update(expo_ab=trainer.exposure.ab.data, expo_m=trainer.expo_m, expo_v=trainer.expo_v)
     if trainer.envmap is not None:      # and the environment map
         ckpt.update(env_table=trainer.envmap.table.data, env_m=trainer.env_m, env_v=trainer.env_v)
+    if trainer.bands is not None:      # and the band schedule, with the weights of the step that comes next (the state dicts above are the
+        # parameters themselves, never the effective networks: after the ramp this is a plain checkpoint of the reference's)
+        ckpt.update(band_schedule=trainer.bands.settings(), band_weights=trainer.bands.weights(trainer.adam_t))
     torch.save(ckpt, path)
     mgr.save_trees(tree_pkl_path(args, epoch_id))
     return path
@@ -1358,8 +1488,15 @@ def train(images, poses, H, W, focal, args, near=2., far=6., device='cuda', log=
         from .envmap import EnvMap
         env_kw = dict(envmap=EnvMap(res=int(getattr(args, 'envmap_res', 64))).to(dev), envmap_lrate=float(getattr(args, 'envmap_lrate', 1e-2)))
         kw_test['envmap'] = env_kw['envmap']
+    # args.band_window, args.band_start, args.band_end, args.band_view (no such flags in the reference's parser; default off): the band
+    # weights of the encodings ramp from low to high frequency over the steps band_start .. band_end (bands.BandSchedule)
+    band_kw = {}
+    if getattr(args, 'band_window', None):
+        from .bands import BandSchedule
+        band_kw = dict(bands=BandSchedule(args.band_window, getattr(args, 'band_start', 0), getattr(args, 'band_end', 0),
+                                          view=bool(getattr(args, 'band_view', True))))
     trainer = Trainer(kw_train, H, W, K, near, far, lrate=args.lrate, lrate_decay=args.lrate_decay, bkgd='random' if random_bkgd else None,
-                      lambda_dist=float(getattr(args, 'lambda_dist', 0.)), **occ_kw, **pose_kw, **expo_kw, **env_kw)
+                      lambda_dist=float(getattr(args, 'lambda_dist', 0.)), **occ_kw, **pose_kw, **expo_kw, **env_kw, **band_kw)
     trainer.global_iter = global_iter
     if len(optimizer.state_dict()['state']) > 0:   # create_nerf restored a checkpoint (ours or the reference's)
         trainer.load_torch_optimizer(optimizer)

@@ -1160,6 +1160,22 @@ int64_t fastnerf_env_grad_ws_bytes(int R);
 int fastnerf_env_grad(int64_t n, const float* dirs, int64_t stride, int R, const float* g_rgb1, const float* acc1, const float* g_rgb0,
                       const float* acc0, void* ws, float* d_table, fn_stream_t stream);
 
+/* ---- band weights: a weight per column of the positional encodings, for coarse-to-fine training (csrc/bands.hip) ------------------------
+ * A weighted encoding w (.) gamma(x) enters a network through three matrices only -- layer 0, the skip layer and the view layer -- and
+ * W (w (.) gamma) = (W diag(w)) gamma.  So every MLP kernel runs, unchanged, on an EFFECTIVE network whose encoding columns are the
+ * master's times w, and the master's gradient is the effective network's with the same columns times w.  The three regions of a net of
+ * layout `kind` (offsets of csrc/mlp_layout.h, [out][in] row-major): LW[0][:, 0:in_pe] and LW[5][:, 0:in_pe] take w_pos[col], in_pe = 63
+ * (84 for kind 2) floats; VW[:, 256:283] takes w_view[col - 256], 27 floats.
+ *
+ * fastnerf_band_apply: effective[e] = master[e] for every float of the net, copied bit for bit without a multiply, except in the three
+ * regions, where effective[e] = master[e] * w[col], one fp32 multiply.  One grid-stride launch over the net's floats.
+ *
+ * fastnerf_band_grad: in place, the three regions of a gradient buffer times w[col]; no other float is read or written.
+ *
+ * -1 before anything is enqueued: a kind outside 0..2, a NULL pointer, master == effective. */
+int fastnerf_band_apply(int kind, const float* w_pos, const float* w_view, const float* master, float* effective, fn_stream_t stream);
+int fastnerf_band_grad(int kind, const float* w_pos, const float* w_view, float* grads, fn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
